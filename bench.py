@@ -21,8 +21,13 @@ random text tokens.  Prints ONE JSON line on rank 0.
 `value` is the REFERENCE-DEFINED rate: (gen_len - 1) / gen_time over the K timed steps through `_generate`'s own loop
 (per-token D2H copy = the reference's mx.eval, Streamer, TokenStopper, detokenisation; phi_3_vision_mlx.py:390-403);
 `device_rate` is K further steps as back-to-back graph replays between two syncs (what the kernels sustain), run AFTER that loop.
-At N = 1 the line also carries `configs`: BASELINE configs[0], [2], [3] (one GPU's share) and [4] measured in the same
-process with the same definitions, each with its own roofline fractions (`--no-configs` skips them).
+
+A plain run does only what `value` and `ms_per_step` need: set up (weights, request, one prefill), W warm-up steps, the K timed
+steps, the outputs of `--dump-outputs DIR` (the last timed step's logits and the tokens the loop handed to the streamer, as .npy),
+the result line.  Everything else is measured under `--full`: the prefill (`prefill_ms`, median of `--prefill-reps`), the image
+stage (`preprocess_ms`), `device_rate`, `decode_step_hbm`, the rooflines, `rccl` (N > 1), the CPU baseline and, at N = 1,
+`configs`: BASELINE configs[0], [2], [3] (one GPU's share) and [4] measured in the same process with the same definitions, each
+with its own roofline fractions (`--no-configs` skips them).
 """
 import argparse
 import json
@@ -50,6 +55,9 @@ def parse():
     ap.add_argument("--config5", action="store_true", help="BASELINE configs[4]: fp8 (e4m3) weights, W8A8 prefill on the fp8 MFMA, int8 KV cache")
     ap.add_argument("--fp8-weight-only", action="store_true", help="with --config5: fp8_activations=False (dequantise + bf16 MFMA prefill)")
     ap.add_argument("--tiny", action="store_true", help="tiny config (debug only; the result is NOT the headline metric)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: prefill, device rate, "
+                    "rooflines, rccl, CPU baseline, the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (rank 0; e.g. bench_outputs)")
     return ap.parse_args()
 
 
@@ -266,6 +274,18 @@ def other_configs(model, processor, dev, args):
     return out
 
 
+def dump_outputs(out_dir, streamer, cache):
+    """What a caller of the timed loop receives, written after its last step: `logits` = that step's logits [B, V] and `tokens` =
+    every token the loop handed to the streamer, the prefill's first one included [B, K + 1] (ids as float64: exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    st = cache[0].state
+    logits = st.graphs["greedy"]["logits"].reshape(st.B, -1)         # the step's persistent output buffer (model.greedy_step)
+    np.save(os.path.join(out_dir, "logits.npy"), logits.float().cpu().numpy())
+    steps = [s if isinstance(s, list) else [s] for s in streamer.list_tokens]
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(steps, dtype=np.float64).T)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -320,7 +340,7 @@ def main():
             share_reqs[:] = c4_share(ip, rank, device=pdev)
             return collate_requests(share_reqs)                   # (the padded batch: shapes / token counts for the report)
         return vqa_request(ip, rank, device=pdev)
-    if not host_pre:
+    if not host_pre and args.full:
         build()                                                   # warm-up (first launch of the preprocessing kernels)
         torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -342,7 +362,8 @@ def main():
     # ---- prefill (ViT + projector + decoder prefill + lm_head + argmax + sync)
     prefill_ms = []
     n_warm = 2      # untimed: the first sight of a geometry runs eager, the second captures the vision tower's graph
-    for rep in range(args.prefill_reps + n_warm):
+    n_prefill = args.prefill_reps + n_warm if args.full else 1    # plain run: the one prefill the decode steps need
+    for rep in range(n_prefill):
         barrier()
         t0 = time.perf_counter()
         pre = None
@@ -356,10 +377,11 @@ def main():
             token = ops.argmax(logits[:, -1, :].contiguous())[:, None]
         first = token.tolist()
         dt = (time.perf_counter() - t0) * 1e3
-        if rep >= n_warm:
+        if args.full and rep >= n_warm:
             prefill_ms.append(dt)
-    prefill = float(np.median(prefill_ms))
-    print("prefill reps ms:", [round(v, 1) for v in prefill_ms], file=sys.stderr)
+    if args.full:
+        prefill = float(np.median(prefill_ms))
+        print("prefill reps ms:", [round(v, 1) for v in prefill_ms], file=sys.stderr)
 
     # ---- decode, the reference-defined rate FIRST (the K steps that follow the prefill, as phi_3_vision_mlx.py:390-403 times them):
     #      W untimed steps, then K steps through `_generate`'s own loop -- the step's tokens read per step (the reference's mx.eval),
@@ -376,114 +398,120 @@ def main():
     barrier()
     gen_elapsed = time.perf_counter() - t0
     gen_tps = (gen_len - 1) / gen_elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, streamer, cache)
 
-    # ---- the same number of steps as bare graph replays (device rate: no host work between replays; K keys further into the cache)
-    for _ in range(args.warmup):
-        logits, token = model.greedy_step(token, cache)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        logits, token = model.greedy_step(token, cache)
-    barrier()
-    elapsed = time.perf_counter() - t0
-    local_elapsed = elapsed                                        # this rank's own span (the reported one is the max over ranks)
-    # ---- how repeatable is that span?  (20 driver-timed steps are a 35 ms region, ~1 % of run-to-run noise.)  The same K
-    #      replays again, REWOUND to the same cache offset each time (same context, same bytes), until >= 0.25 s have been timed in all
-    #      (3 .. 40 regions); `steps` / `ms_per_step` / `value` above keep describing the one contracted region, the spread goes beside it.
-    st_ = cache[0].state
-    rep_ms = [elapsed / args.steps * 1e3]
-    total_s = elapsed
-    n_regions = int(min(40, max(3, np.ceil(0.25 / max(elapsed, 1e-6)))))
-    if world > 1:                                                 # (every rank runs the same number of bracketed regions)
-        nr = torch.tensor([n_regions], device="cpu" if share else dev)
-        dist.all_reduce(nr, op=dist.ReduceOp.MAX)
-        n_regions = int(nr.item())
-    while len(rep_ms) < n_regions:
-        cache[0].offset = st_.offset - args.steps                   # (the graph re-synchronises its device-side length: model.greedy_step)
+    if args.full:
+        # ---- the same number of steps as bare graph replays (device rate: no host work between replays; K keys further into the cache)
+        for _ in range(args.warmup):
+            logits, token = model.greedy_step(token, cache)
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             logits, token = model.greedy_step(token, cache)
         barrier()
-        dt = time.perf_counter() - t0
-        total_s += dt
-        rep_ms.append(dt / args.steps * 1e3)
+        elapsed = time.perf_counter() - t0
+        local_elapsed = elapsed                                        # this rank's own span (the reported one is the max over ranks)
+        # ---- how repeatable is that span?  (20 driver-timed steps are a 35 ms region, ~1 % of run-to-run noise.)  The same K
+        #      replays again, REWOUND to the same cache offset each time (same context, same bytes), until >= 0.25 s have been timed in all
+        #      (3 .. 40 regions); `steps` / `ms_per_step` / `value` above keep describing the one contracted region, the spread goes beside it.
+        st_ = cache[0].state
+        rep_ms = [elapsed / args.steps * 1e3]
+        total_s = elapsed
+        n_regions = int(min(40, max(3, np.ceil(0.25 / max(elapsed, 1e-6)))))
+        if world > 1:                                                 # (every rank runs the same number of bracketed regions)
+            nr = torch.tensor([n_regions], device="cpu" if share else dev)
+            dist.all_reduce(nr, op=dist.ReduceOp.MAX)
+            n_regions = int(nr.item())
+        while len(rep_ms) < n_regions:
+            cache[0].offset = st_.offset - args.steps                   # (the graph re-synchronises its device-side length: model.greedy_step)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                logits, token = model.greedy_step(token, cache)
+            barrier()
+            dt = time.perf_counter() - t0
+            total_s += dt
+            rep_ms.append(dt / args.steps * 1e3)
+    valid = int(np.asarray(inputs["mask"]).sum()) if "mask" in inputs else B * S
     if world > 1:
-        t = torch.tensor([elapsed, prefill, gen_elapsed], device="cpu" if share else dev)
+        t = torch.tensor([gen_elapsed] + ([elapsed, prefill] if args.full else []), device="cpu" if share else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, prefill, gen_elapsed = t.tolist()
+        gen_elapsed = t[0].item()
+        if args.full:
+            elapsed, prefill = t[1:].tolist()
         gen_tps = (gen_len - 1) / gen_elapsed
         hist = cache[0].state.graphs["greedy"]["history"]
         hist = hist.cpu() if share else hist.to(dev)                # (the graph keeps it in pinned host memory)
         gathered = [torch.empty_like(hist) for _ in range(world)] if rank == 0 else None
         dist.gather(hist, gathered, dst=0)                        # token gather over RCCL (request boundary only)
-    tokens_per_s = world * B * args.steps / elapsed                # device rate: K graph replays between two syncs
-    rccl = None
-    if world > 1:                                                 # how many ranks really joined, counted on DEVICE tensors over RCCL
-        one = torch.ones(1, device="cpu" if share else dev)
-        dist.all_reduce(one)
-        per_rank = [torch.zeros(1, device="cpu" if share else dev) for _ in range(world)]
-        dist.all_gather(per_rank, torch.tensor([B * args.steps / local_elapsed], device="cpu" if share else dev))
-        rccl = {"backend": dist.get_backend(), "ranks": int(one.item()), "world_size": dist.get_world_size(),
-                "per_rank_tokens_per_s": [round(float(t.item()), 2) for t in per_rank]}
+    if args.full:
+        tokens_per_s = world * B * args.steps / elapsed                # device rate: K graph replays between two syncs
+        rccl = None
+        if world > 1:                                                 # how many ranks really joined, counted on DEVICE tensors over RCCL
+            one = torch.ones(1, device="cpu" if share else dev)
+            dist.all_reduce(one)
+            per_rank = [torch.zeros(1, device="cpu" if share else dev) for _ in range(world)]
+            dist.all_gather(per_rank, torch.tensor([B * args.steps / local_elapsed], device="cpu" if share else dev))
+            rccl = {"backend": dist.get_backend(), "ranks": int(one.item()), "world_size": dist.get_world_size(),
+                    "per_rank_tokens_per_s": [round(float(t.item()), 2) for t in per_rank]}
 
-    # ---- roofline of the dominant decode kernel (gate_up GEMV + fused RMSNorm + SiLU*up): the 32 layers' launches
-    #      replayed as one hipGraph on the launch stream (exactly the launches of a B = 1 decode step, weights of every
-    #      layer in turn so nothing is cache-resident), HIP events around the replay
-    I, H, L = cfg.intermediate_size, cfg.hidden_size, cfg.num_hidden_layers
-    wbytes = 1 if model.w8 else 2
-    alg_bytes = 2 * I * H * wbytes                                # [2I, H] weights (bf16, or e4m3 under --config5) streamed once per launch
-    xb = torch.randn((1, H), device=dev).to(torch.bfloat16)
-    ab = torch.empty((1, I), dtype=torch.bfloat16, device=dev)
+        # ---- roofline of the dominant decode kernel (gate_up GEMV + fused RMSNorm + SiLU*up): the 32 layers' launches
+        #      replayed as one hipGraph on the launch stream (exactly the launches of a B = 1 decode step, weights of every
+        #      layer in turn so nothing is cache-resident), HIP events around the replay
+        I, H, L = cfg.intermediate_size, cfg.hidden_size, cfg.num_hidden_layers
+        wbytes = 1 if model.w8 else 2
+        alg_bytes = 2 * I * H * wbytes                                # [2I, H] weights (bf16, or e4m3 under --config5) streamed once per launch
+        xb = torch.randn((1, H), device=dev).to(torch.bfloat16)
+        ab = torch.empty((1, I), dtype=torch.bfloat16, device=dev)
 
-    def gate_up_all_layers():
-        for i in range(L):
-            k, nw = f"model.layers.{i}.mlp.gate_up_proj.weight", model.w[f"model.layers.{i}.post_attention_layernorm.weight"]
-            if model.w8:
-                ops.gemv_fp8(xb, *model.w8[k], ops.EPI_SILU_MUL, norm_w=nw, norm_eps=cfg.rms_norm_eps, out=ab)
-            else:
-                ops.gemv(xb, model.w[k], ops.EPI_SILU_MUL, norm_w=nw, norm_eps=cfg.rms_norm_eps, out=ab)
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        gate_up_all_layers()
-        gr = ops.Graph()
-        gr.begin()
-        gate_up_all_layers()
-        gr.end()
-        gr.launch()
-        side.synchronize()
-        reps = []
-        for _ in range(5):
-            e0, e1 = ops.Event(), ops.Event()
-            e0.record()
+        def gate_up_all_layers():
+            for i in range(L):
+                k, nw = f"model.layers.{i}.mlp.gate_up_proj.weight", model.w[f"model.layers.{i}.post_attention_layernorm.weight"]
+                if model.w8:
+                    ops.gemv_fp8(xb, *model.w8[k], ops.EPI_SILU_MUL, norm_w=nw, norm_eps=cfg.rms_norm_eps, out=ab)
+                else:
+                    ops.gemv(xb, model.w[k], ops.EPI_SILU_MUL, norm_w=nw, norm_eps=cfg.rms_norm_eps, out=ab)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            gate_up_all_layers()
+            gr = ops.Graph()
+            gr.begin()
+            gate_up_all_layers()
+            gr.end()
             gr.launch()
-            e1.record()
             side.synchronize()
-            reps.append(e0.elapsed_ms(e1) / L)
-    k_ms = float(np.median(reps))
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+            reps = []
+            for _ in range(5):
+                e0, e1 = ops.Event(), ops.Event()
+                e0.record()
+                gr.launch()
+                e1.record()
+                side.synchronize()
+                reps.append(e0.elapsed_ms(e1) / L)
+        k_ms = float(np.median(reps))
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
 
-    # HBM bytes per launch from the PMC passes (tools/pmc_gemv.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate
-    # runs, FETCH_SIZE x2 on gfx950); a committed measurement, not re-collected inside the timed benchmark
-    traffic = None
-    try:
-        if not model.w8:
-            with open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)) as f:
-                rec = json.load(f)
-            # the counters belong to ONE build of the kernel: a record taken from other sources is stale -> null
-            if rec.get("kernel_source_sha16") == kernel_source_sha16():
-                traffic = rec["gemv"]["hbm_bytes_per_launch_corrected"]
-    except Exception:
-        pass
-    hd = cfg.hidden_size // cfg.num_attention_heads
-    valid = int(np.asarray(inputs["mask"]).sum()) if "mask" in inputs else B * S
-    kv_elt = 1 if args.config5 else 2
-    kv_bytes = 2 * L * cfg.num_key_value_heads * hd * kv_elt * (valid + B * (args.warmup + args.steps // 2))
-    w_bytes = sum(v.numel() * 2 for k, v in model.w.items() if k.startswith("model.layers.") or k == "lm_head.weight") \
-        + sum(v[0].numel() for v in model.w8.values())
-    step_s = elapsed / args.steps
-    pf = prefill_flops(cfg, S, n_img, n_crops) if B == 1 else None
+        # HBM bytes per launch from the PMC passes (tools/pmc_gemv.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate
+        # runs, FETCH_SIZE x2 on gfx950); a committed measurement, not re-collected inside the timed benchmark
+        traffic = None
+        try:
+            if not model.w8:
+                with open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)) as f:
+                    rec = json.load(f)
+                # the counters belong to ONE build of the kernel: a record taken from other sources is stale -> null
+                if rec.get("kernel_source_sha16") == kernel_source_sha16():
+                    traffic = rec["gemv"]["hbm_bytes_per_launch_corrected"]
+        except Exception:
+            pass
+        hd = cfg.hidden_size // cfg.num_attention_heads
+        kv_elt = 1 if args.config5 else 2
+        kv_bytes = 2 * L * cfg.num_key_value_heads * hd * kv_elt * (valid + B * (args.warmup + args.steps // 2))
+        w_bytes = sum(v.numel() * 2 for k, v in model.w.items() if k.startswith("model.layers.") or k == "lm_head.weight") \
+            + sum(v[0].numel() for v in model.w8.values())
+        step_s = elapsed / args.steps
+        pf = prefill_flops(cfg, S, n_img, n_crops) if B == 1 else None
     if args.config4:
         workload = (f"BASELINE configs[3], one GPU's share per rank: {B} requests = {n_crops // 17} single-image VQA (2531 tokens) + "
                     f"{B - n_crops // 17} text prompts (16..256 tokens) as one left-padded batch; greedy, EOS suppressed")
@@ -508,37 +536,40 @@ def main():
                             "B tokens per step INCLUDING the B first tokens the prefill produced while gen_time starts after the prefill, "
                             "so the figure is (B * (K + 1) - 1) / gen_time -- slightly above the device rate B * K / time by construction "
                             "(phi_3_vision_mlx.py:77,401-403), not a faster step",
-        "device_rate": {"tokens_per_s": round(tokens_per_s, 2), "ms_per_step": round(step_s * 1e3, 4),
-                        "definition": "K further steps as back-to-back graph replays between two syncs (no per-token host work; run after the reference-defined loop, K keys deeper into the cache)",
-                        "repeats": {"regions": len(rep_ms), "steps_each": args.steps, "timed_s": round(total_s, 3),
-                                    "ms_per_step_median": round(float(np.median(rep_ms)), 4), "ms_per_step_min": round(min(rep_ms), 4),
-                                    "ms_per_step_max": round(max(rep_ms), 4),
-                                    "spread_pct": round((max(rep_ms) - min(rep_ms)) / float(np.median(rep_ms)) * 100, 2),
-                                    "note": "this rank's own spans of the same K replays, rewound to the same cache offset; region 0 is the reported one"}},
-        "rccl": rccl,
         "dtype": "fp8(e4m3)+int8kv" if args.config5 else "bf16", "data": "synthetic",
         "config": {"workload": workload, "parallelism": f"batch-sharded replicas x{world}", "batch_per_gpu": int(B), "tiny": bool(args.tiny)},
-        "prefill_ms": round(prefill, 3), "prefill_tokens": int(valid), "preprocess_ms": round(host_pre_ms, 1),
-        "preprocess": "host" if host_pre else "device",
-        "decode_step_hbm": {"span": "device-rate step", "algorithmic_GB_per_token": round((w_bytes + kv_bytes) / 1e9, 3),
-                            "achieved_GBps": round((w_bytes + kv_bytes) / step_s / 1e9, 1),
-                            "frac_of_peak": round((w_bytes + kv_bytes) / step_s / 1e9 / HBM_PEAK_GBS, 4)},
-        "roofline": {"bound": "hbm", "kernel": ("k_gemv3_f8" if model.w8 else "k_gemv3<1,1,6>") + " (RMSNorm + gate_up_proj + SiLU*up), 32 launches per B=1 step", "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(k_ms, 5)},
-        "roofline_prefill": None if pf is None else {
-            "bound": "mfma", "algorithmic_TFLOP": round(pf / 1e12, 2), "achieved": round(pf / (prefill * 1e-3) / 1e12, 1),
-            "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(pf / (prefill * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-            "peak_note": "bf16 dense MFMA peak (under --config5 the decoder projections run on the fp8 MFMA, 2x that peak; the ViT stays bf16)",
-            "span": "whole prefill wall time (ViT + projector + 32 layers + lm_head + argmax + sync), not a single kernel"},
-        "first_token": first, "weights_init_s": round(t_weights, 1),
+        "prefill_tokens": int(valid), "first_token": first, "weights_init_s": round(t_weights, 1),
     }
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not args.tiny:
-        out["cpu_baseline"] = cpu_baseline(model)
-    elif rank == 0:
-        out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not args.no_configs and not (args.config4 or args.config5):
-        out["configs"] = other_configs(model, processor, dev, args)
+    if args.full:
+        out.update({
+            "device_rate": {"tokens_per_s": round(tokens_per_s, 2), "ms_per_step": round(step_s * 1e3, 4),
+                            "definition": "K further steps as back-to-back graph replays between two syncs (no per-token host work; run after the reference-defined loop, K keys deeper into the cache)",
+                            "repeats": {"regions": len(rep_ms), "steps_each": args.steps, "timed_s": round(total_s, 3),
+                                        "ms_per_step_median": round(float(np.median(rep_ms)), 4), "ms_per_step_min": round(min(rep_ms), 4),
+                                        "ms_per_step_max": round(max(rep_ms), 4),
+                                        "spread_pct": round((max(rep_ms) - min(rep_ms)) / float(np.median(rep_ms)) * 100, 2),
+                                        "note": "this rank's own spans of the same K replays, rewound to the same cache offset; region 0 is the reported one"}},
+            "rccl": rccl,
+            "prefill_ms": round(prefill, 3), "preprocess_ms": round(host_pre_ms, 1),
+            "preprocess": "host" if host_pre else "device",
+            "decode_step_hbm": {"span": "device-rate step", "algorithmic_GB_per_token": round((w_bytes + kv_bytes) / 1e9, 3),
+                                "achieved_GBps": round((w_bytes + kv_bytes) / step_s / 1e9, 1),
+                                "frac_of_peak": round((w_bytes + kv_bytes) / step_s / 1e9 / HBM_PEAK_GBS, 4)},
+            "roofline": {"bound": "hbm", "kernel": ("k_gemv3_f8" if model.w8 else "k_gemv3<1,1,6>") + " (RMSNorm + gate_up_proj + SiLU*up), 32 launches per B=1 step", "achieved": round(achieved, 1),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(k_ms, 5)},
+            "roofline_prefill": None if pf is None else {
+                "bound": "mfma", "algorithmic_TFLOP": round(pf / 1e12, 2), "achieved": round(pf / (prefill * 1e-3) / 1e12, 1),
+                "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(pf / (prefill * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                "peak_note": "bf16 dense MFMA peak (under --config5 the decoder projections run on the fp8 MFMA, 2x that peak; the ViT stays bf16)",
+                "span": "whole prefill wall time (ViT + projector + 32 layers + lm_head + argmax + sync), not a single kernel"},
+        })
+        if rank == 0 and not args.no_cpu_baseline and world == 1 and not args.tiny:
+            out["cpu_baseline"] = cpu_baseline(model)
+        elif rank == 0:
+            out["cpu_baseline"] = None
+        if rank == 0 and world == 1 and not args.no_configs and not (args.config4 or args.config5):
+            out["configs"] = other_configs(model, processor, dev, args)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

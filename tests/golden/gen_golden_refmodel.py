@@ -13,6 +13,7 @@ The lm_head seeds are searched with the oracle (fast, replayable decode) so that
 run under that head and the clearance is recomputed from ITS logits.
 
     python tests/golden/gen_golden_refmodel.py
+    python tests/golden/gen_golden_refmodel.py live      (ref_live_blind.json only)
 """
 import hashlib
 import json
@@ -32,7 +33,8 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), HERE):
 import phi3v_oracle as orc  # noqa: E402
 import ref_env  # noqa: E402
 from gen_golden_oracle import REL_TOL, SPREAD, Prefilled, bits, clearance, row_norms, search_head  # noqa: E402
-from golden_inputs import make_image  # noqa: E402
+from golden_inputs import (LIVE_BEAM, LIVE_GEN_PROMPTS, LIVE_PROMPTS, LIVE_STEP, live_blind_weights, make_image,  # noqa: E402
+                           one_thread, tensor_digest)
 from phi_3_vision_mlx_amd.config import make_config, tiny_config_dict  # noqa: E402
 from phi_3_vision_mlx_amd.processor import ByteTokenizer, Phi3FProcessor, Phi3VProcessor  # noqa: E402
 from phi_3_vision_mlx_amd.weights import peaked_lm_head, save_adapter, save_safetensors_dir, synth_weights  # noqa: E402
@@ -664,8 +666,66 @@ def wc_retol():
     print(f"ref_model_wc: rel_tol {old} -> {REL_TOL_WC}; clear steps plain {meta['plain']['clear']}, peaked0 {meta['peaked0']['clear']}")
 
 
+def live():
+    """ref_live_blind.json: the reference's model-level contract (all-position prefill logits, cached L > 1 calls with
+    advance_offset 0 / 1 / None, a read-only n_beam=3 view, the fp32 cache contents) and `_generate` with EOS + Streamer on a
+    blind tiny checkpoint and prompts that are NOT in ref_model_tiny.  The tensors are recorded as sha256 digests of their
+    bits (the all-position logits alone are MBs); tests/test_refmodel.py holds the oracle to them bit for bit.  The oracle is
+    run beside the reference here too, and the file is only written when the two agree."""
+    t0 = time.time()
+    d, w = live_blind_weights()
+    cfg = make_config(d)
+    path = os.path.join(TMP, "live_blind")
+    shutil.rmtree(path, ignore_errors=True)
+    os.makedirs(path)
+    save_safetensors_dir(w, d, path)
+    mx, _, loops = ref_env.load_reference()
+    model, proc = ref_env.load_model(path, ByteTokenizer())
+    oracle, my = orc.OraclePhi3V(cfg, w, cache_fp32=True), Phi3FProcessor(None)
+    meta = {"generator": "tests/golden/gen_golden_refmodel.py live", "reference": "phi.py + phi_3_vision_mlx.py over tests/golden/mlx_shim.py",
+            "weights": "tiny blind, synth_weights(seed=3, std_scale=4.0, lm_head_spread=4.0, lm_head_seed=1)", "threads": 1, "calls": []}
+    with one_thread():
+        live_calls(mx, model, proc, oracle, my, meta)
+    texts = loops._generate(model, proc, LIVE_GEN_PROMPTS, max_tokens=9, verbose=False, stream=False, mute=True)
+    toks, _ = orc.greedy_generate(oracle, dict(my(LIVE_GEN_PROMPTS)), 9)
+    rows = [(r[:r.index(orc.ID_EOS) + 1] if orc.ID_EOS in r else r) for r in toks.tolist()]
+    assert my.tokenizer.batch_decode(rows) == texts
+    meta["generate"] = {"prompts": LIVE_GEN_PROMPTS, "max_tokens": 9, "texts": texts}
+    with open(os.path.join(HERE, "ref_live_blind.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    shutil.rmtree(path, ignore_errors=True)
+    print(f"wrote ref_live_blind.json in {time.time() - t0:.0f}s")
+
+
+def live_calls(mx, model, proc, oracle, my, meta):
+    """The model-level calls of ref_live_blind.json, reference and oracle side by side (see live())."""
+    def rec(what, rl, rc, ol, oc, valid=None):
+        r, o = (rl._t, ol) if valid is None else (rl._t[valid], ol[valid])
+        assert torch.equal(r, o) and rc[0].offset == oc[0].offset, f"{what}: oracle and reference differ"
+        meta["calls"].append({"call": what, "logits": tensor_digest(r), "offset": int(rc[0].offset)})
+    r_in, o_in = proc(LIVE_PROMPTS), my(LIVE_PROMPTS)
+    rl, rc = model(**r_in, max_tokens=12)
+    ol, oc = oracle(**o_in, max_tokens=12)
+    rec("prefill", rl, rc, ol, oc, torch.as_tensor(np.asarray(o_in["mask"])).bool())     # pad query rows are undefined (Q7)
+    step = torch.tensor(LIVE_STEP)
+    for adv in (0, 1, None):
+        rl, rc = model(input_ids=mx.array(step.numpy()), cache=rc, advance_offset=adv)
+        ol, oc = oracle(input_ids=step, cache=oc, advance_offset=adv)
+        rec(f"step_advance_{adv}", rl, rc, ol, oc)
+    beam = torch.tensor(LIVE_BEAM)
+    rl, _ = model(input_ids=mx.array(beam.numpy()), cache=rc, n_beam=3, advance_offset=0)
+    ol, _ = oracle(input_ids=beam, cache=oc, n_beam=3, advance_offset=0)
+    rec("beam_view", rl, rc, ol, oc)
+    meta["cache"] = []
+    for a, b in zip(rc, oc):
+        assert torch.equal(a.kv._t[:, :, :, :a.offset], b.kv[:, :, :, :b.offset])
+        meta["cache"].append(tensor_digest(a.kv._t[:, :, :, :a.offset]))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "wc":
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        live()
+    elif len(sys.argv) > 1 and sys.argv[1] == "wc":
         wc()
     elif len(sys.argv) > 1 and sys.argv[1] == "wc_retol":
         wc_retol()

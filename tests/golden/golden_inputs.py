@@ -1,5 +1,6 @@
 """Seeded inputs shared by the golden-vector generator (which feeds them to the
 reference) and the tests (which feed them to the build)."""
+import contextlib
 import re
 
 import numpy as np
@@ -72,3 +73,40 @@ import os as _os
 import sys as _sys
 _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))))
 from phi_3_vision_mlx_amd.workloads import c4_share, text_request, vqa_request  # noqa: E402,F401
+
+
+# ref_live_blind.json (gen_golden_refmodel.py live): the reference's model-level contract and `_generate` on a blind tiny checkpoint
+LIVE_PROMPTS = ["<|user|>\nabc<|end|>\n<|assistant|>\n", "<|user|>\na much longer second prompt<|end|>\n<|assistant|>\n"]
+LIVE_GEN_PROMPTS = ["<|user|>\nPick A or B.<|end|>\n<|assistant|>\n", "<|user|>\nhello<|end|>\n<|assistant|>\n"]
+LIVE_STEP = [[5, 9, 11], [7, 8, 12]]
+LIVE_BEAM = [[3, 4]] * 6
+
+
+def live_blind_weights():
+    """-> (config dict, weights) of the blind tiny checkpoint of ref_live_blind.json (seed 3, peaked head)."""
+    from phi_3_vision_mlx_amd.config import make_config, tiny_config_dict
+    from phi_3_vision_mlx_amd.weights import synth_weights
+    d = tiny_config_dict(vision=False)
+    return d, synth_weights(make_config(d), seed=3, std_scale=4.0, lm_head_spread=4.0, lm_head_seed=1)
+
+
+@contextlib.contextmanager
+def one_thread():
+    """torch-CPU on one thread: how a multi-threaded fp32 GEMM splits its work follows the thread count, so bits recorded on one
+    machine hold on another only at a fixed count (ref_live_blind.json is recorded and checked at one)."""
+    import torch
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def tensor_digest(t):
+    """dtype, shape and sha256 of a tensor's bytes: equal digests <=> bit-identical tensors."""
+    import hashlib
+    import torch
+    t = t.detach().contiguous()
+    return {"dtype": str(t.dtype), "shape": list(t.shape),
+            "sha256": hashlib.sha256(t.reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()}

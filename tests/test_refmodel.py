@@ -12,8 +12,8 @@ outputs:
   * `_choose_from` / `_constrain` (plain and beam): every model call of the reference's loop is reproduced -- the ids fed,
     (advance_offset, n_beam), and per position the top-8 logits, the log-sum-exp and the constraint-id logits.
 
-When /root/reference is present (build container) `test_live_*` additionally run the reference side by side with the
-oracle on inputs that are NOT in the fixture.  tests/test_model_gpu.py checks the HIP path against the same fixture.
+`test_live_*` hold the oracle to the reference on inputs that are NOT in that fixture (`tests/golden/ref_live_blind.json`,
+written by the same generator).  tests/test_model_gpu.py checks the HIP path against the same fixture.
 """
 import json
 import os
@@ -319,65 +319,53 @@ def test_oracle_choose_and_constrain_match_reference_loops(fx, tiny_models):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# live: the reference next to the oracle (build container only)
+# live: the reference next to the oracle on inputs outside ref_model_tiny -- the reference's side recorded in
+# tests/golden/ref_live_blind.json (gen_golden_refmodel.py live; tensors as sha256 digests of their bits)
 # ------------------------------------------------------------------------------------------------------------------------
-def _live():
-    import ref_env
-    if not ref_env.available():
-        pytest.skip("needs /root/reference (build container only)")
-    return ref_env
-
-
 @pytest.fixture(scope="module")
-def live_blind(tmp_path_factory):
-    ref_env = _live()
-    from phi_3_vision_mlx_amd.processor import ByteTokenizer
-    from phi_3_vision_mlx_amd.weights import save_safetensors_dir
-    d = tiny_config_dict(vision=False)
-    cfg = make_config(d)
-    w = synth_weights(cfg, seed=3, std_scale=4.0, lm_head_spread=4.0, lm_head_seed=1)
-    path = str(tmp_path_factory.mktemp("refblind"))
-    save_safetensors_dir(w, d, path)
-    model, proc = ref_env.load_model(path, ByteTokenizer())
-    return ref_env, model, proc, orc.OraclePhi3V(cfg, w, cache_fp32=True), Phi3FProcessor(None)
+def live_blind():
+    from golden_inputs import live_blind_weights
+    with open(os.path.join(GOLDEN, "ref_live_blind.json")) as f:
+        rec = json.load(f)
+    d, w = live_blind_weights()
+    return rec, orc.OraclePhi3V(make_config(d), w, cache_fp32=True), Phi3FProcessor(None)
 
 
 def test_live_all_positions_rewind_and_beam_view(live_blind):
     """Model-level contract (phi.py:576-592, 509-548): all-position logits of a prefill, a cached L > 1 call that does not
     advance the cache (advance_offset=0), one that commits a single token (advance_offset=1), and a read-only beam view
     (n_beam=3) -- reference and oracle bit for bit, including the cache offsets."""
-    ref_env, model, proc, oracle, my = live_blind
-    mx = ref_env.load_reference()[0]
-    prompts = ["<|user|>\nabc<|end|>\n<|assistant|>\n", "<|user|>\na much longer second prompt<|end|>\n<|assistant|>\n"]
-    r_in, o_in = proc(prompts), my(prompts)
-    rl, rc = model(**r_in, max_tokens=12)
-    ol, oc = oracle(**o_in, max_tokens=12)
-    valid = torch.as_tensor(np.asarray(o_in["mask"])).bool()
-    assert torch.equal(rl._t[valid], ol[valid])                         # pad query rows are undefined in the reference (Q7)
-    assert rc[0].offset == oc[0].offset
-    step = torch.tensor([[5, 9, 11], [7, 8, 12]])
-    for adv in (0, 1, None):
-        rl, rc = model(input_ids=mx.array(step.numpy()), cache=rc, advance_offset=adv)
-        ol, oc = oracle(input_ids=step, cache=oc, advance_offset=adv)
-        assert torch.equal(rl._t, ol) and rc[0].offset == oc[0].offset, adv
-    beam = torch.tensor([[3, 4]] * 6)
-    rl, _ = model(input_ids=mx.array(beam.numpy()), cache=rc, n_beam=3, advance_offset=0)
-    ol, _ = oracle(input_ids=beam, cache=oc, n_beam=3, advance_offset=0)
-    assert torch.equal(rl._t, ol) and rc[0].offset == oc[0].offset
-    for a, b in zip(rc, oc):                                            # the caches themselves: same fp32 contents
-        assert torch.equal(a.kv._t[:, :, :, :a.offset], b.kv[:, :, :, :b.offset])
+    from golden_inputs import LIVE_BEAM, LIVE_PROMPTS, LIVE_STEP, one_thread, tensor_digest
+    rec, oracle, my = live_blind
+    calls = {c["call"]: c for c in rec["calls"]}
+
+    def check(what, logits, cache):
+        assert tensor_digest(logits) == calls[what]["logits"], f"{what}: logits differ from the reference's"
+        assert cache[0].offset == calls[what]["offset"], what
+    with one_thread():                                                  # the thread count the reference's bits were recorded at
+        o_in = my(LIVE_PROMPTS)
+        ol, oc = oracle(**o_in, max_tokens=12)
+        valid = torch.as_tensor(np.asarray(o_in["mask"])).bool()
+        check("prefill", ol[valid], oc)                                 # pad query rows are undefined in the reference (Q7)
+        step = torch.tensor(LIVE_STEP)
+        for adv in (0, 1, None):
+            ol, oc = oracle(input_ids=step, cache=oc, advance_offset=adv)
+            check(f"step_advance_{adv}", ol, oc)
+        ol, _ = oracle(input_ids=torch.tensor(LIVE_BEAM), cache=oc, n_beam=3, advance_offset=0)
+        check("beam_view", ol, oc)
+    assert len(oc) == len(rec["cache"])
+    for b, r in zip(oc, rec["cache"]):                                  # the caches themselves: same fp32 contents
+        assert tensor_digest(b.kv[:, :, :, :b.offset]) == r
 
 
-def test_live_generate_with_eos_and_streamer(live_blind, capsys):
+def test_live_generate_with_eos_and_streamer(live_blind):
     """`_generate` end to end incl. Streamer / TokenStopper (phi_3_vision_mlx.py:45-117, 376-409) vs the build's host loop
     driven by the ORACLE model: same texts, same stop step when a row emits EOS."""
-    ref_env, model, proc, oracle, my = live_blind
-    loops = ref_env.load_reference()[2]
-    prompts = ["<|user|>\nPick A or B.<|end|>\n<|assistant|>\n", "<|user|>\nhello<|end|>\n<|assistant|>\n"]
-    texts = loops._generate(model, proc, prompts, max_tokens=9, verbose=False, stream=False, mute=True)
-    toks, _ = orc.greedy_generate(oracle, dict(my(prompts)), 9)
+    rec, oracle, my = live_blind
+    g = rec["generate"]
+    toks, _ = orc.greedy_generate(oracle, dict(my(g["prompts"])), g["max_tokens"])
     rows = [(r[:r.index(orc.ID_EOS) + 1] if orc.ID_EOS in r else r) for r in toks.tolist()]
-    assert my.tokenizer.batch_decode(rows) == texts
+    assert my.tokenizer.batch_decode(rows) == g["texts"]
 
 
 def test_shim_semantics():

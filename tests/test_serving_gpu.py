@@ -404,7 +404,7 @@ def test_bench_two_gpus_reports_its_rccl_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--tiny", "--steps", "8", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl"]["backend"] == "nccl" and line["rccl"]["ranks"] == 2
@@ -427,7 +427,7 @@ def test_bench_two_ranks_sharing_one_gpu():
     env = dict(os.environ, P3V_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--tiny", "--steps", "8", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -436,6 +436,33 @@ def test_bench_two_ranks_sharing_one_gpu():
     per_rank = line["rccl"]["per_rank_tokens_per_s"]
     assert len(per_rank) == 2 and min(per_rank) > 0
     assert line["value"] > 0 and line["steps"] == 8 and line["scaling"] == "weak"
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run (tiny model): the headline keys without the `--full` measurements, `steps` as asked, and
+    `--dump-outputs` writes the last timed step's logits and the streamed tokens -- the same arrays in a second run."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--tiny", "--steps", "6", "--warmup", "2",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 6 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "tokens/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+        assert not {"device_rate", "prefill_ms", "roofline", "cpu_baseline", "configs"} & set(line)
+        got.append((np.load(d / "logits.npy"), np.load(d / "tokens.npy")))
+    (l0, t0), (l1, t1) = got
+    assert l0.dtype == np.float32 and l0.shape == (1, 32064) and np.isfinite(l0).all()
+    assert t0.dtype == np.float64 and t0.shape == (1, 7)
+    assert np.argmax(l0[0]) == t0[0, -1]                                 # the last step's logits chose its token
+    assert np.array_equal(t0, t1) and np.array_equal(l0, l1)
 
 
 def _fleet_worker(rank, world, port, out_dir):
