@@ -429,6 +429,40 @@ int p3v_gemv_fp8_step(const p3v_gemv_fp8_args_t* args /* host */, const p3v_gemv
 /* and on MLX 4-bit group-64 weights (`args` as for p3v_gemv_q4, one row, no epilogue) */
 int p3v_gemv_q4_step(const p3v_gemv_q4_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
 
+/* ---- seeded sampling (temperature, top-k, top-p): added after round 6, no version change.
+ * One record per row, on the device; every launch reads it and increments `counter`, so a replayed graph needs no host input.
+ * The rule, for one row of bf16 logits l[0..n) with temperature T, top_k k (0 = off), top_p p (1 = off), 64-bit seed
+ * s = seed_hi:seed_lo and draw index c = counter (the index of this token in the row's generated sequence, 0 = the token
+ * drawn from the prefill logits):
+ *   0. T <= 0: the arg-max, exactly as p3v_argmax (first maximum, -1 for a NaN row).  Also when the row has no finite
+ *      logit or when m (step 2) overflows to +inf.
+ *   1. a NaN logit: the token is -1.
+ *   2. z_i = f32(l_i) / T (IEEE fp32 division, correctly rounded); m = max z.
+ *   3. w_i = floor(exp((double)z_i - (double)m) * 2^32) as uint64, computed in fp64 (a -inf logit: 0).
+ *   4. top-k, when 1 <= k < n: keep i iff l_i >= the k-th largest bf16 value (every token tied at the cut is kept).
+ *   5. top-p, when 0 < p < 1, over the kept tokens: Q = sum w, P = ceil((double)p * (double)Q); keep l_i >= kappa, kappa the
+ *      largest bf16 value with sum_{kept, l_i >= kappa} w_i >= P (ties at kappa kept).
+ *   6. r = word 0 of Philox4x32-10 with counter (c, 0, 0, 0) and key (seed_lo, seed_hi); Q' = sum_kept w;
+ *      t = floor(Q' * r / 2^32) (exact 128-bit product); the token is the smallest i with sum_{kept, j <= i} w_j > t.
+ *   7. counter += 1 for every row, greedy rows included.
+ * Everything after step 3 is integer arithmetic: a token does not depend on the launch geometry, the batch neighbours or graph
+ * versus eager execution.  n <= 32768 and rows <= 1024, otherwise P3V_ERR_UNSUPPORTED. */
+typedef struct {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint32_t seed_lo, seed_hi;
+  int32_t counter;
+} p3v_sample_row_t;
+/* eager form: out[r] = the token of row r (logits row r at logits + r * row_stride); rows_params[r].counter += 1 */
+int p3v_sample(const uint16_t* logits, int64_t row_stride, p3v_sample_row_t* rows_params, int32_t* out, int rows, int n,
+               void* stream);
+/* graph tail of a sampled step: p3v_step_end's bookkeeping with the sampled token (next_tok[b] = tok[b] = it,
+ * history[b, *d_step] = it, then *d_step += 1 and *d_past += 1 done once via `ticket`, which is left at zero) */
+int p3v_sample_step_end(const uint16_t* logits, p3v_sample_row_t* rows_params, int32_t* next_tok, int32_t* tok,
+                        int32_t* history, int32_t* d_step, int32_t* d_past, int32_t* ticket, int B, int n, int max_steps,
+                        void* stream);
+
 /* ---- hipGraph helpers: capture a sequence of the launches above and replay it */
 int p3v_graph_begin(void* stream);
 int p3v_graph_end(void* stream, void** graph_exec_out /* host */);

@@ -89,6 +89,13 @@ class AttnDecQ8Args(C.Structure):
                 ("o_proj_w8", vp), ("o_proj_scale", vp), ("o_proj_x", vp), ("o_rearm", vp), ("o_n", i32)]   # optional fused o_proj (e4m3)
 
 
+class SampleRow(C.Structure):
+    """p3v_sample_row_t: one row's sampling settings + its draw counter (include/p3v.h)."""
+    _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+                ("counter", i32)]
+
+
+SAMPLE_MAX_N, SAMPLE_MAX_ROWS = 32768, 1024      # p3v_sample / p3v_sample_step_end: larger -> P3V_ERR_UNSUPPORTED
 # name -> (restype, argtypes); must list every symbol include/p3v.h declares
 SIGNATURES = {
     "p3v_version": (i32, []),
@@ -141,6 +148,8 @@ SIGNATURES = {
     "p3v_lora_up": (i32, [vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, vp]),
     "p3v_step_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "p3v_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p3v_sample": (i32, [vp, i64, vp, vp, i32, i32, vp]),
+    "p3v_sample_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_graph_begin": (i32, [vp]),
     "p3v_graph_end": (i32, [vp, C.POINTER(vp)]),
     "p3v_graph_launch": (i32, [vp, vp]),

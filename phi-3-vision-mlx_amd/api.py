@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops as model_ops
+from . import sampling as sampling_mod
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
@@ -290,7 +291,7 @@ def _last_logits(logits):
     return logits[:, -1, :].contiguous()
 
 
-def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None):
+def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None, sampling=None):
     """The decode loop of `_generate` (reference phi_3_vision_mlx.py:390-398): `n_steps` greedy steps after the prefill token,
     every token handed to the streamer and the stoppers in order, stops as the reference stops.
 
@@ -299,8 +300,19 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     D2H copy, Streamer, TokenStopper -- runs while the GPU computes the next step.  Tokens, texts and stop step are identical;
     when a stop fires one speculative step has been enqueued: it is dropped -- the cache offset is rewound past it and the
     STOP step's token is returned, so cache and return value are what the one-sync-per-token loop leaves.  With a logit stopper (it reads step i's logits
-    on the host before deciding) or an eager model the loop is the reference's, one sync per token."""
+    on the host before deciding) or an eager model the loop is the reference's, one sync per token.
+
+    sampling: per-row (temperature, top_k, top_p, seed) tuples (sampling.rows) -- the loop then drives the SAMPLED replay
+    (model.sample_step) on records whose draw index starts at 1 (the prefill token was draw 0); None: the greedy replay."""
     graph_step = getattr(model, "greedy_step", None)
+    records = None
+    if sampling is not None:
+        records = sampling_mod.pack(sampling, counter=1)
+        graph_step = getattr(model, "sample_step", None)
+        if graph_step is not None:
+            model.set_sampling(cache[0].state, records)
+        else:                                                       # an eager model: the records ride with the loop
+            records = records.to(token.device)
     ahead = graph_step is not None and (logit_stopper is None or not logit_stopper.early_stop) and torch.is_tensor(token) and token.is_cuda
     if not ahead:
         for _ in range(n_steps):
@@ -308,7 +320,8 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                 logits, token = graph_step(token, cache)
             else:
                 logits, cache = model(input_ids=token, cache=cache, mask=mask, pids=pids)
-                token = model_ops.argmax(_last_logits(logits))[:, None]
+                token = (model_ops.argmax(_last_logits(logits)) if records is None else
+                         model_ops.sample(_last_logits(logits), records))[:, None]
             rows = _rows(token)                                     # ONE D2H copy per step, shared by the streamer and the stopper
             streamer(rows)
             if logit_stopper is not None and logit_stopper(logits):
@@ -392,15 +405,22 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             st.scrub(st.offset, st.offset + i - n_done)             # (their cache rows hold NaN: 0 x NaN would poison every later step)
             i, pending = n_done, None
             token = torch.tensor(taken, dtype=torch.int32, device=token0.device).view(-1, 1) if n_done else token0
+            if records is not None:                                 # the draw index rewinds with the offset: step n_done draws n_done + 1
+                model.set_sampling(st, sampling_mod.pack(sampling, counter=1 + n_done))
             print("[phi3v] a decode step timed out in the fused attention + o_proj launch (is another process using this GPU?): "
                   "continuing with separate launches", file=sys.stderr)
 
 
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
-              stream=True, mute=False):
-    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409)."""
+              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None):
+    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  temperature > 0 samples instead (include/p3v.h:
+    p3v_sample_row_t; each of temperature / top_k / top_p / seed a scalar or a per-row list, see sampling.rows); temperature 0
+    -- the default -- is today's greedy path, launch for launch."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
+    B = len(prompt) if isinstance(prompt, list) else 1
+    rows = sampling_mod.rows(B, temperature, top_k, top_p, seed)
+    sampled = None if sampling_mod.greedy(rows) else rows
     logit_stopper = LogitStopper(max_tokens, early_stop)
     streamer = Streamer(processor, stream, mute)
     dict_input = processor(prompt, images)
@@ -408,10 +428,16 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     token_stopper = TokenStopper(processor, dict_input["input_ids"].shape[0])
     tic = Tic()
     logits, cache = model(**dict_input, max_tokens=max_tokens)
-    token = model_ops.argmax(_last_logits(logits))[:, None]
+    if sampled is None:
+        token = model_ops.argmax(_last_logits(logits))[:, None]
+    else:                                                       # draw 0 of every row: from the prefill logits
+        token = model_ops.sample(logits[:, -1, :], sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
     streamer(_rows(token))                                      # D2H copy = the per-token sync the reference has (mx.eval)
     prompt_time = tic()
-    greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids)
+    if sampled is None:
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids)
+    else:
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled)
     result, gen_len = streamer.end()
     gen_time = tic()
     prompt_len = dict_input["input_ids"].size
@@ -427,14 +453,15 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
-             apply_chat_template=True, enable_api=False):
-    """reference phi_3_vision_mlx.py:1324-1374."""
+             apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None):
+    """reference phi_3_vision_mlx.py:1324-1374, plus seeded sampling (`_generate`; temperature 0 = greedy, the default)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
-                     verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream)
+                     verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
+                     top_k=top_k, top_p=top_p, seed=seed)
 
 
 # ----------------------------------------------------------------------------- choose

@@ -58,10 +58,11 @@ def _set_device(device):
 
 
 class Request:
-    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at")
+    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling")
 
-    def __init__(self, inputs, max_tokens):
+    def __init__(self, inputs, max_tokens, sampling=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
+        self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
         self.tokens, self.row, self.error = [], None, None
         self.cancelled, self.blocked_at = False, None
@@ -102,9 +103,17 @@ class ContinuousEngine:
             return False
         return (S + max_tokens > ROPE_WINDOW) == self.long_rope
 
-    def submit(self, inputs, max_tokens):
-        """inputs: a B = 1 `processor(text[, images])` result.  Returns the Request; wait on `.done`, read `.tokens`."""
-        r = Request(inputs, max_tokens)
+    def submit(self, inputs, max_tokens, sampling=None):
+        """inputs: a B = 1 `processor(text[, images])` result.  Returns the Request; wait on `.done`, read `.tokens`.
+        sampling: None (greedy) or {"temperature", "top_k", "top_p", "seed"} (missing keys: 0, 0, 1.0, 64 random bits; see
+        sampling.rows) -- the request's tokens are then drawn under its own record, whoever shares the batch."""
+        try:
+            rec = _sampling_row(sampling)
+        except ValueError as e:
+            r = Request(inputs, max_tokens)
+            r.fail(e)
+            return r
+        r = Request(inputs, max_tokens, rec)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -198,7 +207,16 @@ class ContinuousEngine:
         g = self.model.decode_graph(st)
         for i, r in enumerate(group):
             r.row = row0 + i
-        toks = self.model.prefill_slot(st, row0, collate_requests([r.inputs for r in group]) if n > 1 else group[0].inputs)
+        inputs = collate_requests([r.inputs for r in group]) if n > 1 else group[0].inputs
+        if any(r.sampling is not None for r in group):
+            # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
+            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
+            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True)
+            toks = self.model.sample_logits(st, logits, row0)
+        else:
+            if getattr(st, "sample_rows", None) is not None:     # a sampled request had these rows before: greedy records now
+                self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
+            toks = self.model.prefill_slot(st, row0, inputs)
         first = toks.reshape(-1).tolist()
         if min(first) < 0:
             raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
@@ -259,7 +277,9 @@ class ContinuousEngine:
         if not active:
             return 0
         g = self.model.decode_graph(self.st)
-        _, tok = self.model.greedy_step(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
+        # the sampled replay while any active row samples (its greedy rows take the arg-max there too), the greedy one otherwise
+        replay = self.model.sample_step if any(r.sampling is not None for r in active) else self.model.greedy_step
+        _, tok = replay(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
         rows = tok.reshape(-1).tolist()                          # ONE D2H copy per step (the reference's mx.eval)
         self.steps += 1
         poisoned = False
@@ -302,18 +322,44 @@ class ContinuousEngine:
                 stop_event.wait(idle_sleep)
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)
 
 
-def _generate_text(engine, processor, prompts, images, max_tokens, timeout):
+_GREEDY = (0.0, 0, 1.0, 0)
+
+
+def _sampling_row(sampling):
+    """submit's `sampling` dict -> one checked (temperature, top_k, top_p, seed) tuple; None stays None (greedy)."""
+    if sampling is None:
+        return None
+    if isinstance(sampling, tuple):
+        sampling = dict(zip(("temperature", "top_k", "top_p", "seed"), sampling))
+    unknown = set(sampling) - {"temperature", "top_k", "top_p", "seed"}
+    if unknown:
+        raise ValueError(f"unknown sampling settings {sorted(unknown)}")
+    from .sampling import rows
+    return rows(1, sampling.get("temperature", 0.0), sampling.get("top_k", 0), sampling.get("top_p", 1.0), sampling.get("seed"))[0]
+
+
+def _pack(rows_, counter=0):
+    from .sampling import pack
+    return pack(rows_, counter)
+
+
+def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None):
+    """sampling: None, or one settings dict per prompt (engine.submit)."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     images = images if images is not None else [None] * len(prompts)
+    if sampling is not None and len(sampling) != len(prompts):
+        raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
     reqs = []
-    for p, im in zip(prompts, images):
+    for i, (p, im) in enumerate(zip(prompts, images)):
         text, imgs = api._apply_chat_template(p, im, False)
-        reqs.append(engine.submit(processor(text, imgs) if imgs is not None else processor(text), max_tokens))
+        inputs = processor(text, imgs) if imgs is not None else processor(text)
+        reqs.append(engine.submit(inputs, max_tokens) if sampling is None or sampling[i] is None else
+                    engine.submit(inputs, max_tokens, sampling=sampling[i]))
     out = []
     try:
         for r in reqs:
@@ -340,11 +386,11 @@ class RegimeRouter:
         self.engines = list(engines)
         self.processor = self.engines[0].processor
 
-    def submit(self, inputs, max_tokens):
+    def submit(self, inputs, max_tokens, sampling=None):
         S = int(np.asarray(inputs["input_ids"]).shape[-1])
         for e in self.engines:
             if e.accepts(S, int(max_tokens)):
-                return e.submit(inputs, max_tokens)
+                return e.submit(inputs, max_tokens) if sampling is None else e.submit(inputs, max_tokens, sampling=sampling)
         r = Request(inputs, max_tokens)
         r.fail(ValueError(f"prompt {S} + max_tokens {max_tokens} fits no engine window"))
         return r
@@ -362,5 +408,5 @@ class RegimeRouter:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)

@@ -82,14 +82,14 @@ class EngineFleet:
             if force or not self.closed:
                 _send(msg, rank, self.down)
 
-    def submit(self, inputs, max_tokens):
+    def submit(self, inputs, max_tokens, sampling=None):
         with self.lock:
             self.local = [h for h in self.local if not h.done.is_set()]
             loads = [len(self.local)] + self.load[1:]
             dst = min(range(self.world), key=lambda r: (loads[r], r))
             self.sent[dst] += 1
             if dst == 0:
-                h = self.engine.submit(inputs, max_tokens)
+                h = self.engine.submit(inputs, max_tokens) if sampling is None else self.engine.submit(inputs, max_tokens, sampling=sampling)
                 self.local.append(h)
                 return h
             h = RemoteRequest(inputs, max_tokens)
@@ -98,7 +98,7 @@ class EngineFleet:
             self.pending[h.rid] = h
             self.load[dst] += 1
         try:
-            self._send_to(dst, ("submit", h.rid, inputs, int(max_tokens)))
+            self._send_to(dst, ("submit", h.rid, inputs, int(max_tokens), sampling))
         except Exception as e:                                   # noqa: BLE001  the request never left: fail it here
             with self.lock:
                 self.pending.pop(h.rid, None)
@@ -146,8 +146,8 @@ class EngineFleet:
     def serve_forever(self, stop_event, idle_sleep=0.002):
         self.engine.serve_forever(stop_event, idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""
@@ -195,7 +195,7 @@ def worker(engine, groups, poll_s=0.002):
         if msg[0] == "stop":
             break
         if msg[0] == "submit":
-            h = engine.submit(msg[2], msg[3])
+            h = engine.submit(msg[2], msg[3]) if msg[4] is None else engine.submit(msg[2], msg[3], sampling=msg[4])
             with lock:
                 live[msg[1]] = h
         elif msg[0] == "cancel":

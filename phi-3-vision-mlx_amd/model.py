@@ -892,6 +892,86 @@ class Phi3VModel:
         g["host_tok"] = g["next_tok"].view(-1, 1)
         return g["logits"].view(st.B, 1, -1), g["host_tok"]
 
+    # ------------------------------------------------------------------ seeded sampling (include/p3v.h: p3v_sample_row_t)
+    @_on_device
+    def set_sampling(self, st, records, row0=0):
+        """Write the per-row sampling records (sampling.pack: int32 [n, 6] on the host) of rows row0 .. row0+n-1 of a state (one
+        H2D copy, outside any graph).  Rows never written are greedy (temperature 0).  The records live with the state's decode
+        graphs and are read -- and their counters advanced -- by `sample_logits` and every replay of `sample_step`."""
+        if getattr(st, "sample_rows", None) is None:
+            st.sample_rows = torch.zeros((st.B, 6), dtype=I32, device=self.device)
+        st.sample_rows[row0:row0 + records.shape[0]].copy_(records)
+
+    @_on_device
+    def sample_logits(self, st, logits, row0=0):
+        """The first token of rows row0 .. row0+n-1 from their prefill logits ([n, L, V] or [n, V]) under their records (the
+        draw index is the record's counter, 0 after `set_sampling(..., counter=0)`).  int32 [n, 1] on the device."""
+        last = logits[:, -1, :] if logits.dim() == 3 else logits
+        return ops.sample(last, st.sample_rows[row0:row0 + last.shape[0]])[:, None]
+
+    @_on_device
+    def sample_step(self, token, cache):
+        """One SAMPLED decode step through its captured graph: `greedy_step` with each row's token drawn under its record
+        (`set_sampling`) instead of the arg-max.  The sampled graph is a second capture over the greedy graph's loop-state buffers
+        (built on first use): greedy and sampled replays may alternate on one state.  Returns (logits [B,1,V], next_token [B,1])."""
+        st = cache[0].state
+        if getattr(st, "sample_rows", None) is None:
+            raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
+        if st.offset + 1 > st.T:
+            raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
+        if st.epoch != self.epoch:
+            st.graphs.clear()
+            st.epoch = self.epoch
+        g = st.graphs.get("greedy")
+        if g is not None and st.offset < g["bufs"].get("past_lb", -1):
+            g = None
+        if g is None:
+            g = st.graphs["greedy"] = self._build_decode_graph(st)
+            g["host_tok"] = None
+        if g["host_tok"] is None or token is not g["host_tok"]:
+            g["tok"].copy_(token.reshape(-1).to(self.device, I32))
+        g["d_past"].fill_(st.offset) if g.get("synced_offset") != st.offset else None
+        if "sample_graph" not in g:
+            g["sample_graph"] = self._build_sample_graph(st, g)
+        g["sample_graph"].launch()
+        g["n_replays"] = g.get("n_replays", 0) + 1              # (one history column per replay, greedy or sampled)
+        st.offset += 1
+        g["synced_offset"] = st.offset
+        g["host_tok"] = g["next_tok"].view(-1, 1)
+        return g["logits"].view(st.B, 1, -1), g["host_tok"]
+
+    def _build_sample_graph(self, st, g):
+        """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
+        through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
+        The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it."""
+        cfg, w, B, dev, bufs = self.cfg, self.w, st.B, self.device, g["bufs"]
+
+        def step():
+            self._layers(g["x"], st, B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
+                         step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
+            self._proj(g["x"], "lm_head.weight", norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])
+            ops.sample_step_end(g["logits"], st.sample_rows, g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
+        torch.cuda.synchronize()
+        saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
+        saved_rows = st.sample_rows.clone()
+        g["gemm_ws_sampled"] = {}
+        with ops.owned_gemm_workspace(g["gemm_ws_sampled"], frozen=False):
+            step()                                               # warm-up run
+        torch.cuda.synchronize()
+        graph = ops.Graph()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), ops.owned_gemm_workspace(g["gemm_ws_sampled"], frozen=True):
+            graph.begin()
+            step()
+            graph.end()
+        torch.cuda.current_stream().wait_stream(side)
+        for k, v in saved.items():
+            g[k].copy_(v)
+        st.sample_rows.copy_(saved_rows)
+        torch.cuda.synchronize()
+        return graph
+
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,
                  max_tokens=0, advance_offset=None, n_beam=1, full_logits=None):

@@ -593,6 +593,34 @@ def step_end(logits, next_tok, tok, history, d_step, d_past, ticket):
                                  history.shape[1], _stream()), "step_end")
 
 
+def _chk_rows(rows_params, B):
+    _chk(rows_params, I32, "rows_params")
+    if rows_params.shape != (B, 6):                             # p3v_sample_row_t: 24 bytes per row
+        raise ValueError(f"rows_params: expected int32 [{B}, 6] records, got {tuple(rows_params.shape)}")
+
+
+def sample(logits2d, rows_params, out=None):
+    """Seeded sampling (include/p3v.h: p3v_sample): one token per bf16 row under that row's record (temperature, top_k, top_p,
+    seed, counter); every record's counter advances by one.  Rows may be strided (logits[:, -1, :])."""
+    if not logits2d.is_cuda:
+        raise RuntimeError("logits: expected a device tensor (the hot path has no CPU fallback)")
+    if logits2d.dtype != BF16 or logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError("logits: expected bf16 [rows, n] with unit stride along n")
+    rows, n = logits2d.shape
+    _chk_rows(rows_params, rows)
+    out = torch.empty((rows,), dtype=I32, device=logits2d.device) if out is None else out
+    L.check(L.lib().p3v_sample(_p(logits2d), logits2d.stride(0), _p(rows_params), _p(out), rows, n, _stream()), "sample")
+    return out
+
+
+def sample_step_end(logits, rows_params, next_tok, tok, history, d_step, d_past, ticket):
+    """Tail of a replayed SAMPLED step: `step_end` with the token drawn under each row's record (one launch)."""
+    B, n = logits.shape[0], logits.shape[-1]
+    _chk_rows(rows_params, B)
+    L.check(L.lib().p3v_sample_step_end(_p(logits), _p(rows_params), _p(next_tok), _p(tok), _p(history), _p(d_step), _p(d_past),
+                                        _p(ticket), B, n, history.shape[1], _stream()), "sample_step_end")
+
+
 def store_token(tok, history, d_step, tok_next=None):
     B, max_steps = history.shape
     L.check(L.lib().p3v_store_token(_p(tok), _p(history), _p(d_step), _p(tok_next), B, max_steps, _stream()), "store_token")

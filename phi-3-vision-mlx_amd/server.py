@@ -2,6 +2,8 @@
 
     POST /v1/completions   {"prompt": str | [str, ...], "max_tokens": int (default 512)}
       -> 200 {"model": "phi-3-vision", "responses": [str, ...]}            anything else -> 404
+    (extension: "temperature" (default 0 = greedy), "top_k" (0 = off), "top_p" (1 = off), "seed" (default: 64 random bits) --
+     seeded sampling, include/p3v.h; a sampled response adds "seeds": [one per prompt], which reproduce it.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -34,11 +36,32 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling")
 
-    def __init__(self, prompts, max_tokens, images=None):
-        self.prompts, self.max_tokens, self.images = prompts, max_tokens, images
+    def __init__(self, prompts, max_tokens, images=None, sampling=None):
+        self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
         self.done, self.result, self.error = threading.Event(), None, None
+
+
+SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "seed")
+
+
+def parse_sampling(request, n_prompts):
+    """The sampling fields of a request body -> None (greedy: none given, or temperature 0) or one settings dict per prompt
+    {"temperature", "top_k", "top_p", "seed"} with a concrete seed: the client's (row b of the request gets seed + b), or 64
+    random bits drawn here, before the request is queued -- so its text does not depend on who shares its batch.  ValueError
+    (-> 400) on a bad type or range, whether or not temperature is 0."""
+    from .sampling import rows
+    if not any(f in request for f in SAMPLING_FIELDS):
+        return None
+    t, k, p, seed = (request.get("temperature", 0.0), request.get("top_k", 0), request.get("top_p", 1.0), request.get("seed"))
+    for name, v in (("temperature", t), ("top_k", k), ("top_p", p), ("seed", seed)):
+        if isinstance(v, (list, tuple, dict)):
+            raise ValueError(f"{name} must be a single value")
+    recs = rows(n_prompts, t, k, p, seed)
+    if recs[0][0] == 0.0:
+        return None
+    return [dict(temperature=r[0], top_k=r[1], top_p=r[2], seed=r[3]) for r in recs]
 
 
 class ImagePolicy:
@@ -117,7 +140,10 @@ class EngineQueue:
     """Single consumer in front of a non-re-entrant `generate_fn(prompts: list[str], max_tokens) -> str | list[str]`."""
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
-                 length_fn=None, window_tokens=4096, device=None):
+                 length_fn=None, window_tokens=4096, device=None, sharded_fn=None):
+        # sharded_fn(prompts, images) -> True when generate_fn would run that request on the batch-sharded path (dist.py), which
+        # does not sample: the handler answers 400 to a sampled request bound there
+        self.sharded_fn = sharded_fn
         self.generate_fn, self.max_batch, self.window_s = generate_fn, max_batch, window_s
         self.merge, self.max_tokens_cap, self.timeout_s = merge, max_tokens_cap, timeout_s
         self.length_fn, self.window_tokens, self.device = length_fn, window_tokens, device
@@ -127,8 +153,8 @@ class EngineQueue:
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images)
+    def submit(self, prompts, max_tokens, images=None, sampling=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -163,7 +189,7 @@ class EngineQueue:
                 self.jobs.put(None)
                 break
             if job.images is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
-                    and self._regime(job.prompts, job.max_tokens) == regime:
+                    and self._regime(job.prompts, job.max_tokens) == regime and (job.sampling is None) == (first.sampling is None):
                 group.append(job)
                 n += len(job.prompts)
             else:
@@ -183,8 +209,12 @@ class EngineQueue:
             group = self._collect(first)
             flat = [p for j in group for p in j.prompts]
             try:
-                out = self.generate_fn(flat, first.max_tokens) if first.images is None else \
-                    self.generate_fn(flat, first.max_tokens, first.images)
+                if first.sampling is not None:                  # (sampled jobs merge only with sampled jobs: one record per row)
+                    out = self.generate_fn(flat, first.max_tokens, first.images, sampling=[r for j in group for r in j.sampling])
+                elif first.images is None:
+                    out = self.generate_fn(flat, first.max_tokens)
+                else:
+                    out = self.generate_fn(flat, first.max_tokens, first.images)
                 out = [out] if isinstance(out, str) else list(out)
                 if len(out) != len(flat):
                     raise RuntimeError(f"generate returned {len(out)} texts for {len(flat)} prompts")
@@ -230,15 +260,26 @@ def make_handler(engine, image_policy=None):
                         raise ValueError("images must list one entry (or null) per prompt")
                     images = [decode_image(i, image_policy) for i in images]      # fetched + decoded in THIS thread
                     images = None if all(i is None for i in images) else images
+                sampling = parse_sampling(request, len(prompts))
+                sharded = getattr(engine, "sharded_fn", None)
+                if sampling is not None and sharded is not None and sharded(prompts, images):
+                    raise ValueError("sampling is not available on the batch-sharded path (image requests and process groups of "
+                                     "the queue server); run the server with --continuous to sample, or send temperature 0")
             except (ValueError, TypeError, AttributeError, OSError) as e:
                 self._send(400, {"error": str(e)})
                 return
             try:
-                responses = engine.submit(prompts, max_tokens, images) if images is not None else engine.submit(prompts, max_tokens)
+                if sampling is not None:
+                    responses = engine.submit(prompts, max_tokens, images, sampling=sampling)
+                else:
+                    responses = engine.submit(prompts, max_tokens, images) if images is not None else engine.submit(prompts, max_tokens)
             except Exception as e:              # noqa: BLE001
                 self._send(500, {"error": f"{type(e).__name__}: {e}"})
                 return
-            self._send(200, {"model": MODEL_NAME, "responses": responses})
+            out = {"model": MODEL_NAME, "responses": responses}
+            if sampling is not None:
+                out["seeds"] = [r["seed"] for r in sampling]
+            self._send(200, out)
 
         def log_message(self, *args):           # quiet
             pass
@@ -263,8 +304,11 @@ class ContinuousBackend:
         self.thread = threading.Thread(target=engine.serve_forever, args=(self.stop,), daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None):
-        return self.engine.generate(prompts, images, max(1, min(int(max_tokens), self.max_tokens_cap)), self.timeout_s)
+    def submit(self, prompts, max_tokens, images=None, sampling=None):
+        mt = max(1, min(int(max_tokens), self.max_tokens_cap))
+        if sampling is None:
+            return self.engine.generate(prompts, images, mt, self.timeout_s)
+        return self.engine.generate(prompts, images, mt, self.timeout_s, sampling=sampling)
 
     def close(self):
         self.stop.set()
@@ -307,8 +351,15 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
                 front.close()
         return
 
-    def generate_fn(prompts, max_tokens, images=None):
+    def sharded_fn(prompts, images):
         import torch.distributed as dist
+        return images is not None or (dist.is_available() and dist.is_initialized())
+
+    def generate_fn(prompts, max_tokens, images=None, sampling=None):
+        import torch.distributed as dist
+        if sampling is not None:                                     # (the handler kept sampled requests off the sharded path)
+            kw = {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
+            return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, **kw)
         if images is not None or (dist.is_available() and dist.is_initialized() and len(prompts) > 1):
             # mixed image + text requests -- and text-only batches whenever a process group exists -- go through the
             # batch-sharded path (dist.py: one left-padded batch per rank; world size 1 = this GPU alone)
@@ -321,7 +372,7 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return len(processor.tokenizer(_apply_chat_template(prompt, None, False)[0]).input_ids)
 
     httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
-                          image_policy=image_policy)
+                          image_policy=image_policy, sharded_fn=sharded_fn)
     print(f"Starting server on port {port}")
     try:
         httpd.serve_forever()
