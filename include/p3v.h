@@ -385,6 +385,41 @@ int p3v_lora_down(const uint16_t* x, const float* lora_a, float* t, int M, int K
 int p3v_lora_up(const uint16_t* y, const float* t, const float* lora_b, float scale, int epilogue,
                 const uint16_t* resid, uint16_t* out, int M, int N, int r, void* stream);
 
+/* ---- adapter bank: the per-row ("gathered") forms of the pair above.  Added after round 6, no version change.
+ * N adapters stay resident beside one set of frozen weights; every row of a call names the one it wants.
+ * A BANK TABLE per adapted projection (device memory): one p3v_lora_entry_t per bank slot -- lora_a [K, rank] and
+ * lora_b [rank, N] fp32, rank 1..64 (0, or a null pointer: this adapter leaves this projection alone), scale.
+ * A ROW TABLE row_adapter[M] (device memory, int32): the bank slot of each row; -1 (or any value outside 0..n_slots-1) = no
+ * adapter.  Both tables are READ BY THE KERNELS and are not launch arguments: a captured step keeps working when rows change
+ * adapter, or when entries change, between replays.
+ * The rule, for row m with entry e = table[row_adapter[m]] and rank r = min(e.rank, r_max):
+ *   h      = x[m], or with norm_w: RMSNorm(x[m]) * norm_w with exactly the arithmetic and rounding of p3v_rmsnorm
+ *            (computed inside the launch: the frozen projection keeps its own fused norm, no materialised copy is needed);
+ *   K is cut into S = p3v_lora_rows_slices(K) = ceil(K / P3V_LORA_SLICE_K) slices, one workgroup per (row, slice):
+ *   t[m, s, j] = sum over the slice's k of h[k] * e.lora_a[k, j]          fp32, j < r   (p3v_lora_down_rows; t is [M, S, r_max])
+ *   T[j]       = t[m, 0, j] + t[m, 1, j] + .. + t[m, S-1, j]              fp32, in slice order   (prologue of p3v_lora_up_rows)
+ *   v[n]       = bf16(y[m, n] + e.scale * sum_{j < r} T[j] * e.lora_b[j, n])   j ascending
+ *   out[m]     = epilogue(v) as p3v_lora_up (none / residual / SiLU * up, same per-op rounding).
+ * A row without an adapter (slot -1, rank 0) does no work in the down launch and gets epilogue(y[m]) with v = y[m] bit for
+ * bit.  The slice boundaries and every summation order depend on K and r alone: a row's output bits depend only on its own
+ * input, its own entry and (K, N, epilogue) -- not on M, on the row's position, on other rows' slots, or on eager versus
+ * graph execution.  Any M >= 0 (decode rows and prompt-sized token rows), mixed ranks within one call.
+ * P3V_ERR_ARG: a null pointer, r_max outside 1..64, n_slots < 1, norm_w with K % 8 != 0.
+ * Call sites: model.py `_proj` with an adapter bank attached (set_adapter_bank / set_row_adapters). */
+#define P3V_LORA_SLICE_K 256
+typedef struct {
+  const float* lora_a;
+  const float* lora_b;
+  int32_t rank;
+  float scale;
+} p3v_lora_entry_t;
+int p3v_lora_rows_slices(int K);
+int p3v_lora_down_rows(const uint16_t* x, const uint16_t* norm_w /* or NULL */, float eps, const p3v_lora_entry_t* table,
+                       const int32_t* row_adapter, float* t, int M, int K, int r_max, int n_slots, void* stream);
+int p3v_lora_up_rows(const uint16_t* y, const float* t, const p3v_lora_entry_t* table, const int32_t* row_adapter,
+                     int epilogue, const uint16_t* resid, uint16_t* out, int M, int N, int K, int r_max, int n_slots,
+                     void* stream);
+
 /* ---- decode-step helpers (device-resident loop state for graph replay) */
 int p3v_add_i32(int32_t* x, int n, int delta, void* stream);
 /* history[b, *d_step] = tok[b]; if tok_next != NULL also tok_next[b] = tok[b] (feeds the next replayed step) */

@@ -95,6 +95,7 @@ class SampleRow(C.Structure):
                 ("counter", i32)]
 
 
+LORA_SLICE_K, LORA_MAX_RANK = 256, 64            # P3V_LORA_SLICE_K; largest rank of p3v_lora_* (include/p3v.h)
 SAMPLE_MAX_N, SAMPLE_MAX_ROWS = 32768, 1024      # p3v_sample / p3v_sample_step_end: larger -> P3V_ERR_UNSUPPORTED
 # name -> (restype, argtypes); must list every symbol include/p3v.h declares
 SIGNATURES = {
@@ -146,6 +147,9 @@ SIGNATURES = {
     "p3v_hd_preprocess": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "p3v_lora_down": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "p3v_lora_up": (i32, [vp, vp, vp, f32, i32, vp, vp, i32, i32, i32, vp]),
+    "p3v_lora_rows_slices": (i32, [i32]),
+    "p3v_lora_down_rows": (i32, [vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "p3v_lora_up_rows": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p3v_step_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
     "p3v_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_sample": (i32, [vp, i64, vp, vp, i32, i32, vp]),

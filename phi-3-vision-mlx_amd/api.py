@@ -241,6 +241,23 @@ def _attach_adapter(model, adapter_path, model_path=None):
     model.set_adapters(resolve_adapter(model.cfg, lora_cfg, tensors))
 
 
+def load_adapters(preload, adapters, model_path=None):
+    """Attach an adapter BANK to a loaded model: {name: adapter directory} in the reference's format (adapter_config.json +
+    adapters.safetensors, what `train_lora` writes).  All of them stay resident beside the one set of frozen weights;
+    `generate(..., adapter=name)`, `engine.submit(..., adapter=name)` and the server's "adapter" field pick one per request, rows
+    with different adapters (or none) share one captured decode step (model.set_adapter_bank).  `model_path`: warn, as `load`
+    does for its one adapter, when an adapter was trained for another checkpoint.  Returns the names."""
+    model = preload[0]
+    bank = {}
+    for name, path in dict(adapters).items():
+        lora_cfg, tensors = load_adapter(path)
+        if model_path is not None and lora_cfg.get("model_path") != model_path:
+            print(f"WARNING: LoRA trained for {lora_cfg.get('model_path')} is being used with {model_path}")
+        bank[name] = resolve_adapter(model.cfg, lora_cfg, tensors)
+    model.set_adapter_bank(bank)
+    return list(model.adapter_names)
+
+
 def load_synthetic(blind_model=False, tiny=False, seed=0, device=None, std_scale=1.0, adapter_path=None, lm_head_spread=0.0,
                    lm_head_seed=0, outliers=None, residual_scale=None, **kwargs):
     """Seeded random weights of the real (or tiny) architecture -- no checkpoint needed.
@@ -412,13 +429,21 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
 
 
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
-              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None):
-    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  temperature > 0 samples instead (include/p3v.h:
+              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None):
+    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  adapter: the name of one adapter of the model's bank
+    (`load_adapters`) for every row, or one name / None per prompt of a batched call; None -- the default -- is the base model.  temperature > 0 samples instead (include/p3v.h:
     p3v_sample_row_t; each of temperature / top_k / top_p / seed a scalar or a per-row list, see sampling.rows); temperature 0
     -- the default -- is today's greedy path, launch for launch."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     B = len(prompt) if isinstance(prompt, list) else 1
+    kw_adapter = {}
+    if adapter is not None:
+        from .engine import _check_adapter, adapter_list
+        names = adapter_list(adapter, B)
+        for a in names:
+            _check_adapter(a, list(getattr(model, "adapter_names", None) or []))
+        kw_adapter = {"row_adapters": names}
     rows = sampling_mod.rows(B, temperature, top_k, top_p, seed)
     sampled = None if sampling_mod.greedy(rows) else rows
     logit_stopper = LogitStopper(max_tokens, early_stop)
@@ -427,7 +452,7 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     mask, pids = dict_input.get("mask", None), dict_input.get("pids", None)
     token_stopper = TokenStopper(processor, dict_input["input_ids"].shape[0])
     tic = Tic()
-    logits, cache = model(**dict_input, max_tokens=max_tokens)
+    logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter)
     if sampled is None:
         token = model_ops.argmax(_last_logits(logits))[:, None]
     else:                                                       # draw 0 of every row: from the prefill logits
@@ -453,15 +478,16 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
-             apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None):
-    """reference phi_3_vision_mlx.py:1324-1374, plus seeded sampling (`_generate`; temperature 0 = greedy, the default)."""
+             apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None):
+    """reference phi_3_vision_mlx.py:1324-1374, plus seeded sampling (`_generate`; temperature 0 = greedy, the default) and
+    per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
-                     top_k=top_k, top_p=top_p, seed=seed)
+                     top_k=top_k, top_p=top_p, seed=seed, adapter=adapter)
 
 
 # ----------------------------------------------------------------------------- choose

@@ -58,10 +58,11 @@ def _set_device(device):
 
 
 class Request:
-    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling")
+    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter")
 
-    def __init__(self, inputs, max_tokens, sampling=None):
+    def __init__(self, inputs, max_tokens, sampling=None, adapter=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
+        self.adapter = adapter                                   # None (the base model) or the name of an adapter of the model's bank
         self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
         self.tokens, self.row, self.error = [], None, None
@@ -103,17 +104,25 @@ class ContinuousEngine:
             return False
         return (S + max_tokens > ROPE_WINDOW) == self.long_rope
 
-    def submit(self, inputs, max_tokens, sampling=None):
+    def adapter_names(self):
+        """Names of the model's adapter bank (model.set_adapter_bank); empty without one."""
+        return list(getattr(self.model, "adapter_names", None) or [])
+
+    def submit(self, inputs, max_tokens, sampling=None, adapter=None):
         """inputs: a B = 1 `processor(text[, images])` result.  Returns the Request; wait on `.done`, read `.tokens`.
         sampling: None (greedy) or {"temperature", "top_k", "top_p", "seed"} (missing keys: 0, 0, 1.0, 64 random bits; see
-        sampling.rows) -- the request's tokens are then drawn under its own record, whoever shares the batch."""
+        sampling.rows) -- the request's tokens are then drawn under its own record, whoever shares the batch.
+        adapter: None (the base model) or the name of one adapter of the model's bank: the request's row runs with it, next to
+        rows with other adapters or none, in the one captured step.  An unknown name fails the handle at once (ValueError);
+        nothing is queued."""
         try:
             rec = _sampling_row(sampling)
+            _check_adapter(adapter, self.adapter_names())
         except ValueError as e:
             r = Request(inputs, max_tokens)
             r.fail(e)
             return r
-        r = Request(inputs, max_tokens, rec)
+        r = Request(inputs, max_tokens, rec, adapter)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -208,6 +217,9 @@ class ContinuousEngine:
         for i, r in enumerate(group):
             r.row = row0 + i
         inputs = collate_requests([r.inputs for r in group]) if n > 1 else group[0].inputs
+        if self.adapter_names():
+            # the rows' adapters (None -> -1: a refilled row must not keep its last occupant's) BEFORE their prefill reads them
+            self.model.set_row_adapters(st, [r.adapter for r in group], row0)
         if any(r.sampling is not None for r in group):
             # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
@@ -322,11 +334,42 @@ class ContinuousEngine:
                 stop_event.wait(idle_sleep)
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
+
+
+def _check_adapter(adapter, known):
+    if adapter is None:
+        return
+    if not isinstance(adapter, str):
+        raise ValueError(f"adapter must be a name (string) or None, got {type(adapter).__name__}; known adapters: {known}")
+    if adapter not in known:
+        raise ValueError(f"unknown adapter {adapter!r}; known adapters: {known}")
+
+
+def adapter_list(adapter, n):
+    """`adapter` argument of a text-level call -> one name / None per prompt: a name (or None) serves every prompt, a list gives
+    one per prompt."""
+    if adapter is None or isinstance(adapter, str):
+        return [adapter] * n
+    if not isinstance(adapter, (list, tuple)):
+        raise ValueError(f"adapter must be a name, None, or a list of one per prompt, got {type(adapter).__name__}")
+    if len(adapter) != n:
+        raise ValueError(f"adapter: {len(adapter)} names for {n} prompts")
+    return list(adapter)
+
+
+def _submit(engine, inputs, max_tokens, sampling, adapter):
+    """submit with only the keywords in use (an engine-like object without them keeps working for plain requests)."""
+    kw = {}
+    if sampling is not None:
+        kw["sampling"] = sampling
+    if adapter is not None:
+        kw["adapter"] = adapter
+    return engine.submit(inputs, max_tokens, **kw)
 
 
 def _sampling_row(sampling):
@@ -347,19 +390,19 @@ def _pack(rows_, counter=0):
     return pack(rows_, counter)
 
 
-def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None):
-    """sampling: None, or one settings dict per prompt (engine.submit)."""
+def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None):
+    """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     images = images if images is not None else [None] * len(prompts)
     if sampling is not None and len(sampling) != len(prompts):
         raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
+    adapters = adapter_list(adapter, len(prompts))
     reqs = []
     for i, (p, im) in enumerate(zip(prompts, images)):
         text, imgs = api._apply_chat_template(p, im, False)
         inputs = processor(text, imgs) if imgs is not None else processor(text)
-        reqs.append(engine.submit(inputs, max_tokens) if sampling is None or sampling[i] is None else
-                    engine.submit(inputs, max_tokens, sampling=sampling[i]))
+        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i]))
     out = []
     try:
         for r in reqs:
@@ -386,11 +429,14 @@ class RegimeRouter:
         self.engines = list(engines)
         self.processor = self.engines[0].processor
 
-    def submit(self, inputs, max_tokens, sampling=None):
+    def adapter_names(self):
+        return self.engines[0].adapter_names()
+
+    def submit(self, inputs, max_tokens, sampling=None, adapter=None):
         S = int(np.asarray(inputs["input_ids"]).shape[-1])
         for e in self.engines:
             if e.accepts(S, int(max_tokens)):
-                return e.submit(inputs, max_tokens) if sampling is None else e.submit(inputs, max_tokens, sampling=sampling)
+                return _submit(e, inputs, max_tokens, sampling, adapter)
         r = Request(inputs, max_tokens)
         r.fail(ValueError(f"prompt {S} + max_tokens {max_tokens} fits no engine window"))
         return r
@@ -408,5 +454,5 @@ class RegimeRouter:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)

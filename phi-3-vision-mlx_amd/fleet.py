@@ -16,7 +16,7 @@ one receiver thread per source takes them in order).  RCCL is not involved; the 
 import threading
 import time
 
-from .engine import Request, _generate_text
+from .engine import Request, _check_adapter, _generate_text, _submit
 
 _ERRORS = {"ValueError": ValueError, "TimeoutError": TimeoutError, "TypeError": TypeError}   # what the HTTP handler tells apart
 
@@ -82,14 +82,24 @@ class EngineFleet:
             if force or not self.closed:
                 _send(msg, rank, self.down)
 
-    def submit(self, inputs, max_tokens, sampling=None):
+    def adapter_names(self):
+        """The bank every rank loaded at start-up (rank 0's own engine answers for all)."""
+        return self.engine.adapter_names()
+
+    def submit(self, inputs, max_tokens, sampling=None, adapter=None):
+        try:
+            _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
+        except ValueError as e:
+            h = Request(inputs, max_tokens)
+            h.fail(e)
+            return h
         with self.lock:
             self.local = [h for h in self.local if not h.done.is_set()]
             loads = [len(self.local)] + self.load[1:]
             dst = min(range(self.world), key=lambda r: (loads[r], r))
             self.sent[dst] += 1
             if dst == 0:
-                h = self.engine.submit(inputs, max_tokens) if sampling is None else self.engine.submit(inputs, max_tokens, sampling=sampling)
+                h = _submit(self.engine, inputs, max_tokens, sampling, adapter)
                 self.local.append(h)
                 return h
             h = RemoteRequest(inputs, max_tokens)
@@ -98,7 +108,7 @@ class EngineFleet:
             self.pending[h.rid] = h
             self.load[dst] += 1
         try:
-            self._send_to(dst, ("submit", h.rid, inputs, int(max_tokens), sampling))
+            self._send_to(dst, ("submit", h.rid, inputs, int(max_tokens), sampling, adapter))
         except Exception as e:                                   # noqa: BLE001  the request never left: fail it here
             with self.lock:
                 self.pending.pop(h.rid, None)
@@ -146,8 +156,8 @@ class EngineFleet:
     def serve_forever(self, stop_event, idle_sleep=0.002):
         self.engine.serve_forever(stop_event, idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""
@@ -195,7 +205,7 @@ def worker(engine, groups, poll_s=0.002):
         if msg[0] == "stop":
             break
         if msg[0] == "submit":
-            h = engine.submit(msg[2], msg[3]) if msg[4] is None else engine.submit(msg[2], msg[3], sampling=msg[4])
+            h = _submit(engine, msg[2], msg[3], msg[4], msg[5] if len(msg) > 5 else None)
             with lock:
                 live[msg[1]] = h
         elif msg[0] == "cancel":

@@ -164,6 +164,10 @@ class Phi3VModel:
         self.adapters = {}                           # weight key -> (lora_a, lora_b, scale), see set_adapters
         self._lora_tmp = {}                          # decode-sized (M <= 16) adapter scratch: captured graphs point at it
         self._lora_flat = None                       # ONE grow-only scratch for prefill-sized calls (not graph-captured)
+        self.adapter_names = []                      # bank slot -> name (set_adapter_bank); a row names its slot in st.row_adapter
+        self._bank = {}                              # weight key -> (bank table int64 [n_slots, 3], r_max), union of the adapters' targets
+        self._bank_keep = []                         # the uploaded lora_a / lora_b tensors the tables point at
+        self._rows_cur = None                        # row table of the _layers call in flight (int32 [M] on the device)
         # A long-lived owner that may share the GPU with other streams / processes (server.py) sets this: the decode step then
         # uses no launch that needs all of its workgroups resident at once (the fused attention + o_proj launch, the in-launch
         # split-KV merge on grids larger than the machine) -- ADVICE r04.  One-shot generate() on an exclusive GPU keeps them.
@@ -196,14 +200,18 @@ class Phi3VModel:
         self._deq = torch.empty(n_max, dtype=BF16, device=self.device)      # one dequantised matrix (prefill GEMM scratch)
 
     # ------------------------------------------------------------------ LoRA adapters (use_adapter=True)
-    @_on_device
     def set_adapters(self, adapters):
         """Attach LoRA adapters: {"model.layers.<i>.<target>.weight": (lora_a [in,r] f32, lora_b [r,out] f32, scale)}
         (weights.resolve_adapter).  An adapted projection runs unfused: materialised RMSNorm -> frozen projection with a
         plain epilogue -> p3v_lora_down / p3v_lora_up, which carries the residual / SiLU*up epilogue (phi.py:129-133)."""
+        if adapters and self._bank:
+            raise ValueError("this model carries an adapter bank (set_adapter_bank): detach it before set_adapters -- one or the other")
+        self._set_adapters(adapters)
+
+    @_on_device
+    def _set_adapters(self, adapters):
         for k, (a, b, _) in adapters.items():
-            w = self.w.get(k)
-            shape = w.shape if w is not None else (self.w8[k][0].shape if k in self.w8 else (self.w4[k][0].shape[0], self.w4[k][0].shape[1] * 8))
+            shape = self._weight_shape(k)
             if tuple(a.shape[:1]) != (shape[1],) or tuple(b.shape[1:]) != (shape[0],):
                 raise ValueError(f"LoRA shapes {tuple(a.shape)} x {tuple(b.shape)} do not fit {k} {tuple(shape)}")
         self.adapters = {k: (a.to(self.device, F32).contiguous(), b.to(self.device, F32).contiguous(), float(s))
@@ -213,6 +221,116 @@ class Phi3VModel:
             st.graphs.clear()
         self._lora_tmp, self._lora_flat = {}, None
         self._prefill_graphs.clear()
+
+    def _weight_shape(self, k):
+        """(out, in) of a projection in whichever format the model holds it."""
+        if k in self.w:
+            return tuple(self.w[k].shape)
+        if k in self.w8:
+            return tuple(self.w8[k][0].shape)
+        return (self.w4[k][0].shape[0], self.w4[k][0].shape[1] * 8)
+
+    # ------------------------------------------------------------------ adapter bank: N resident adapters, one per row
+    def set_adapter_bank(self, bank):
+        """Attach N LoRA adapters beside the one set of frozen weights: {name: weights.resolve_adapter(...) result}.  Bank slot i is
+        the i-th name (`adapter_names`); every batch row names its slot in the state's row table (`set_row_adapters`, -1 = the base
+        model), which the kernels read from device memory: rows with different adapters -- or none -- share one captured decode
+        step, and a row changes adapter without a recapture.  Every projection in the UNION of the adapters' targets runs
+        frozen projection (own fused norm, plain epilogue) -> p3v_lora_down_rows -> p3v_lora_up_rows (include/p3v.h); the others
+        run untouched.  A/B are uploaded once, `epoch` is bumped once.  An empty dict removes the bank.  A bank and a
+        `set_adapters` adapter on one model is a ValueError."""
+        bank = dict(bank or {})
+        if not bank and not self._bank:
+            return                                   # nothing attached, nothing to remove: the captured steps stay valid
+        if bank and self.adapters:
+            raise ValueError("this model carries a set_adapters adapter: detach it (set_adapters({})) before set_adapter_bank -- one or the other")
+        for name, ad in bank.items():
+            if not isinstance(name, str) or not name:
+                raise ValueError(f"adapter names are non-empty strings, got {name!r}")
+            for k, (a, b, _) in ad.items():
+                if not (k.startswith("model.layers.") and k.endswith("_proj.weight")) or not (k in self.w or k in self.w8 or k in self.w4):
+                    raise ValueError(f"adapter {name!r}: {k} is not a decoder projection of this model")
+                shape = self._weight_shape(k)
+                if a.dim() != 2 or b.dim() != 2 or a.shape[0] != shape[1] or b.shape[1] != shape[0] or a.shape[1] != b.shape[0]:
+                    raise ValueError(f"adapter {name!r}: LoRA shapes {tuple(a.shape)} x {tuple(b.shape)} do not fit {k} {tuple(shape)}")
+                if not 1 <= a.shape[1] <= ops.L.LORA_MAX_RANK:
+                    raise ValueError(f"adapter {name!r}: rank {a.shape[1]} of {k} is outside 1..{ops.L.LORA_MAX_RANK}")
+        self._attach_bank(bank)
+
+    @_on_device
+    def _attach_bank(self, bank):
+        names = list(bank)
+        dev = {n: {k: (a.to(self.device, F32).contiguous(), b.to(self.device, F32).contiguous(), float(s)) for k, (a, b, s) in ad.items()}
+               for n, ad in bank.items()}
+        union = sorted({k for ad in dev.values() for k in ad})
+        self._bank = {k: (ops.lora_table([dev[n].get(k) for n in names], self.device), max(dev[n][k][0].shape[1] for n in names if k in dev[n]))
+                      for k in union}
+        self._bank_keep, self.adapter_names = dev, names
+        self.epoch += 1                              # as set_adapters: the captured steps bake the kernel sequence and the scratch
+        for st in list(self._states):
+            st.graphs.clear()
+        self._lora_tmp, self._lora_flat = {}, None
+        self._prefill_graphs.clear()
+
+    def _bank_has(self, suffix):
+        return any(k.endswith(suffix) for k in self._bank)
+
+    def _state_rows(self, st):
+        """The state's row table (int32 [B] on the device, -1 = no adapter), made on first use."""
+        ra = getattr(st, "row_adapter", None)
+        if ra is None:
+            ra = st.row_adapter = torch.full((st.B,), -1, dtype=I32, device=self.device)
+        return ra
+
+    @_on_device
+    def set_row_adapters(self, st, adapters, row0=0):
+        """Name the adapter of rows row0 .. row0+n-1 of a state: bank slots, adapter names, or None / -1 for the base model.  One small
+        H2D copy outside any graph, like `set_sampling`: the captured steps read the table, so the next replay serves the new
+        assignment.  Rows never written are -1."""
+        if isinstance(adapters, (str, int)) or adapters is None:
+            adapters = [adapters]
+        slots = []
+        for a in adapters:
+            if a is None:
+                slots.append(-1)
+            elif isinstance(a, str):
+                if a not in self.adapter_names:
+                    raise ValueError(f"unknown adapter {a!r}; known: {self.adapter_names}")
+                slots.append(self.adapter_names.index(a))
+            else:
+                a = int(a)
+                if not -1 <= a < len(self.adapter_names):
+                    raise ValueError(f"adapter slot {a} is outside -1..{len(self.adapter_names) - 1}")
+                slots.append(a)
+        if row0 < 0 or row0 + len(slots) > st.B:
+            raise ValueError(f"rows {row0}..{row0 + len(slots) - 1} are outside the state's {st.B} rows")
+        self._state_rows(st)[row0:row0 + len(slots)].copy_(torch.tensor(slots, dtype=I32))
+        return st
+
+    def _proj_bank(self, x, key, table, r_max, epilogue, resid, norm_w, out, h):
+        M, K = x.shape
+        N, S = self._weight_shape(key)[0], ops.lora_slices(K)
+        if M <= ops.GEMV_MAX_M:                                 # decode-sized: persistent buffers (graph replays read them)
+            def buf(tag, shape, dtype):
+                t_ = self._lora_tmp.get((tag,) + shape)
+                if t_ is None:
+                    t_ = self._lora_tmp[(tag,) + shape] = torch.empty(shape, dtype=dtype, device=self.device)
+                return t_
+            y, t = buf("y", (M, N), BF16), buf("t", (M, S, r_max), F32)
+        else:                                                   # prefill-sized: the one grow-only allocation of _proj
+            o1 = (M * N * 2 + 255) // 256 * 256
+            nb = o1 + M * S * r_max * 4
+            if self._lora_flat is None or self._lora_flat.numel() < nb:
+                self._lora_flat = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            y = self._lora_flat[:M * N * 2].view(BF16).view(M, N)
+            t = self._lora_flat[o1:o1 + M * S * r_max * 4].view(F32).view(M, S, r_max)
+        rows = self._rows_cur
+        if rows is None or rows.numel() != M:
+            raise RuntimeError(f"{key}: no row table for {M} rows (an adapter bank serves the decoder stack only)")
+        # the frozen projection keeps its own fused norm; the down kernel norms the rows it streams itself (bit-identical)
+        self._proj_frozen(x, key, EPI_NONE, None, norm_w, y, h)
+        ops.lora_down_rows(x, table, rows, r_max, norm_w=norm_w, norm_eps=self.cfg.rms_norm_eps, out=t)
+        return ops.lora_up_rows(y, t, table, rows, K, r_max, epilogue, resid=resid, out=out)
 
     def _quantize_decoder_q4(self):
         """Decoder projections + lm_head -> 4-bit group-64 (the reference's nn.quantize(model, 64, 4)): 7.4 GB -> 2.1 GB
@@ -225,6 +343,9 @@ class Phi3VModel:
         """One projection of the decoder (+ its LoRA adapter, if one is attached)."""
         ad = self.adapters.get(key)
         if ad is None:
+            bk = self._bank.get(key) if self._bank else None
+            if bk is not None:
+                return self._proj_bank(x, key, bk[0], bk[1], epilogue, resid, norm_w, out, h)
             return self._proj_frozen(x, key, epilogue, resid, norm_w, out, h)
         a, b, scale = ad
         M, K, N, r = x.shape[0], x.shape[1], b.shape[1], a.shape[1]
@@ -291,7 +412,7 @@ class Phi3VModel:
         """x += bf16(o @ W^T) and h = RMSNorm(x) * norm_w from the projection's own launches (ops.gemm_resid_norm); False -- nothing
         done -- where that does not apply (adapters, quantised weights, shapes the library does not run as K slices)."""
         M = o.shape[0]
-        if (key in self.adapters or key not in self.w or M <= 8 or h.shape[0] < M
+        if (key in self.adapters or key in self._bank or key not in self.w or M <= 8 or h.shape[0] < M
                 or os.environ.get("P3V_RESID_NORM_FUSE", "1") == "0"):
             return False
         return ops.gemm_resid_norm(o, self.w[key], x, norm_w, self.cfg.rms_norm_eps, h[:M], out=x)
@@ -544,6 +665,8 @@ class Phi3VModel:
                                  k_tmp=st.k_tmp[rows], v_tmp=st.v_tmp[rows])
         else:
             view.__dict__.update(k=st.k[:, rows], v=st.v[:, rows])
+        if self._bank:
+            view.row_adapter = self._state_rows(st)[rows]        # (the rows' adapters: set_row_adapters BEFORE this prefill)
         kw = {k: v for k, v in inputs.items() if k in ("pixel_values", "image_sizes", "positions")}
         logits, _ = self(input_ids=ids, cache=[LayerCache(view, i) for i in range(cfg.num_hidden_layers)], full_logits=False, **kw)
         assert view.offset == st.offset
@@ -590,7 +713,7 @@ class Phi3VModel:
         ok = (os.environ.get("P3V_ATTN_FUSE_OPROJ", "1") != "0" and os.environ.get("P3V_PROFILING") != "1"
               and B == 1 and L == 1
               and cfg.num_hidden_layers % 2 == 0 and not self.serving
-              and not self.adapters and (o_key in self.w8) == bool(quantized) and not (quantized and o_key in self.w4)
+              and not self.adapters and not self._bank_has("self_attn.o_proj.weight") and (o_key in self.w8) == bool(quantized) and not (quantized and o_key in self.w4)
               # (without the in-launch merge -- long contexts: the MERGE launch carries the o_proj, k_attn_combine_o, round 6)
               and can(B, L, cfg.num_attention_heads, self.hd, bufs["n_split"], T, cfg.hidden_size, bool(bufs.get("attn_merge", False))))
         if not ok and bufs.get("attn_merge", False) and B == 1 and L == 1 and not quantized:
@@ -669,6 +792,9 @@ class Phi3VModel:
             if L <= ops.L.DECODE_MAX_L and n_beam == 1:
                 self._plan_fused_oproj(bufs, B, L, st.Tp, st.quantized)
         q, o, qkv, a, h, n_split, ws = (bufs[k] for k in ("q", "o", "qkv", "a", "h", "n_split", "ws"))
+        if self._bank:                                          # adapter bank: one table entry per row of x (token rows share their request's)
+            ra = self._state_rows(st)                           # (a captured step reads the state's own table: L = 1, no copy)
+            self._rows_cur = ra if M == st.B else ra.repeat_interleave(M // st.B)
         mlx4 = getattr(st, "mlx4", False)
         if (st.quantized or mlx4) and n_beam > 1:
             raise NotImplementedError("Beam Search is not yet compatible with Quantized Cache")       # as phi.py:525
@@ -684,7 +810,7 @@ class Phi3VModel:
             # its own epilogue (ops.gemm_qkv: bit-identical to the projection + rope_kv_append, one launch sequence instead of two).
             fused_qkv = False
             k_w = p + "self_attn.qkv_proj.weight"
-            if (L > ops.L.DECODE_MAX_L and n_beam == 1 and k_w in w and k_w not in self.adapters and not mlx4_first
+            if (L > ops.L.DECODE_MAX_L and n_beam == 1 and k_w in w and k_w not in self.adapters and k_w not in self._bank and not mlx4_first
                     and (M >= 1024 or M <= 256) and os.environ.get("P3V_QKV_FUSE", "1") != "0"):
                 kd, vd = (st.k_tmp, st.v_tmp) if st.quantized else (st.k[i], st.v[i])
                 if not (st.quantized and past > 0 and not getattr(st, "fresh_rows", False)):
@@ -695,7 +821,7 @@ class Phi3VModel:
             if i == 0 and step_begin is not None:               # replayed greedy step: the embedding gather + rotation-row staging
                 sb = step_begin                                 # ride in this projection's prologue when the library takes the shape
                 w_fold = w.get(k_w) if k_w in w else (self.w8.get(k_w) or self.w4.get(k_w))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
-                if not (w_fold is not None and k_w not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
+                if not (w_fold is not None and k_w not in self.adapters and k_w not in self._bank and os.environ.get("P3V_STEP_FOLD", "1") != "0"
                         and ops.gemv_step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"], sb["sin_o"],
                                                 w_fold, w[p + "input_layernorm.weight"], eps, qkv)):
                     ops.step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"], sb["sin_o"])
@@ -767,6 +893,8 @@ class Phi3VModel:
                 o = o.view(B, L, -1)[:, -1].contiguous()
                 x = x.view(B, L, -1)[:, -1].contiguous()
                 a, h = a[:B], h[:B]
+                if self._bank:
+                    self._rows_cur = self._state_rows(st) if B == st.B else self._state_rows(st).repeat_interleave(B // st.B)
             # Short prompts and decode batches (9 .. 256 rows): o_proj and down_proj run as K slices, and the launch that adds the slices also writes the
             # RMSNorm of the new residual stream into `h` -- the next projection's input (ops.gemm_resid_norm; bit-identical to the
             # two launches it replaces).
@@ -974,8 +1102,10 @@ class Phi3VModel:
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,
-                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None):
+                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None, row_adapters=None):
         """Phi3ForCausalLM.__call__ (phi.py:606-608) + Phi3F.__call__ (phi.py:576-592).
+        `row_adapters` (adapter bank only): one bank slot / name / None per batch row, written to the state's row table first
+        (a prefill call's new state starts with every row at -1; later calls keep what `set_row_adapters` wrote).
 
         Returns (logits bf16 [B, L', V], cache).  On a prefill call (cache is None)
         only the last position is projected through lm_head (L' = 1) unless
@@ -1004,6 +1134,8 @@ class Phi3VModel:
             cache = [LayerCache(st, i) for i in range(cfg.num_hidden_layers)]
         else:
             st = cache[0].state
+        if row_adapters is not None:
+            self.set_row_adapters(st, row_adapters)
         x = ops.embed_gather(ids.view(-1), w["model.embed_tokens.weight"])
         if pixel_values is not None and self.vision:
             self.vision_embed(x, pixel_values, image_sizes, positions, L)
@@ -1040,7 +1172,7 @@ class Phi3VModel:
         kernels, same order).  P3V_PREFILL_GRAPH=0 switches it off.  Returns None when not applicable."""
         cfg = self.cfg
         if (os.environ.get("P3V_PREFILL_GRAPH", "1") == "0" or S <= ops.L.DECODE_MAX_L or S > self.PREFILL_GRAPH_MAX_S or max_tokens < 1
-                or getattr(cfg, "use_quantized_cache", False) or self.adapters or self.hidden_hook is not None or self.w8):
+                or getattr(cfg, "use_quantized_cache", False) or self.adapters or self._bank or self.hidden_hook is not None or self.w8):
             return None                                           # (4-bit weights are captured too, round 6: their prefill is the bf16 one + a
                                                                   #  dequantise launch per projection into the model's own scratch)
         if 4 * cfg.num_hidden_layers * cfg.num_key_value_heads * self.hd * (S + max_tokens + 256) > self.PREFILL_GRAPH_MAX_CACHE_BYTES:

@@ -7,6 +7,7 @@ Each op names the MLX call site of the reference it replaces.
 import contextlib
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -214,6 +215,65 @@ def lora_up(y, t, lora_b, scale, epilogue=EPI_NONE, resid=None, out=None):
     if out is None:
         out = torch.empty((M, N // 2 if epilogue == EPI_SILU_MUL else N), dtype=BF16, device=y.device)
     L.check(L.lib().p3v_lora_up(_p(y), _p(t), _p(lora_b), float(scale), epilogue, _p(resid), _p(out), M, N, r, _stream()), "lora_up")
+    return out
+
+
+def lora_slices(K):
+    """K slices of the gathered LoRA kernels (P3V_LORA_SLICE_K elements each): t of lora_down_rows is [M, lora_slices(K), r_max]."""
+    return -(-int(K) // L.LORA_SLICE_K)
+
+
+def lora_table(entries, device):
+    """Bank table of one projection (p3v_lora_entry_t per bank slot) as an int64 [n_slots, 3] device tensor.  `entries`: per
+    slot None (this adapter leaves the projection alone) or (lora_a [K, r] f32, lora_b [r, N] f32, scale), tensors on `device`
+    and kept alive by the caller (the table holds their addresses)."""
+    rows = []
+    for e in entries:
+        if e is None:
+            rows.append([0, 0, 0])
+            continue
+        a, b, scale = e
+        _chk(a, F32, "lora_a"), _chk(b, F32, "lora_b")
+        r = a.shape[1]
+        if not (1 <= r <= L.LORA_MAX_RANK) or b.shape[0] != r:
+            raise ValueError(f"LoRA rank must be 1..{L.LORA_MAX_RANK} and agree between lora_a and lora_b, got {tuple(a.shape)} x {tuple(b.shape)}")
+        word = int(np.array([r], dtype=np.int32).view(np.uint32)[0]) | (int(np.array([scale], dtype=np.float32).view(np.uint32)[0]) << 32)
+        rows.append([a.data_ptr(), b.data_ptr(), word if word < (1 << 63) else word - (1 << 64)])
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(device)
+
+
+def lora_down_rows(x, table, row_adapter, r_max, norm_w=None, norm_eps=0.0, out=None):
+    """Per-row adapters, first half (include/p3v.h, adapter bank): t[m, s, :rank] = h[m, slice s] @ lora_a[slot(m)] with h = x or,
+    with norm_w, RMSNorm(x) * norm_w computed in the launch.  x [M,K] bf16, table from `lora_table`, row_adapter int32 [M]
+    (-1 = none) -> t [M, lora_slices(K), r_max] f32 (rows without an adapter are left untouched)."""
+    _chk(x, BF16, "x"), _chk(table, torch.int64, "table"), _chk(row_adapter, I32, "row_adapter")
+    M, K = x.shape
+    if row_adapter.numel() < M:
+        raise ValueError(f"row_adapter has {row_adapter.numel()} entries for {M} rows")
+    if norm_w is not None:
+        _chk(norm_w, BF16, "norm_w")
+    if out is None:
+        out = torch.empty((M, lora_slices(K), r_max), dtype=F32, device=x.device)
+    elif out.numel() < M * lora_slices(K) * r_max:
+        raise ValueError("lora_down_rows: `out` is too small")
+    L.check(L.lib().p3v_lora_down_rows(_p(x), _p(norm_w), float(norm_eps), _p(table), _p(row_adapter), _p(out), M, K, int(r_max),
+                                       table.shape[0], _stream()), "lora_down_rows")
+    return out
+
+
+def lora_up_rows(y, t, table, row_adapter, K, r_max, epilogue=EPI_NONE, resid=None, out=None):
+    """Per-row adapters, second half: out = epilogue(bf16(y + scale * (sum_s t[m, s] @ lora_b[slot(m)]))); a row without an
+    adapter gets epilogue(y).  y [M,N] bf16 (frozen projection, plain epilogue), t from `lora_down_rows` on the same K / r_max."""
+    _chk(y, BF16, "y"), _chk(t, F32, "t"), _chk(table, torch.int64, "table"), _chk(row_adapter, I32, "row_adapter")
+    M, N = y.shape
+    if row_adapter.numel() < M or t.numel() < M * lora_slices(K) * r_max:
+        raise ValueError("lora_up_rows: row_adapter / t too small for y")
+    if epilogue == EPI_RESID_BF16:
+        _chk(resid, BF16, "resid")
+    if out is None:
+        out = torch.empty((M, N // 2 if epilogue == EPI_SILU_MUL else N), dtype=BF16, device=y.device)
+    L.check(L.lib().p3v_lora_up_rows(_p(y), _p(t), _p(table), _p(row_adapter), epilogue, _p(resid), _p(out), M, N, int(K),
+                                     int(r_max), table.shape[0], _stream()), "lora_up_rows")
     return out
 
 

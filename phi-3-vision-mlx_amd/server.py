@@ -4,6 +4,9 @@
       -> 200 {"model": "phi-3-vision", "responses": [str, ...]}            anything else -> 404
     (extension: "temperature" (default 0 = greedy), "top_k" (0 = off), "top_p" (1 = off), "seed" (default: 64 random bits) --
      seeded sampling, include/p3v.h; a sampled response adds "seeds": [one per prompt], which reproduce it.)
+    (extension: "adapter": a name, or a list of one name / null per prompt -- the LoRA adapter of the server's bank
+     (`--adapter NAME=DIR`, repeatable) that prompt runs with; absent / null = the base model.  GET /v1/adapters lists the names;
+     an unknown name or a wrong type -> 400 with that list.  Rows with different adapters share one engine and one set of weights.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -36,10 +39,11 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter")
 
-    def __init__(self, prompts, max_tokens, images=None, sampling=None):
+    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
         self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
+        self.adapter = adapter                  # None, or one name / None per prompt
         self.done, self.result, self.error = threading.Event(), None, None
 
 
@@ -62,6 +66,34 @@ def parse_sampling(request, n_prompts):
     if recs[0][0] == 0.0:
         return None
     return [dict(temperature=r[0], top_k=r[1], top_p=r[2], seed=r[3]) for r in recs]
+
+
+def known_adapters(engine):
+    """Adapter names a backend serves: its `adapter_names` (a list, or a method returning one); [] when it has none."""
+    names = getattr(engine, "adapter_names", None)
+    return list((names() if callable(names) else names) or [])
+
+
+def parse_adapter(request, n_prompts, known):
+    """The "adapter" field of a request body -> None (absent, null, or null for every prompt: the base model) or one name / None per
+    prompt.  ValueError (-> 400) naming the known adapters on a wrong type, a wrong count or an unknown name."""
+    a = request.get("adapter")
+    if a is None:
+        return None
+    hint = f"known adapters: {sorted(known)}"
+    if isinstance(a, str):
+        a = [a] * n_prompts
+    elif isinstance(a, list):
+        if len(a) != n_prompts:
+            raise ValueError(f"adapter must be a name or list one name (or null) per prompt; {hint}")
+    else:
+        raise ValueError(f"adapter must be a string or a list of strings / nulls, got {type(a).__name__}; {hint}")
+    for name in a:
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"adapter names are strings (or null), got {type(name).__name__}; {hint}")
+        if name is not None and name not in known:
+            raise ValueError(f"unknown adapter {name!r}; {hint}")
+    return None if all(name is None for name in a) else a
 
 
 class ImagePolicy:
@@ -140,7 +172,8 @@ class EngineQueue:
     """Single consumer in front of a non-re-entrant `generate_fn(prompts: list[str], max_tokens) -> str | list[str]`."""
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
-                 length_fn=None, window_tokens=4096, device=None, sharded_fn=None):
+                 length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=()):
+        self.adapter_names = list(adapter_names)                # what generate_fn's `adapter` keyword may name (GET /v1/adapters)
         # sharded_fn(prompts, images) -> True when generate_fn would run that request on the batch-sharded path (dist.py), which
         # does not sample: the handler answers 400 to a sampled request bound there
         self.sharded_fn = sharded_fn
@@ -153,8 +186,8 @@ class EngineQueue:
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling)
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -177,7 +210,7 @@ class EngineQueue:
         """merge=False: `first` alone.  merge=True: plus every queued job with the same max_tokens that fits and keeps the
         RoPE regime of each member unchanged, waiting at most `window_s` for stragglers."""
         group, n, held = [first], len(first.prompts), []
-        if not self.merge or first.images is not None:          # image requests are never merged
+        if not self.merge or first.images is not None or first.adapter is not None:   # image / adapter requests are never merged
             return group
         regime = self._regime(first.prompts, first.max_tokens)
         while n < self.max_batch:
@@ -188,7 +221,7 @@ class EngineQueue:
             if job is None:
                 self.jobs.put(None)
                 break
-            if job.images is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
+            if job.images is None and job.adapter is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
                     and self._regime(job.prompts, job.max_tokens) == regime and (job.sampling is None) == (first.sampling is None):
                 group.append(job)
                 n += len(job.prompts)
@@ -209,8 +242,11 @@ class EngineQueue:
             group = self._collect(first)
             flat = [p for j in group for p in j.prompts]
             try:
+                kw = {} if first.adapter is None else {"adapter": first.adapter}
                 if first.sampling is not None:                  # (sampled jobs merge only with sampled jobs: one record per row)
-                    out = self.generate_fn(flat, first.max_tokens, first.images, sampling=[r for j in group for r in j.sampling])
+                    out = self.generate_fn(flat, first.max_tokens, first.images, sampling=[r for j in group for r in j.sampling], **kw)
+                elif kw:
+                    out = self.generate_fn(flat, first.max_tokens, first.images, **kw)
                 elif first.images is None:
                     out = self.generate_fn(flat, first.max_tokens)
                 else:
@@ -242,6 +278,12 @@ def make_handler(engine, image_policy=None):
             self.end_headers()
             self.wfile.write(body)
 
+        def do_GET(self):
+            if self.path != "/v1/adapters":
+                self.send_error(404, "Not Found")
+                return
+            self._send(200, {"model": MODEL_NAME, "adapters": known_adapters(engine)})
+
         def do_POST(self):
             if self.path != "/v1/completions":
                 self.send_error(404, "Not Found")
@@ -261,15 +303,22 @@ def make_handler(engine, image_policy=None):
                     images = [decode_image(i, image_policy) for i in images]      # fetched + decoded in THIS thread
                     images = None if all(i is None for i in images) else images
                 sampling = parse_sampling(request, len(prompts))
+                adapter = parse_adapter(request, len(prompts), known_adapters(engine))
                 sharded = getattr(engine, "sharded_fn", None)
                 if sampling is not None and sharded is not None and sharded(prompts, images):
                     raise ValueError("sampling is not available on the batch-sharded path (image requests and process groups of "
                                      "the queue server); run the server with --continuous to sample, or send temperature 0")
+                if adapter is not None and sharded is not None and sharded(prompts, images):
+                    raise ValueError("adapters are not available on the batch-sharded path (image requests and process groups of "
+                                     "the queue server); run the server with --continuous, or send no adapter")
             except (ValueError, TypeError, AttributeError, OSError) as e:
                 self._send(400, {"error": str(e)})
                 return
             try:
-                if sampling is not None:
+                if adapter is not None:
+                    kw = {"adapter": adapter} if sampling is None else {"adapter": adapter, "sampling": sampling}
+                    responses = engine.submit(prompts, max_tokens, images, **kw)
+                elif sampling is not None:
                     responses = engine.submit(prompts, max_tokens, images, sampling=sampling)
                 else:
                     responses = engine.submit(prompts, max_tokens, images) if images is not None else engine.submit(prompts, max_tokens)
@@ -304,11 +353,15 @@ class ContinuousBackend:
         self.thread = threading.Thread(target=engine.serve_forever, args=(self.stop,), daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None):
+    def adapter_names(self):
+        return known_adapters(self.engine)
+
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
         mt = max(1, min(int(max_tokens), self.max_tokens_cap))
+        kw = {} if adapter is None else {"adapter": adapter}
         if sampling is None:
-            return self.engine.generate(prompts, images, mt, self.timeout_s)
-        return self.engine.generate(prompts, images, mt, self.timeout_s, sampling=sampling)
+            return self.engine.generate(prompts, images, mt, self.timeout_s, **kw)
+        return self.engine.generate(prompts, images, mt, self.timeout_s, sampling=sampling, **kw)
 
     def close(self):
         self.stop.set()
@@ -321,9 +374,12 @@ def serve_continuous(engine, port=8000, host="127.0.0.1", image_policy=None, **k
 
 
 def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=False, host="127.0.0.1", image_policy=None,
-        long_window=0, slots=8):
-    from .api import _apply_chat_template, generate, load
+        long_window=0, slots=8, adapters=None):
+    """adapters: {name: adapter directory} -- the server's adapter bank (every rank of a fleet loads the same one)."""
+    from .api import _apply_chat_template, generate, load, load_adapters
     preload = load(blind_model=blind_model, synthetic=synthetic or None)
+    if adapters:
+        load_adapters(preload, adapters)
     processor = preload[1]
     preload[0].serving = True            # a server does not own the GPU: no launch that needs its whole grid resident at once (model.py)
     if continuous:
@@ -355,10 +411,12 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         import torch.distributed as dist
         return images is not None or (dist.is_available() and dist.is_initialized())
 
-    def generate_fn(prompts, max_tokens, images=None, sampling=None):
+    def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None):
         import torch.distributed as dist
-        if sampling is not None:                                     # (the handler kept sampled requests off the sharded path)
-            kw = {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
+        if sampling is not None or adapter is not None:              # (the handler kept these requests off the sharded path)
+            kw = {} if sampling is None else {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
+            if adapter is not None:
+                kw["adapter"] = adapter if len(prompts) > 1 else adapter[0]
             return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, **kw)
         if images is not None or (dist.is_available() and dist.is_initialized() and len(prompts) > 1):
             # mixed image + text requests -- and text-only batches whenever a process group exists -- go through the
@@ -372,7 +430,7 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return len(processor.tokenizer(_apply_chat_template(prompt, None, False)[0]).input_ids)
 
     httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
-                          image_policy=image_policy, sharded_fn=sharded_fn)
+                          image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}))
     print(f"Starting server on port {port}")
     try:
         httpd.serve_forever()
@@ -391,10 +449,19 @@ if __name__ == "__main__":
     ap.add_argument("--continuous", action="store_true", help="continuous batching engine (requests join / leave between decode steps)")
     ap.add_argument("--long-window", type=int, default=0, help="with --continuous: also serve prompt + max_tokens > 4096 up to this many tokens")
     ap.add_argument("--slots", type=int, default=8, help="with --continuous: batch rows of the engine")
+    ap.add_argument("--adapter", action="append", default=[], metavar="NAME=DIR",
+                    help="load the LoRA adapter in DIR (adapter_config.json + adapters.safetensors) into the adapter bank as NAME "
+                         "(repeatable); a request picks one with its \"adapter\" field")
     ap.add_argument("--host", default="127.0.0.1", help='interface to bind ("" = all, as the reference)')
     ap.add_argument("--image-dir", default=None, help="allow `images` entries naming files under this directory")
     ap.add_argument("--image-host", action="append", default=[], help="allow `images` URLs on this host (repeatable)")
     a = ap.parse_args()
+    bank = {}
+    for spec in a.adapter:
+        name, sep, path = spec.partition("=")
+        if not sep or not name or not path or name in bank:
+            ap.error(f"--adapter takes NAME=DIR with distinct names, got {spec!r}")
+        bank[name] = path
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:               # python -m torch.distributed.run --nproc-per-node N -m ...server --continuous
         if not a.continuous:
             # the one-shot paths have no worker loop: every rank would bind the same port and rank 0's batches would wait in
@@ -406,4 +473,4 @@ if __name__ == "__main__":
         if torch.cuda.is_available():
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # (fewer GPUs than ranks: shared)
         dist.init_process_group("gloo")                          # requests and token lists only: host memory (fleet.py)
-    run(a.port, "tiny" if a.synthetic and a.tiny else a.synthetic, a.blind, a.merge, a.continuous, a.host, ImagePolicy(a.image_dir, a.image_host), a.long_window, a.slots)
+    run(a.port, "tiny" if a.synthetic and a.tiny else a.synthetic, a.blind, a.merge, a.continuous, a.host, ImagePolicy(a.image_dir, a.image_host), a.long_window, a.slots, bank)
