@@ -498,6 +498,31 @@ int p3v_sample_step_end(const uint16_t* logits, p3v_sample_row_t* rows_params, i
                         int32_t* history, int32_t* d_step, int32_t* d_past, int32_t* ticket, int B, int n, int max_steps,
                         void* stream);
 
+/* ---- prompt prefix cache: KV block copy at any column phase (added after round 6, no version change).
+ * One job copies tokens [t0_src, t0_src + n_tok) of batch row b_src of a source cache to tokens [t0_dst, t0_dst + n_tok) of
+ * batch row b_dst of a destination cache, for ALL nl layers and nkv heads; up to P3V_KV_COPY_MAX_JOBS jobs share ONE launch
+ * (the job records are copied into the launch arguments: `jobs` is host memory, free to reuse on return).
+ *   k_*   K    [nl, B, nkv, T, hd]   elem_size bytes per element (2: bf16 cache, 1: int8 cache codes); 16-byte aligned bases,
+ *                                     hd * elem_size a multiple of 16
+ *   v_*   V^T  [nl, B, nkv, hd, T]   hd runs of n_tok elements per (layer, head) at element offsets t0_src / t0_dst in rows of
+ *                                     stride T_src / T_dst: ANY pair of offsets and strides (the destination run may start at any
+ *                                     element phase relative to the source)
+ *   ks_*, vs_*  fp32 scale rows [nl, B, nkv, T] of the int8 cache: all four, or all four NULL
+ * B and T are per side: a compact store entry (B = 1, T = tokens rounded up to 8) on one, a slot state on the other.
+ * The destination is written in [t0_dst, t0_dst + n_tok) ONLY: no byte next to a run changes.  The source may be read up to
+ * 3 bytes outside a run, inside the aligned 32-bit word that holds the run's first / last byte.
+ * P3V_ERR_ARG, nothing launched: null / misaligned pointers, n_jobs outside 1..P3V_KV_COPY_MAX_JOBS, elem_size other than 1 / 2,
+ * a row index outside its B, a run that leaves its row ([t0, t0 + n_tok) outside [0, T)), a source that overlaps a
+ * destination of the launch (its own or another job's; two different views that share memory are refused outright), two
+ * destinations that overlap.  n_tok = 0 is an empty job. */
+#define P3V_KV_COPY_MAX_JOBS 4
+typedef struct {
+  const void* k_src; const void* v_src; void* k_dst; void* v_dst;
+  const float* ks_src; const float* vs_src; float* ks_dst; float* vs_dst;
+  int32_t B_src, b_src, T_src, t0_src, B_dst, b_dst, T_dst, t0_dst, n_tok;
+} p3v_kv_copy_job_t;
+int p3v_kv_copy(const p3v_kv_copy_job_t* jobs /* host */, int n_jobs, int nl, int nkv, int hd, int elem_size, void* stream);
+
 /* ---- hipGraph helpers: capture a sequence of the launches above and replay it */
 int p3v_graph_begin(void* stream);
 int p3v_graph_end(void* stream, void** graph_exec_out /* host */);

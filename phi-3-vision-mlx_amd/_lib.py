@@ -95,6 +95,15 @@ class SampleRow(C.Structure):
                 ("counter", i32)]
 
 
+class KvCopyJob(C.Structure):
+    """p3v_kv_copy_job_t: one row's token run, source -> destination (include/p3v.h)."""
+    _fields_ = [("k_src", vp), ("v_src", vp), ("k_dst", vp), ("v_dst", vp),
+                ("ks_src", vp), ("vs_src", vp), ("ks_dst", vp), ("vs_dst", vp),
+                ("B_src", i32), ("b_src", i32), ("T_src", i32), ("t0_src", i32),
+                ("B_dst", i32), ("b_dst", i32), ("T_dst", i32), ("t0_dst", i32), ("n_tok", i32)]
+
+
+KV_COPY_MAX_JOBS = 4                             # P3V_KV_COPY_MAX_JOBS
 LORA_SLICE_K, LORA_MAX_RANK = 256, 64            # P3V_LORA_SLICE_K; largest rank of p3v_lora_* (include/p3v.h)
 SAMPLE_MAX_N, SAMPLE_MAX_ROWS = 32768, 1024      # p3v_sample / p3v_sample_step_end: larger -> P3V_ERR_UNSUPPORTED
 # name -> (restype, argtypes); must list every symbol include/p3v.h declares
@@ -154,6 +163,7 @@ SIGNATURES = {
     "p3v_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_sample": (i32, [vp, i64, vp, vp, i32, i32, vp]),
     "p3v_sample_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p3v_kv_copy": (i32, [C.POINTER(KvCopyJob), i32, i32, i32, i32, i32, vp]),
     "p3v_graph_begin": (i32, [vp]),
     "p3v_graph_end": (i32, [vp, C.POINTER(vp)]),
     "p3v_graph_launch": (i32, [vp, vp]),

@@ -428,12 +428,36 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                   "continuing with separate launches", file=sys.stderr)
 
 
+def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapter, batched, cache_prompt=True, prefix_len=None):
+    """The prefill of `_generate` through a prefix store: look up, restore + compute the rest (or the cold call), capture."""
+    from . import prefix as prefix_mod
+    ids = np.asarray(dict_input["input_ids"])
+    cfg = model.cfg
+    kind = "int8" if getattr(cfg, "use_quantized_cache", False) else "bf16"
+    if batched or ids.shape[0] != 1 or "mask" in dict_input or max_tokens < 1 or \
+            (kind == "int8" and getattr(cfg, "cache_format", "int8") == "mlx4"):
+        store.bypass()
+        return model(**dict_input, max_tokens=max_tokens, **kw_adapter)
+    ids = ids.reshape(-1)
+    adapter = (kw_adapter.get("row_adapters") or [None])[0]
+    key = store.key(model.epoch, adapter, ids.size + max_tokens > cfg.original_max_position_embeddings, kind)
+    hit = store.lookup(ids, digests, key)
+    logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter, **({} if hit is None else {"prefix": hit}))
+    P = prefix_mod.capture_len(ids, prefix_len)
+    nbytes = prefix_mod.kv_bytes(P, cfg.num_hidden_layers, cfg.num_key_value_heads, model.hd, kind)
+    if cache_prompt and store.wants(ids, digests, key, P, nbytes):
+        store.insert(ids[:P], digests, key, model.capture_prefix(cache[0].state, 0, 0, P))
+    return logits, cache
+
+
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
-              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None):
+              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  adapter: the name of one adapter of the model's bank
     (`load_adapters`) for every row, or one name / None per prompt of a batched call; None -- the default -- is the base model.  temperature > 0 samples instead (include/p3v.h:
     p3v_sample_row_t; each of temperature / top_k / top_p / seed a scalar or a per-row list, see sampling.rows); temperature 0
-    -- the default -- is today's greedy path, launch for launch."""
+    -- the default -- is today's greedy path, launch for launch.  prefix_cache: a prefix.PrefixCache -- a single prompt (string)
+    reuses the K/V of the longest stored prefix with the same tokens and pictures and leaves its own prefix in the store; a list
+    of prompts ignores it (counted as a bypass)."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     B = len(prompt) if isinstance(prompt, list) else 1
@@ -448,11 +472,18 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     sampled = None if sampling_mod.greedy(rows) else rows
     logit_stopper = LogitStopper(max_tokens, early_stop)
     streamer = Streamer(processor, stream, mute)
+    digests = None
+    if prefix_cache is not None and B == 1 and images is not None:
+        from .prefix import image_digests                       # of the source images, next to the processor call
+        digests = image_digests(images)
     dict_input = processor(prompt, images)
     mask, pids = dict_input.get("mask", None), dict_input.get("pids", None)
     token_stopper = TokenStopper(processor, dict_input["input_ids"].shape[0])
     tic = Tic()
-    logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter)
+    if prefix_cache is not None:
+        logits, cache = _prefill_with_store(model, prefix_cache, dict_input, digests, max_tokens, kw_adapter, isinstance(prompt, list))
+    else:
+        logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter)
     if sampled is None:
         token = model_ops.argmax(_last_logits(logits))[:, None]
     else:                                                       # draw 0 of every row: from the prefill logits
@@ -478,16 +509,18 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
-             apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None):
+             apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
+             prefix_cache=None):
     """reference phi_3_vision_mlx.py:1324-1374, plus seeded sampling (`_generate`; temperature 0 = greedy, the default) and
-    per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt)."""
+    per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
+    prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
-                     top_k=top_k, top_p=top_p, seed=seed, adapter=adapter)
+                     top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache)
 
 
 # ----------------------------------------------------------------------------- choose

@@ -30,6 +30,11 @@ refuses new work.  A negative token id (the device's report of NaN logits or a t
 include/p3v.h) on an active row fails that request and re-arms the workspace.  A request whose waiter gave up
 (`cancel()`) leaves its slot at the next step.
 
+Prompt prefix cache (`prefix_cache=prefix.PrefixCache(...)`, off by default): every admitted request is looked up in the store; a
+hit is prefilled ALONE -- its prefix K/V copied into its row, the rest of the prompt computed (`model.prefill_slot(prefix=)`) --
+and a miss goes the way it always went and leaves its prefix in the store afterwards (`cache_prompt`).  Without a store no call
+into the model changes.
+
 Cost model: a row reads the cache columns [0, column) whatever its own length (static split ranges), so a short request
 that joins late pays for the padding it attends over with zero weight; the weights (7.4 GB/step) are shared by all rows.
 """
@@ -58,10 +63,18 @@ def _set_device(device):
 
 
 class Request:
-    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter")
+    __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
+                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit")
 
     def __init__(self, inputs, max_tokens, sampling=None, adapter=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
+        # prompt prefix cache (engine with a store only; `cache_args` puts them beside the inputs): digests of the request's source
+        # images, whether its prompt may be captured, an explicit capture length; `cached_tokens`: prompt tokens restored from the
+        # store instead of computed
+        pa = inputs.get(PREFIX_ARGS) if isinstance(inputs, dict) else None
+        pa = pa if isinstance(pa, dict) else {}
+        self.image_digests, self.cache_prompt, self.prefix_len = pa.get("image_digests"), bool(pa.get("cache_prompt", True)), pa.get("prefix_len")
+        self.cached_tokens, self.hit = 0, None
         self.adapter = adapter                                   # None (the base model) or the name of an adapter of the model's bank
         self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
@@ -79,8 +92,9 @@ class Request:
 
 
 class ContinuousEngine:
-    def __init__(self, model, processor, slots=8, window=ROPE_WINDOW, patience=64):
+    def __init__(self, model, processor, slots=8, window=ROPE_WINDOW, patience=64, prefix_cache=None):
         self.model, self.processor, self.slots, self.window, self.patience = model, processor, slots, window, patience
+        self.prefix_cache = prefix_cache                         # prefix.PrefixCache or None (off: every path as without the feature)
         self.long_rope = window > ROPE_WINDOW
         self.rows = [None] * slots                               # row -> active Request
         self.waiting = collections.deque()
@@ -110,6 +124,12 @@ class ContinuousEngine:
 
     def submit(self, inputs, max_tokens, sampling=None, adapter=None):
         """inputs: a B = 1 `processor(text[, images])` result.  Returns the Request; wait on `.done`, read `.tokens`.
+        Engines with a `prefix_cache`: `submit(cache_args(inputs, image_digests=, cache_prompt=True, prefix_len=None), ...)` puts
+        the request's prefix-cache arguments beside its inputs (they travel with them through a router or a fleet): one
+        `prefix.image_digest` per source image -- without them a prompt with images is reused up to its first image slot only --,
+        whether this prompt's K/V may be captured for later requests, and how many of its tokens to capture (default: through
+        the last image slot, or the whole prompt).  A request always LOOKS UP the store; its `cached_tokens` says how many
+        tokens it reused.
         sampling: None (greedy) or {"temperature", "top_k", "top_p", "seed"} (missing keys: 0, 0, 1.0, 64 random bits; see
         sampling.rows) -- the request's tokens are then drawn under its own record, whoever shares the batch.
         adapter: None (the base model) or the name of one adapter of the model's bank: the request's row runs with it, next to
@@ -118,6 +138,7 @@ class ContinuousEngine:
         try:
             rec = _sampling_row(sampling)
             _check_adapter(adapter, self.adapter_names())
+            _check_prefix_args(inputs)
         except ValueError as e:
             r = Request(inputs, max_tokens)
             r.fail(e)
@@ -217,21 +238,28 @@ class ContinuousEngine:
         for i, r in enumerate(group):
             r.row = row0 + i
         inputs = collate_requests([r.inputs for r in group]) if n > 1 else group[0].inputs
+        hit = group[0].hit if n == 1 else None                   # a request with a hit is prefilled alone (_admit)
+        kw_prefix = {} if hit is None else {"prefix": hit}       # (without a hit: prefill_slot is called exactly as without a store)
+        for r in group:
+            r.hit = None                                         # (the handle must not pin a store entry once it is served)
         if self.adapter_names():
             # the rows' adapters (None -> -1: a refilled row must not keep its last occupant's) BEFORE their prefill reads them
             self.model.set_row_adapters(st, [r.adapter for r in group], row0)
         if any(r.sampling is not None for r in group):
             # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
-            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True)
+            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
             toks = self.model.sample_logits(st, logits, row0)
         else:
             if getattr(st, "sample_rows", None) is not None:     # a sampled request had these rows before: greedy records now
                 self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
-            toks = self.model.prefill_slot(st, row0, inputs)
+            toks = self.model.prefill_slot(st, row0, inputs, **kw_prefix)
         first = toks.reshape(-1).tolist()
         if min(first) < 0:
             raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
+        if hit is not None:
+            group[0].cached_tokens = int(hit[1])
+        self._capture(group)                                     # (after the NaN check: a poisoned row is never captured)
         g["tok"][row0:row0 + n].copy_(toks.reshape(-1))
         for r, t in zip(group, first):
             self.rows[r.row] = r
@@ -240,11 +268,51 @@ class ContinuousEngine:
             if t == ID_EOS or len(r.tokens) >= r.max_tokens:
                 self._release(r)
 
+    # ---- prompt prefix cache
+    def _prefix_key(self, adapter=None):
+        """The store key of a row of this engine with that adapter, or None when its cache can neither be captured nor restored
+        (cache_format="mlx4")."""
+        st = self.st
+        if getattr(st, "mlx4", False):
+            return None
+        return self.prefix_cache.key(getattr(self.model, "epoch", 0), adapter, self.long_rope, "int8" if getattr(st, "quantized", False) else "bf16")
+
+    def _lookup(self, r):
+        key = self._prefix_key(r.adapter)
+        if key is None:
+            self.prefix_cache.bypass()
+            return None
+        return self.prefix_cache.lookup(np.asarray(r.inputs["input_ids"]).reshape(-1), r.image_digests, key)
+
+    def _capture(self, group):
+        """After a successful prefill: store the prefix of every request that asks for it and is not covered yet."""
+        store = self.prefix_cache
+        if store is None:
+            return
+        if self._prefix_key() is None:
+            return
+        from .prefix import capture_len, kv_bytes
+        for r in group:
+            if not r.cache_prompt:
+                continue
+            try:
+                ids = np.asarray(r.inputs["input_ids"]).reshape(-1)
+                P, key = capture_len(ids, r.prefix_len), self._prefix_key(r.adapter)
+                cfg = getattr(self.model, "cfg", None)
+                nbytes = None if cfg is None else kv_bytes(P, cfg.num_hidden_layers, cfg.num_key_value_heads, self.model.hd, key[3])
+                if store.wants(ids, r.image_digests, key, P, nbytes):
+                    store.insert(ids[:P], r.image_digests, key, self.model.capture_prefix(self.st, r.row, self.st.offset - r.S, P))
+            except Exception:                                   # noqa: BLE001 -- (out of memory for the copy, ...) the request itself is fine
+                _sync(self.model.device)
+
     def _admit(self):
         with self.lock:
             admit, free = self._pick()
         if not admit:
             return
+        if self.prefix_cache is not None:
+            for r in admit:
+                r.hit = self._lookup(r)
         busy = bool(self._active())
         # requests of nearly equal length that get ADJACENT free rows are prefilled as one left-padded group (one pass over
         # the weights instead of one per request; dist.GROUP_PAD bounds the padding a request may carry)
@@ -256,7 +324,7 @@ class ContinuousEngine:
             while run < len(free) and free[run] == free[0] + run:
                 run += 1
             n = 1
-            while n < min(run, len(admit)) and admit[0].S - admit[n].S <= GROUP_PAD:
+            while n < min(run, len(admit)) and admit[0].S - admit[n].S <= GROUP_PAD and admit[0].hit is None and admit[n].hit is None:
                 n += 1
             group, admit = admit[:n], admit[n:]
             row0, free = free[0], free[n:]
@@ -334,8 +402,8 @@ class ContinuousEngine:
                 stop_event.wait(idle_sleep)
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
@@ -362,9 +430,41 @@ def adapter_list(adapter, n):
     return list(adapter)
 
 
-def _submit(engine, inputs, max_tokens, sampling, adapter):
-    """submit with only the keywords in use (an engine-like object without them keeps working for plain requests)."""
+PREFIX_ARGS = "prefix_cache_args"   # key of a request's prefix-cache arguments inside its `inputs` (no model call forwards it)
+
+
+def cache_args(inputs, image_digests=None, cache_prompt=True, prefix_len=None):
+    """A copy of a B = 1 `processor(...)` result that carries the request's prefix-cache arguments (ContinuousEngine.submit).
+    The processor's own result is not touched; `submit` checks the values."""
+    return dict(inputs, **{PREFIX_ARGS: {"image_digests": image_digests, "cache_prompt": cache_prompt, "prefix_len": prefix_len}})
+
+
+def _check_prefix_args(inputs):
+    pa = inputs.get(PREFIX_ARGS) if isinstance(inputs, dict) else None
+    if pa is None:
+        return
+    if not isinstance(pa, dict) or set(pa) - {"image_digests", "cache_prompt", "prefix_len"}:
+        raise ValueError(f"{PREFIX_ARGS} must be what engine.cache_args makes")
+    image_digests, prefix_len = pa.get("image_digests"), pa.get("prefix_len")
+    if not isinstance(pa.get("cache_prompt", True), bool):
+        raise ValueError("cache_prompt must be True or False")
+    if image_digests is not None:
+        if isinstance(image_digests, (str, bytes)) or not all(isinstance(d, str) and d for d in image_digests):
+            raise ValueError("image_digests must be a list of non-empty strings, one per image")
+        n_img = 0 if inputs.get("image_sizes") is None else len(np.asarray(inputs["image_sizes"]))
+        if len(image_digests) != n_img:
+            raise ValueError(f"image_digests: {len(image_digests)} digests for {n_img} images")
+    if prefix_len is not None:
+        if isinstance(prefix_len, bool) or not isinstance(prefix_len, (int, np.integer)) or prefix_len < 1:
+            raise ValueError(f"prefix_len must be a positive integer, got {prefix_len!r}")
+
+
+def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None):
+    """submit with only the keywords in use (an engine-like object without them keeps working for plain requests); the prefix-cache
+    arguments, when one of them is in use, ride beside the inputs (`cache_args`)."""
     kw = {}
+    if image_digests is not None or prefix_len is not None or (cache_prompt is not None and not cache_prompt):
+        inputs = cache_args(inputs, image_digests, True if cache_prompt is None else bool(cache_prompt), prefix_len)
     if sampling is not None:
         kw["sampling"] = sampling
     if adapter is not None:
@@ -390,8 +490,18 @@ def _pack(rows_, counter=0):
     return pack(rows_, counter)
 
 
-def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None):
-    """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt."""
+def has_prefix_cache(engine):
+    """Does this engine (or any engine behind a router / fleet) carry a prefix store?"""
+    if getattr(engine, "prefix_cache", None) is not None:
+        return True
+    inner = list(getattr(engine, "engines", ()) or ()) + [e for e in (getattr(engine, "engine", None),) if e is not None]
+    return any(has_prefix_cache(e) for e in inner)
+
+
+def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None):
+    """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt.
+    cache_prompt: None / True (the prompt may be captured by the engine's prefix store) or False.  info: a dict that receives
+    "cached_tokens" (one count per prompt)."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     images = images if images is not None else [None] * len(prompts)
@@ -401,8 +511,12 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
     reqs = []
     for i, (p, im) in enumerate(zip(prompts, images)):
         text, imgs = api._apply_chat_template(p, im, False)
+        digests = None
+        if imgs is not None and has_prefix_cache(engine):       # of the decoded source images, before the processor runs
+            from .prefix import image_digests
+            digests = image_digests(imgs)
         inputs = processor(text, imgs) if imgs is not None else processor(text)
-        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i]))
+        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt))
     out = []
     try:
         for r in reqs:
@@ -412,6 +526,8 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
                 raise r.error
             ids = r.tokens[:r.tokens.index(ID_EOS) + 1] if ID_EOS in r.tokens else r.tokens
             out.append(processor.tokenizer.decode(ids))
+        if info is not None:
+            info["cached_tokens"] = [int(getattr(r, "cached_tokens", 0)) for r in reqs]
     except BaseException:
         for r in reqs:                                          # nobody is waiting for these any more: free their slots
             if not r.done.is_set():
@@ -436,7 +552,7 @@ class RegimeRouter:
         S = int(np.asarray(inputs["input_ids"]).shape[-1])
         for e in self.engines:
             if e.accepts(S, int(max_tokens)):
-                return _submit(e, inputs, max_tokens, sampling, adapter)
+                return _submit(e, inputs, max_tokens, sampling, adapter)    # (`cache_args` inputs pass through as they are)
         r = Request(inputs, max_tokens)
         r.fail(ValueError(f"prompt {S} + max_tokens {max_tokens} fits no engine window"))
         return r
@@ -454,5 +570,5 @@ class RegimeRouter:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)

@@ -87,6 +87,8 @@ class EngineFleet:
         return self.engine.adapter_names()
 
     def submit(self, inputs, max_tokens, sampling=None, adapter=None):
+        """Prefix-cache arguments (`engine.cache_args`) travel inside `inputs` to whichever rank takes the request (one store per
+        engine; no cache-affinity routing: the least-loaded rank wins as before)."""
         try:
             _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
         except ValueError as e:
@@ -156,8 +158,8 @@ class EngineFleet:
     def serve_forever(self, stop_event, idle_sleep=0.002):
         self.engine.serve_forever(stop_event, idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""

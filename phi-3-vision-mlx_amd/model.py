@@ -623,17 +623,22 @@ class Phi3VModel:
         return st
 
     @_on_device
-    def prefill_slot(self, st, row, inputs, return_logits=False):
+    def prefill_slot(self, st, row, inputs, return_logits=False, prefix=None):
         """Prefill one request (a B = 1 `processor(...)` result) -- or n requests as one batch (`collate_requests` of them:
         equal lengths, or shorter rows left-padded inside the group) -- into the batch rows row .. row+n-1 of a slot state so
         that every row's LAST prompt token sits in column st.offset - 1: row i gets left padding pad_i = st.offset - S_i and
         position ids 0..S_i-1 from column pad_i on.  Keys left of pad_i (stale rows of an earlier occupant, the group's own
         padding) are masked by pad_len.  Returns the first greedy tokens (int32 [n, 1] on the device; with return_logits also
-        the last-position logits).  Each row computes what a B = 1 run of its request computes (pad invariance)."""
+        the last-position logits).  Each row computes what a B = 1 run of its request computes (pad invariance).
+        prefix=(entry, P) (prefix.PrefixCache.lookup; one request only): the row keeps the same geometry, the entry's first P
+        tokens are copied to columns [pad, pad + P) (ops.kv_copy) and the model runs on the LAST S - P ids alone, as a cached call
+        at offset pad + P.  Images whose slots the prefix covers are not computed: no vision tower when it covers them all."""
         cfg = self.cfg
         ids = np.asarray(inputs["input_ids"])
         ids = ids[None] if ids.ndim == 1 else ids
         n, S = ids.shape
+        if prefix is not None and (n != 1 or "mask" in inputs):
+            raise ValueError("prefill_slot: a prefix is restored for ONE unpadded request")
         lens = np.full(n, S, dtype=np.int64)
         if "mask" in inputs:
             m = np.asarray(inputs["mask"]).reshape(n, S)
@@ -668,10 +673,64 @@ class Phi3VModel:
         if self._bank:
             view.row_adapter = self._state_rows(st)[rows]        # (the rows' adapters: set_row_adapters BEFORE this prefill)
         kw = {k: v for k, v in inputs.items() if k in ("pixel_values", "image_sizes", "positions")}
+        if prefix is not None:
+            P, kw = self._prefix_split(ids, prefix, kw)
+            self._restore_prefix(st, row, win, prefix[0], P)
+            del view.fresh_rows                                  # columns [win, win + P) hold keys these rows DO see
+            view.offset, ids = win + P, ids[:, P:]
         logits, _ = self(input_ids=ids, cache=[LayerCache(view, i) for i in range(cfg.num_hidden_layers)], full_logits=False, **kw)
         assert view.offset == st.offset
         tok = ops.argmax(logits[:, -1, :].contiguous())[:, None]
         return (tok, logits) if return_logits else tok
+
+    # ------------------------------------------------------------------ prompt prefix cache (prefix.py)
+    def _state_kv(self, st):
+        if getattr(st, "mlx4", False):
+            raise ValueError('cache_format="mlx4" states are never captured or restored')
+        return (st.k8, st.v8, st.ks, st.vs) if st.quantized else (st.k, st.v)
+
+    def _prefix_split(self, ids, prefix, kw):
+        """(P, vision inputs of the suffix) for a prompt `ids` [1, S] whose first P tokens come from `prefix` = (entry, P): only
+        the images whose slots lie in the suffix are kept, their slot positions re-based by -P."""
+        from .prefix import slot_runs
+        entry, P = prefix
+        P, S = int(P), ids.shape[1]
+        runs = slot_runs(ids[0])
+        if not 1 <= P <= min(S - 1, entry.P) or any(a < P < b for a, b, _ in runs):
+            raise ValueError(f"prefix of {P} tokens does not fit a prompt of {S} (entry: {entry.P}; never inside an image's slots)")
+        if not np.array_equal(ids[0, :P], entry.ids[:P]):
+            raise ValueError("prefix entry does not hold these token ids")
+        covered = [i for a, b, i in runs if b <= P]
+        if covered != list(range(len(covered))) or [i for _, _, i in runs] != list(range(len(runs))):
+            raise ValueError("prefix reuse needs the images in tag order")
+        if kw.get("pixel_values") is None or not runs:
+            return P, kw
+        k = len(covered)
+        if k == len(runs):
+            return P, {}                                         # every image is cached: no vision tower at all
+        pos = np.asarray(kw["positions"])
+        pos = pos[pos[:, 1] >= P].copy()
+        pos[:, 1] -= P
+        return P, {"pixel_values": kw["pixel_values"][k:], "image_sizes": np.asarray(kw["image_sizes"])[k:], "positions": pos}
+
+    def _restore_prefix(self, st, row, col, entry, P):
+        kind = "int8" if st.quantized else "bf16"
+        if entry.key[3] != kind or len(entry.kv) != (4 if st.quantized else 2):
+            raise ValueError(f"prefix entry holds a {entry.key[3]} cache, the state a {kind} one")
+        ops.kv_copy([(tuple(t.unsqueeze(1) for t in entry.kv), 0, 0, self._state_kv(st), row, col, P)])
+
+    @_on_device
+    def capture_prefix(self, st, row, pad, P):
+        """K/V of tokens [0, P) of the request in batch row `row` (its first token in column `pad`) as compact tensors for the
+        prefix store: (k [nl, nkv, P8, hd], vt [nl, nkv, hd, P8]) bf16, or int8 codes + two fp32 scale rows.  One launch."""
+        from .prefix import alloc_kv
+        cfg = self.cfg
+        src = self._state_kv(st)
+        if P < 1 or pad < 0 or pad + P > st.Tp:
+            raise ValueError(f"capture_prefix: columns [{pad}, {pad + P}) are outside the state")
+        kv = alloc_kv(P, cfg.num_hidden_layers, cfg.num_key_value_heads, self.hd, "int8" if st.quantized else "bf16", self.device)
+        ops.kv_copy([(src, row, pad, tuple(t.unsqueeze(1) for t in kv), 0, 0, P)])
+        return kv
 
     @_on_device
     def decode_graph(self, st):
@@ -1102,10 +1161,12 @@ class Phi3VModel:
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,
-                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None, row_adapters=None):
+                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None, row_adapters=None, prefix=None):
         """Phi3ForCausalLM.__call__ (phi.py:606-608) + Phi3F.__call__ (phi.py:576-592).
         `row_adapters` (adapter bank only): one bank slot / name / None per batch row, written to the state's row table first
         (a prefill call's new state starts with every row at -1; later calls keep what `set_row_adapters` wrote).
+        `prefix` = (entry, P) of a prefix.PrefixCache (B = 1 prefill calls only): the new state's columns [0, P) are restored from
+        the entry and the call computes the last S - P ids at offset P; the captured short-prompt prefill is bypassed.
 
         Returns (logits bf16 [B, L', V], cache).  On a prefill call (cache is None)
         only the last position is projected through lm_head (L' = 1) unless
@@ -1122,12 +1183,22 @@ class Phi3VModel:
         B, L = ids.shape
         H = cfg.hidden_size
         prefill = cache is None
-        if prefill and pixel_values is None and B == 1 and pids is None and mask is None and n_beam == 1 and not full_logits \
+        if prefix is not None:
+            if not prefill or B != 1 or pids is not None or mask is not None or n_beam != 1:
+                raise ValueError("prefix: B = 1 prefill calls without padding only")
+            ids_h = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids).reshape(1, -1)
+            P, kw = self._prefix_split(ids_h, prefix, dict(pixel_values=pixel_values, image_sizes=image_sizes, positions=positions))
+            pixel_values, image_sizes, positions = kw.get("pixel_values"), kw.get("image_sizes"), kw.get("positions")
+            st = self._new_state(1, L, max_tokens, None, None)
+            cache = [LayerCache(st, i) for i in range(cfg.num_hidden_layers)]
+            self._restore_prefix(st, 0, 0, prefix[0], P)
+            st.offset, ids, L = P, ids[:, P:].contiguous(), L - P
+        elif prefill and pixel_values is None and B == 1 and pids is None and mask is None and n_beam == 1 and not full_logits \
                 and advance_offset is None:
             got = self._prefill_captured(ids, L, max_tokens)
             if got is not None:
                 return got
-        if prefill:
+        if prefill and prefix is None:
             # (before the vision tower is enqueued: the host is launch-bound through the ViT's ~280 launches, so whatever it does between
             #  the tower and the decoder -- cache allocation, its zero fill, the rotation tables -- would show as idle GPU time there)
             st = self._new_state(B, L, max_tokens, pids, mask)

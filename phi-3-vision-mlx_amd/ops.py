@@ -492,6 +492,47 @@ def kv_dequantize(k8, v8t, k_scale, v_scale, k, vt, n_tok):
                                       int(n_tok), _stream()), "kv_dequantize")
 
 
+def kv_copy(jobs):
+    """Prompt prefix cache (p3v_kv_copy): every job moves tokens [t0_src, +n) of batch row b_src of a source cache to tokens
+    [t0_dst, +n) of row b_dst of a destination cache, all layers and heads, up to KV_COPY_MAX_JOBS jobs per launch.
+    A job is (src, b_src, t0_src, dst, b_dst, t0_dst, n_tok); src / dst are (k, vt) of a bf16 cache -- K [nl,B,nkv,T,hd],
+    V^T [nl,B,nkv,hd,T] -- or (k8, v8t, k_scale, v_scale) of an int8 cache (uint8 codes + fp32 [nl,B,nkv,T]).  The two
+    sides may differ in B and T only.  Nothing outside the destination runs is written."""
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= L.KV_COPY_MAX_JOBS:
+        raise ValueError(f"kv_copy: 1..{L.KV_COPY_MAX_JOBS} jobs per launch, got {len(jobs)}")
+    recs = (L.KvCopyJob * len(jobs))()
+    geom = None
+    for rec, (src, b_src, t0_src, dst, b_dst, t0_dst, n_tok) in zip(recs, jobs):
+        if len(src) != len(dst) or len(src) not in (2, 4):
+            raise ValueError("kv_copy: a cache is (k, vt) or (k8, v8t, k_scale, v_scale), the same kind on both sides")
+        dt = src[0].dtype
+        if dt not in (BF16, torch.uint8) or (dt == BF16) != (len(src) == 2):
+            raise TypeError(f"kv_copy: bf16 (k, vt) or uint8 codes with scales, got {dt} with {len(src)} tensors")
+        for side in (src, dst):
+            _chk(side[0], dt, "k"), _chk(side[1], dt, "vt")
+            nl, B, nkv, T, hd = side[0].shape
+            if tuple(side[1].shape) != (nl, B, nkv, hd, T):
+                raise ValueError("kv_copy: V^T must be [nl, B, nkv, hd, T] of its K [nl, B, nkv, T, hd]")
+            for sc in side[2:]:
+                _chk(sc, F32, "scale")
+                if tuple(sc.shape) != (nl, B, nkv, T):
+                    raise ValueError("kv_copy: scale rows must be [nl, B, nkv, T]")
+            g = (nl, nkv, hd, dt)
+            if geom is None:
+                geom = g
+            elif g != geom:
+                raise ValueError("kv_copy: every cache of a launch has the same layers, heads, head size and element type")
+        rec.k_src, rec.v_src, rec.k_dst, rec.v_dst = _p(src[0]), _p(src[1]), _p(dst[0]), _p(dst[1])
+        if len(src) == 4:
+            rec.ks_src, rec.vs_src, rec.ks_dst, rec.vs_dst = _p(src[2]), _p(src[3]), _p(dst[2]), _p(dst[3])
+        rec.B_src, rec.b_src, rec.T_src, rec.t0_src = src[0].shape[1], int(b_src), src[0].shape[3], int(t0_src)
+        rec.B_dst, rec.b_dst, rec.T_dst, rec.t0_dst = dst[0].shape[1], int(b_dst), dst[0].shape[3], int(t0_dst)
+        rec.n_tok = int(n_tok)
+    nl, nkv, hd, dt = geom
+    L.check(L.lib().p3v_kv_copy(recs, len(jobs), nl, nkv, hd, 2 if dt == BF16 else 1, _stream()), "kv_copy")
+
+
 def attention_decode_q8(qkv, cos_new, sin_new, rope_bstride, k8, v8t, k_scale, v_scale, out, B, Lq, nh, nkv, hd, scale, past,
                         cache_t, ws, n_split, pad_len=None, d_past=None, merge_in_launch=False, o_proj_w8=None, o_proj_scale=None,
                         o_proj_x=None, o_rearm=None):

@@ -7,6 +7,11 @@
     (extension: "adapter": a name, or a list of one name / null per prompt -- the LoRA adapter of the server's bank
      (`--adapter NAME=DIR`, repeatable) that prompt runs with; absent / null = the base model.  GET /v1/adapters lists the names;
      an unknown name or a wrong type -> 400 with that list.  Rows with different adapters share one engine and one set of weights.)
+    (extension: prompt prefix cache, `--prefix-cache-gb G` with `--continuous`: the K/V of a prompt's prefix -- through its last
+     image slot, or the whole prompt -- is kept under an LRU byte budget and restored for later requests that start with the same
+     tokens AND the same pictures (prefix.py).  "cache_prompt": false keeps a request's prompt out of the store (it may still
+     reuse entries); responses gain "cached_tokens": [one per prompt]; GET /v1/prefix_cache returns the counters.  Without
+     the flag none of this exists: no field in the response, 404 for the GET.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -94,6 +99,21 @@ def parse_adapter(request, n_prompts, known):
         if name is not None and name not in known:
             raise ValueError(f"unknown adapter {name!r}; {hint}")
     return None if all(name is None for name in a) else a
+
+
+def parse_cache_prompt(request):
+    """The "cache_prompt" field of a request body -> None (absent or true: the default) or False.  ValueError (-> 400) on a
+    value that is not a boolean."""
+    v = request.get("cache_prompt", True)
+    if not isinstance(v, bool):
+        raise ValueError(f"cache_prompt must be true or false, got {type(v).__name__}")
+    return None if v else False
+
+
+def prefix_counters(engine):
+    """Counters of the prefix store(s) behind a backend (summed over the engines of a router), or None when it has none."""
+    fn = getattr(engine, "prefix_counters", None)
+    return fn() if callable(fn) else None
 
 
 class ImagePolicy:
@@ -279,6 +299,9 @@ def make_handler(engine, image_policy=None):
             self.wfile.write(body)
 
         def do_GET(self):
+            if self.path == "/v1/prefix_cache" and prefix_counters(engine) is not None:
+                self._send(200, {"model": MODEL_NAME, "prefix_cache": prefix_counters(engine)})
+                return
             if self.path != "/v1/adapters":
                 self.send_error(404, "Not Found")
                 return
@@ -304,6 +327,7 @@ def make_handler(engine, image_policy=None):
                     images = None if all(i is None for i in images) else images
                 sampling = parse_sampling(request, len(prompts))
                 adapter = parse_adapter(request, len(prompts), known_adapters(engine))
+                cache_prompt = parse_cache_prompt(request)
                 sharded = getattr(engine, "sharded_fn", None)
                 if sampling is not None and sharded is not None and sharded(prompts, images):
                     raise ValueError("sampling is not available on the batch-sharded path (image requests and process groups of "
@@ -314,8 +338,13 @@ def make_handler(engine, image_policy=None):
             except (ValueError, TypeError, AttributeError, OSError) as e:
                 self._send(400, {"error": str(e)})
                 return
+            info = None
             try:
-                if adapter is not None:
+                if prefix_counters(engine) is not None:         # a backend with a prefix store: it reports what each prompt reused
+                    info = {}
+                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("cache_prompt", cache_prompt)) if v is not None}
+                    responses = engine.submit(prompts, max_tokens, images, info=info, **kw)
+                elif adapter is not None:
                     kw = {"adapter": adapter} if sampling is None else {"adapter": adapter, "sampling": sampling}
                     responses = engine.submit(prompts, max_tokens, images, **kw)
                 elif sampling is not None:
@@ -328,6 +357,8 @@ def make_handler(engine, image_policy=None):
             out = {"model": MODEL_NAME, "responses": responses}
             if sampling is not None:
                 out["seeds"] = [r["seed"] for r in sampling]
+            if info is not None:
+                out["cached_tokens"] = list(info.get("cached_tokens", [0] * len(prompts)))
             self._send(200, out)
 
         def log_message(self, *args):           # quiet
@@ -356,9 +387,33 @@ class ContinuousBackend:
     def adapter_names(self):
         return known_adapters(self.engine)
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
+    def _stores(self):
+        # (the engines of a router, the engine itself, or a fleet's own engine)
+        engines = getattr(self.engine, "engines", None) or [getattr(self.engine, "engine", self.engine)]
+        return [e.prefix_cache for e in engines if getattr(e, "prefix_cache", None) is not None]
+
+    @property
+    def prefix_counters(self):
+        """None without a store; else a callable -> the counters, summed over the engines' stores."""
+        stores = self._stores()
+        if not stores:
+            return None
+
+        def counters():
+            out = {}
+            for s in stores:
+                for k, v in s.counters().items():
+                    out[k] = v if k == "min_tokens" else out.get(k, 0) + v
+            return out
+        return counters
+
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None):
         mt = max(1, min(int(max_tokens), self.max_tokens_cap))
         kw = {} if adapter is None else {"adapter": adapter}
+        if cache_prompt is not None:
+            kw["cache_prompt"] = cache_prompt
+        if info is not None:
+            kw["info"] = info
         if sampling is None:
             return self.engine.generate(prompts, images, mt, self.timeout_s, **kw)
         return self.engine.generate(prompts, images, mt, self.timeout_s, sampling=sampling, **kw)
@@ -374,8 +429,9 @@ def serve_continuous(engine, port=8000, host="127.0.0.1", image_policy=None, **k
 
 
 def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=False, host="127.0.0.1", image_policy=None,
-        long_window=0, slots=8, adapters=None):
-    """adapters: {name: adapter directory} -- the server's adapter bank (every rank of a fleet loads the same one)."""
+        long_window=0, slots=8, adapters=None, prefix_cache_gb=0.0):
+    """adapters: {name: adapter directory} -- the server's adapter bank (every rank of a fleet loads the same one).
+    prefix_cache_gb (with continuous): byte budget of the prompt prefix store of EACH engine (0 = off)."""
     from .api import _apply_chat_template, generate, load, load_adapters
     preload = load(blind_model=blind_model, synthetic=synthetic or None)
     if adapters:
@@ -385,9 +441,14 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
     if continuous:
         import torch.distributed as dist
         from .engine import ContinuousEngine, RegimeRouter
-        eng = ContinuousEngine(*preload, slots=slots)                 # requests with prompt + max_tokens <= 4096 (short RoPE factors)
+        def store():                                                 # one store per engine: its key carries the engine's regime
+            if prefix_cache_gb <= 0:
+                return {}
+            from .prefix import PrefixCache
+            return {"prefix_cache": PrefixCache(int(prefix_cache_gb * (1 << 30)))}
+        eng = ContinuousEngine(*preload, slots=slots, **store())      # requests with prompt + max_tokens <= 4096 (short RoPE factors)
         if long_window > 4096:                                       # + one engine for the long-RoPE regime (phi.py:492)
-            eng = RegimeRouter([eng, ContinuousEngine(*preload, slots=max(1, slots // 2), window=long_window)])
+            eng = RegimeRouter([eng, ContinuousEngine(*preload, slots=max(1, slots // 2), window=long_window, **store())])
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         front = None
         if world > 1:                                                # one engine per rank (= per GPU), rank 0 dispatches (fleet.py)
@@ -452,6 +513,9 @@ if __name__ == "__main__":
     ap.add_argument("--adapter", action="append", default=[], metavar="NAME=DIR",
                     help="load the LoRA adapter in DIR (adapter_config.json + adapters.safetensors) into the adapter bank as NAME "
                          "(repeatable); a request picks one with its \"adapter\" field")
+    ap.add_argument("--prefix-cache-gb", type=float, default=0.0, metavar="G",
+                    help="with --continuous: keep up to G GiB of prompt-prefix K/V per engine and reuse it for requests that start with "
+                         "the same tokens and pictures (393 KB per token at full size: ~1 GB per cached image)")
     ap.add_argument("--host", default="127.0.0.1", help='interface to bind ("" = all, as the reference)')
     ap.add_argument("--image-dir", default=None, help="allow `images` entries naming files under this directory")
     ap.add_argument("--image-host", action="append", default=[], help="allow `images` URLs on this host (repeatable)")
@@ -462,6 +526,8 @@ if __name__ == "__main__":
         if not sep or not name or not path or name in bank:
             ap.error(f"--adapter takes NAME=DIR with distinct names, got {spec!r}")
         bank[name] = path
+    if a.prefix_cache_gb and not a.continuous:
+        ap.error("--prefix-cache-gb needs --continuous")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:               # python -m torch.distributed.run --nproc-per-node N -m ...server --continuous
         if not a.continuous:
             # the one-shot paths have no worker loop: every rank would bind the same port and rank 0's batches would wait in
@@ -473,4 +539,5 @@ if __name__ == "__main__":
         if torch.cuda.is_available():
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # (fewer GPUs than ranks: shared)
         dist.init_process_group("gloo")                          # requests and token lists only: host memory (fleet.py)
-    run(a.port, "tiny" if a.synthetic and a.tiny else a.synthetic, a.blind, a.merge, a.continuous, a.host, ImagePolicy(a.image_dir, a.image_host), a.long_window, a.slots, bank)
+    run(a.port, "tiny" if a.synthetic and a.tiny else a.synthetic, a.blind, a.merge, a.continuous, a.host, ImagePolicy(a.image_dir, a.image_host), a.long_window, a.slots, bank,
+        a.prefix_cache_gb)
