@@ -523,6 +523,60 @@ typedef struct {
 } p3v_kv_copy_job_t;
 int p3v_kv_copy(const p3v_kv_copy_job_t* jobs /* host */, int n_jobs, int nl, int nkv, int hd, int elem_size, void* stream);
 
+/* ---- speculative greedy decoding (B = 1): prompt-lookup drafts, one verify step per replay (added after round 6, no
+ * version change).  The rule (speculate.py states it once more in plain Python; the kernels are held to it exactly):
+ *   State of one sequence: ctx[0..n) -- every token id so far, prompt included; the newest token ctx[n-1] is not yet in
+ *   the cache; *d_past = n - 1.
+ *   Propose (K, n_max, n_min; defaults P3V_SPEC_DEFAULT_K = 4, P3V_SPEC_NGRAM_MAX = 3, P3V_SPEC_NGRAM_MIN = 1): for
+ *   m = n_max down to n_min, skipping m >= n: s = ctx[n-m .. n).  Take the LARGEST p < n - m with ctx[p .. p+m) == s.  If
+ *   one exists the draft is ctx[p+m .. min(p+m+K, n)), cut in front of the first id outside [0, vocab) (image-slot ids
+ *   are never proposed), and the search ends.  No match at any m: the draft is empty.
+ *   Verify: rows 0..K of the step are ctx[n-1], d_0 .. d_{k-1} and, where k < K, padding (a valid id; those rows are
+ *   causal dead weight and their K/V rows lie beyond the new offset).  a_j = arg-max of row j by p3v_argmax's rule (first
+ *   maximum of the bf16 values, -1 for a NaN row).  acc = the largest i <= k with d_j == a_j for all j < i.  Emitted:
+ *   a_0 .. a_acc.  If a_acc is -1 the step FAILED: a_0 .. a_acc go to the history (the host raises on the negative
+ *   token), *d_step counts them, tok[0] = -1, and ctx, n and *d_past stay as they were.  Otherwise the emitted run is cut
+ *   to the budget (c = min(acc + 1, n_limit - n, ctx_cap - n) tokens, possibly none), ctx grows by it, *d_past += c,
+ *   *d_step += c, the next step's row 0 is the last emitted token and the next draft is proposed from the new ctx.
+ * One state record describes the loop state; every pointer is device memory unless stated:
+ *   tok      [L]   rows of the NEXT step: tok[0] = ctx[n-1], tok[1 .. 1+n_draft) the draft, then padding
+ *   ctx      [ctx_cap]
+ *   ctl      [P3V_SPEC_CTL_INTS]: n, n_draft, forced (non-zero: the tail proposes nothing and leaves n_draft = 0 -- the
+ *            host writes tok[1..L) and n_draft before the next launch), replay (launches so far), n_limit, and the token
+ *            count of the last launch
+ *   amax     [L] scratch, ticket [1]: the arrival counter, ZERO before the first launch and left zero by every launch
+ *   history  [hist_cap] PINNED HOST memory: token i of the run at history[i] (i = *d_step + 0 .. c-1)
+ *   rec      [rec_cap][P3V_SPEC_REC_INTS] PINNED HOST memory: launch r writes {tokens emitted, drafts verified (k),
+ *            d_0 .. d_{k-1}} to record r
+ * p3v_spec_end: L = K + 1 rows of [L, n] bf16 logits; one 1024-thread workgroup per row takes its arg-max, the last one
+ * to arrive does the rest.  p3v_spec_begin: x_out[j] = table[clamp(tok[j])], rotation rows of positions *d_past + j
+ * (clamped to the table) into cos_out / sin_out [L, half_dim].  p3v_ngram_propose: the proposal alone, ctx[0..n) ->
+ * draft[0 .. *n_draft).  L outside 1..P3V_DECODE_MAX_L, n_max outside n_min..P3V_SPEC_NGRAM_CAP, null pointers:
+ * P3V_ERR_ARG, nothing launched. */
+#define P3V_SPEC_DEFAULT_K 4
+#define P3V_SPEC_NGRAM_MAX 3
+#define P3V_SPEC_NGRAM_MIN 1
+#define P3V_SPEC_NGRAM_CAP 8
+#define P3V_SPEC_REC_INTS 18
+#define P3V_SPEC_CTL_INTS 8
+#define P3V_SPEC_CTL_N 0
+#define P3V_SPEC_CTL_NDRAFT 1
+#define P3V_SPEC_CTL_FORCED 2
+#define P3V_SPEC_CTL_REPLAY 3
+#define P3V_SPEC_CTL_NLIMIT 4
+#define P3V_SPEC_CTL_ACC 5
+typedef struct {
+  int32_t* tok; int32_t* ctx; int32_t* ctl; int32_t* amax; int32_t* ticket;
+  int32_t* history; int32_t* rec; int32_t* d_step; int32_t* d_past;
+  int32_t ctx_cap, hist_cap, rec_cap, n_max, n_min;
+} p3v_spec_state_t;
+int p3v_spec_begin(const int32_t* tok, const uint16_t* table, uint16_t* x_out, const float* cos_t, const float* sin_t,
+                   const int32_t* d_past, float* cos_out, float* sin_out, int L, int hidden, int vocab, int tab_t,
+                   int half_dim, void* stream);
+int p3v_spec_end(const uint16_t* logits, const p3v_spec_state_t* state /* host */, int L, int n, void* stream);
+int p3v_ngram_propose(const int32_t* ctx, int n, int K, int n_max, int n_min, int vocab, int32_t* draft, int32_t* n_draft,
+                      void* stream);
+
 /* ---- hipGraph helpers: capture a sequence of the launches above and replay it */
 int p3v_graph_begin(void* stream);
 int p3v_graph_end(void* stream, void** graph_exec_out /* host */);

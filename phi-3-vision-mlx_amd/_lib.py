@@ -103,6 +103,15 @@ class KvCopyJob(C.Structure):
                 ("B_dst", i32), ("b_dst", i32), ("T_dst", i32), ("t0_dst", i32), ("n_tok", i32)]
 
 
+class SpecState(C.Structure):
+    """p3v_spec_state_t: the loop state of the speculative greedy step (include/p3v.h)."""
+    _fields_ = [("tok", vp), ("ctx", vp), ("ctl", vp), ("amax", vp), ("ticket", vp),
+                ("history", vp), ("rec", vp), ("d_step", vp), ("d_past", vp),
+                ("ctx_cap", i32), ("hist_cap", i32), ("rec_cap", i32), ("n_max", i32), ("n_min", i32)]
+
+
+SPEC_REC_INTS, SPEC_CTL_INTS, SPEC_NGRAM_CAP = 18, 8, 8     # P3V_SPEC_REC_INTS, P3V_SPEC_CTL_INTS, P3V_SPEC_NGRAM_CAP
+SPEC_CTL_N, SPEC_CTL_NDRAFT, SPEC_CTL_FORCED, SPEC_CTL_REPLAY, SPEC_CTL_NLIMIT, SPEC_CTL_ACC = range(6)
 KV_COPY_MAX_JOBS = 4                             # P3V_KV_COPY_MAX_JOBS
 LORA_SLICE_K, LORA_MAX_RANK = 256, 64            # P3V_LORA_SLICE_K; largest rank of p3v_lora_* (include/p3v.h)
 SAMPLE_MAX_N, SAMPLE_MAX_ROWS = 32768, 1024      # p3v_sample / p3v_sample_step_end: larger -> P3V_ERR_UNSUPPORTED
@@ -163,6 +172,9 @@ SIGNATURES = {
     "p3v_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_sample": (i32, [vp, i64, vp, vp, i32, i32, vp]),
     "p3v_sample_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p3v_spec_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "p3v_spec_end": (i32, [vp, C.POINTER(SpecState), i32, i32, vp]),
+    "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "p3v_kv_copy": (i32, [C.POINTER(KvCopyJob), i32, i32, i32, i32, i32, vp]),
     "p3v_graph_begin": (i32, [vp]),
     "p3v_graph_end": (i32, [vp, C.POINTER(vp)]),

@@ -428,6 +428,83 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                   "continuing with separate launches", file=sys.stderr)
 
 
+def speculative_loop(model, ids, token, cache, n_steps, K, streamer, token_stopper, info=None):
+    """`greedy_loop` with speculative verify steps (B = 1, greedy; include/p3v.h "speculative greedy decoding"): up to `n_steps`
+    tokens after the prefill token `token`, every one handed to the streamer and the token stopper in order.  `ids`: the ids
+    the cache holds (the prompt).  Each replay of model.spec_step emits accepted + 1 tokens; replays are enqueued ahead of the
+    host (a step needs no host input), tokens and per-step records are read from pinned memory behind an event.  A stop token
+    inside an accepted run, or the n_steps budget, cuts the output there; the cache offset is then what the plain loop leaves:
+    prompt + delivered tokens - 1 (rows of dropped tokens lie beyond it).  A negative token raises, as in greedy_loop.
+    info (a dict) receives steps / drafted / accepted / emitted.  Returns the last delivered token as an int32 [1, 1] tensor."""
+    st = cache[0].state
+    S0 = st.offset
+    stats = dict(steps=0, drafted=0, accepted=0, emitted=0)
+    last = token
+    if n_steps > 0:
+        g = model.spec_start(cache, ids, token, K, n_limit=S0 + 1 + n_steps)
+        hist, rec = g["history"], g["rec"]
+        pending, pos, r, delivered, done = [], 0, 0, 0, False
+        while not done:
+            # every step emits at least one token until the budget is reached: never more replays in flight than tokens missing
+            while len(pending) < 2 and len(pending) < n_steps - pos:
+                model.spec_step(cache, K)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append(ev)
+            if not pending:
+                break
+            pending.pop(0).synchronize()
+            c, kd = int(rec[r, 0]), int(rec[r, 1])
+            r += 1
+            toks = hist[pos:pos + c].tolist()
+            pos += c
+            if c == 0:
+                break
+            if min(toks) < 0:
+                torch.cuda.current_stream().synchronize()
+                st.offset = S0 + delivered
+                st.mark_dirty() if hasattr(st, "mark_dirty") else None
+                raise RuntimeError(f"device step failed: NaN logits (token ids {toks})")
+            stats["steps"] += 1
+            stats["drafted"] += kd
+            stats["accepted"] += c - 1
+            stats["emitted"] += c
+            for t in toks:
+                streamer([t])
+                delivered += 1
+                last = t
+                if token_stopper([t]):
+                    done = True
+                    break
+            if pos >= n_steps:
+                done = True
+        if pending:
+            torch.cuda.current_stream().synchronize()              # replays enqueued ahead: their rows lie beyond the offset
+        st.offset = S0 + delivered
+        if not torch.is_tensor(last):
+            last = torch.tensor([[last]], dtype=torch.int32, device=token.device)
+    if info is not None:
+        info.update(stats)
+    return last
+
+
+def _check_speculate(model, speculate, batched, sampled, early_stop):
+    """The refusals of speculative decoding: a ValueError that names the limit, never a silent fallback."""
+    K = int(speculate)
+    if K < 0:
+        raise ValueError(f"speculate must be >= 0, got {speculate}")
+    if batched:
+        raise ValueError("speculate: one prompt at a time (B = 1); a list of prompts is not supported")
+    if sampled:
+        raise ValueError("speculate: greedy decoding only (temperature must be 0)")
+    if early_stop:
+        raise ValueError("speculate: early_stop is not supported (the logit stopper reads one row per step)")
+    why = model.spec_refusal(None, K)
+    if why:
+        raise ValueError(why)
+    return K
+
+
 def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapter, batched, cache_prompt=True, prefix_len=None):
     """The prefill of `_generate` through a prefix store: look up, restore + compute the rest (or the cold call), capture."""
     from . import prefix as prefix_mod
@@ -451,8 +528,11 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 
 
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
-              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None):
-    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  adapter: the name of one adapter of the model's bank
+              stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
+              speculate=0, spec_info=None):
+    """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
+    drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
+    receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
     (`load_adapters`) for every row, or one name / None per prompt of a batched call; None -- the default -- is the base model.  temperature > 0 samples instead (include/p3v.h:
     p3v_sample_row_t; each of temperature / top_k / top_p / seed a scalar or a per-row list, see sampling.rows); temperature 0
     -- the default -- is today's greedy path, launch for launch.  prefix_cache: a prefix.PrefixCache -- a single prompt (string)
@@ -470,6 +550,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         kw_adapter = {"row_adapters": names}
     rows = sampling_mod.rows(B, temperature, top_k, top_p, seed)
     sampled = None if sampling_mod.greedy(rows) else rows
+    if speculate:
+        speculate = _check_speculate(model, speculate, isinstance(prompt, list), sampled is not None, early_stop)
+        kw_adapter = dict(kw_adapter, extra_tokens=speculate)   # (rides with the prefill call: cache columns for the draft rows)
     logit_stopper = LogitStopper(max_tokens, early_stop)
     streamer = Streamer(processor, stream, mute)
     digests = None
@@ -490,7 +573,12 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         token = model_ops.sample(logits[:, -1, :], sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
     streamer(_rows(token))                                      # D2H copy = the per-token sync the reference has (mx.eval)
     prompt_time = tic()
-    if sampled is None:
+    if speculate:
+        stats = {}
+        speculative_loop(model, dict_input["input_ids"], token, cache, max_tokens - 1, speculate, streamer, token_stopper, stats)
+        if spec_info is not None:
+            spec_info.update(stats)
+    elif sampled is None:
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids)
     else:
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled)
@@ -502,6 +590,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     if verbose:
         print(f"\nPrompt: {prompt_tps:.2f} tokens-per-sec ({prompt_len} tokens / {prompt_time:.1f} sec)")
         print(f"Generate: {gen_tps:.2f} tokens-per-sec ({gen_len} tokens / {gen_time:.1f} sec)")
+        if speculate:
+            print(f"Speculation: {stats['steps']} verify steps, {stats['accepted']} of {stats['drafted']} drafts accepted, "
+                  f"{stats['emitted']} tokens emitted")
     if return_tps:
         return prompt_tps, gen_tps
     return result
@@ -510,8 +601,8 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
-             prefix_cache=None):
-    """reference phi_3_vision_mlx.py:1324-1374, plus seeded sampling (`_generate`; temperature 0 = greedy, the default) and
+             prefix_cache=None, speculate=0, spec_info=None):
+    """reference phi_3_vision_mlx.py:1324-1374, plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only)."""
     if "<|api_input|>" in prompt and enable_api:
@@ -520,7 +611,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
-                     top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache)
+                     top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache, speculate=speculate,
+                     spec_info=spec_info)
 
 
 # ----------------------------------------------------------------------------- choose

@@ -571,9 +571,11 @@ class Phi3VModel:
     # ------------------------------------------------------------------ per-prompt state
     ROPE_TABLE_ENTRIES = 8
 
-    def _new_state(self, B, S, max_tokens, pids, mask, shared_tables=True):
+    def _new_state(self, B, S, max_tokens, pids, mask, shared_tables=True, extra_tokens=0):
         cfg = self.cfg
-        st = CacheState(cfg, B, S, max_tokens, self.device)
+        # extra_tokens: columns beyond prompt + max_tokens (a speculative verify step writes K/V rows up to offset + K); the
+        # short / long RoPE-factor choice below stays on prompt + max_tokens, as the plain path takes it
+        st = CacheState(cfg, B, S, max_tokens + int(extra_tokens) if max_tokens > 0 else max_tokens, self.device)
         self._states.add(st)
         L_all = S + max_tokens                                  # reference sizes tables with max_tokens as given
         half = self.hd // 2
@@ -1079,6 +1081,161 @@ class Phi3VModel:
         g["host_tok"] = g["next_tok"].view(-1, 1)
         return g["logits"].view(st.B, 1, -1), g["host_tok"]
 
+    # ------------------------------------------------------------------ speculative greedy decoding (include/p3v.h, speculate.py)
+    def spec_refusal(self, st=None, K=None):
+        """Why this model (and state) cannot run verify steps -- a sentence that names the limit -- or None."""
+        from . import speculate
+        cfg = self.cfg
+        if K is not None and not 1 <= int(K) <= ops.L.DECODE_MAX_L - 1:
+            return f"speculate must be 1 .. {ops.L.DECODE_MAX_L - 1} (P3V_DECODE_MAX_L - 1 draft rows), got {K}"
+        if getattr(cfg, "use_quantized_cache", False):
+            fmt = getattr(cfg, "cache_format", "int8")
+            return f"speculative decoding needs the bf16 KV cache (cache_format={fmt!r} is not supported)"
+        if self.w8 or self.w4:
+            return "speculative decoding needs bf16 weights (fp8 / 4-bit weights are not supported)"
+        if self.adapters or self._bank:
+            return "speculative decoding does not support LoRA adapters or an adapter bank"
+        if st is not None and st.B != 1:
+            return f"speculative decoding is B = 1 only (got a batch of {st.B})"
+        if st is not None and getattr(st, "slots", False):
+            return "speculative decoding does not run on a slot state of the continuous engine"
+        return None
+
+    def _build_spec_graph(self, st, K, n_max, n_min):
+        """Capture ONE verify step (B = 1, L = K + 1 rows: p3v_spec_begin -> the layers at L rows -> final norm + lm_head on L rows
+        -> p3v_spec_end) beside the greedy capture, over loop-state buffers of its own.  Same conventions: split plan from the cache
+        CAPACITY, the graph owns its GEMM workspace, a warm-up run before the capture, nothing allocated under it."""
+        cfg, w, dev, Lq = self.cfg, self.w, self.device, K + 1
+        n_tok = max(1, st.max_tokens)
+        g = dict(K=K, tok=torch.zeros((Lq,), dtype=I32, device=dev), ctx=torch.zeros((st.T + Lq,), dtype=I32, device=dev),
+                 ctl=torch.zeros((ops.L.SPEC_CTL_INTS,), dtype=I32, device=dev), amax=torch.zeros((Lq,), dtype=I32, device=dev),
+                 ticket=torch.zeros((1,), dtype=I32, device=dev), d_past=torch.zeros((1,), dtype=I32, device=dev),
+                 d_step=torch.zeros((1,), dtype=I32, device=dev),
+                 # pinned host memory, written by p3v_spec_end itself: the run's tokens and one record per replay
+                 history=torch.zeros((n_tok + K + 1,), dtype=I32).pin_memory(),
+                 rec=torch.zeros((n_tok + 2, ops.L.SPEC_REC_INTS), dtype=I32).pin_memory(),
+                 x=torch.empty((Lq, cfg.hidden_size), dtype=BF16, device=dev),
+                 logits=torch.empty((Lq, cfg.vocab_size), dtype=BF16, device=dev), n_replays=0)
+        g["state"] = ops.spec_state(g, n_max, n_min)
+        bufs = self._alloc_bufs(1, Lq)
+        self._split_plan(bufs, 1, Lq, st.Tp, st.quantized, serving=getattr(st, "serving", False) or self.serving)
+        bufs["past_lb"] = int(st.offset)
+        bufs["fuse_o"] = False                                   # (the fused attention + o_proj launch is B = L = 1 only)
+        bufs["rope_cos"] = torch.empty((1, Lq, self.hd // 2), dtype=F32, device=dev)
+        bufs["rope_sin"] = torch.empty_like(bufs["rope_cos"])
+        g["bufs"] = bufs
+
+        def step():
+            ops.spec_begin(g["tok"], w["model.embed_tokens.weight"], g["x"], st.cos, st.sin, g["d_past"], bufs["rope_cos"], bufs["rope_sin"])
+            self._layers(g["x"], st, 1, Lq, 0, 1, bufs=bufs, d_past=g["d_past"])
+            self._proj(g["x"], "lm_head.weight", norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])
+            ops.spec_end(g["logits"], g["state"])
+        g["step"] = step
+        # the warm-up run is a step at the budget (n = n_limit = 0): it emits nothing and moves no counter but `replay`
+        g["d_past"].fill_(st.offset)
+        g["gemm_ws"] = {}
+        with ops.owned_gemm_workspace(g["gemm_ws"], frozen=False):
+            step()
+        torch.cuda.synchronize()
+        graph = ops.Graph()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), ops.owned_gemm_workspace(g["gemm_ws"], frozen=True):
+            graph.begin()
+            step()
+            graph.end()
+        torch.cuda.current_stream().wait_stream(side)
+        g["graph"] = graph
+        return g
+
+    @_on_device
+    def spec_start(self, cache, ids, token, K, n_limit=None, forced=False, n_max=None, n_min=None):
+        """Arm the verify-step capture of a state for a run: `ids` (the ids in the cache, prompt first: st.offset of them) and
+        `token` (the newest token, not yet in the cache) become ctx with ONE host -> device copy, the first draft is proposed by
+        p3v_ngram_propose.  n_limit: ctx never grows beyond it (default: the state's prompt + max_tokens budget).  forced: the tail
+        proposes nothing; the caller writes the drafts before every step (`spec_force`).  Returns the capture's buffers."""
+        from . import speculate
+        st = cache[0].state
+        why = self.spec_refusal(st, K)
+        if why:
+            raise ValueError(why)
+        n_max, n_min = speculate.N_MAX if n_max is None else n_max, speculate.N_MIN if n_min is None else n_min
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids).reshape(-1).astype(np.int32)
+        if ids.size != st.offset:
+            raise ValueError(f"spec_start: {ids.size} ids for a cache that holds {st.offset}")
+        budget = st.T - K                                         # a step at n writes cache rows n - 1 .. n - 1 + K
+        n_limit = budget if n_limit is None else int(n_limit)
+        if n_limit > budget or ids.size + 1 > budget:
+            raise ValueError(f"KV cache too small for verify steps up to {n_limit} tokens: capacity {st.T}, K = {K} "
+                             "(prefill with extra_tokens=K)")
+        if st.epoch != self.epoch:
+            st.graphs.clear()
+            st.epoch = self.epoch
+        key = ("spec", K, n_max, n_min)
+        g = st.graphs.get(key)
+        if g is not None and st.offset < g["bufs"]["past_lb"]:  # rewound below the captured lower bound (as greedy_step)
+            g = None
+        if g is None:
+            g = st.graphs[key] = self._build_spec_graph(st, K, n_max, n_min)
+        n = ids.size + 1
+        tok0 = int(np.asarray(token.cpu() if torch.is_tensor(token) else token).reshape(-1)[0])
+        host = torch.empty((n + ops.L.SPEC_CTL_INTS,), dtype=I32).pin_memory() if g.get("host_ctx") is None or g["host_ctx"].numel() < n + ops.L.SPEC_CTL_INTS else g["host_ctx"]
+        g["host_ctx"] = host
+        host[:ids.size] = torch.from_numpy(ids)
+        host[ids.size] = tok0
+        g["ctx"][:n].copy_(host[:n], non_blocking=True)          # the one H2D copy of the run
+        ctl = [n, 0, int(bool(forced)), 0, n_limit, 0, 0, 0]
+        g["ctl"].copy_(torch.tensor(ctl, dtype=I32))
+        g["tok"].fill_(tok0)
+        g["d_past"].fill_(st.offset)
+        g["d_step"].zero_()
+        g["n_replays"], g["forced"], g["n0"] = 0, bool(forced), n
+        if not forced:
+            ops.ngram_propose(g["ctx"], n, K, n_max, n_min, self.cfg.vocab_size, g["tok"][1:], g["ctl"][ops.L.SPEC_CTL_NDRAFT:ops.L.SPEC_CTL_NDRAFT + 1])
+        st.graphs["spec"] = g                                    # the armed capture
+        return g
+
+    @_on_device
+    def spec_force(self, cache, drafts):
+        """Forced-draft hook (tests): the next verify step checks `drafts` (at most K ids) instead of a proposal."""
+        g = cache[0].state.graphs["spec"]
+        d = [int(t) for t in drafts][:g["K"]]
+        if d:
+            g["tok"][1:1 + len(d)].copy_(torch.tensor(d, dtype=I32))
+        g["ctl"][ops.L.SPEC_CTL_NDRAFT:ops.L.SPEC_CTL_NDRAFT + 1].fill_(len(d))
+
+    @_on_device
+    def spec_step(self, cache, K, eager=False):
+        """One verify step through its captured graph (after `spec_start`): feeds the last token + up to K drafts, accepts the
+        longest run the arg-maxes confirm, emits accepted + 1 tokens into the capture's pinned `history`, records
+        {emitted, drafted, drafts} in `rec[replay]`, advances the device's cache length and proposes the next drafts -- no host
+        input, so steps replay back to back.  The host's `st.offset` is NOT advanced here: the caller adds what `rec` reports
+        (`spec_sync`).  eager=True runs the same launches outside the graph.  Returns the capture's buffers."""
+        st = cache[0].state
+        g = st.graphs.get("spec")
+        if g is None or g["K"] != K or st.epoch != self.epoch:
+            raise RuntimeError("spec_step: no armed capture for this K on this state (model.spec_start)")
+        if g["n_replays"] >= g["rec"].shape[0]:
+            raise ValueError(f"spec_step: more than {g['rec'].shape[0]} steps on a run of {st.max_tokens} tokens")
+        if eager:
+            with ops.owned_gemm_workspace(g["gemm_ws"], frozen=True):
+                g["step"]()
+        else:
+            g["graph"].launch()
+        g["n_replays"] += 1
+        return g
+
+    @_on_device
+    def spec_sync(self, cache):
+        """Wait for the steps enqueued so far and bring the host's offset up to the device's: returns the run's tokens so far
+        (a list, from the pinned history)."""
+        st = cache[0].state
+        g = st.graphs["spec"]
+        torch.cuda.current_stream().synchronize()
+        n_emit = int(g["rec"][:g["n_replays"], 0].sum())
+        st.offset = g["n0"] - 1 + (n_emit if not (n_emit and g["history"][n_emit - 1] < 0) else 0)
+        return g["history"][:n_emit].tolist()
+
     # ------------------------------------------------------------------ seeded sampling (include/p3v.h: p3v_sample_row_t)
     @_on_device
     def set_sampling(self, st, records, row0=0):
@@ -1161,8 +1318,9 @@ class Phi3VModel:
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,
-                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None, row_adapters=None, prefix=None):
+                 max_tokens=0, advance_offset=None, n_beam=1, full_logits=None, row_adapters=None, prefix=None, extra_tokens=0):
         """Phi3ForCausalLM.__call__ (phi.py:606-608) + Phi3F.__call__ (phi.py:576-592).
+        `extra_tokens` (prefill calls): cache columns beyond prompt + max_tokens, for speculative verify steps (`spec_step`).
         `row_adapters` (adapter bank only): one bank slot / name / None per batch row, written to the state's row table first
         (a prefill call's new state starts with every row at -1; later calls keep what `set_row_adapters` wrote).
         `prefix` = (entry, P) of a prefix.PrefixCache (B = 1 prefill calls only): the new state's columns [0, P) are restored from
@@ -1189,19 +1347,19 @@ class Phi3VModel:
             ids_h = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids).reshape(1, -1)
             P, kw = self._prefix_split(ids_h, prefix, dict(pixel_values=pixel_values, image_sizes=image_sizes, positions=positions))
             pixel_values, image_sizes, positions = kw.get("pixel_values"), kw.get("image_sizes"), kw.get("positions")
-            st = self._new_state(1, L, max_tokens, None, None)
+            st = self._new_state(1, L, max_tokens, None, None, extra_tokens=extra_tokens)
             cache = [LayerCache(st, i) for i in range(cfg.num_hidden_layers)]
             self._restore_prefix(st, 0, 0, prefix[0], P)
             st.offset, ids, L = P, ids[:, P:].contiguous(), L - P
         elif prefill and pixel_values is None and B == 1 and pids is None and mask is None and n_beam == 1 and not full_logits \
-                and advance_offset is None:
+                and advance_offset is None and not extra_tokens:
             got = self._prefill_captured(ids, L, max_tokens)
             if got is not None:
                 return got
         if prefill and prefix is None:
             # (before the vision tower is enqueued: the host is launch-bound through the ViT's ~280 launches, so whatever it does between
             #  the tower and the decoder -- cache allocation, its zero fill, the rotation tables -- would show as idle GPU time there)
-            st = self._new_state(B, L, max_tokens, pids, mask)
+            st = self._new_state(B, L, max_tokens, pids, mask, extra_tokens=extra_tokens)
             cache = [LayerCache(st, i) for i in range(cfg.num_hidden_layers)]
         else:
             st = cache[0].state

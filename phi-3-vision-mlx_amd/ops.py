@@ -722,6 +722,46 @@ def sample_step_end(logits, rows_params, next_tok, tok, history, d_step, d_past,
                                         _p(ticket), B, n, history.shape[1], _stream()), "sample_step_end")
 
 
+def spec_state(g, n_max, n_min):
+    """p3v_spec_state_t over the loop-state buffers of a speculative capture (model._build_spec_graph)."""
+    _chk(g["tok"], I32, "tok"), _chk(g["ctx"], I32, "ctx"), _chk(g["ctl"], I32, "ctl"), _chk(g["amax"], I32, "amax")
+    if g["ctl"].numel() < L.SPEC_CTL_INTS or g["amax"].numel() < g["tok"].numel():
+        raise ValueError("spec_state: ctl / amax too small")
+    for k in ("history", "rec"):
+        if g[k].dtype != I32 or not g[k].is_contiguous() or not (g[k].is_pinned() or g[k].is_cuda):
+            raise ValueError(f"spec_state: {k} must be contiguous int32 in pinned host (or device) memory")
+    if g["rec"].shape[-1] != L.SPEC_REC_INTS:
+        raise ValueError("spec_state: rec rows hold P3V_SPEC_REC_INTS words")
+    return L.SpecState(_p(g["tok"]), _p(g["ctx"]), _p(g["ctl"]), _p(g["amax"]), _p(g["ticket"]), _p(g["history"]), _p(g["rec"]),
+                       _p(g["d_step"]), _p(g["d_past"]), g["ctx"].numel(), g["history"].numel(), g["rec"].shape[0], int(n_max), int(n_min))
+
+
+def spec_begin(tok, table, x_out, cos_t, sin_t, d_past, cos_out, sin_out):
+    """Head of a verify step (B = 1): embedding rows of tok[0..L) + rotation rows of positions *d_past + j, one launch."""
+    _chk(tok, I32, "tok"), _chk(table, BF16, "table"), _chk(x_out, BF16, "x_out")
+    Lq, tab_t, half = tok.numel(), cos_t.shape[-2], cos_t.shape[-1]
+    if x_out.shape != (Lq, table.shape[1]) or cos_out.numel() != Lq * half or sin_out.numel() != Lq * half or cos_t.shape[0] != 1:
+        raise ValueError("spec_begin: x_out [L, H], cos_out / sin_out [1, L, half], one table row")
+    L.check(L.lib().p3v_spec_begin(_p(tok), _p(table), _p(x_out), _p(cos_t), _p(sin_t), _p(d_past), _p(cos_out), _p(sin_out),
+                                   Lq, table.shape[1], table.shape[0], tab_t, half, _stream()), "spec_begin")
+
+
+def spec_end(logits, state):
+    """Tail of a verify step: arg-max of the L rows, acceptance, history / record stores, counters, the next proposal."""
+    _chk(logits, BF16, "logits")
+    Lq, n = logits.shape
+    L.check(L.lib().p3v_spec_end(_p(logits), C.byref(state), Lq, n, _stream()), "spec_end")
+
+
+def ngram_propose(ctx, n, K, n_max, n_min, vocab, draft, n_draft):
+    """Prompt-lookup proposal alone: ctx[0..n) -> draft[0 .. n_draft[0]) (speculate.propose on the device)."""
+    _chk(ctx, I32, "ctx"), _chk(draft, I32, "draft"), _chk(n_draft, I32, "n_draft")
+    if n > ctx.numel() or draft.numel() < K or n_draft.numel() < 1:
+        raise ValueError("ngram_propose: n beyond ctx, or draft / n_draft too small")
+    L.check(L.lib().p3v_ngram_propose(_p(ctx), int(n), int(K), int(n_max), int(n_min), int(vocab), _p(draft), _p(n_draft), _stream()),
+            "ngram_propose")
+
+
 def store_token(tok, history, d_step, tok_next=None):
     B, max_steps = history.shape
     L.check(L.lib().p3v_store_token(_p(tok), _p(history), _p(d_step), _p(tok_next), B, max_steps, _stream()), "store_token")

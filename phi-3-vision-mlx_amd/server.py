@@ -12,6 +12,10 @@
      tokens AND the same pictures (prefix.py).  "cache_prompt": false keeps a request's prompt out of the store (it may still
      reuse entries); responses gain "cached_tokens": [one per prompt]; GET /v1/prefix_cache returns the counters.  Without
      the flag none of this exists: no field in the response, 404 for the GET.)
+    (extension: "speculate": K (0 .. 15; default: the server's `--speculate K`, default 0) -- speculative greedy decoding on the
+     one-request path: K prompt-lookup draft tokens verified per decode step, the same text in fewer steps (api.speculative_loop).
+     The response gains "speculation": {"steps", "drafted", "accepted"}.  One prompt, greedy, no image; an explicit K > 0 anywhere
+     else -- a list of prompts, temperature > 0, a server started with --continuous or --merge -- is answered with 400.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -44,11 +48,12 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info")
 
-    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
+    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None):
         self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
         self.adapter = adapter                  # None, or one name / None per prompt
+        self.speculate, self.info = speculate, info             # draft rows per verify step (0 = off), the caller's statistics dict
         self.done, self.result, self.error = threading.Event(), None, None
 
 
@@ -99,6 +104,38 @@ def parse_adapter(request, n_prompts, known):
         if name is not None and name not in known:
             raise ValueError(f"unknown adapter {name!r}; {hint}")
     return None if all(name is None for name in a) else a
+
+
+SPECULATE_MAX = 15                              # P3V_DECODE_MAX_L - 1 draft rows
+
+
+def parse_speculate(request, n_prompts, engine, sampling=None):
+    """The "speculate" field of a request body -> K (0 = off; absent: the engine's `speculate_default`, the server's
+    --speculate flag).  ValueError (-> 400) on a wrong type or range, and for K > 0 wherever speculative decoding does not run:
+    a backend without it (the continuous engine, the merging queue), more than one prompt, a sampled request."""
+    K = request.get("speculate", None)
+    explicit = K is not None
+    if not explicit:
+        K = int(getattr(engine, "speculate_default", 0) or 0)
+    if isinstance(K, bool) or not isinstance(K, int):
+        raise ValueError(f"speculate must be an integer 0 .. {SPECULATE_MAX}, got {type(K).__name__}")
+    if not 0 <= K <= SPECULATE_MAX:
+        raise ValueError(f"speculate must be 0 .. {SPECULATE_MAX} (draft tokens per verify step), got {K}")
+    if K == 0:
+        return 0
+    why = None
+    if not getattr(engine, "speculate", False):
+        why = ("speculative decoding runs on the one-request path only: this server was started with --continuous or --merge "
+               "(per-row acceptance in the batched engine is not built)")
+    elif n_prompts != 1:
+        why = "speculative decoding takes one prompt per request (B = 1)"
+    elif sampling is not None and any(float(r["temperature"]) > 0 for r in sampling):
+        why = "speculative decoding is greedy only (temperature must be 0)"
+    if why is None:
+        return K
+    if explicit:
+        raise ValueError(why)
+    return 0                                    # (the server-wide default applies where it can; only an explicit field is refused)
 
 
 def parse_cache_prompt(request):
@@ -192,7 +229,10 @@ class EngineQueue:
     """Single consumer in front of a non-re-entrant `generate_fn(prompts: list[str], max_tokens) -> str | list[str]`."""
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
-                 length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=()):
+                 length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=(), speculate=False,
+                 speculate_default=0):
+        # speculate: generate_fn takes `speculate=K, spec_info=dict` (one prompt, greedy); never with merge (B > 1 batches)
+        self.speculate, self.speculate_default = bool(speculate) and not merge, int(speculate_default)
         self.adapter_names = list(adapter_names)                # what generate_fn's `adapter` keyword may name (GET /v1/adapters)
         # sharded_fn(prompts, images) -> True when generate_fn would run that request on the batch-sharded path (dist.py), which
         # does not sample: the handler answers 400 to a sampled request bound there
@@ -206,8 +246,8 @@ class EngineQueue:
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter)
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -263,7 +303,12 @@ class EngineQueue:
             flat = [p for j in group for p in j.prompts]
             try:
                 kw = {} if first.adapter is None else {"adapter": first.adapter}
-                if first.sampling is not None:                  # (sampled jobs merge only with sampled jobs: one record per row)
+                if first.speculate:                             # (one prompt, never merged: self.speculate excludes merge)
+                    stats = {}
+                    out = self.generate_fn(flat, first.max_tokens, first.images, speculate=first.speculate, spec_info=stats, **kw)
+                    if first.info is not None:
+                        first.info["speculation"] = {k: int(stats.get(k, 0)) for k in ("steps", "drafted", "accepted")}
+                elif first.sampling is not None:                  # (sampled jobs merge only with sampled jobs: one record per row)
                     out = self.generate_fn(flat, first.max_tokens, first.images, sampling=[r for j in group for r in j.sampling], **kw)
                 elif kw:
                     out = self.generate_fn(flat, first.max_tokens, first.images, **kw)
@@ -328,7 +373,13 @@ def make_handler(engine, image_policy=None):
                 sampling = parse_sampling(request, len(prompts))
                 adapter = parse_adapter(request, len(prompts), known_adapters(engine))
                 cache_prompt = parse_cache_prompt(request)
+                speculate = parse_speculate(request, len(prompts), engine, sampling)
                 sharded = getattr(engine, "sharded_fn", None)
+                if speculate and sharded is not None and sharded(prompts, images):
+                    if "speculate" in request:
+                        raise ValueError("speculative decoding is not available on the batch-sharded path (image requests and "
+                                         "process groups of the queue server)")
+                    speculate = 0
                 if sampling is not None and sharded is not None and sharded(prompts, images):
                     raise ValueError("sampling is not available on the batch-sharded path (image requests and process groups of "
                                      "the queue server); run the server with --continuous to sample, or send temperature 0")
@@ -340,7 +391,11 @@ def make_handler(engine, image_policy=None):
                 return
             info = None
             try:
-                if prefix_counters(engine) is not None:         # a backend with a prefix store: it reports what each prompt reused
+                if speculate:
+                    info = {}
+                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
+                    responses = engine.submit(prompts, max_tokens, images, speculate=speculate, info=info, **kw)
+                elif prefix_counters(engine) is not None:         # a backend with a prefix store: it reports what each prompt reused
                     info = {}
                     kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("cache_prompt", cache_prompt)) if v is not None}
                     responses = engine.submit(prompts, max_tokens, images, info=info, **kw)
@@ -357,7 +412,9 @@ def make_handler(engine, image_policy=None):
             out = {"model": MODEL_NAME, "responses": responses}
             if sampling is not None:
                 out["seeds"] = [r["seed"] for r in sampling]
-            if info is not None:
+            if speculate:
+                out["speculation"] = info.get("speculation", {"steps": 0, "drafted": 0, "accepted": 0})
+            elif info is not None:
                 out["cached_tokens"] = list(info.get("cached_tokens", [0] * len(prompts)))
             self._send(200, out)
 
@@ -429,7 +486,7 @@ def serve_continuous(engine, port=8000, host="127.0.0.1", image_policy=None, **k
 
 
 def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=False, host="127.0.0.1", image_policy=None,
-        long_window=0, slots=8, adapters=None, prefix_cache_gb=0.0):
+        long_window=0, slots=8, adapters=None, prefix_cache_gb=0.0, speculate=0):
     """adapters: {name: adapter directory} -- the server's adapter bank (every rank of a fleet loads the same one).
     prefix_cache_gb (with continuous): byte budget of the prompt prefix store of EACH engine (0 = off)."""
     from .api import _apply_chat_template, generate, load, load_adapters
@@ -472,8 +529,11 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         import torch.distributed as dist
         return images is not None or (dist.is_available() and dist.is_initialized())
 
-    def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None):
+    def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None):
         import torch.distributed as dist
+        if speculate:                                                # (one prompt, greedy, no image: the handler saw to it)
+            return generate(prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, speculate=speculate, spec_info=spec_info,
+                            **({} if adapter is None else {"adapter": adapter[0]}))
         if sampling is not None or adapter is not None:              # (the handler kept these requests off the sharded path)
             kw = {} if sampling is None else {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
             if adapter is not None:
@@ -491,7 +551,8 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return len(processor.tokenizer(_apply_chat_template(prompt, None, False)[0]).input_ids)
 
     httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
-                          image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}))
+                          image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True,
+                          speculate_default=speculate)
     print(f"Starting server on port {port}")
     try:
         httpd.serve_forever()
@@ -516,6 +577,9 @@ if __name__ == "__main__":
     ap.add_argument("--prefix-cache-gb", type=float, default=0.0, metavar="G",
                     help="with --continuous: keep up to G GiB of prompt-prefix K/V per engine and reuse it for requests that start with "
                          "the same tokens and pictures (393 KB per token at full size: ~1 GB per cached image)")
+    ap.add_argument("--speculate", type=int, default=0, metavar="K",
+                    help="default of the request field \"speculate\": verify K prompt-lookup draft tokens per decode step (one-request "
+                         "path, greedy; 0 = off).  Not with --continuous / --merge")
     ap.add_argument("--host", default="127.0.0.1", help='interface to bind ("" = all, as the reference)')
     ap.add_argument("--image-dir", default=None, help="allow `images` entries naming files under this directory")
     ap.add_argument("--image-host", action="append", default=[], help="allow `images` URLs on this host (repeatable)")
@@ -526,6 +590,10 @@ if __name__ == "__main__":
         if not sep or not name or not path or name in bank:
             ap.error(f"--adapter takes NAME=DIR with distinct names, got {spec!r}")
         bank[name] = path
+    if a.speculate and (a.continuous or a.merge):
+        ap.error("--speculate runs on the one-request path: not with --continuous or --merge")
+    if not 0 <= a.speculate <= SPECULATE_MAX:
+        ap.error(f"--speculate takes 0 .. {SPECULATE_MAX}")
     if a.prefix_cache_gb and not a.continuous:
         ap.error("--prefix-cache-gb needs --continuous")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:               # python -m torch.distributed.run --nproc-per-node N -m ...server --continuous
@@ -540,4 +608,4 @@ if __name__ == "__main__":
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())   # (fewer GPUs than ranks: shared)
         dist.init_process_group("gloo")                          # requests and token lists only: host memory (fleet.py)
     run(a.port, "tiny" if a.synthetic and a.tiny else a.synthetic, a.blind, a.merge, a.continuous, a.host, ImagePolicy(a.image_dir, a.image_host), a.long_window, a.slots, bank,
-        a.prefix_cache_gb)
+        a.prefix_cache_gb, a.speculate)
