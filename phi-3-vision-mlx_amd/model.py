@@ -107,6 +107,41 @@ class CacheState:
         self.graphs = {}
         self.epoch = None                                       # model.epoch the graphs were captured under
         self.shared = {"dirty": False}                          # shared by the per-request views of a captured-prefill entry (copy.copy)
+        self.slots = False                                      # a slot state of the continuous-batching engine (model.new_slot_state)
+        self.serving = False                                    # owned by a long-lived server (engine.py): see model._split_plan
+        self.fresh_rows = False                                 # a rows_view whose columns left of its offset hold nothing its rows may see
+        self.row_adapter = None                                 # adapter bank: int32 [B] slot per row, made on first use (model._state_rows)
+        self.sample_rows = None                                 # sampling records int32 [B, 6] (model.set_sampling)
+
+    def rows_view(self, rows, offset, S):
+        """Batch rows `rows` (a slice) as a cache of their own at `offset`, for a prompt of S tokens (model.prefill_slot): the same
+        buffers sliced, no captured graphs, none of the slot state's roles (slots, serving, sampling records; the caller names the
+        rows' adapters).  fresh_rows: columns left of `offset` hold nothing these rows may see (pad_len >= offset)."""
+        view = copy.copy(self)
+        view.B = rows.stop - rows.start
+        view.S = S
+        view.offset = offset
+        view.graphs = {}
+        view.fresh_rows = True
+        view.slots = False
+        view.serving = False
+        view.row_adapter = None
+        view.sample_rows = None
+        view.mlx4 = False                                       # (the view carries k / v alone, never the 4-bit prompt codes)
+        view.cos = self.cos[rows]
+        view.sin = self.sin[rows]
+        view.pad_len = self.pad_len[rows]
+        if self.quantized:
+            view.k8 = self.k8[:, rows]
+            view.v8 = self.v8[:, rows]
+            view.ks = self.ks[:, rows]
+            view.vs = self.vs[:, rows]
+            view.k_tmp = self.k_tmp[rows]
+            view.v_tmp = self.v_tmp[rows]
+        else:
+            view.k = self.k[:, rows]
+            view.v = self.v[:, rows]
+        return view
 
     def mark_dirty(self):
         """An unrecovered failed step may have left NaN rows beyond the offset and half-armed buffers in the decode graph: a
@@ -277,10 +312,9 @@ class Phi3VModel:
 
     def _state_rows(self, st):
         """The state's row table (int32 [B] on the device, -1 = no adapter), made on first use."""
-        ra = getattr(st, "row_adapter", None)
-        if ra is None:
-            ra = st.row_adapter = torch.full((st.B,), -1, dtype=I32, device=self.device)
-        return ra
+        if st.row_adapter is None:
+            st.row_adapter = torch.full((st.B,), -1, dtype=I32, device=self.device)
+        return st.row_adapter
 
     @_on_device
     def set_row_adapters(self, st, adapters, row0=0):
@@ -307,23 +341,27 @@ class Phi3VModel:
         self._state_rows(st)[row0:row0 + len(slots)].copy_(torch.tensor(slots, dtype=I32))
         return st
 
+    def _lora_scratch(self, M, specs):
+        """The adapter scratch tensors of one projection call on M rows, one per (tag, shape, dtype) of `specs`."""
+        if M <= ops.GEMV_MAX_M:                                 # decode-sized: persistent buffers (graph replays read them)
+            for tag, shape, dtype in specs:
+                if (tag,) + shape not in self._lora_tmp:
+                    self._lora_tmp[(tag,) + shape] = torch.empty(shape, dtype=dtype, device=self.device)
+            return [self._lora_tmp[(tag,) + shape] for tag, shape, _ in specs]
+        # prefill-sized: carved out of one grow-only allocation at 256-byte offsets, not one set per prompt length (a server
+        # would leak VRAM)
+        sizes = [math.prod(shape) * dtype.itemsize for _, shape, dtype in specs]
+        offs = [0]
+        for nb in sizes:
+            offs.append((offs[-1] + nb + 255) // 256 * 256)
+        if self._lora_flat is None or self._lora_flat.numel() < offs[-1]:
+            self._lora_flat = torch.empty(offs[-1], dtype=torch.uint8, device=self.device)
+        return [self._lora_flat[o:o + nb].view(dtype).view(shape) for o, nb, (_, shape, dtype) in zip(offs, sizes, specs)]
+
     def _proj_bank(self, x, key, table, r_max, epilogue, resid, norm_w, out, h):
         M, K = x.shape
         N, S = self._weight_shape(key)[0], ops.lora_slices(K)
-        if M <= ops.GEMV_MAX_M:                                 # decode-sized: persistent buffers (graph replays read them)
-            def buf(tag, shape, dtype):
-                t_ = self._lora_tmp.get((tag,) + shape)
-                if t_ is None:
-                    t_ = self._lora_tmp[(tag,) + shape] = torch.empty(shape, dtype=dtype, device=self.device)
-                return t_
-            y, t = buf("y", (M, N), BF16), buf("t", (M, S, r_max), F32)
-        else:                                                   # prefill-sized: the one grow-only allocation of _proj
-            o1 = (M * N * 2 + 255) // 256 * 256
-            nb = o1 + M * S * r_max * 4
-            if self._lora_flat is None or self._lora_flat.numel() < nb:
-                self._lora_flat = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            y = self._lora_flat[:M * N * 2].view(BF16).view(M, N)
-            t = self._lora_flat[o1:o1 + M * S * r_max * 4].view(F32).view(M, S, r_max)
+        y, t = self._lora_scratch(M, [("y", (M, N), BF16), ("t", (M, S, r_max), F32)])
         rows = self._rows_cur
         if rows is None or rows.numel() != M:
             raise RuntimeError(f"{key}: no row table for {M} rows (an adapter bank serves the decoder stack only)")
@@ -349,22 +387,7 @@ class Phi3VModel:
             return self._proj_frozen(x, key, epilogue, resid, norm_w, out, h)
         a, b, scale = ad
         M, K, N, r = x.shape[0], x.shape[1], b.shape[1], a.shape[1]
-        if M <= ops.GEMV_MAX_M:                                 # decode-sized: persistent buffers (graph replays read them)
-            def buf(tag, shape, dtype):
-                t_ = self._lora_tmp.get((tag,) + shape)
-                if t_ is None:
-                    t_ = self._lora_tmp[(tag,) + shape] = torch.empty(shape, dtype=dtype, device=self.device)
-                return t_
-            hbuf, y, t = buf("h", (M, K), BF16), buf("y", (M, N), BF16), buf("t", (M, r), F32)
-        else:                                                   # prefill-sized: carved out of one grow-only allocation,
-            nb = (M * K + M * N) * 2 + M * r * 4 + 512          # not one set per prompt length (a server would leak VRAM)
-            if self._lora_flat is None or self._lora_flat.numel() < nb:
-                self._lora_flat = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            f, o1 = self._lora_flat, (M * K * 2 + 255) // 256 * 256
-            o2 = o1 + (M * N * 2 + 255) // 256 * 256
-            hbuf = f[:M * K * 2].view(BF16).view(M, K)
-            y = f[o1:o1 + M * N * 2].view(BF16).view(M, N)
-            t = f[o2:o2 + M * r * 4].view(F32).view(M, r)
+        hbuf, y, t = self._lora_scratch(M, [("h", (M, K), BF16), ("y", (M, N), BF16), ("t", (M, r), F32)])
         if norm_w is not None:                                  # the adapter needs the normalised input itself
             x = ops.rmsnorm(x, norm_w, self.cfg.rms_norm_eps, out=hbuf)
         self._proj_frozen(x, key, EPI_NONE, None, None, y, None)
@@ -480,22 +503,30 @@ class Phi3VModel:
         e["graph"].launch()
         return e["bufs"]["x"]
 
-    def _build_vit_graph(self, pix):
-        dev = self.device
-        e = dict(pix=torch.empty_like(pix), bufs=self._clip_bufs(pix.shape[0]), ws={})
-        e["pix"].copy_(pix)
-        with ops.owned_gemm_workspace(e["ws"], frozen=False):
-            self._clip_body(e["pix"], e["bufs"])                 # warm-up (sizes whatever workspace the graph owns)
+    def _capture(self, run, ws):
+        """`run()` -- a launch sequence over buffers its caller owns -- as one ops.Graph: the capture protocol of every captured
+        path of the model (vision tower, short-prompt prefill, greedy / sampled / verify decode step).  A warm-up run first (sets
+        func attributes, pages code in, sizes the split-K GEMM workspace in `ws`, a dict the caller keeps alive as long as the
+        graph), then the capture on a side stream with that workspace frozen: nothing may be allocated under capture, and the
+        pointer is baked into the graph (ops.owned_gemm_workspace).  `run` executes twice: loop state the warm-up must not
+        advance is the builder's to reset or restore."""
+        with ops.owned_gemm_workspace(ws, frozen=False):
+            run()
         torch.cuda.synchronize()
         graph = ops.Graph()
-        side = torch.cuda.Stream(device=dev)
+        side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.owned_gemm_workspace(e["ws"], frozen=True):
+        with torch.cuda.stream(side), ops.owned_gemm_workspace(ws, frozen=True):
             graph.begin()
-            self._clip_body(e["pix"], e["bufs"])
+            run()
             graph.end()
         torch.cuda.current_stream().wait_stream(side)
-        e["graph"] = graph
+        return graph
+
+    def _build_vit_graph(self, pix):
+        e = dict(pix=torch.empty_like(pix), bufs=self._clip_bufs(pix.shape[0]), ws={})
+        e["pix"].copy_(pix)
+        e["graph"] = self._capture(lambda: self._clip_body(e["pix"], e["bufs"]), e["ws"])
         return e
 
     def _clip_body(self, pix, B_):
@@ -571,26 +602,36 @@ class Phi3VModel:
     # ------------------------------------------------------------------ per-prompt state
     ROPE_TABLE_ENTRIES = 8
 
+    def _rope_factors(self, n_tokens):
+        """The su-scaled RoPE factors for a context of n_tokens: ONE short / long choice per prompt (phi.py:492), long beyond the
+        original context length."""
+        cfg = self.cfg
+        return cfg.rope_scaling["long_factor" if n_tokens > cfg.original_max_position_embeddings else "short_factor"]
+
+    def _inv_freq(self, n_tokens):
+        """Inverse frequencies (f32 [hd / 2] on the host) of the su-scaled RoPE for a context of n_tokens."""
+        return 1.0 / (torch.tensor(self._rope_factors(n_tokens), dtype=F32)
+                      * (torch.tensor(float(self.cfg.rope_theta), dtype=F32) ** (torch.arange(0, self.hd, 2, dtype=F32) / self.hd)))
+
     def _new_state(self, B, S, max_tokens, pids, mask, shared_tables=True, extra_tokens=0):
         cfg = self.cfg
         # extra_tokens: columns beyond prompt + max_tokens (a speculative verify step writes K/V rows up to offset + K); the
         # short / long RoPE-factor choice below stays on prompt + max_tokens, as the plain path takes it
         st = CacheState(cfg, B, S, max_tokens + int(extra_tokens) if max_tokens > 0 else max_tokens, self.device)
         self._states.add(st)
-        L_all = S + max_tokens                                  # reference sizes tables with max_tokens as given
         half = self.hd // 2
-        su = cfg.rope_scaling["long_factor"] if L_all > cfg.original_max_position_embeddings else cfg.rope_scaling["short_factor"]
+        L_all = S + max_tokens                                  # reference sizes tables with max_tokens as given
+        su = self._rope_factors(L_all)
+        if mask is not None:
+            st.pad_len = torch.as_tensor((np.asarray(mask) == 0).sum(axis=1).astype(np.int32)).to(self.device)
         # Prompts without explicit position ids (every unpadded request) of one geometry rotate by the same table: it is built once
         # and shared read-only between their states (a server's requests repeat a few geometries; building it costs three small host ->
         # device copies and a launch in front of every prefill).  Slot states write per-row tables: they get their own.
         tkey = (B, st.T, tuple(float(v) for v in su), float(cfg.rope_theta), rope_scaling_factor(cfg), self.hd) if pids is None and shared_tables else None
         if tkey is not None and tkey in self._rope_tables:
             st.cos, st.sin = self._rope_tables[tkey]
-            if mask is not None:
-                st.pad_len = torch.as_tensor((np.asarray(mask) == 0).sum(axis=1).astype(np.int32)).to(self.device)
             return st
-        inv_freq = 1.0 / (torch.tensor(su, dtype=F32) * (torch.tensor(float(cfg.rope_theta), dtype=F32)
-                                                        ** (torch.arange(0, self.hd, 2, dtype=F32) / self.hd)))
+        inv_freq = self._inv_freq(L_all)
         T = st.T
         if pids is None:
             pos = torch.arange(T, dtype=F32)[None].expand(B, T)
@@ -605,9 +646,6 @@ class Phi3VModel:
             if len(self._rope_tables) >= self.ROPE_TABLE_ENTRIES:
                 self._rope_tables.pop(next(iter(self._rope_tables)))
             self._rope_tables[tkey] = (st.cos, st.sin)
-        if mask is not None:
-            m = np.asarray(mask)
-            st.pad_len = torch.as_tensor((m == 0).sum(axis=1).astype(np.int32)).to(self.device)
         return st
 
     # ------------------------------------------------------------------ slot state of the continuous-batching engine
@@ -652,9 +690,7 @@ class Phi3VModel:
             raise ValueError(f"prompt of {S} tokens does not fit left of column {st.offset}")
         pads = torch.as_tensor(st.offset - lens, dtype=torch.int32)
         half = self.hd // 2
-        su = cfg.rope_scaling["long_factor" if st.T > cfg.original_max_position_embeddings else "short_factor"]   # as _new_state
-        inv_freq = 1.0 / (torch.tensor(su, dtype=F32)
-                          * (torch.tensor(float(cfg.rope_theta), dtype=F32) ** (torch.arange(0, self.hd, 2, dtype=F32) / self.hd)))
+        inv_freq = self._inv_freq(st.T)                          # (a slot state's T is its window: new_slot_state)
         rows = slice(row, row + n)
         uniq = np.unique(lens)
         for L_ in uniq:                                          # one table per distinct length
@@ -663,22 +699,15 @@ class Phi3VModel:
             for i in np.nonzero(lens == L_)[0]:
                 st.cos[row + i].copy_(cos.view(st.T, half)), st.sin[row + i].copy_(sin.view(st.T, half))
         st.pad_len[rows].copy_(pads.to(self.device))
-        view = CacheState.__new__(CacheState)                   # these rows as an n-row cache at offset `win`
-        view.__dict__.update(B=n, S=S, max_tokens=st.max_tokens, T=st.T, Tp=st.Tp, quantized=st.quantized, offset=win, graphs={},
-                             epoch=self.epoch, cos=st.cos[rows], sin=st.sin[rows], pad_len=st.pad_len[rows],
-                             fresh_rows=True)    # columns left of `win` hold nothing these rows may see (pad_len >= win)
-        if st.quantized:
-            view.__dict__.update(k8=st.k8[:, rows], v8=st.v8[:, rows], ks=st.ks[:, rows], vs=st.vs[:, rows],
-                                 k_tmp=st.k_tmp[rows], v_tmp=st.v_tmp[rows])
-        else:
-            view.__dict__.update(k=st.k[:, rows], v=st.v[:, rows])
+        view = st.rows_view(rows, win, S)                        # these rows as an n-row cache at offset `win`
+        view.epoch = self.epoch
         if self._bank:
             view.row_adapter = self._state_rows(st)[rows]        # (the rows' adapters: set_row_adapters BEFORE this prefill)
         kw = {k: v for k, v in inputs.items() if k in ("pixel_values", "image_sizes", "positions")}
         if prefix is not None:
             P, kw = self._prefix_split(ids, prefix, kw)
             self._restore_prefix(st, row, win, prefix[0], P)
-            del view.fresh_rows                                  # columns [win, win + P) hold keys these rows DO see
+            view.fresh_rows = False                              # columns [win, win + P) hold keys these rows DO see
             view.offset, ids = win + P, ids[:, P:]
         logits, _ = self(input_ids=ids, cache=[LayerCache(view, i) for i in range(cfg.num_hidden_layers)], full_logits=False, **kw)
         assert view.offset == st.offset
@@ -687,7 +716,7 @@ class Phi3VModel:
 
     # ------------------------------------------------------------------ prompt prefix cache (prefix.py)
     def _state_kv(self, st):
-        if getattr(st, "mlx4", False):
+        if st.mlx4:
             raise ValueError('cache_format="mlx4" states are never captured or restored')
         return (st.k8, st.v8, st.ks, st.vs) if st.quantized else (st.k, st.v)
 
@@ -737,16 +766,43 @@ class Phi3VModel:
     @_on_device
     def decode_graph(self, st):
         """The captured greedy step of a state (built on first use): its `tok` / `next_tok` / `d_past` device buffers."""
+        return self._greedy_capture(st)
+
+    def _sync_epoch(self, st):
+        """Drop the state's captures if the adapters changed since they were made: they bake stale pointers in."""
         if st.epoch != self.epoch:
             st.graphs.clear()
             st.epoch = self.epoch
+
+    def _greedy_capture(self, st):
+        """The state's greedy capture (`st.graphs["greedy"]`, see _build_decode_graph) of the current epoch: built on first use,
+        and rebuilt if the cache was rewound below the lower bound it was captured with."""
+        self._sync_epoch(st)
         g = st.graphs.get("greedy")
-        if g is None:
+        if g is None or st.offset < g["bufs"]["past_lb"]:
             g = st.graphs["greedy"] = self._build_decode_graph(st)
             g["host_tok"] = None
         return g
 
     # ------------------------------------------------------------------ decoder stack
+    def _plan(self, st, B, L, fuse_o, captured=False):
+        """The buffers and the attention plan of a pass over B x L rows of a state.  fuse_o: also plan the fused attention + o_proj
+        launch (_plan_fused_oproj; it sets bufs["fuse_o"]).  captured:
+        the plan is for a captured step, which reads the cache length from the device -- it carries the step's staging rows for the
+        rotation tables and `past_lb`, the host's lower bound of that length: the cache only grows under a captured step (the
+        capture is rebuilt if it is ever found below the bound); a slot state's column moves both ways (engine.py), so it gets none."""
+        bufs = self._alloc_bufs(B, L)
+        # split plan from the cache CAPACITY, eager or captured: same kernel, same split boundaries -> eager and replayed steps
+        # agree bit for bit
+        self._split_plan(bufs, B, L, st.Tp, st.quantized, serving=st.serving or self.serving)
+        if captured:
+            bufs["past_lb"] = -1 if st.slots else int(st.offset)
+            bufs["rope_cos"] = torch.empty((B, L, self.hd // 2), dtype=F32, device=self.device)
+            bufs["rope_sin"] = torch.empty_like(bufs["rope_cos"])
+        if fuse_o:
+            self._plan_fused_oproj(bufs, B, L, st.Tp, st.quantized)
+        return bufs
+
     def _alloc_bufs(self, B, L):
         cfg = self.cfg
         nh, nkv, hd, H, I = cfg.num_attention_heads, cfg.num_key_value_heads, self.hd, cfg.hidden_size, cfg.intermediate_size
@@ -846,17 +902,19 @@ class Phi3VModel:
         M = B * L
         skinny = M <= 8 or (M <= ops.GEMV_MAX_M and cfg.hidden_size % 512 == 0)   # weight-streaming projections
         scale = hd ** -0.5
+        decode = L <= ops.L.DECODE_MAX_L                        # decode-shaped rows: one fused attention launch (+ merge) per layer
         if bufs is None:
-            bufs = self._alloc_bufs(B, L)
-            self._split_plan(bufs, B, L, st.Tp, st.quantized, serving=getattr(st, "serving", False) or self.serving)   # the CAPACITY, as the captured graph plans: same kernel, same
-                                                                # split boundaries -> eager and replayed steps agree bit for bit
-            if L <= ops.L.DECODE_MAX_L and n_beam == 1:
-                self._plan_fused_oproj(bufs, B, L, st.Tp, st.quantized)
+            bufs = self._plan(st, B, L, fuse_o=decode and n_beam == 1)
         q, o, qkv, a, h, n_split, ws = (bufs[k] for k in ("q", "o", "qkv", "a", "h", "n_split", "ws"))
+        fuse_o, attn_merge = bufs.get("fuse_o", False), bufs.get("attn_merge", False)
+        if decode and d_past is not None:                       # graph replay: rotation rows staged once per step by the caller
+            rc, rs, rb = bufs["rope_cos"], bufs["rope_sin"], L
+        elif decode:                                            # eager: views into the prompt tables at `past`
+            rc, rs, rb = st.cos[:, past:], st.sin[:, past:], st.T
         if self._bank:                                          # adapter bank: one table entry per row of x (token rows share their request's)
             ra = self._state_rows(st)                           # (a captured step reads the state's own table: L = 1, no copy)
             self._rows_cur = ra if M == st.B else ra.repeat_interleave(M // st.B)
-        mlx4 = getattr(st, "mlx4", False)
+        mlx4 = st.mlx4
         if (st.quantized or mlx4) and n_beam > 1:
             raise NotImplementedError("Beam Search is not yet compatible with Quantized Cache")       # as phi.py:525
         mlx4_first = mlx4 and past == 0 and st.mlx4_tokens == 0 and L <= st.k4.shape[3]             # the call that fills the cache (phi.py:531-533)
@@ -871,10 +929,10 @@ class Phi3VModel:
             # its own epilogue (ops.gemm_qkv: bit-identical to the projection + rope_kv_append, one launch sequence instead of two).
             fused_qkv = False
             k_w = p + "self_attn.qkv_proj.weight"
-            if (L > ops.L.DECODE_MAX_L and n_beam == 1 and k_w in w and k_w not in self.adapters and k_w not in self._bank and not mlx4_first
+            if (not decode and n_beam == 1 and k_w in w and k_w not in self.adapters and k_w not in self._bank and not mlx4_first
                     and (M >= 1024 or M <= 256) and os.environ.get("P3V_QKV_FUSE", "1") != "0"):
                 kd, vd = (st.k_tmp, st.v_tmp) if st.quantized else (st.k[i], st.v[i])
-                if not (st.quantized and past > 0 and not getattr(st, "fresh_rows", False)):
+                if not (st.quantized and past > 0 and not st.fresh_rows):
                     hn = h if normed_in else ops.rmsnorm(x, w[p + "input_layernorm.weight"], eps, out=h)
                     normed_in = True                            # (`h` holds the normalised input now, whatever the fused call answers)
                     fused_qkv = ops.gemm_qkv(hn, w[k_w], st.cos, st.sin, q, kd, vd, B, L, nh, nkv, hd, past, st.Tp, True, st.T, 1,
@@ -892,22 +950,20 @@ class Phi3VModel:
                     self._proj(h, p + "self_attn.qkv_proj.weight", out=qkv)
                 else:
                     self._proj(x, p + "self_attn.qkv_proj.weight", norm_w=w[p + "input_layernorm.weight"], out=qkv, h=h)
+            o_i = o
+            if fuse_o:                                          # (B = L = 1 plans only) + o_proj + residual in the attention's launch,
+                o_i, o_other = (bufs["o_f"], bufs["o_f2"]) if i % 2 == 0 else (bufs["o_f2"], bufs["o_f"])   # x += bf16(W_o . o)
             if st.quantized:
-                if L <= ops.L.DECODE_MAX_L:
-                    if d_past is not None:
-                        rc, rs, rb = bufs["rope_cos"], bufs["rope_sin"], L
-                    else:
-                        rc, rs, rb = st.cos[:, past:], st.sin[:, past:], st.T
-                    kq, o_i = {}, o
-                    if bufs.get("fuse_o", False):               # + o_proj (e4m3) + residual in the same launch
-                        o_i, o_other = (bufs["o_f"], bufs["o_f2"]) if i % 2 == 0 else (bufs["o_f2"], bufs["o_f"])
+                if decode:
+                    kw_o = {}
+                    if fuse_o:                                  # (o_proj on e4m3 weights)
                         w8o = self.w8[p + "self_attn.o_proj.weight"]
-                        kq = dict(o_proj_w8=w8o[0], o_proj_scale=w8o[1], o_proj_x=x, o_rearm=o_other)
-                    ops.attention_decode_q8(qkv, rc, rs, rb, st.k8[i], st.v8[i], st.ks[i], st.vs[i], o_i, B, L, nh, nkv, hd, scale,
-                                            past, st.Tp, ws, n_split, pad_len=st.pad_len, d_past=d_past,
-                                            merge_in_launch=bufs.get("attn_merge", False), **kq)
+                        kw_o = dict(o_proj_w8=w8o[0], o_proj_scale=w8o[1], o_proj_x=x, o_rearm=o_other)
+                    ops.attention_decode_q8(qkv, rc, rs, rb, st.k8[i], st.v8[i], st.ks[i], st.vs[i], o_i, B, L, nh, nkv,
+                                            hd, scale, past, st.Tp, ws, n_split, pad_len=st.pad_len, d_past=d_past,
+                                            merge_in_launch=attn_merge, **kw_o)
                 else:                                           # prefill: exact attention, quantised copy stored
-                    if past > 0 and not getattr(st, "fresh_rows", False):   # long cached call (constrain with > 16 tokens): attend on a
+                    if past > 0 and not st.fresh_rows:          # long cached call (constrain with > 16 tokens): attend on a
                         ops.kv_dequantize(st.k8[i], st.v8[i], st.ks[i], st.vs[i], st.k_tmp, st.v_tmp, past)   # dequantised copy
                     if not fused_qkv:
                         ops.rope_kv_append(qkv, st.cos, st.sin, q, st.k_tmp, st.v_tmp, B, L, nh, nkv, hd, past, st.Tp, True, st.T, 1,
@@ -920,26 +976,17 @@ class Phi3VModel:
                 ops.attention(q, o, B, L, nh, nkv, hd, scale, True, k_new=k_new, v_new=v_new, new_t=Lp, past=past,
                               k_past=st.k[i], v_past=st.v[i], past_t=st.Tp, past_div=n_beam, pad_len=st.pad_len,
                               pad_div=n_beam, ws=ws, n_split=n_split)
-            elif L <= ops.L.DECODE_MAX_L:                       # decode-shaped step: one fused launch (+ merge)
-                if d_past is not None:                          # graph replay: rows staged once per step by the caller
-                    rc, rs, rb = bufs["rope_cos"], bufs["rope_sin"], L
-                else:                                           # eager: views into the prompt tables at `past`
-                    rc, rs, rb = st.cos[:, past:], st.sin[:, past:], st.T
-                # (captured step: `past` is read from d_past; the host value passed along is a LOWER BOUND of it -- the kernel fetches
-                #  tiles below it at once and lets the others wait for the length, so tiles beyond the live keys cost nothing)
-                fuse_o = bufs.get("fuse_o", False)
-                if fuse_o:                                      # + o_proj + residual in the same launch: x += bf16(W_o . o)
-                    o_i, o_other = (bufs["o_f"], bufs["o_f2"]) if i % 2 == 0 else (bufs["o_f2"], bufs["o_f"])
+            elif decode:
+                kw_o = {}
+                if fuse_o:                                      # (o_proj on bf16 or 4-bit weights)
                     q4o = self.w4.get(p + "self_attn.o_proj.weight")
                     kw_o = dict(o_proj_w=q4o[0], o_proj_sb=q4o[1]) if q4o is not None else dict(o_proj_w=w[p + "self_attn.o_proj.weight"])
-                    ops.attention_decode(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, L, nh, nkv, hd, scale,
-                                         past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split,
-                                         pad_len=st.pad_len, d_past=d_past, merge_in_launch=bufs.get("attn_merge", False), o_proj_x=x,
-                                         o_rearm=o_other, **kw_o)
-                else:
-                    ops.attention_decode(qkv, rc, rs, rb, st.k[i], st.v[i], o, B, L, nh, nkv, hd, scale,
-                                         past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split,
-                                         pad_len=st.pad_len, d_past=d_past, merge_in_launch=bufs.get("attn_merge", False))
+                    kw_o.update(o_proj_x=x, o_rearm=o_other)
+                # (captured step: `past` is read from d_past; the host value passed along is a LOWER BOUND of it -- the kernel fetches
+                #  tiles below it at once and lets the others wait for the length, so tiles beyond the live keys cost nothing)
+                ops.attention_decode(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, L, nh, nkv, hd, scale,
+                                     past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split,
+                                     pad_len=st.pad_len, d_past=d_past, merge_in_launch=attn_merge, **kw_o)
             else:
                 # queries leave the RoPE kernel multiplied by scale * log2(e) (before their one rounding to bf16, as
                 # phi.py:454 scales q before the product): the prefill attention's softmax is then the exponential alone
@@ -960,7 +1007,7 @@ class Phi3VModel:
             # RMSNorm of the new residual stream into `h` -- the next projection's input (ops.gemm_resid_norm; bit-identical to the
             # two launches it replaces).
             normed = False
-            if not (bufs.get("fuse_o", False) and L <= ops.L.DECODE_MAX_L and n_beam == 1):
+            if not (fuse_o and decode and n_beam == 1):
                 normed = self._proj_resid_norm(o, p + "self_attn.o_proj.weight", x, w[p + "post_attention_layernorm.weight"], h)
                 if not normed:
                     self._proj(o, p + "self_attn.o_proj.weight", EPI_RESID_BF16, resid=x, out=x)
@@ -995,7 +1042,7 @@ class Phi3VModel:
         bookkeeping) as a hipGraph.  All loop state lives in HBM: `tok` (next input ids),
         `d_past` (cache length), `d_step`, `history` -- so replays need no host input and
         a token costs one graph launch instead of ~170 kernel launches."""
-        cfg, w, B, dev = self.cfg, self.w, st.B, self.device
+        cfg, B, dev = self.cfg, st.B, self.device
         g = dict(tok=torch.zeros((B,), dtype=I32, device=dev), d_past=torch.zeros((1,), dtype=I32, device=dev),
                  d_step=torch.zeros((1,), dtype=I32, device=dev),
                  # the step's tokens land in PINNED HOST memory straight from `k_step_end` (one 4-byte store per row and step):
@@ -1004,47 +1051,62 @@ class Phi3VModel:
                  x=torch.empty((B, cfg.hidden_size), dtype=BF16, device=dev),
                  logits=torch.empty((B, cfg.vocab_size), dtype=BF16, device=dev),
                  next_tok=torch.zeros((B,), dtype=I32, device=dev), ticket=torch.zeros((1,), dtype=I32, device=dev))
-        bufs = self._alloc_bufs(B, 1)
-        self._split_plan(bufs, B, 1, st.Tp, st.quantized, serving=getattr(st, "serving", False) or self.serving)   # one split per tile of CAPACITY
-        # the cache length only grows under a captured step (greedy_step rebuilds the graph if it ever finds it below this); a
-        # slot state's column moves both ways (engine.py), so it gets no bound
-        bufs["past_lb"] = -1 if getattr(st, "slots", False) else int(st.offset)
-        if not getattr(st, "slots", False):
-            self._plan_fused_oproj(bufs, B, 1, st.Tp, st.quantized)
-        bufs["rope_cos"] = torch.empty((B, 1, self.hd // 2), dtype=F32, device=dev)
-        bufs["rope_sin"] = torch.empty_like(bufs["rope_cos"])
-        g["bufs"] = bufs
-
+        g["bufs"] = self._plan(st, B, 1, fuse_o=not st.slots, captured=True)
         g["amax_ws"] = torch.zeros((ops.L.GEMV_STEP_WS_BYTES // 4,), dtype=F32, device=dev)   # (its arrival counters start at zero)
-
-        def step():
-            # (round 6) the step's two ends have no launch of their own where the library folds them into the first / last projection
-            # (B = 1 on bf16, e4m3 or 4-bit weights: ops.gemv_step_begin / gemv_step_end; 129 launches per step instead of 131)
-            self._layers(g["x"], st, B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
-                         step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
-            head = "lm_head.weight"
-            w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
-            if not (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
-                    and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], g["next_tok"], g["tok"],
-                                          g["history"], g["d_step"], g["d_past"], g["ticket"], g["amax_ws"])):
-                self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output
-                ops.step_end(g["logits"], g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
         g["d_past"].fill_(st.offset)
         g["gemm_ws"] = {}                                        # B > 16 rows: the projections are split-K GEMMs; their workspace
-        with ops.owned_gemm_workspace(g["gemm_ws"], frozen=False):   # belongs to the graph (sized here, baked in below)
-            step()                                               # warm-up run (sets func attributes, pages code in)
-        torch.cuda.synchronize()
-        graph = ops.Graph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.owned_gemm_workspace(g["gemm_ws"], frozen=True):
-            graph.begin()
-            step()
-            graph.end()
-        torch.cuda.current_stream().wait_stream(side)
-        g["d_step"].zero_()                                      # the warm-up run above counted as a step
-        g["graph"] = graph
+        g["graph"] = self._capture(lambda: self._decode_step(st, g), g["gemm_ws"])   # belongs to the graph
+        g["d_step"].zero_()                                      # the warm-up run counted as a step
         return g
+
+    def _decode_step(self, st, g, sampled=False):
+        """The launches of one decode step over the loop state `g` of a greedy capture: the layers, then the step's tail -- final
+        norm + lm_head + arg-max + bookkeeping, or with sampled=True each row's token drawn under its record (`set_sampling`)
+        where the greedy step has its arg-max.
+        (round 6) the step's two ends have no launch of their own where the library folds them into the first / last projection
+        (B = 1 on bf16, e4m3 or 4-bit weights: ops.gemv_step_begin / gemv_step_end; 129 launches per step instead of 131); the
+        sampled tail always goes through `_proj` (every weight format, adapters honoured)."""
+        cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
+        self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
+                     step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
+        end = (g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
+        if not sampled:
+            w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
+            if (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
+                    and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
+                return
+        self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output)
+        if sampled:
+            ops.sample_step_end(g["logits"], st.sample_rows, *end)
+        else:
+            ops.step_end(g["logits"], *end)
+
+    def _replay(self, token, cache, which):
+        """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy) or "sample_graph" (a
+        second capture over the same loop state, built on first use -- after the token and the cache length are in place, which
+        its warm-up run reads).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
+        st = cache[0].state
+        if st.offset + 1 > st.T:
+            raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
+        g = self._greedy_capture(st)
+        if g["host_tok"] is None or token is not g["host_tok"]:
+            g["tok"].copy_(token.reshape(-1).to(self.device, I32))   # first step / caller-chosen token
+        if g.get("synced_offset") != st.offset:
+            g["d_past"].fill_(st.offset)
+        if which == "sample_graph" and which not in g:
+            g[which] = self._build_sample_graph(st, g)
+        g[which].launch()
+        g["n_replays"] = g.get("n_replays", 0) + 1              # replay r, greedy or sampled, wrote its token to history[:, r - 1] (while it fits)
+        st.offset += 1
+        g["synced_offset"] = st.offset
+        g["host_tok"] = g["next_tok"].view(-1, 1)
+        return g["logits"].view(st.B, 1, -1), g["host_tok"]
+
+    @staticmethod
+    def _reset_replays(g):
+        """A greedy capture starts a new run on the same buffers (a reused captured-prefill entry): forget the last run's replays."""
+        g["n_replays"], g["host_tok"], g["synced_offset"] = 0, None, None
+        g["d_step"].zero_()
 
     @_on_device
     def greedy_prefill(self, max_tokens, **inputs):
@@ -1059,27 +1121,7 @@ class Phi3VModel:
         `logits, cache = model(input_ids=token, cache=cache); next = argmax(logits[:, -1])`
         (reference phi_3_vision_mlx.py:391-392).  Returns (logits [B,1,V], next_token [B,1])
         -- views of persistent buffers, valid until the next call."""
-        st = cache[0].state
-        if st.offset + 1 > st.T:
-            raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
-        if st.epoch != self.epoch:                              # adapters changed since the capture: stale pointers
-            st.graphs.clear()
-            st.epoch = self.epoch
-        g = st.graphs.get("greedy")
-        if g is not None and st.offset < g["bufs"].get("past_lb", -1):   # the cache was rewound below the captured lower bound
-            g = None
-        if g is None:
-            g = st.graphs["greedy"] = self._build_decode_graph(st)
-            g["host_tok"] = None
-        if g["host_tok"] is None or token is not g["host_tok"]:
-            g["tok"].copy_(token.reshape(-1).to(self.device, I32))   # first step / caller-chosen token
-        g["d_past"].fill_(st.offset) if g.get("synced_offset") != st.offset else None
-        g["graph"].launch()
-        g["n_replays"] = g.get("n_replays", 0) + 1              # replay r wrote its token to history[:, r - 1] (while it fits)
-        st.offset += 1
-        g["synced_offset"] = st.offset
-        g["host_tok"] = g["next_tok"].view(-1, 1)
-        return g["logits"].view(st.B, 1, -1), g["host_tok"]
+        return self._replay(token, cache, "graph")
 
     # ------------------------------------------------------------------ speculative greedy decoding (include/p3v.h, speculate.py)
     def spec_refusal(self, st=None, K=None):
@@ -1097,7 +1139,7 @@ class Phi3VModel:
             return "speculative decoding does not support LoRA adapters or an adapter bank"
         if st is not None and st.B != 1:
             return f"speculative decoding is B = 1 only (got a batch of {st.B})"
-        if st is not None and getattr(st, "slots", False):
+        if st is not None and st.slots:
             return "speculative decoding does not run on a slot state of the continuous engine"
         return None
 
@@ -1117,13 +1159,8 @@ class Phi3VModel:
                  x=torch.empty((Lq, cfg.hidden_size), dtype=BF16, device=dev),
                  logits=torch.empty((Lq, cfg.vocab_size), dtype=BF16, device=dev), n_replays=0)
         g["state"] = ops.spec_state(g, n_max, n_min)
-        bufs = self._alloc_bufs(1, Lq)
-        self._split_plan(bufs, 1, Lq, st.Tp, st.quantized, serving=getattr(st, "serving", False) or self.serving)
-        bufs["past_lb"] = int(st.offset)
+        bufs = g["bufs"] = self._plan(st, 1, Lq, fuse_o=False, captured=True)
         bufs["fuse_o"] = False                                   # (the fused attention + o_proj launch is B = L = 1 only)
-        bufs["rope_cos"] = torch.empty((1, Lq, self.hd // 2), dtype=F32, device=dev)
-        bufs["rope_sin"] = torch.empty_like(bufs["rope_cos"])
-        g["bufs"] = bufs
 
         def step():
             ops.spec_begin(g["tok"], w["model.embed_tokens.weight"], g["x"], st.cos, st.sin, g["d_past"], bufs["rope_cos"], bufs["rope_sin"])
@@ -1134,18 +1171,7 @@ class Phi3VModel:
         # the warm-up run is a step at the budget (n = n_limit = 0): it emits nothing and moves no counter but `replay`
         g["d_past"].fill_(st.offset)
         g["gemm_ws"] = {}
-        with ops.owned_gemm_workspace(g["gemm_ws"], frozen=False):
-            step()
-        torch.cuda.synchronize()
-        graph = ops.Graph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.owned_gemm_workspace(g["gemm_ws"], frozen=True):
-            graph.begin()
-            step()
-            graph.end()
-        torch.cuda.current_stream().wait_stream(side)
-        g["graph"] = graph
+        g["graph"] = self._capture(step, g["gemm_ws"])
         return g
 
     @_on_device
@@ -1168,12 +1194,10 @@ class Phi3VModel:
         if n_limit > budget or ids.size + 1 > budget:
             raise ValueError(f"KV cache too small for verify steps up to {n_limit} tokens: capacity {st.T}, K = {K} "
                              "(prefill with extra_tokens=K)")
-        if st.epoch != self.epoch:
-            st.graphs.clear()
-            st.epoch = self.epoch
+        self._sync_epoch(st)
         key = ("spec", K, n_max, n_min)
         g = st.graphs.get(key)
-        if g is not None and st.offset < g["bufs"]["past_lb"]:  # rewound below the captured lower bound (as greedy_step)
+        if g is not None and st.offset < g["bufs"]["past_lb"]:  # rewound below the captured lower bound (as _greedy_capture)
             g = None
         if g is None:
             g = st.graphs[key] = self._build_spec_graph(st, K, n_max, n_min)
@@ -1242,7 +1266,7 @@ class Phi3VModel:
         """Write the per-row sampling records (sampling.pack: int32 [n, 6] on the host) of rows row0 .. row0+n-1 of a state (one
         H2D copy, outside any graph).  Rows never written are greedy (temperature 0).  The records live with the state's decode
         graphs and are read -- and their counters advanced -- by `sample_logits` and every replay of `sample_step`."""
-        if getattr(st, "sample_rows", None) is None:
+        if st.sample_rows is None:
             st.sample_rows = torch.zeros((st.B, 6), dtype=I32, device=self.device)
         st.sample_rows[row0:row0 + records.shape[0]].copy_(records)
 
@@ -1258,58 +1282,19 @@ class Phi3VModel:
         """One SAMPLED decode step through its captured graph: `greedy_step` with each row's token drawn under its record
         (`set_sampling`) instead of the arg-max.  The sampled graph is a second capture over the greedy graph's loop-state buffers
         (built on first use): greedy and sampled replays may alternate on one state.  Returns (logits [B,1,V], next_token [B,1])."""
-        st = cache[0].state
-        if getattr(st, "sample_rows", None) is None:
+        if cache[0].state.sample_rows is None:
             raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
-        if st.offset + 1 > st.T:
-            raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
-        if st.epoch != self.epoch:
-            st.graphs.clear()
-            st.epoch = self.epoch
-        g = st.graphs.get("greedy")
-        if g is not None and st.offset < g["bufs"].get("past_lb", -1):
-            g = None
-        if g is None:
-            g = st.graphs["greedy"] = self._build_decode_graph(st)
-            g["host_tok"] = None
-        if g["host_tok"] is None or token is not g["host_tok"]:
-            g["tok"].copy_(token.reshape(-1).to(self.device, I32))
-        g["d_past"].fill_(st.offset) if g.get("synced_offset") != st.offset else None
-        if "sample_graph" not in g:
-            g["sample_graph"] = self._build_sample_graph(st, g)
-        g["sample_graph"].launch()
-        g["n_replays"] = g.get("n_replays", 0) + 1              # (one history column per replay, greedy or sampled)
-        st.offset += 1
-        g["synced_offset"] = st.offset
-        g["host_tok"] = g["next_tok"].view(-1, 1)
-        return g["logits"].view(st.B, 1, -1), g["host_tok"]
+        return self._replay(token, cache, "sample_graph")
 
     def _build_sample_graph(self, st, g):
         """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
         through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
         The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it."""
-        cfg, w, B, dev, bufs = self.cfg, self.w, st.B, self.device, g["bufs"]
-
-        def step():
-            self._layers(g["x"], st, B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
-                         step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
-            self._proj(g["x"], "lm_head.weight", norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])
-            ops.sample_step_end(g["logits"], st.sample_rows, g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
         torch.cuda.synchronize()
         saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
         saved_rows = st.sample_rows.clone()
         g["gemm_ws_sampled"] = {}
-        with ops.owned_gemm_workspace(g["gemm_ws_sampled"], frozen=False):
-            step()                                               # warm-up run
-        torch.cuda.synchronize()
-        graph = ops.Graph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.owned_gemm_workspace(g["gemm_ws_sampled"], frozen=True):
-            graph.begin()
-            step()
-            graph.end()
-        torch.cuda.current_stream().wait_stream(side)
+        graph = self._capture(lambda: self._decode_step(st, g, sampled=True), g["gemm_ws_sampled"])
         for k, v in saved.items():
             g[k].copy_(v)
         st.sample_rows.copy_(saved_rows)
@@ -1436,8 +1421,7 @@ class Phi3VModel:
         st.offset = 0
         g = st.graphs.get("greedy")
         if g is not None:                                         # the decode graph of this cache geometry stays valid: same buffers
-            g["n_replays"], g["host_tok"], g["synced_offset"] = 0, None, None
-            g["d_step"].zero_()
+            self._reset_replays(g)
         e["graph"].launch()
         st.offset = S
         e["lease"] = weakref.ref(st)
@@ -1454,18 +1438,7 @@ class Phi3VModel:
             ops.embed_gather(e["ids"], w["model.embed_tokens.weight"], out=e["x"])
             xl = self._layers(e["x"], st, 1, S, 0, 1, bufs=e["bufs"], last_only=True)
             self._proj(xl.view(1, -1), "lm_head.weight", norm_w=w["model.norm.weight"], out=e["logits"])
-        with ops.owned_gemm_workspace(e["ws"], frozen=False):
-            run()                                                # warm-up (sizes the split-K workspace the graph owns)
-        torch.cuda.synchronize()
-        graph = ops.Graph()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.owned_gemm_workspace(e["ws"], frozen=True):
-            graph.begin()
-            run()
-            graph.end()
-        torch.cuda.current_stream().wait_stream(side)
-        e["graph"] = graph
+        e["graph"] = self._capture(run, e["ws"])
         return e
 
     @property

@@ -282,6 +282,32 @@ def test_captured_short_prompt_prefill_with_4bit_weights_equals_eager(monkeypatc
     assert len(model._prefill_graphs) == 1
 
 
+def test_captured_vision_tower_equals_eager(vis, monkeypatch):
+    """Round 6: a crop count seen for the SECOND time runs the vision tower as one hipGraph over buffers the entry owns
+    (model.clip_forward).  Per crop count: first sighting eager, second captured and launched, third replayed on other pixels -- all
+    three bit-identical to the eager launches (P3V_VIT_GRAPH=0) on the same pixels.  The returned features ARE the entry's buffer, so
+    each result is cloned before the next call."""
+    model, _, _ = vis
+    model._vit_graphs.clear(), model._vit_seen.clear()
+    counts = (1, 3)
+    pix = {(n, rep): torch.from_numpy(np.random.default_rng(100 * n + rep).standard_normal((n, 3, 336, 336)).astype(np.float32)).to(model.device)
+           for n in counts for rep in range(3)}
+    try:
+        monkeypatch.setenv("P3V_VIT_GRAPH", "0")
+        ref = {k: model.clip_forward(p).clone() for k, p in pix.items()}
+        assert not model._vit_graphs and not model._vit_seen
+        monkeypatch.setenv("P3V_VIT_GRAPH", "1")
+        for j, n in enumerate(counts):
+            for rep in range(3):
+                got = model.clip_forward(pix[n, rep]).clone()
+                assert len(model._vit_graphs) == (j if rep == 0 else j + 1), (n, rep)   # captured on the second sighting, reused on the third
+                assert got.shape == (n, 577, model.cfg.clip["hidden_size"]) and torch.isfinite(got).all()
+                assert torch.equal(got, ref[n, rep]), (n, rep)
+        assert sorted(k[0] for k in model._vit_graphs) == list(counts)
+    finally:                                                      # (the model is module-scoped: leave it as the other tests expect it)
+        model._vit_graphs.clear(), model._vit_seen.clear()
+
+
 def test_graph_decode_with_more_than_16_rows(text):
     """B = 20 rows: the decode projections are split-K GEMMs (M > 16), whose workspace the captured graph must own (ADVICE r03:
     no allocation under capture, no dangling pointer after a regrow).  Graph replays == eager steps, bit for bit, also after
