@@ -498,6 +498,44 @@ int p3v_sample_step_end(const uint16_t* logits, p3v_sample_row_t* rows_params, i
                         int32_t* history, int32_t* d_step, int32_t* d_past, int32_t* ticket, int B, int n, int max_steps,
                         void* stream);
 
+/* ---- token log-probabilities: added after round 6, no version change.  Read-only on the logits: no token, no loop state and
+ * no number of any other entry point changes.
+ * The rule, for one row of bf16 logits l[0..n), a token id t and a count N, 0 <= N <= P3V_LOGPROBS_MAX (the limit p3v_topk has;
+ * a larger N counts as P3V_LOGPROBS_MAX):
+ *   1. the row is UNDEFINED if it holds a NaN or a +inf, or has no finite logit: logprob = NaN, rank = 0, n_top = 0.
+ *   2. m = max f32(l_i).
+ *   3. w_i = floor(exp((double)l_i - (double)m) * 2^32) as uint64: step 3 of the sampling rule at T = 1 (a -inf logit: 0).
+ *   4. W = sum w_i, an exact integer, 2^32 <= W < 2^48.
+ *   5. lse = (double)m + log((double)W) - 32 ln 2, in fp64.
+ *   6. logprob(i) = (float)((double)f32(l_i) - lse); a -inf logit: -inf.
+ *   7. rank(t) = 1 + #{j : l_j > l_t} + #{j < t : l_j == l_t}, on the float values (-0 == +0): the token of p3v_argmax has rank 1.
+ *   8. top: the n_top = min(N, n) tokens with the largest value, ties to the lower index (p3v_topk's order), each with its
+ *      logprob.  Unused entries: id -1, logprob NaN.
+ *   9. t outside [0, n) (an image-slot id, the -1 of a failed step): logprob = NaN, rank = 0; the top list is still filled.
+ * These are the log-probabilities of the RAW logits: no temperature, no top-k, no top-p.  W is a sum of integers, so every bit
+ * of a record is independent of the reduction order, the launch geometry, the batch neighbours and graph versus eager execution.
+ * (p3v_log_softmax is the reference's bf16 composite, rounded twice: not a usable probability.) */
+#define P3V_LOGPROBS_MAX 8
+typedef struct {
+  int32_t token;
+  float   logprob;
+  int32_t rank;
+  int32_t n_top;
+  int32_t top_id[P3V_LOGPROBS_MAX];
+  float   top_logprob[P3V_LOGPROBS_MAX];
+} p3v_logprob_t;   /* 80 bytes */
+/* eager form: out[r] = the record of token[r] on logits row r (at logits + r * row_stride) with N = want[r]; want[r] < 0: the
+ * row is skipped and out[r] is not written.  Any rows >= 1, 1 <= n <= 65536, row_stride >= n; P3V_ERR_ARG otherwise or for a
+ * null pointer (`want` included). */
+int p3v_logprobs(const uint16_t* logits, int64_t row_stride, const int32_t* token, const int32_t* want,
+                 p3v_logprob_t* out, int rows, int n, void* stream);
+/* graph form, the launch AFTER a step's tail (p3v_gemv_step's end, p3v_step_end or p3v_sample_step_end): next_tok[b] is the
+ * token the step emitted and *d_step already counts it.  Row b's record (logits [B, n] contiguous) goes to
+ * records[b * max_steps + (*d_step - 1)] when that index lies in [0, max_steps) and want[b] >= 0; nothing is written
+ * otherwise.  `records` may be pinned host memory, as `history` is: it is written with plain 4-byte vector stores. */
+int p3v_logprobs_step(const uint16_t* logits, const int32_t* next_tok, const int32_t* want, const int32_t* d_step,
+                      p3v_logprob_t* records, int B, int n, int max_steps, void* stream);
+
 /* ---- prompt prefix cache: KV block copy at any column phase (added after round 6, no version change).
  * One job copies tokens [t0_src, t0_src + n_tok) of batch row b_src of a source cache to tokens [t0_dst, t0_dst + n_tok) of
  * batch row b_dst of a destination cache, for ALL nl layers and nkv heads; up to P3V_KV_COPY_MAX_JOBS jobs share ONE launch

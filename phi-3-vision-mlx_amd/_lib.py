@@ -95,6 +95,18 @@ class SampleRow(C.Structure):
                 ("counter", i32)]
 
 
+LOGPROBS_MAX = 8                                 # P3V_LOGPROBS_MAX
+
+
+class LogprobRecord(C.Structure):
+    """p3v_logprob_t: one token's log-probability, rank and top list (include/p3v.h)."""
+    _fields_ = [("token", C.c_int32), ("logprob", f32), ("rank", C.c_int32), ("n_top", C.c_int32),
+                ("top_id", C.c_int32 * LOGPROBS_MAX), ("top_logprob", f32 * LOGPROBS_MAX)]
+
+
+LOGPROB_WORDS = C.sizeof(LogprobRecord) // 4     # 20
+
+
 class KvCopyJob(C.Structure):
     """p3v_kv_copy_job_t: one row's token run, source -> destination (include/p3v.h)."""
     _fields_ = [("k_src", vp), ("v_src", vp), ("k_dst", vp), ("v_dst", vp),
@@ -172,6 +184,8 @@ SIGNATURES = {
     "p3v_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_sample": (i32, [vp, i64, vp, vp, i32, i32, vp]),
     "p3v_sample_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p3v_logprobs": (i32, [vp, i64, vp, vp, vp, i32, i32, vp]),
+    "p3v_logprobs_step": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_spec_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p3v_spec_end": (i32, [vp, C.POINTER(SpecState), i32, i32, vp]),
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -30,6 +30,7 @@ import torch
 
 from . import ops as model_ops
 from . import sampling as sampling_mod
+from . import logprobs as logprobs_mod
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
@@ -308,7 +309,8 @@ def _last_logits(logits):
     return logits[:, -1, :].contiguous()
 
 
-def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None, sampling=None):
+def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None, sampling=None,
+                logprobs=None):
     """The decode loop of `_generate` (reference phi_3_vision_mlx.py:390-398): `n_steps` greedy steps after the prefill token,
     every token handed to the streamer and the stoppers in order, stops as the reference stops.
 
@@ -320,7 +322,12 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     on the host before deciding) or an eager model the loop is the reference's, one sync per token.
 
     sampling: per-row (temperature, top_k, top_p, seed) tuples (sampling.rows) -- the loop then drives the SAMPLED replay
-    (model.sample_step) on records whose draw index starts at 1 (the prefill token was draw 0); None: the greedy replay."""
+    (model.sample_step) on records whose draw index starts at 1 (the prefill token was draw 0); None: the greedy replay.
+
+    logprobs: a logprobs.Collector -- the loop then drives the replay that ends in the log-probability launch
+    (model.logprob_step / sample_logprob_step: the same step plus one launch) and hands the collector every step's records
+    right after the streamer got its tokens.  The one-step-ahead loop reads them from the capture's pinned `records` buffer
+    behind the event that guards `history`: no sync and no copy of their own.  None: the replays and launches of today."""
     graph_step = getattr(model, "greedy_step", None)
     records = None
     if sampling is not None:
@@ -330,6 +337,20 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             model.set_sampling(cache[0].state, records)
         else:                                                       # an eager model: the records ride with the loop
             records = records.to(token.device)
+    want_dev = None
+    if logprobs is not None:
+        if graph_step is not None:
+            graph_step = getattr(model, "logprob_step" if sampling is None else "sample_logprob_step")
+            model.set_logprobs(cache[0].state, logprobs.wants)
+        else:                                                       # an eager model: one eager launch per step
+            want_dev = torch.tensor(logprobs.wants, dtype=torch.int32, device=token.device)
+
+    def slot(g_):
+        """the pinned records of the replay just enqueued ([B, 20], valid once the step has run)"""
+        k_ = g_["n_replays"] - 1
+        if k_ >= g_["records"].shape[1]:
+            raise RuntimeError(f"logprobs: step {k_} lies beyond the {g_['records'].shape[1]} record slots of this cache (max_tokens)")
+        return g_["records"][:, k_]
     ahead = graph_step is not None and (logit_stopper is None or not logit_stopper.early_stop) and torch.is_tensor(token) and token.is_cuda
     if not ahead:
         for _ in range(n_steps):
@@ -341,6 +362,9 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                          model_ops.sample(_last_logits(logits), records))[:, None]
             rows = _rows(token)                                     # ONE D2H copy per step, shared by the streamer and the stopper
             streamer(rows)
+            if logprobs is not None:                                # (the copy above waited for the step, its last launch included)
+                logprobs.add(slot(cache[0].state.graphs["greedy"]) if want_dev is None else
+                             model_ops.logprobs(_last_logits(logits), token.reshape(-1).to(torch.int32).contiguous(), want_dev))
             if logit_stopper is not None and logit_stopper(logits):
                 break
             if token_stopper(rows):
@@ -373,6 +397,8 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
         taken[:] = rows
         n_done += 1
         streamer(rows)
+        if p[3] is not None:
+            logprobs.add(p[3])
         return token_stopper(rows)
     st = cache[0].state
     token0 = token.clone()                                          # (the caller's tensor may be the step's own output buffer)
@@ -397,7 +423,7 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                     host[i & 1].copy_(token.reshape(-1), non_blocking=True)   # stream-ordered copy, before the next replay overwrites it
                     ev.record()
                     src, chk = host[i & 1], None
-                prev, pending = pending, (ev, src, chk)
+                prev, pending = pending, (ev, src, chk, slot(g) if logprobs is not None else None)
                 if prev is not None and take(prev):                 # host work of step i - 2 under the GPU's step i - 1
                     st.offset -= 1                                  # drop the speculative step: its K/V row lies beyond the offset
                     return torch.tensor(taken, dtype=torch.int32, device=token.device).view(-1, 1)
@@ -529,7 +555,7 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
-              speculate=0, spec_info=None):
+              speculate=0, spec_info=None, logprobs=None, logprob_info=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -537,10 +563,15 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     p3v_sample_row_t; each of temperature / top_k / top_p / seed a scalar or a per-row list, see sampling.rows); temperature 0
     -- the default -- is today's greedy path, launch for launch.  prefix_cache: a prefix.PrefixCache -- a single prompt (string)
     reuses the K/V of the longest stored prefix with the same tokens and pictures and leaves its own prefix in the store; a list
-    of prompts ignores it (counted as a bypass)."""
+    of prompts ignores it (counted as a bypass).  logprobs: None (off: today's path, launch for launch), an int N in 0..8, or one
+    such value per prompt -- every generated token's log-probability under the RAW logits, its rank and the N most likely
+    tokens (include/p3v.h: p3v_logprob_t); logprob_info (a dict) receives token_ids / token_logprobs / ranks / top_logprobs,
+    each a list per prompt (None for a prompt that did not ask) with one entry per token handed to the streamer."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     B = len(prompt) if isinstance(prompt, list) else 1
+    lp_wants = logprobs_mod.wants(logprobs, B)                  # (checked before anything runs)
+    logprobs_mod.refuse_speculation(lp_wants, speculate)
     kw_adapter = {}
     if adapter is not None:
         from .engine import _check_adapter, adapter_list
@@ -572,6 +603,11 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     else:                                                       # draw 0 of every row: from the prefill logits
         token = model_ops.sample(logits[:, -1, :], sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
     streamer(_rows(token))                                      # D2H copy = the per-token sync the reference has (mx.eval)
+    collector = None
+    if lp_wants is not None:                                    # the first token's record: from the prefill logits
+        collector = logprobs_mod.Collector(lp_wants)
+        collector.add(model_ops.logprobs(logits[:, -1, :], token.reshape(-1).to(torch.int32).contiguous(),
+                                         torch.tensor(lp_wants, dtype=torch.int32, device=logits.device)))
     prompt_time = tic()
     if speculate:
         stats = {}
@@ -579,10 +615,13 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         if spec_info is not None:
             spec_info.update(stats)
     elif sampled is None:
-        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids)
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, logprobs=collector)
     else:
-        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled)
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
+                    logprobs=collector)
     result, gen_len = streamer.end()
+    if collector is not None and logprob_info is not None:
+        logprob_info.update(collector.result())
     gen_time = tic()
     prompt_len = dict_input["input_ids"].size
     prompt_tps = prompt_len / prompt_time
@@ -601,18 +640,73 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
-             prefix_cache=None, speculate=0, spec_info=None):
+             prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None):
     """reference phi_3_vision_mlx.py:1324-1374, plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
-    prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only)."""
+    prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
+    log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
+    lp_wants = logprobs_mod.wants(logprobs, len(prompt) if isinstance(prompt, list) else 1)   # before a model is loaded or run
+    logprobs_mod.refuse_speculation(lp_wants, speculate)
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
                      top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache, speculate=speculate,
-                     spec_info=spec_info)
+                     spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info)
+
+
+# ----------------------------------------------------------------------------- score
+def _score(model, processor, prompt, images, top):
+    return _score_inputs(model, processor(prompt, images), top)
+
+
+def _score_inputs(model, dict_input, top):
+    """One prefill with every position's logits and ONE p3v_logprobs launch over its rows: row i - 1 scores token i."""
+    ids = np.asarray(dict_input["input_ids"]).astype(np.int64)
+    ids = ids[None] if ids.ndim == 1 else ids
+    B, S = ids.shape
+    logits, _ = model(**dict_input, full_logits=True)
+    V = logits.shape[-1]
+    pad = (np.asarray(dict_input["mask"]).reshape(B, S) == 0).sum(1) if "mask" in dict_input else np.zeros(B, dtype=np.int64)
+    # row (b, i) scores the token after it; the last row of a prompt has none, rows inside the left padding are skipped
+    tok = np.full((B, S), -1, dtype=np.int32)
+    tok[:, :-1] = ids[:, 1:]
+    want = np.full((B, S), top, dtype=np.int32)
+    want[:, -1] = logprobs_mod.OFF
+    for b in range(B):
+        want[b, :pad[b]] = logprobs_mod.OFF
+    dev = logits.device
+    words = model_ops.logprobs(logits.view(B * S, V), torch.as_tensor(tok.reshape(-1)).to(dev), torch.as_tensor(want.reshape(-1)).to(dev))
+    recs = logprobs_mod.unpack(words)
+    out = []
+    for b in range(B):
+        p = int(pad[b])
+        row = [None] * (p + 1) + [recs[b * S + i - 1] if 0 <= ids[b, i] < V else None for i in range(p + 1, S)]
+        out.append(dict(token_ids=[int(t) for t in ids[b]], token_logprobs=[None if r is None else r["logprob"] for r in row],
+                        ranks=[None if r is None else r["rank"] for r in row],
+                        top_logprobs=[None if r is None else list(r["top"]) for r in row]))
+    return out
+
+
+def score(prompt, images=None, preload=None, top=0, apply_chat_template=True):
+    """The log-probability of GIVEN text under the model (evaluation, perplexity, reranking): per prompt a dict of token_ids,
+    token_logprobs, ranks and top_logprobs (`top` = 0..8 most likely tokens per position), aligned with the prompt's row of
+    input ids.  The first token has nothing in front of it: its entries are None, as are those of a batched call's left
+    padding and of ids outside the vocabulary (image slots).  The rule is p3v_logprob_t's (include/p3v.h): raw logits, fp64
+    log-sum-exp over integer weights.  Returns one dict for a single prompt, a list of them for a list of prompts."""
+    top = logprobs_mod.check(top, "top")
+    if top == logprobs_mod.OFF:
+        raise ValueError(f"top must be an integer in 0..{logprobs_mod.MAX}, got None")
+    if images is not None and isinstance(prompt, list):
+        raise ValueError("Images cannot be provided when prompt is a list")
+    if preload is None:
+        preload = load()
+    model, processor = preload
+    prompt, images = _apply_chat_template(prompt, images, False, apply_chat_template)
+    out = _score(model, processor, prompt, images, top)
+    return out if isinstance(prompt, list) else out[0]
 
 
 # ----------------------------------------------------------------------------- choose

@@ -64,9 +64,9 @@ def _set_device(device):
 
 class Request:
     __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
-                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit")
+                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records")
 
-    def __init__(self, inputs, max_tokens, sampling=None, adapter=None):
+    def __init__(self, inputs, max_tokens, sampling=None, adapter=None, logprobs=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
         # prompt prefix cache (engine with a store only; `cache_args` puts them beside the inputs): digests of the request's source
         # images, whether its prompt may be captured, an explicit capture length; `cached_tokens`: prompt tokens restored from the
@@ -77,6 +77,8 @@ class Request:
         self.cached_tokens, self.hit = 0, None
         self.adapter = adapter                                   # None (the base model) or the name of an adapter of the model's bank
         self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
+        self.logprobs = logprobs                                 # None (off) or N in 0..8: one record per token in `logprob_records`
+        self.logprob_records = []                                # (logprobs.unpack dicts, aligned with `tokens`)
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
         self.tokens, self.row, self.error = [], None, None
         self.cancelled, self.blocked_at = False, None
@@ -134,8 +136,14 @@ class ContinuousEngine:
         sampling.rows) -- the request's tokens are then drawn under its own record, whoever shares the batch.
         adapter: None (the base model) or the name of one adapter of the model's bank: the request's row runs with it, next to
         rows with other adapters or none, in the one captured step.  An unknown name fails the handle at once (ValueError);
-        nothing is queued."""
+        nothing is queued.
+        Token log-probabilities: `submit(logprob_args(inputs, N), ...)`, N in 0..8, puts the request's `logprobs` beside its inputs,
+        as `cache_args` does (so it travels through a router or a fleet too) -- every token of the request then comes with its
+        log-probability under the raw logits, its rank and the N most likely tokens (include/p3v.h: p3v_logprob_t) in
+        `logprob_records`, aligned with `tokens`.  While no active request asks, the engine replays exactly what it replays
+        without the feature."""
         try:
+            want = _check_logprobs(requested_logprobs(inputs))
             rec = _sampling_row(sampling)
             _check_adapter(adapter, self.adapter_names())
             _check_prefix_args(inputs)
@@ -143,7 +151,7 @@ class ContinuousEngine:
             r = Request(inputs, max_tokens)
             r.fail(e)
             return r
-        r = Request(inputs, max_tokens, rec, adapter)
+        r = Request(inputs, max_tokens, rec, adapter, want)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -162,6 +170,8 @@ class ContinuousEngine:
         if r.row is not None and self.rows[r.row] is r:
             self.rows[r.row] = None
             self.st.pad_len[r.row:r.row + 1].fill_(self.window)  # every key masked: the row idles at zero cost of correctness
+            if r.logprobs is not None:
+                self.model.set_logprobs(self.st, [-1], r.row)    # the row's next occupant costs the launch one early exit
         r.done.set()
 
     _finish = _release
@@ -250,6 +260,10 @@ class ContinuousEngine:
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
             _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
             toks = self.model.sample_logits(st, logits, row0)
+        elif any(r.logprobs is not None for r in group):         # (greedy, scored: the same prefill, its logits kept)
+            if getattr(st, "sample_rows", None) is not None:
+                self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
+            toks, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
         else:
             if getattr(st, "sample_rows", None) is not None:     # a sampled request had these rows before: greedy records now
                 self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
@@ -257,6 +271,13 @@ class ContinuousEngine:
         first = toks.reshape(-1).tolist()
         if min(first) < 0:
             raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
+        if any(r.logprobs is not None for r in group):
+            # the rows' wants into the table (-1 for the members that did not ask), the first token's record from the prefill logits
+            self.model.set_logprobs(st, [-1 if r.logprobs is None else r.logprobs for r in group], row0)
+            recs0 = _unpack_records(self.model.logprobs_of(st, logits, toks, row0))
+            for r, rec0 in zip(group, recs0):
+                if r.logprobs is not None:
+                    r.logprob_records.append(rec0)
         if hit is not None:
             group[0].cached_tokens = int(hit[1])
         self._capture(group)                                     # (after the NaN check: a poisoned row is never captured)
@@ -335,6 +356,9 @@ class ContinuousEngine:
                     if self.rows[r.row] is r:
                         self.rows[r.row] = None
                     self.st.pad_len[r.row:r.row + 1].fill_(self.window)
+                    del r.logprob_records[:]
+                if getattr(self.st, "logprob_want", None) is not None and any(r.logprobs is not None for r in group):
+                    self.model.set_logprobs(self.st, [-1] * n, row0)
                 if n == 1:
                     group[0].fail(e)
                     continue
@@ -359,8 +383,18 @@ class ContinuousEngine:
         g = self.model.decode_graph(self.st)
         # the sampled replay while any active row samples (its greedy rows take the arg-max there too), the greedy one otherwise
         replay = self.model.sample_step if any(r.sampling is not None for r in active) else self.model.greedy_step
+        scored = any(r.logprobs is not None for r in active)
+        if scored:
+            # ... followed by the log-probability launch while any active row wants records (the others: one early exit each).
+            # Records are indexed by the capture's step counter, which EVERY replay advances, plain and sampled ones too, and
+            # they have as many slots as `history` (made with the first scored replay): a long-lived state starts the counter
+            # afresh when the slots have run out, whether or not the record buffer exists yet.
+            replay = self.model.sample_logprob_step if any(r.sampling is not None for r in active) else self.model.logprob_step
+            if g.get("n_replays", 0) >= g["history"].shape[1]:
+                self.model.restart_history(self.st)
         _, tok = replay(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
         rows = tok.reshape(-1).tolist()                          # ONE D2H copy per step (the reference's mx.eval)
+        recs = _unpack_records(g["records"][:, g["n_replays"] - 1]) if scored else None   # (pinned: the step wrote them itself)
         self.steps += 1
         poisoned = False
         for r in active:
@@ -371,6 +405,8 @@ class ContinuousEngine:
                 self._release(r)
                 continue
             r.tokens.append(t)
+            if r.logprobs is not None:
+                r.logprob_records.append(recs[r.row])
             if t == ID_EOS or len(r.tokens) >= r.max_tokens:
                 self._release(r)
         if poisoned:
@@ -402,11 +438,31 @@ class ContinuousEngine:
                 stop_event.wait(idle_sleep)
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
+                 logprobs=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
+
+
+def _check_logprobs(logprobs):
+    """submit's `logprobs` -> None (off) or the checked N; ValueError names the range."""
+    from .logprobs import OFF, check
+    want = check(logprobs)
+    return None if want == OFF else want
+
+
+def _unpack_records(words):
+    from .logprobs import unpack
+    return unpack(words)
+
+
+def logprobs_list(logprobs, n):
+    """`logprobs` argument of a text-level call -> one checked value / None per prompt."""
+    from .logprobs import OFF, wants
+    w = wants(logprobs, n)
+    return [None] * n if w is None else [None if x == OFF else x for x in w]
 
 
 def _check_adapter(adapter, known):
@@ -428,6 +484,19 @@ def adapter_list(adapter, n):
     if len(adapter) != n:
         raise ValueError(f"adapter: {len(adapter)} names for {n} prompts")
     return list(adapter)
+
+
+LOGPROB_ARGS = "logprobs"           # key of a request's `logprobs` value inside its `inputs` (no model call forwards it)
+
+
+def logprob_args(inputs, logprobs):
+    """A copy of a B = 1 `processor(...)` result that carries the request's `logprobs` (None, or N in 0..8: ContinuousEngine.submit).
+    The processor's own result is not touched; `submit` checks the value."""
+    return dict(inputs, **{LOGPROB_ARGS: logprobs})
+
+
+def requested_logprobs(inputs):
+    return inputs.get(LOGPROB_ARGS) if isinstance(inputs, dict) else None
 
 
 PREFIX_ARGS = "prefix_cache_args"   # key of a request's prefix-cache arguments inside its `inputs` (no model call forwards it)
@@ -459,9 +528,9 @@ def _check_prefix_args(inputs):
             raise ValueError(f"prefix_len must be a positive integer, got {prefix_len!r}")
 
 
-def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None):
+def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None, logprobs=None):
     """submit with only the keywords in use (an engine-like object without them keeps working for plain requests); the prefix-cache
-    arguments, when one of them is in use, ride beside the inputs (`cache_args`)."""
+    arguments, when one of them is in use, ride beside the inputs (`cache_args`), and so does `logprobs` (`logprob_args`)."""
     kw = {}
     if image_digests is not None or prefix_len is not None or (cache_prompt is not None and not cache_prompt):
         inputs = cache_args(inputs, image_digests, True if cache_prompt is None else bool(cache_prompt), prefix_len)
@@ -469,6 +538,8 @@ def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, c
         kw["sampling"] = sampling
     if adapter is not None:
         kw["adapter"] = adapter
+    if logprobs is not None:
+        inputs = logprob_args(inputs, logprobs)
     return engine.submit(inputs, max_tokens, **kw)
 
 
@@ -498,16 +569,20 @@ def has_prefix_cache(engine):
     return any(has_prefix_cache(e) for e in inner)
 
 
-def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None):
+def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None,
+                   logprobs=None):
     """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt.
     cache_prompt: None / True (the prompt may be captured by the engine's prefix store) or False.  info: a dict that receives
-    "cached_tokens" (one count per prompt)."""
+    "cached_tokens" (one count per prompt) and, when a prompt asked for them, "logprobs" (per prompt: logprobs.entry of its
+    records -- token_ids / token_logprobs / ranks / top_logprobs over the tokens of the returned text -- or None).
+    logprobs: None, N in 0..8, or one such value per prompt."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     images = images if images is not None else [None] * len(prompts)
     if sampling is not None and len(sampling) != len(prompts):
         raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
     adapters = adapter_list(adapter, len(prompts))
+    lps = logprobs_list(logprobs, len(prompts))
     reqs = []
     for i, (p, im) in enumerate(zip(prompts, images)):
         text, imgs = api._apply_chat_template(p, im, False)
@@ -516,8 +591,9 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
             from .prefix import image_digests
             digests = image_digests(imgs)
         inputs = processor(text, imgs) if imgs is not None else processor(text)
-        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt))
-    out = []
+        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt,
+                            logprobs=lps[i]))
+    out, kept = [], []
     try:
         for r in reqs:
             if not r.done.wait(timeout):
@@ -525,9 +601,14 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
             if r.error is not None:
                 raise r.error
             ids = r.tokens[:r.tokens.index(ID_EOS) + 1] if ID_EOS in r.tokens else r.tokens
+            kept.append(ids)
             out.append(processor.tokenizer.decode(ids))
         if info is not None:
             info["cached_tokens"] = [int(getattr(r, "cached_tokens", 0)) for r in reqs]
+            if any(w is not None for w in lps):
+                from .logprobs import entry
+                info["logprobs"] = [None if w is None else entry(list(r.logprob_records)[:len(ids_out)])
+                                    for w, r, ids_out in zip(lps, reqs, kept)]
     except BaseException:
         for r in reqs:                                          # nobody is waiting for these any more: free their slots
             if not r.done.is_set():
@@ -552,7 +633,7 @@ class RegimeRouter:
         S = int(np.asarray(inputs["input_ids"]).shape[-1])
         for e in self.engines:
             if e.accepts(S, int(max_tokens)):
-                return _submit(e, inputs, max_tokens, sampling, adapter)    # (`cache_args` inputs pass through as they are)
+                return _submit(e, inputs, max_tokens, sampling, adapter)    # (`cache_args` / `logprob_args` inputs pass through as they are)
         r = Request(inputs, max_tokens)
         r.fail(ValueError(f"prompt {S} + max_tokens {max_tokens} fits no engine window"))
         return r
@@ -570,5 +651,6 @@ class RegimeRouter:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
+                 logprobs=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)

@@ -16,7 +16,7 @@ one receiver thread per source takes them in order).  RCCL is not involved; the 
 import threading
 import time
 
-from .engine import Request, _check_adapter, _generate_text, _submit
+from .engine import Request, _check_adapter, _check_logprobs, _generate_text, _submit, requested_logprobs
 
 _ERRORS = {"ValueError": ValueError, "TimeoutError": TimeoutError, "TypeError": TypeError}   # what the HTTP handler tells apart
 
@@ -88,9 +88,11 @@ class EngineFleet:
 
     def submit(self, inputs, max_tokens, sampling=None, adapter=None):
         """Prefix-cache arguments (`engine.cache_args`) travel inside `inputs` to whichever rank takes the request (one store per
-        engine; no cache-affinity routing: the least-loaded rank wins as before)."""
+        engine; no cache-affinity routing: the least-loaded rank wins as before).  So does `logprobs` (`engine.logprob_args`);
+        the records come back with the tokens."""
         try:
             _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
+            logprobs = _check_logprobs(requested_logprobs(inputs))   # nor does a bad N
         except ValueError as e:
             h = Request(inputs, max_tokens)
             h.fail(e)
@@ -104,7 +106,7 @@ class EngineFleet:
                 h = _submit(self.engine, inputs, max_tokens, sampling, adapter)
                 self.local.append(h)
                 return h
-            h = RemoteRequest(inputs, max_tokens)
+            h = RemoteRequest(inputs, max_tokens, logprobs=logprobs)
             h.fleet, h.rank, h.rid = self, dst, self.next_id
             self.next_id += 1
             self.pending[h.rid] = h
@@ -128,13 +130,14 @@ class EngineFleet:
                 break
             if msg[0] == "bye":
                 break
-            _, rid, tokens, err = msg
+            rid, tokens, err = msg[1:4]
             with self.lock:
                 h = self.pending.pop(rid, None)
                 self.load[rank] -= 1
             if h is None:
                 continue
             h.tokens = list(tokens)
+            h.logprob_records = list(msg[4]) if len(msg) > 4 else []
             if err is None:
                 h.done.set()
             else:
@@ -158,8 +161,9 @@ class EngineFleet:
     def serve_forever(self, stop_event, idle_sleep=0.002):
         self.engine.serve_forever(stop_event, idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info)
+    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
+                 logprobs=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""
@@ -193,7 +197,8 @@ def worker(engine, groups, poll_s=0.002):
                 idle = not live
             for rid, h in done:
                 err = None if h.error is None else (type(h.error).__name__, str(h.error))
-                _send(("done", rid, [int(t) for t in h.tokens], err), 0, up)
+                recs = list(getattr(h, "logprob_records", None) or [])
+                _send(("done", rid, [int(t) for t in h.tokens], err) + ((recs,) if recs else ()), 0, up)
             if closing.is_set() and idle and not done:
                 _send(("bye",), 0, up)                            # from THIS thread: the only sender on `up`, so the size / payload
                 return                                           # pairs of two messages can never interleave

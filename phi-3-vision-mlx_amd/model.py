@@ -113,6 +113,12 @@ class CacheState:
         self.row_adapter = None                                 # adapter bank: int32 [B] slot per row, made on first use (model._state_rows)
         self.sample_rows = None                                 # sampling records int32 [B, 6] (model.set_sampling)
 
+    @property
+    def logprob_want(self):
+        """The log-probability want-table, int32 [B] on the device (-1 = off), or None before `model.set_logprobs` made it.  It
+        lives with `shared`: the leases of a captured-prefill entry share their captures, which bake its address in."""
+        return self.shared.get("logprob_want")
+
     def rows_view(self, rows, offset, S):
         """Batch rows `rows` (a slice) as a cache of their own at `offset`, for a prompt of S tokens (model.prefill_slot): the same
         buffers sliced, no captured graphs, none of the slot state's roles (slots, serving, sampling records; the caller names the
@@ -1059,13 +1065,15 @@ class Phi3VModel:
         g["d_step"].zero_()                                      # the warm-up run counted as a step
         return g
 
-    def _decode_step(self, st, g, sampled=False):
+    def _decode_step(self, st, g, sampled=False, logprobs=False):
         """The launches of one decode step over the loop state `g` of a greedy capture: the layers, then the step's tail -- final
         norm + lm_head + arg-max + bookkeeping, or with sampled=True each row's token drawn under its record (`set_sampling`)
         where the greedy step has its arg-max.
         (round 6) the step's two ends have no launch of their own where the library folds them into the first / last projection
         (B = 1 on bf16, e4m3 or 4-bit weights: ops.gemv_step_begin / gemv_step_end; 129 launches per step instead of 131); the
-        sampled tail always goes through `_proj` (every weight format, adapters honoured)."""
+        sampled tail always goes through `_proj` (every weight format, adapters honoured).
+        logprobs=True: ONE more launch behind that tail, whichever it is -- the record of each row's emitted token
+        (p3v_logprobs_step) into the pinned `records` buffer; it reads the logits and the loop state and changes neither."""
         cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
         self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
                      step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
@@ -1074,17 +1082,23 @@ class Phi3VModel:
             w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
             if (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
                     and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
-                return
+                return self._logprobs_tail(st, g) if logprobs else None
         self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output)
         if sampled:
             ops.sample_step_end(g["logits"], st.sample_rows, *end)
         else:
             ops.step_end(g["logits"], *end)
+        if logprobs:
+            self._logprobs_tail(st, g)
+
+    def _logprobs_tail(self, st, g):
+        ops.logprobs_step(g["logits"], g["next_tok"], st.logprob_want, g["d_step"], g["records"])
 
     def _replay(self, token, cache, which):
-        """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy) or "sample_graph" (a
+        """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy), "sample_graph" (a
         second capture over the same loop state, built on first use -- after the token and the cache length are in place, which
-        its warm-up run reads).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
+        its warm-up run reads), or "logprob_graph" / "sample_logprob_graph" (either step followed by the log-probability launch,
+        built the same way).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
         st = cache[0].state
         if st.offset + 1 > st.T:
             raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
@@ -1093,8 +1107,9 @@ class Phi3VModel:
             g["tok"].copy_(token.reshape(-1).to(self.device, I32))   # first step / caller-chosen token
         if g.get("synced_offset") != st.offset:
             g["d_past"].fill_(st.offset)
-        if which == "sample_graph" and which not in g:
-            g[which] = self._build_sample_graph(st, g)
+        if which != "graph" and which not in g:
+            g[which] = self._build_sample_graph(st, g, sampled=which in ("sample_graph", "sample_logprob_graph"),
+                                                logprobs=which in ("logprob_graph", "sample_logprob_graph"))
         g[which].launch()
         g["n_replays"] = g.get("n_replays", 0) + 1              # replay r, greedy or sampled, wrote its token to history[:, r - 1] (while it fits)
         st.offset += 1
@@ -1107,6 +1122,14 @@ class Phi3VModel:
         """A greedy capture starts a new run on the same buffers (a reused captured-prefill entry): forget the last run's replays."""
         g["n_replays"], g["host_tok"], g["synced_offset"] = 0, None, None
         g["d_step"].zero_()
+
+    @_on_device
+    def restart_history(self, st):
+        """A long-lived state (the engine's slot state) has used up the `history` / `records` slots of its greedy capture: count
+        its steps from 0 again.  Tokens, logits and the cache are untouched; the next replay writes slot 0."""
+        g = st.graphs.get("greedy")
+        if g is not None:
+            self._reset_replays(g)
 
     @_on_device
     def greedy_prefill(self, max_tokens, **inputs):
@@ -1267,7 +1290,11 @@ class Phi3VModel:
         H2D copy, outside any graph).  Rows never written are greedy (temperature 0).  The records live with the state's decode
         graphs and are read -- and their counters advanced -- by `sample_logits` and every replay of `sample_step`."""
         if st.sample_rows is None:
-            st.sample_rows = torch.zeros((st.B, 6), dtype=I32, device=self.device)
+            # (kept with `shared`, as the want-table is: the leases of a captured-prefill entry share their sampled captures,
+            #  which bake the records' address in -- a later lease must write the SAME tensor, not one of its own)
+            st.sample_rows = st.shared.get("sample_rows")
+            if st.sample_rows is None or st.sample_rows.shape[0] != st.B:
+                st.sample_rows = st.shared["sample_rows"] = torch.zeros((st.B, 6), dtype=I32, device=self.device)
         st.sample_rows[row0:row0 + records.shape[0]].copy_(records)
 
     @_on_device
@@ -1286,20 +1313,66 @@ class Phi3VModel:
             raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
         return self._replay(token, cache, "sample_graph")
 
-    def _build_sample_graph(self, st, g):
+    def _build_sample_graph(self, st, g, sampled=True, logprobs=False):
         """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
         through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
-        The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it."""
+        The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it.
+        The two log-probability captures are made here as well: sampled=False keeps the greedy step as `_decode_step` runs it
+        (the folded tail included), logprobs=True appends p3v_logprobs_step; their records land in a pinned buffer beside
+        `history`, made with the first of them."""
         torch.cuda.synchronize()
+        if logprobs and "records" not in g:
+            g["records"] = torch.zeros((st.B, g["history"].shape[1], ops.L.LOGPROB_WORDS), dtype=I32).pin_memory()
         saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
-        saved_rows = st.sample_rows.clone()
-        g["gemm_ws_sampled"] = {}
-        graph = self._capture(lambda: self._decode_step(st, g, sampled=True), g["gemm_ws_sampled"])
+        saved_rows = st.sample_rows.clone() if sampled else None
+        ws = g["gemm_ws_" + ("sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
+        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs), ws)
         for k, v in saved.items():
             g[k].copy_(v)
-        st.sample_rows.copy_(saved_rows)
+        if sampled:
+            st.sample_rows.copy_(saved_rows)
         torch.cuda.synchronize()
         return graph
+
+    # ------------------------------------------------------------------ token log-probabilities (include/p3v.h: p3v_logprob_t)
+    @_on_device
+    def set_logprobs(self, st, wants, row0=0):
+        """Write the want-table entries of rows row0 .. row0+n-1 of a state: the N (0 .. 8) of a row whose tokens are to be
+        scored, -1 for a row nobody asks about (every row, before the first call).  Like `set_sampling`, one H2D copy outside
+        any graph: the captured log-probability launch reads the table."""
+        wants = torch.as_tensor(list(wants), dtype=I32)
+        if wants.numel() and (int(wants.min()) < -1 or int(wants.max()) > ops.L.LOGPROBS_MAX):
+            raise ValueError(f"set_logprobs: entries are -1 (off) or 0..{ops.L.LOGPROBS_MAX}")
+        if st.logprob_want is None:
+            st.shared["logprob_want"] = torch.full((st.B,), -1, dtype=I32, device=self.device)
+        st.logprob_want[row0:row0 + wants.numel()].copy_(wants)
+
+    @_on_device
+    def logprobs_of(self, st, logits, tokens, row0=0):
+        """The records of `tokens` (int32 [n] or [n, 1] on the device) on rows row0 .. row0+n-1's logits ([n, L, V] or [n, V]:
+        the last position) under their want-table entries -- the eager call for a request's FIRST token, from its prefill
+        logits.  int32 [n, 20] on the device (logprobs.unpack); rows at -1 are left zero."""
+        if st.logprob_want is None:
+            raise RuntimeError("logprobs_of: no want-table on this state (model.set_logprobs)")
+        last = logits[:, -1, :] if logits.dim() == 3 else logits
+        return ops.logprobs(last, tokens.reshape(-1).to(I32).contiguous(), st.logprob_want[row0:row0 + last.shape[0]])
+
+    @_on_device
+    def logprob_step(self, token, cache):
+        """`greedy_step` followed by the log-probability launch (a capture of its own over the greedy capture's loop state, built
+        on first use): the same logits and tokens, plus row b's record at `records[b, n_replays - 1]` of the greedy capture.
+        Plain, sampled and log-probability replays may alternate on one state."""
+        if cache[0].state.logprob_want is None:
+            raise RuntimeError("logprob_step: no want-table on this state (model.set_logprobs)")
+        return self._replay(token, cache, "logprob_graph")
+
+    @_on_device
+    def sample_logprob_step(self, token, cache):
+        """`sample_step` followed by the log-probability launch."""
+        st = cache[0].state
+        if st.sample_rows is None or st.logprob_want is None:
+            raise RuntimeError("sample_logprob_step: needs sampling records and a want-table (set_sampling, set_logprobs)")
+        return self._replay(token, cache, "sample_logprob_graph")
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,

@@ -722,6 +722,46 @@ def sample_step_end(logits, rows_params, next_tok, tok, history, d_step, d_past,
                                         _p(ticket), B, n, history.shape[1], _stream()), "sample_step_end")
 
 
+def _chk_want(want, rows):
+    _chk(want, I32, "want")
+    if want.shape != (rows,):
+        raise ValueError(f"want: expected int32 [{rows}], got {tuple(want.shape)}")
+
+
+def logprobs(logits2d, token, want, out=None):
+    """Token log-probabilities (include/p3v.h: p3v_logprobs): the record of token[r] on bf16 row r with N = want[r] top entries;
+    rows with want[r] < 0 are skipped and their `out` rows left alone.  Rows may be strided (logits[:, -1, :]).  Returns the
+    records as int32 [rows, 20] on the device (logprobs.unpack reads them)."""
+    if not logits2d.is_cuda:
+        raise RuntimeError("logits: expected a device tensor (the hot path has no CPU fallback)")
+    if logits2d.dtype != BF16 or logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError("logits: expected bf16 [rows, n] with unit stride along n")
+    rows, n = logits2d.shape
+    _chk(token, I32, "token"), _chk_want(want, rows)
+    if token.shape != (rows,):
+        raise ValueError(f"token: expected int32 [{rows}], got {tuple(token.shape)}")
+    if out is None:
+        out = torch.zeros((rows, L.LOGPROB_WORDS), dtype=I32, device=logits2d.device)
+    elif out.dtype != I32 or out.shape != (rows, L.LOGPROB_WORDS) or not out.is_contiguous():
+        raise ValueError(f"out: expected contiguous int32 [{rows}, {L.LOGPROB_WORDS}] records")
+    stride = logits2d.stride(0) if rows > 1 else n              # (a one-row tensor's row stride is arbitrary, 0 included: never used)
+    L.check(L.lib().p3v_logprobs(_p(logits2d), stride, _p(token), _p(want), _p(out), rows, n, _stream()), "logprobs")
+    return out
+
+
+def logprobs_step(logits, next_tok, want, d_step, records):
+    """The launch after a replayed step's tail: row b's record of the token the step emitted -> records[b, *d_step - 1]
+    (int32 [B, max_steps, 20], pinned host or device memory) for rows with want[b] >= 0."""
+    _chk(logits, BF16, "logits"), _chk(next_tok, I32, "next_tok"), _chk(d_step, I32, "d_step")
+    B, n = logits.shape[0], logits.shape[-1]
+    _chk_want(want, B)
+    if (records.dtype != I32 or records.dim() != 3 or records.shape[0] != B or records.shape[2] != L.LOGPROB_WORDS
+            or not records.is_contiguous() or not (records.is_pinned() or records.is_cuda)):
+        raise ValueError(f"records: expected contiguous int32 [{B}, max_steps, {L.LOGPROB_WORDS}] in pinned host (or device) memory")
+    L.check(L.lib().p3v_logprobs_step(_p(logits), _p(next_tok), _p(want), _p(d_step), _p(records), B, n, records.shape[1],
+                                      _stream()), "logprobs_step")
+
+
 def spec_state(g, n_max, n_min):
     """p3v_spec_state_t over the loop-state buffers of a speculative capture (model._build_spec_graph)."""
     _chk(g["tok"], I32, "tok"), _chk(g["ctx"], I32, "ctx"), _chk(g["ctl"], I32, "ctl"), _chk(g["amax"], I32, "amax")

@@ -16,6 +16,12 @@
      one-request path: K prompt-lookup draft tokens verified per decode step, the same text in fewer steps (api.speculative_loop).
      The response gains "speculation": {"steps", "drafted", "accepted"}.  One prompt, greedy, no image; an explicit K > 0 anywhere
      else -- a list of prompts, temperature > 0, a server started with --continuous or --merge -- is answered with 400.)
+    (extension: "logprobs": N (0 .. 8; absent / null = off) -- every generated token's log-probability under the RAW logits (no
+     temperature, no top-k, no top-p: the OpenAI / vLLM convention), its rank and the N most likely tokens at its position
+     (include/p3v.h: p3v_logprob_t).  The response gains "logprobs": one object per prompt with the aligned lists "token_ids",
+     "tokens" (the decoded pieces), "token_logprobs", "ranks" and "top_logprobs" (per token a list of {"id", "token", "logprob"});
+     non-finite values travel as null.  A bool, a string or a value outside 0 .. 8 -> 400 naming the range; so does an explicit
+     "speculate" > 0 next to it, and the batch-sharded path.  Merged requests keep their own N.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -48,9 +54,10 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs")
 
-    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None):
+    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None):
+        self.logprobs = logprobs                # None, or one N per prompt
         self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
         self.adapter = adapter                  # None, or one name / None per prompt
         self.speculate, self.info = speculate, info             # draft rows per verify step (0 = off), the caller's statistics dict
@@ -136,6 +143,45 @@ def parse_speculate(request, n_prompts, engine, sampling=None):
     if explicit:
         raise ValueError(why)
     return 0                                    # (the server-wide default applies where it can; only an explicit field is refused)
+
+
+def parse_logprobs(request, n_prompts):
+    """The "logprobs" field of a request body -> None (absent or null: off) or [N] * n_prompts.  ValueError (-> 400) naming the
+    range on a bool, a string, a list, or a value outside 0 .. 8."""
+    from .logprobs import OFF, check
+    v = request.get("logprobs")
+    if isinstance(v, (list, tuple, dict)):
+        raise ValueError(f"logprobs must be a single integer 0 .. 8 (or null), got {type(v).__name__}")
+    want = check(v)
+    return None if want == OFF else [want] * n_prompts
+
+
+def token_decoder(engine):
+    """id -> text piece for the "tokens" of a logprobs response: the backend's `decode_fn`, or its tokenizer; None without one."""
+    fn = getattr(engine, "decode_fn", None)
+    if fn is not None:
+        return fn
+    inner = getattr(engine, "engine", engine)
+    tok = getattr(getattr(inner, "processor", None), "tokenizer", None)
+    return None if tok is None else (lambda i: tok.decode([int(i)]))
+
+
+def format_logprobs(entry, decode=None, eos_id=None):
+    """One prompt's logprobs.entry (or None) -> the response object: lists cut behind the first `eos_id` (where the text ends),
+    decoded pieces beside the ids, null for every non-finite value."""
+    from .logprobs import finite_or_none
+    if entry is None:
+        return None
+    ids = list(entry["token_ids"])
+    n = ids.index(eos_id) + 1 if eos_id is not None and eos_id in ids else len(ids)
+
+    def piece(i):
+        return decode(i) if decode is not None and i >= 0 else None
+    return {"token_ids": ids[:n], "tokens": [piece(i) for i in ids[:n]],
+            "token_logprobs": [finite_or_none(x) for x in entry["token_logprobs"][:n]],
+            "ranks": list(entry["ranks"][:n]),
+            "top_logprobs": [[{"id": i, "token": piece(i), "logprob": finite_or_none(lp)} for i, lp in top]
+                             for top in entry["top_logprobs"][:n]]}
 
 
 def parse_cache_prompt(request):
@@ -230,7 +276,8 @@ class EngineQueue:
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
                  length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=(), speculate=False,
-                 speculate_default=0):
+                 speculate_default=0, decode_fn=None):
+        self.decode_fn = decode_fn                              # token id -> text piece (the "tokens" of a logprobs response)
         # speculate: generate_fn takes `speculate=K, spec_info=dict` (one prompt, greedy); never with merge (B > 1 batches)
         self.speculate, self.speculate_default = bool(speculate) and not merge, int(speculate_default)
         self.adapter_names = list(adapter_names)                # what generate_fn's `adapter` keyword may name (GET /v1/adapters)
@@ -246,8 +293,8 @@ class EngineQueue:
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info)
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info, logprobs)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -303,6 +350,10 @@ class EngineQueue:
             flat = [p for j in group for p in j.prompts]
             try:
                 kw = {} if first.adapter is None else {"adapter": first.adapter}
+                lp_info = None
+                if any(j.logprobs is not None for j in group):  # every row keeps its own request's N (None: that row is off)
+                    lp_info = {}
+                    kw.update(logprobs=[w for j in group for w in (j.logprobs or [None] * len(j.prompts))], logprob_info=lp_info)
                 if first.speculate:                             # (one prompt, never merged: self.speculate excludes merge)
                     stats = {}
                     out = self.generate_fn(flat, first.max_tokens, first.images, speculate=first.speculate, spec_info=stats, **kw)
@@ -323,6 +374,9 @@ class EngineQueue:
                 i = 0
                 for j in group:
                     j.result = out[i:i + len(j.prompts)]
+                    if j.logprobs is not None and j.info is not None:
+                        j.info["logprobs"] = [None if lp_info["token_ids"][b] is None else {k: lp_info[k][b] for k in lp_info}
+                                              for b in range(i, i + len(j.prompts))]
                     i += len(j.prompts)
             except Exception as e:              # noqa: BLE001 -- reported to every waiting request
                 for j in group:
@@ -374,7 +428,16 @@ def make_handler(engine, image_policy=None):
                 adapter = parse_adapter(request, len(prompts), known_adapters(engine))
                 cache_prompt = parse_cache_prompt(request)
                 speculate = parse_speculate(request, len(prompts), engine, sampling)
+                logprobs = parse_logprobs(request, len(prompts))
                 sharded = getattr(engine, "sharded_fn", None)
+                if logprobs is not None and speculate:
+                    if "speculate" in request:
+                        raise ValueError("logprobs are not available under speculative decoding (a verify step emits several "
+                                         "tokens per replay); send speculate 0")
+                    speculate = 0                               # (the server-wide default steps aside)
+                if logprobs is not None and sharded is not None and sharded(prompts, images):
+                    raise ValueError("logprobs are not available on the batch-sharded path (image requests and process groups of "
+                                     "the queue server); run the server with --continuous, or send no logprobs")
                 if speculate and sharded is not None and sharded(prompts, images):
                     if "speculate" in request:
                         raise ValueError("speculative decoding is not available on the batch-sharded path (image requests and "
@@ -391,7 +454,13 @@ def make_handler(engine, image_policy=None):
                 return
             info = None
             try:
-                if speculate:
+                if logprobs is not None:
+                    info = {}
+                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
+                    if prefix_counters(engine) is not None and cache_prompt is not None:
+                        kw["cache_prompt"] = cache_prompt
+                    responses = engine.submit(prompts, max_tokens, images, logprobs=logprobs, info=info, **kw)
+                elif speculate:
                     info = {}
                     kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
                     responses = engine.submit(prompts, max_tokens, images, speculate=speculate, info=info, **kw)
@@ -414,8 +483,12 @@ def make_handler(engine, image_policy=None):
                 out["seeds"] = [r["seed"] for r in sampling]
             if speculate:
                 out["speculation"] = info.get("speculation", {"steps": 0, "drafted": 0, "accepted": 0})
-            elif info is not None:
+            elif info is not None and (logprobs is None or prefix_counters(engine) is not None):
                 out["cached_tokens"] = list(info.get("cached_tokens", [0] * len(prompts)))
+            if logprobs is not None:
+                from .api import ID_EOS
+                decode = token_decoder(engine)
+                out["logprobs"] = [format_logprobs(e, decode, ID_EOS) for e in info.get("logprobs") or [None] * len(prompts)]
             self._send(200, out)
 
         def log_message(self, *args):           # quiet
@@ -464,9 +537,11 @@ class ContinuousBackend:
             return out
         return counters
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None):
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None):
         mt = max(1, min(int(max_tokens), self.max_tokens_cap))
         kw = {} if adapter is None else {"adapter": adapter}
+        if logprobs is not None:
+            kw["logprobs"] = logprobs
         if cache_prompt is not None:
             kw["cache_prompt"] = cache_prompt
         if info is not None:
@@ -529,13 +604,16 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         import torch.distributed as dist
         return images is not None or (dist.is_available() and dist.is_initialized())
 
-    def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None):
+    def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
+                    logprob_info=None):
         import torch.distributed as dist
         if speculate:                                                # (one prompt, greedy, no image: the handler saw to it)
             return generate(prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, speculate=speculate, spec_info=spec_info,
                             **({} if adapter is None else {"adapter": adapter[0]}))
-        if sampling is not None or adapter is not None:              # (the handler kept these requests off the sharded path)
+        if sampling is not None or adapter is not None or logprobs is not None:   # (the handler kept these requests off the sharded path)
             kw = {} if sampling is None else {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
+            if logprobs is not None:
+                kw.update(logprobs=logprobs, logprob_info=logprob_info)
             if adapter is not None:
                 kw["adapter"] = adapter if len(prompts) > 1 else adapter[0]
             return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, **kw)
@@ -552,7 +630,7 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
 
     httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
                           image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True,
-                          speculate_default=speculate)
+                          speculate_default=speculate, decode_fn=lambda i: processor.tokenizer.decode([int(i)]))
     print(f"Starting server on port {port}")
     try:
         httpd.serve_forever()
