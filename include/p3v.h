@@ -242,7 +242,12 @@ int64_t p3v_attention_ws_bytes(int B, int L, int n_heads, int hd, int n_split);
  * Key ranges of the splits are a static function of cache_t, so loads start before d_past arrives.
  * `past` with d_past != NULL: a LOWER BOUND of *d_past known when the launch is recorded (a captured decode step: the prompt
  * length), or negative for "none".  The 128-key kernel requests tiles below the bound at once; tiles at or beyond it wait
- * for *d_past and fetch nothing when they lie wholly past the live keys (the capacity is prompt + max_tokens). */
+ * for *d_past and fetch nothing when they lie wholly past the live keys (the capacity is prompt + max_tokens).
+ * Query row i of batch row b sees key t iff pad_len[b] <= t <= past + i.  Every other position of the caches -- the left padding
+ * [0, pad_len[b]) and everything at or beyond the live length past + L -- must hold FINITE values and is otherwise ignored: whatever
+ * finite K rows / V^T columns lie there, however large, the output does not depend on them (nothing is promised for NaN or
+ * infinities), and no byte outside [past, past + L) is written.  Splits that hold no live key contribute nothing.
+ * (tests/test_attn_probe_gpu.py pins this against fp64 with 1e4 in every dead position, at 640 .. 33,280 keys of capacity.) */
 typedef struct {
   const uint16_t* qkv; const float* cos_t; const float* sin_t;
   uint16_t* k_cache; uint16_t* v_cache; uint16_t* out;
@@ -285,7 +290,8 @@ int p3v_stage_rope(const float* cos_t, const float* sin_t, int past, const int32
 int p3v_kv_quantize(const uint16_t* k, const uint16_t* vt, uint8_t* k8, uint8_t* v8t, float* k_scale, float* v_scale,
                     int BH, int hd, int src_t, int dst_t, int t0, int n_tok, void* stream);
 /* p3v_attention_decode on the int8 cache: same contract; the step's own new rows are quantised,
- * appended, and attended in their quantised form (one representation per key, whenever it is read). */
+ * appended, and attended in their quantised form (one representation per key, whenever it is read).
+ * Dead positions (left padding, at or beyond past + L): any codes with FINITE scales, otherwise ignored, as for the bf16 cache. */
 /* the inverse, tokens [0, n_tok) of every (batch row, kv head): bf16 K [BH, dst_t, hd] / V^T [BH, hd, dst_t] = (code - 128) * scale.
  * For cached calls with more than 16 new tokens on the int8 cache (they attend through p3v_attention on this copy). */
 int p3v_kv_dequantize(const uint8_t* k8, const uint8_t* v8t, const float* k_scale, const float* v_scale, uint16_t* k,
