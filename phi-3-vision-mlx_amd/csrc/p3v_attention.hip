@@ -20,9 +20,9 @@
 #include <stdlib.h>
 
 #include "p3v_common.h"
-#include "p3v_gemv3_body.h"      // dot8: the fused o_proj of k_attn_decode128_o repeats k_gemv3's arithmetic exactly
-#include "p3v_dot_f8.h"          // dot16_f8: ... k_attn_decode128_q8<true> repeats k_gemv3_f8's
-#include "p3v_dot_q4.h"          // dot8_q4: ... and k_attn_decode128_o4 repeats k_gemv3_q4's
+#include "p3v_dot_bf16.h"        // dot8: the fused o_proj of k_attn_decode128_o repeats k_gemv3's arithmetic exactly
+#include "p3v_dot_f8.h"          // dot16_f8: ... k_attn_decode128_q8<true> repeats k_gemv3<GemvF8, ..>'s
+#include "p3v_dot_q4.h"          // dot8_q4: ... and k_attn_decode128_o4 repeats k_gemv3<GemvQ4, ..>'s
 
 struct AttnP {
   const bf16_t* q; const bf16_t* k_past; const bf16_t* v_past; const bf16_t* k_new; const bf16_t* v_new;
@@ -1905,8 +1905,8 @@ __host__ __device__ __forceinline__ FoMap fo_map(int L, int n_split, int nh, int
 #endif
 // The projection half of the fused decode launches (k_attn_decode128_o, k_attn_decode128_q8_o): workgroup `o_wl` of the launch's
 // non-merging workgroups owns rows [8 o_wl, 8 o_wl + 8) of W_o, one row pair per wave, requested when the workgroup's partial has
-// been stored.  KIND: FO_BF16 (k_gemv3's arithmetic), FO_F8 (e4m3 weights, one fp32 scale per row: k_gemv3_f8's) or FO_Q4 (MLX
-// 4-bit group-64 in the device layout of p3v_gemv_q4.hip, `o_scale` = its SB words: k_gemv3_q4's).  `lds`: >= 7 KB that nobody
+// been stored.  KIND: FO_BF16 (k_gemv3's arithmetic), FO_F8 (e4m3 weights, one fp32 scale per row: k_gemv3<GemvF8, ..>'s) or FO_Q4 (MLX
+// 4-bit group-64 in the device layout of p3v_gemv_q4.hip, `o_scale` = its SB words: k_gemv3<GemvQ4, ..>'s).  `lds`: >= 7 KB that nobody
 // else uses any more.
 enum { FO_NONE = 0, FO_BF16 = 1, FO_F8 = 2, FO_Q4 = 3 };
 struct FoP { const void* o_w; const void* o_scale; bf16_t* o_x; const bf16_t* out; int nh; };
@@ -1997,7 +1997,7 @@ __device__ __forceinline__ void fo_project(const FoP f, const int o_wl, unsigned
     __syncthreads();
     timeout = o_timeout != 0;
     float* xsum = (float*)(lds + 6144);
-    if (Q4) {                                                  // k_gemv3_q4<1, 3>: X = sum of a piece's 16 activations
+    if (Q4) {                                                  // k_gemv3<GemvQ4, 1, 1, 3>: X = sum of a piece's 16 activations
       if (tid < 192) {
         const u32x4_t a = ((const u32x4_t*)xs)[2 * tid], b = ((const u32x4_t*)xs)[2 * tid + 1];
         float t = 0.f;
@@ -2027,7 +2027,7 @@ __device__ __forceinline__ void fo_project(const FoP f, const int o_wl, unsigned
         if (k == 0) TMARK(13);
         a0 = wave_sum(a0);
         a1 = wave_sum(a1);
-      } else if (F8) {                                         // k_gemv3_f8<1, 3>: weight chunk c = 64 j + lane meets x chunks 2c, 2c + 1
+      } else if (F8) {                                         // k_gemv3<GemvF8, 1, 1, 3>: weight chunk c = 64 j + lane meets x chunks 2c, 2c + 1
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const u32x4_t xa = ((const u32x4_t*)xs)[2 * (j * 64 + lane)], xb = ((const u32x4_t*)xs)[2 * (j * 64 + lane) + 1];

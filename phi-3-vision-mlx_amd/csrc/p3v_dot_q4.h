@@ -1,4 +1,4 @@
-// 8 repacked 4-bit weights . 8 bf16 activations: shared by k_gemv3_q4 (p3v_gemv_q4.hip, which documents the layout) and the
+// 8 repacked 4-bit weights . 8 bf16 activations: shared by the streaming GEMV on 4-bit weights (GemvQ4 in p3v_gemv_q4.hip, which documents the layout) and the
 // o_proj half of k_attn_decode128_o4 (p3v_attention.hip), which must repeat the GEMV's arithmetic bit for bit.
 #pragma once
 #include "p3v_common.h"

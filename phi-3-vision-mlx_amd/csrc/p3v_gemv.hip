@@ -15,8 +15,14 @@
 #include <type_traits>
 
 #include "p3v_common.h"
+#include "p3v_dot_bf16.h"
 #include "p3v_gemv3_body.h"
 
+struct GemvP {
+  const bf16_t* x; const bf16_t* W; void* out; const bf16_t* resid; const bf16_t* norm_w;
+  float eps;
+  int M, N, K, epi, units;
+};
 
 template <int MT>
 __global__ void __launch_bounds__(256) k_gemv(GemvP p) {
@@ -128,17 +134,8 @@ static int launch_gemv(const GemvP& p, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
-// Streaming variant for the B=1 decode shapes (M <= 2; K = 3072 or 8192, compile-time):
-// written so that hipcc can keep COUNTED s_waitcnt vmcnt(N) everywhere -- every load is
-// unconditional and the pipeline body is branch-free (a predicated load or a branch between
-// issue and use makes the compiler fall back to vmcnt(0), which drains the prefetch):
-//   * x (+ norm weight) chunks are requested first, then the wave's first weight stage, so
-//     the RMSNorm prologue waits only for the older x loads while the weights stream in;
-//   * (row pair, K stage) software pipeline with two register buffers: stage s+1 is in
-//     flight (2*CH 16-byte loads per lane) while stage s is reduced; the residual needed by
-//     the epilogue travels with the stage (no dependent load at the end of a row);
-//   * grid = ~8 waves per CU, each wave owning a contiguous run of row pairs (a pure
-//     streaming read on this chip peaks at 2 blocks x 256 threads per CU, see tools/stream_floor.hip).
+// Streaming variant for the B=1 decode shapes (M <= 4; K = 3072 or 8192, compile-time): gemv_stream_body (p3v_gemv3_body.h) on
+// bf16 weights -- a lane load is 16 bytes = 8 weights, nothing travels with a stage, the sum of a row is its result.
 #ifdef P3V_GEMV_TIMING                                         // tools/gemv_timeline.py: 100 MHz stamps per wave (entry, exit)
 __device__ long long p3v_gemv_tbuf[4096 * 2];
 extern "C" int p3v_gemv_timing_read(long long* out, int n) {
@@ -148,52 +145,31 @@ extern "C" int p3v_gemv_timing_read(long long* out, int n) {
 #else
 #define GMARK(k)
 #endif
-template <int MT, int NST, int CH>
-__global__ void __launch_bounds__(256) k_gemv3(GemvP p, int units_per_wave, int wpw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8];
-  GMARK(0);
-  gemv3_body<MT, NST, CH>(p, units_per_wave, blockIdx.x, smem, red, wpw);
-  GMARK(1);
-}
-
-template <int MT, int NST, int CH, int STEP>
-__global__ void __launch_bounds__(256) k_gemv3_step(GemvP p, int units_per_wave, int wpw, GemvStepP sp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[8];
-  gemv3_body<MT, NST, CH, STEP>(p, units_per_wave, blockIdx.x, smem, red, wpw, &sp);
-}
-
-template <int MT, int NST, int CH, int STEP = STEP_NONE>
-static int launch_gemv3(const GemvP& p, hipStream_t s, const GemvStepP* sp = nullptr) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
-    n_cu = pr.multiProcessorCount;
+struct GemvBf16 {
+  typedef GemvP P;
+  static constexpr int WPL = 8, MAX_MT = 4;
+  static constexpr bool XSUM = false;
+  template <int CH> struct Stage { u32x4_t w[2][CH]; };
+  static int wpc() { return p3v_tuning().gemv_wpc; }
+  static __device__ __forceinline__ void mark(int k) { GMARK(k); }
+  template <int K, int CH>
+  static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
+    const u32x4_t* w0 = (const u32x4_t*)(p.W + (size_t)r0 * K) + c0;
+    const u32x4_t* w1 = (const u32x4_t*)(p.W + (size_t)r1 * K) + c0;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      st.w[0][j] = __builtin_nontemporal_load(w0 + j * 64);
+      st.w[1][j] = __builtin_nontemporal_load(w1 + j * 64);
+    }
   }
-  const int wpc = p3v_tuning().gemv_wpc;    // waves per CU
-  int upw = p3v_cdiv(p.units, n_cu * wpc);               // row pairs per wave
-  if (upw < 1) upw = 1;
-  const int waves = p3v_cdiv(p.units, upw);
-  const int wpw_ = p3v_gemv_wpw(waves, n_cu, p3v_tuning().gemv_wpw);   // 4 or 3 row-streaming waves per workgroup
-  const size_t lds = (size_t)MT * p.K * 2;
-  static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)k_gemv3<MT, NST, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
-      return P3V_ERR_HIP;
-    attr_set = true;
+  template <int CH>
+  static __device__ __forceinline__ void dot(const Stage<CH>& st, int j, const u32x4_t* x, const float*, int c, float& a0, float& a1) {
+    const u32x4_t xa = x[c];
+    a0 = dot8(st.w[0][j], xa, a0);
+    a1 = dot8(st.w[1][j], xa, a1);
   }
-  if constexpr (STEP != STEP_NONE) {
-    if (p3v_cdiv(waves, wpw_) > P3V_GEMV_STEP_MAX_WG) return P3V_ERR_UNSUPPORTED;      // (amax_ws holds one candidate per workgroup and row)
-    hipLaunchKernelGGL((k_gemv3_step<MT, NST, CH, STEP>), dim3(p3v_cdiv(waves, wpw_)), dim3(256), lds, s, p, upw, wpw_, *sp);
-  } else {
-    hipLaunchKernelGGL((k_gemv3<MT, NST, CH>), dim3(p3v_cdiv(waves, wpw_)), dim3(256), lds, s, p, upw, wpw_);
-  }
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
+  template <int CH> static __device__ __forceinline__ float finish(float v, const Stage<CH>&, int) { return v; }
+};
 
 // ---------------------------------------------------------------------------
 // Batched decode / constrained decoding (2 <= M <= 16 rows of x): the same weight stream, but the
@@ -547,31 +523,16 @@ static int launch_gemv_mfma(const GemvP& p, hipStream_t s) {
   return P3V_OK;
 }
 
-// The first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in (gemv3_body<.., STEP>): only on
-// the M = 1 streaming kernel (bf16 weights, K = 3072 or 8192); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the
-// separate launches.
+// The first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in (gemv_stream_body<.., STEP>): only
+// on the M = 1 streaming kernel (K = 3072 or 8192); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_step(const p3v_gemv_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->out) return P3V_ERR_ARG;
-  const bool begin = st->tok != nullptr, end = st->next_tok != nullptr;
-  if (begin == end) return P3V_ERR_ARG;                        // exactly one of the two ends
-  if (a->M <= 0 || a->N <= 0 || a->K <= 0) return P3V_ERR_ARG;
-  // one row only: that is where p3v_gemv itself runs this kernel (2 .. 8 rows go to k_gemv_mfma8, whose sums associate differently --
-  // a folded step must stay bit-identical to the eager one)
-  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192) || p3v_tuning().gemv_variant != 3) return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue != P3V_EPI_NONE) return P3V_ERR_UNSUPPORTED;
-  if (begin) {
-    if (!st->embed_table || !st->x_out || !st->cos_t || !st->sin_t || !st->d_past || !st->cos_out || !st->sin_out || st->vocab <= 0) return P3V_ERR_ARG;
-    if (((uintptr_t)st->embed_table | (uintptr_t)st->x_out) & 15) return P3V_ERR_ARG;
-  } else {
-    if (!a->x || !st->tok_out || !st->history || !st->d_step || !st->d_past || !st->ticket || !st->amax_ws) return P3V_ERR_ARG;
-    if ((uintptr_t)st->amax_ws & 7) return P3V_ERR_ARG;
-  }
+  GemvStepP sp; bool begin;
+  if (const int rc = gemv_step_params(a, st, p3v_tuning().gemv_variant == 3, sp, begin)) return rc;
   GemvP p = {a->x, a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, (a->N + 1) / 2};
-  const GemvStepP sp = {st->tok, st->embed_table, st->vocab, st->x_out, st->cos_t, st->sin_t, st->d_past, st->cos_out, st->sin_out, st->tab_t,
-                        st->half_dim, st->next_tok, st->tok_out, st->history, st->d_step, st->d_past, st->ticket, st->amax_ws, st->max_steps};
   hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv3<1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv3<1, 1, 6, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv3<1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv3<1, 4, 4, STEP_END>(p, s, &sp);
+  if (a->K == 3072) return begin ? launch_gemv_stream<GemvBf16, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvBf16, 1, 1, 6, STEP_END>(p, s, &sp);
+  return begin ? launch_gemv_stream<GemvBf16, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvBf16, 1, 4, 4, STEP_END>(p, s, &sp);
 }
 
 extern "C" int p3v_gemv(const p3v_gemv_args_t* a, void* stream) {
@@ -587,8 +548,8 @@ extern "C" int p3v_gemv(const p3v_gemv_args_t* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int variant = p3v_tuning().gemv_variant;       // 1: generic kernel only; 3: streaming kernel where it applies
   if (variant == 3 && mt == 1 && a->N % 2 == 0 && (a->K == 3072 || a->K == 8192)) {
-    if (a->K == 3072) return launch_gemv3<1, 1, 6>(p, s);
-    return launch_gemv3<1, 4, 4>(p, s);                  // 8192 = 4 stages x 4 chunks: keeps 2 waves/SIMD resident
+    if (a->K == 3072) return launch_gemv_stream<GemvBf16, 1, 1, 6>(p, s);
+    return launch_gemv_stream<GemvBf16, 1, 4, 4>(p, s);                  // 8192 = 4 stages x 4 chunks: keeps 2 waves/SIMD resident
   }
   // 2 <= M <= 4: the same streaming kernel with MT activation rows in LDS (full-line weight loads, 4 v_dot2c per row and
   // 16-byte chunk): measured 2.19 vs 2.94 ms/step at B = 2 and 2.64 vs 3.26 at B = 4 against k_gemv_mfma; from M = 5 on the
@@ -601,8 +562,8 @@ extern "C" int p3v_gemv(const p3v_gemv_args_t* a, void* stream) {
   const int rows8_min = p3v_tuning().gemv8_min;
   if (rows_variant && variant == 3 && a->M >= 2 && a->M <= 4 && a->M < rows8_min && a->N % 2 == 0 && a->epilogue != P3V_EPI_F32 &&
       (a->K == 3072 || a->K == 8192)) {
-    if (a->K == 3072) return mt == 2 ? launch_gemv3<2, 1, 6>(p, s) : launch_gemv3<4, 1, 6>(p, s);
-    return mt == 2 ? launch_gemv3<2, 4, 4>(p, s) : launch_gemv3<4, 4, 4>(p, s);
+    if (a->K == 3072) return mt == 2 ? launch_gemv_stream<GemvBf16, 2, 1, 6>(p, s) : launch_gemv_stream<GemvBf16, 4, 1, 6>(p, s);
+    return mt == 2 ? launch_gemv_stream<GemvBf16, 2, 4, 4>(p, s) : launch_gemv_stream<GemvBf16, 4, 4, 4>(p, s);
   }
   const int rows8 = p3v_tuning().gemv_mfma8;
   if (rows8 && a->M >= rows8_min && a->M <= 8) {

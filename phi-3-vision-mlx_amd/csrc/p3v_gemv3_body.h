@@ -1,32 +1,20 @@
-// Body of the streaming M = 1 GEMV (k_gemv3, p3v_gemv.hip), shared with the o_proj stage of the fused attention launch
-// (fo_project, p3v_attention.hip).  (Two more fused launches once shared it -- a GEMV chain and a qkv-projection + attention launch,
-// both bit-exact, both slower than separate launches; removed in round 4, described in DESIGN.md section 3.1.)
+// The streaming M = 1 GEMV of the decode step, written ONCE for every weight format: gemv_stream_body, the two kernels around it
+// (k_gemv3 / k_gemv3_step), their launcher and the argument check of the p3v_gemv*_step entry points.  A weight format is a policy
+// struct F -- GemvBf16 (p3v_gemv.hip), GemvF8 (p3v_gemv_fp8.hip), GemvQ4 (p3v_gemv_q4.hip) -- that supplies only what differs:
+//   P           the kernel's parameter struct (x, W, out, resid, norm_w, eps, M, N, K, epi, units + the format's own pointers)
+//   WPL         weights per lane load (8 bf16 / 16 e4m3 in 16 bytes, 16 nibbles in 8 bytes);  MAX_MT: x rows it can carry (1 unless bf16)
+//   Stage<CH>   one pipeline stage of a row pair in registers: w[2][CH] lane loads + what travels with them (e4m3: the two fp32 row
+//               scales; 4-bit: CH scale | bias words per row)
+//   load        requests a Stage, in the order that format's stream wants;  dot: folds lane load j of both rows into the two
+//               accumulators from the activations in LDS;  finish: applied to a row's sum after wave_sum (the e4m3 row scale)
+//   XSUM        the 4-bit form needs the sum of every 16 activations: one more pass over LDS between staging and streaming
+//   wpc         the format's waves-per-CU tuning knob;  mark: timing stamp hook (tools/gemv_timeline.py, bf16 only)
+// (fo_project, the o_proj stage of the fused attention launches in p3v_attention.hip, repeats this arithmetic from the p3v_dot_*.h
+// helpers; it does not share the body.  Two fused launches that did were removed in round 4: DESIGN.md section 3.1.)
 #pragma once
 #include <type_traits>
 
 #include "p3v_common.h"
-
-struct GemvP {
-  const bf16_t* x; const bf16_t* W; void* out; const bf16_t* resid; const bf16_t* norm_w;
-  float eps;
-  int M, N, K, epi, units;
-};
-
-// 8 bf16 x 8 bf16 -> fp32 accumulate on v_dot2c_f32_bf16 (two products per instruction straight from the packed
-// operands): 4 VALU instructions per 16-byte weight chunk instead of 8 unpacks + 8 FMAs -- the GEMV's VALU pipe was
-// ~60 % busy with unpacking before.
-// (The pairs are taken with shufflevector from an 8 x bf16 view: hipcc 7.2 folds `bit_cast<2 x bf16>(w[j])` of the four
-// dwords of a u32x4 into element 0 -- same family of bug as the permlane-swap fold noted in p3v_common.h.)
-typedef __bf16 bf16pair_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16oct_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float dot8(u32x4_t w, u32x4_t x, float acc) {
-  const bf16oct_t wv = __builtin_bit_cast(bf16oct_t, w), xv = __builtin_bit_cast(bf16oct_t, x);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(wv, wv, 0, 1), __builtin_shufflevector(xv, xv, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(wv, wv, 2, 3), __builtin_shufflevector(xv, xv, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(wv, wv, 4, 5), __builtin_shufflevector(xv, xv, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(wv, wv, 6, 7), __builtin_shufflevector(xv, xv, 6, 7), acc, false);
-  return acc;
-}
 
 typedef std::integral_constant<int, 0> IC0;
 typedef std::integral_constant<int, 1> IC1;
@@ -144,61 +132,71 @@ __device__ __forceinline__ void gemv_step_end_tail(const GemvStepP* sp, const Ar
   }
 }
 
+// Written so that hipcc can keep COUNTED s_waitcnt vmcnt(N) everywhere -- every load is unconditional and the pipeline body is
+// branch-free (a predicated load or a branch between issue and use makes the compiler fall back to vmcnt(0), which drains the prefetch):
+//   * x (+ norm weight) chunks are requested first, then the wave's first weight stage, so the RMSNorm prologue waits only for the
+//     older x loads while the weights stream in;
+//   * (row pair, K stage) software pipeline with two register buffers: stage s+1 is in flight (2*CH lane loads per lane) while stage s
+//     is reduced; the residual needed by the epilogue travels with the stage (no dependent load at the end of a row);
+//   * grid = F::wpc() waves per CU, each wave owning a contiguous run of row pairs (a pure streaming read on this chip peaks at
+//     2 blocks x 256 threads per CU, see tools/stream_floor.hip).
+// K = NST stages x CH lane loads x 64 lanes x F::WPL weights, compile-time.
 // wpw: waves of the 4-wave workgroup that take rows (4, or 3: wave 3 then only helps with the prologue).  1536 streaming waves
 // (qkv, o_proj, down) as 384 four-wave workgroups put two workgroups on half of the CUs and one on the others, and the launch
 // lasts as long as the doubly loaded CUs; 512 workgroups x 3 waves load every CU alike (tools/gemv_timeline.py).
-template <int MT, int NST, int CH, int STEP = STEP_NONE>
-__device__ __forceinline__ void gemv3_body(const GemvP& p, int units_per_wave, int bx, unsigned char* smem, float* red, int wpw = 4,
-                                           const GemvStepP* sp = nullptr) {
-  constexpr int CHUNKS = NST * CH * 64;                 // 16-byte chunks per row (K = 8 * CHUNKS)
-  constexpr int XC = (CHUNKS + 255) / 256;              // x chunks per thread
-  u32x4_t* xs = (u32x4_t*)smem;                         // [MT][CHUNKS] bf16 x (normalised)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+template <class F, int MT, int NST, int CH, int STEP>
+__device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int units_per_wave, int wpw, const GemvStepP* sp) {
+  static_assert(MT <= F::MAX_MT, "this weight format streams one x row only");
+  constexpr int K = NST * CH * 64 * F::WPL;
+  constexpr int XCH = K / 8;                            // 16-byte x chunks per row
+  constexpr int XC = (XCH + 255) / 256;                 // x chunks per thread
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ float red[8];
+  u32x4_t* xs = (u32x4_t*)smem;                         // [MT][XCH] bf16 x (normalised)
+  float* xsum = (float*)(smem + MT * K * 2);            // F::XSUM: [K / 16] sum of the 16 activations of a piece
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, bx = blockIdx.x;
   const bool silu = p.epi == P3V_EPI_SILU_MUL;
   const bool has_res = p.epi == P3V_EPI_RESID_BF16;
   const int u_begin = wave < wpw ? min(p.units, (bx * wpw + wave) * units_per_wave) : p.units;
   const int u_end = min(p.units, u_begin + units_per_wave);
   const int n_st = (u_end - u_begin) * NST;
 
+  // (MT == 1 is launched for M == 1 only: row 0 and "m < M" are then compile-time, as the one-row kernels had them)
+  const auto row = [&](int m) { return MT == 1 ? 0 : min(m, p.M - 1); };
+  const auto live = [&](int m) { return MT == 1 || m < p.M; };
   // ---- 1. x / norm-weight loads (oldest in the queue)
   u32x4_t xv[MT][XC], gv[XC];
   const bf16_t* xrow[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     if (STEP == STEP_BEGIN) {
-      int id = sp->tok[min(m, p.M - 1)];                       // (uniform: a scalar load)
+      int id = sp->tok[row(m)];                       // (uniform: a scalar load)
       id = id < 0 ? 0 : (id >= sp->vocab ? sp->vocab - 1 : id);
-      xrow[m] = sp->table + (size_t)id * (CHUNKS * 8);
+      xrow[m] = sp->table + (size_t)id * K;
     } else {
-      xrow[m] = p.x + (size_t)min(m, p.M - 1) * (CHUNKS * 8);
+      xrow[m] = p.x + (size_t)row(m) * K;
     }
   }
 #pragma unroll
   for (int k = 0; k < XC; ++k) {
-    const int c = min(tid + k * 256, CHUNKS - 1);
+    const int c = min(tid + k * 256, XCH - 1);
 #pragma unroll
     for (int m = 0; m < MT; ++m) xv[m][k] = ((const u32x4_t*)xrow[m])[c];
     gv[k] = p.norm_w ? ((const u32x4_t*)p.norm_w)[c] : (u32x4_t){0, 0, 0, 0};
   }
 
   // ---- 2. weight pipeline state
-  u32x4_t wbuf[2][2][CH];
+  typename F::template Stage<CH> wbuf[2];
   uint32_t rbuf[2][MT];                                  // residual pair (2 bf16) of the row pair, per x row
   auto issue = [&](int gs, auto bufc) {
     constexpr int buf = decltype(bufc)::value;
     const int u = min(u_begin + gs / NST, p.units - 1), s = gs % NST;
     const int r0 = silu ? u : 2 * u;
     const int r1 = silu ? u + p.N : min(2 * u + 1, p.N - 1);
-    const u32x4_t* w0 = (const u32x4_t*)(p.W + (size_t)r0 * (CHUNKS * 8)) + s * CH * 64 + lane;
-    const u32x4_t* w1 = (const u32x4_t*)(p.W + (size_t)r1 * (CHUNKS * 8)) + s * CH * 64 + lane;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      wbuf[buf][0][j] = __builtin_nontemporal_load(w0 + j * 64);
-      wbuf[buf][1][j] = __builtin_nontemporal_load(w1 + j * 64);
-    }
+    F::template load<K, CH>(p, r0, r1, s * CH * 64 + lane, wbuf[buf]);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {                       // 4-byte aligned: r0 = 2u is even, N is even on this path
-      const bf16_t* rp = p.resid + (size_t)min(m, p.M - 1) * p.N + 2 * u;
+      const bf16_t* rp = p.resid + (size_t)row(m) * p.N + 2 * u;
       rbuf[buf][m] = !has_res ? 0u : *(const uint32_t*)rp;
     }
   };
@@ -212,7 +210,7 @@ __device__ __forceinline__ void gemv3_body(const GemvP& p, int units_per_wave, i
       float ss = 0.f;
 #pragma unroll
       for (int k = 0; k < XC; ++k) {
-        if (tid + k * 256 < CHUNKS) {
+        if (tid + k * 256 < XCH) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) { const float a = bf16lo(xv[m][k][j]), b = bf16hi(xv[m][k][j]); ss += a * a + b * b; }
         }
@@ -222,24 +220,35 @@ __device__ __forceinline__ void gemv3_body(const GemvP& p, int units_per_wave, i
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       const float* rr = red + 4 * (m & 1);
-      r = rsqrtf(((rr[0] + rr[1]) + (rr[2] + rr[3])) / (float)(CHUNKS * 8) + p.eps);
+      r = rsqrtf(((rr[0] + rr[1]) + (rr[2] + rr[3])) / (float)K + p.eps);
     }
 #pragma unroll
     for (int k = 0; k < XC; ++k) {
       const int c = tid + k * 256;
-      if (c < CHUNKS) {
+      if (c < XCH) {
         u32x4_t o = xv[m][k];
         if (p.norm_w) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             o[j] = rms_pair(xv[m][k][j], r, gv[k][j]);
         }
-        xs[m * CHUNKS + c] = m < p.M ? o : (u32x4_t){0, 0, 0, 0};
+        xs[m * XCH + c] = live(m) ? o : (u32x4_t){0, 0, 0, 0};
       }
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
+  if constexpr (F::XSUM) {
+    for (int pc = tid; pc < K / 16; pc += 256) {         // X of every piece, from the (rounded) activations the dots see
+      const u32x4_t a = xs[2 * pc], b = xs[2 * pc + 1];
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t += (bf16lo(a[j]) + bf16hi(a[j])) + (bf16lo(b[j]) + bf16hi(b[j]));
+      xsum[pc] = t;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
 
   // ---- 4. pipeline
   float a0[MT], a1[MT];
@@ -254,20 +263,16 @@ __device__ __forceinline__ void gemv3_body(const GemvP& p, int units_per_wave, i
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
 #pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const u32x4_t xa = xs[m * CHUNKS + (s * CH + j) * 64 + lane];
-        a0[m] = dot8(wbuf[buf][0][j], xa, a0[m]);
-        a1[m] = dot8(wbuf[buf][1][j], xa, a1[m]);
-      }
+      for (int m = 0; m < MT; ++m) F::dot(wbuf[buf], j, xs + m * XCH, xsum, (s * CH + j) * 64 + lane, a0[m], a1[m]);
     }
     if (s == NST - 1) {                                   // row pair complete (compile-time true when NST == 1)
       const int u = u_begin + gs / NST;
 #pragma unroll
-      for (int m = 0; m < MT; ++m) { a0[m] = wave_sum(a0[m]); a1[m] = wave_sum(a1[m]); }
+      for (int m = 0; m < MT; ++m) { a0[m] = F::finish(wave_sum(a0[m]), wbuf[buf], 0); a1[m] = F::finish(wave_sum(a1[m]), wbuf[buf], 1); }
       if (lane == 0) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          if (m < p.M) {
+          if (live(m)) {
             if (silu) {
               const float g = bf16_round(a0[m]), up = bf16_round(a1[m]);
               const float sg = bf16_round(g * bf16_round(1.f / (1.f + __expf(-g))));
@@ -308,6 +313,74 @@ __device__ __forceinline__ void gemv3_body(const GemvP& p, int units_per_wave, i
   } else if (gs < n_st) {
     compute(gs, IC0{});
   }
-  if (STEP == STEP_BEGIN && bx == 0) gemv_step_begin_tail<MT>(sp, xrow, p.M, CHUNKS, tid);
-  if (STEP == STEP_END) gemv_step_end_tail<MT>(sp, best, p.M, bx, tid);
+  if (STEP == STEP_BEGIN && bx == 0) gemv_step_begin_tail<MT>(sp, xrow, MT == 1 ? 1 : p.M, XCH, tid);
+  if (STEP == STEP_END) gemv_step_end_tail<MT>(sp, best, MT == 1 ? 1 : p.M, bx, tid);
+}
+
+template <class F, int MT, int NST, int CH>
+__global__ void __launch_bounds__(256) k_gemv3(typename F::P p, int units_per_wave, int wpw) {
+  F::mark(0);
+  gemv_stream_body<F, MT, NST, CH, STEP_NONE>(p, units_per_wave, wpw, nullptr);
+  F::mark(1);
+}
+
+template <class F, int MT, int NST, int CH, int STEP>
+__global__ void __launch_bounds__(256) k_gemv3_step(typename F::P p, int units_per_wave, int wpw, GemvStepP sp) {
+  gemv_stream_body<F, MT, NST, CH, STEP>(p, units_per_wave, wpw, &sp);
+}
+
+template <class F, int MT, int NST, int CH, int STEP = STEP_NONE>
+static int launch_gemv_stream(const typename F::P& p, hipStream_t s, const GemvStepP* sp = nullptr) {
+  static int n_cu = 0;
+  if (!n_cu) {
+    int dev = 0;
+    hipDeviceProp_t pr;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
+    n_cu = pr.multiProcessorCount;
+  }
+  int upw = p3v_cdiv(p.units, n_cu * F::wpc());          // row pairs per wave
+  if (upw < 1) upw = 1;
+  const int waves = p3v_cdiv(p.units, upw);
+  const int wpw = p3v_gemv_wpw(waves, n_cu, p3v_tuning().gemv_wpw);   // 4 or 3 row-streaming waves per workgroup
+  constexpr size_t K = (size_t)NST * CH * 64 * F::WPL, lds = MT * K * 2 + (F::XSUM ? K / 4 : 0);   // x as bf16 (+ the piece sums)
+  if constexpr (lds > 48 * 1024) {                       // (bf16, four x rows of K = 8192)
+    static bool attr_set = false;
+    if (!attr_set) {
+      if (hipFuncSetAttribute((const void*)k_gemv3<F, MT, NST, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
+        return P3V_ERR_HIP;
+      attr_set = true;
+    }
+  }
+  if constexpr (STEP != STEP_NONE) {
+    if (p3v_cdiv(waves, wpw) > P3V_GEMV_STEP_MAX_WG) return P3V_ERR_UNSUPPORTED;       // (amax_ws holds one candidate per workgroup and row)
+    hipLaunchKernelGGL((k_gemv3_step<F, MT, NST, CH, STEP>), dim3(p3v_cdiv(waves, wpw)), dim3(256), lds, s, p, upw, wpw, *sp);
+  } else {
+    hipLaunchKernelGGL((k_gemv3<F, MT, NST, CH>), dim3(p3v_cdiv(waves, wpw)), dim3(256), lds, s, p, upw, wpw);
+  }
+  P3V_CHECK_LAUNCH();
+  return P3V_OK;
+}
+
+// What p3v_gemv_step, p3v_gemv_fp8_step and p3v_gemv_q4_step check alike once their own pointers are known to be there, A = that
+// entry point's argument struct: exactly one end, one row, K = 3072 or 8192, no epilogue (`kernel_on`: the streaming kernel is the one
+// p3v_gemv* would run) -- anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.  P3V_OK: `sp` is
+// filled, `begin` says which end.
+template <class A>
+static int gemv_step_params(const A* a, const p3v_gemv_step_t* st, bool kernel_on, GemvStepP& sp, bool& begin) {
+  begin = st->tok != nullptr;
+  if (begin == (st->next_tok != nullptr)) return P3V_ERR_ARG;   // exactly one of the two ends
+  if (a->M <= 0 || a->N <= 0 || a->K <= 0) return P3V_ERR_ARG;
+  // one row only: that is where p3v_gemv* itself runs this kernel (2 .. 8 rows go to the MFMA kernels, whose sums associate
+  // differently -- a folded step must stay bit-identical to the eager one)
+  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192) || !kernel_on || a->epilogue != P3V_EPI_NONE) return P3V_ERR_UNSUPPORTED;
+  if (begin) {
+    if (!st->embed_table || !st->x_out || !st->cos_t || !st->sin_t || !st->d_past || !st->cos_out || !st->sin_out || st->vocab <= 0) return P3V_ERR_ARG;
+    if (((uintptr_t)st->embed_table | (uintptr_t)st->x_out) & 15) return P3V_ERR_ARG;
+  } else {
+    if (!a->x || !st->tok_out || !st->history || !st->d_step || !st->d_past || !st->ticket || !st->amax_ws) return P3V_ERR_ARG;
+    if ((uintptr_t)st->amax_ws & 7) return P3V_ERR_ARG;
+  }
+  sp = {st->tok, st->embed_table, st->vocab, st->x_out, st->cos_t, st->sin_t, st->d_past, st->cos_out, st->sin_out, st->tab_t,
+        st->half_dim, st->next_tok, st->tok_out, st->history, st->d_step, st->d_past, st->ticket, st->amax_ws, st->max_steps};
+  return P3V_OK;
 }

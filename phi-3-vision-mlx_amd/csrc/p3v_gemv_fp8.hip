@@ -2,7 +2,8 @@
 // replaces the reference's int4 group-64 `nn.quantize`, phi_3_vision_mlx.py:264,296 -- SURVEY.md K23).
 // Weights: u8 [N, K] e4m3 bit patterns, one fp32 scale per output row (w = fp8 * scale[n]); activations stay
 // bf16 and all accumulation is fp32, so the only new error is the weight rounding.  A decode step then
-// streams half the bytes: the kernels below are the fp8 twins of k_gemv3 / k_gemv_mfma in p3v_gemv.hip.
+// streams half the bytes: M = 1 runs the streaming GEMV that every weight format shares (gemv_stream_body, p3v_gemv3_body.h) with
+// the GemvF8 policy below; the MFMA kernels are the e4m3 forms of k_gemv_mfma / k_gemv_mfma8 in p3v_gemv.hip.
 // Prefill uses k_dequant_fp8 (fp8 -> bf16 scratch) + the bf16 MFMA GEMM.
 #include <stdlib.h>
 
@@ -10,7 +11,7 @@
 
 #include "p3v_common.h"
 #include "p3v_dot_f8.h"
-#include "p3v_gemv3_body.h"      // GemvStepP + the step-end helpers shared with the bf16 kernel (IC0 / IC1 come from there too)
+#include "p3v_gemv3_body.h"      // the streaming M = 1 GEMV (IC0 / IC1 come from there too)
 
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
@@ -20,146 +21,35 @@ struct GemvF8P {
   int M, N, K, epi, units;
 };
 
-// ---------------------------------------------------------------- M = 1 streaming (see k_gemv3)
-// STEP (p3v_gemv3_body.h): STEP_BEGIN / STEP_END carry the replayed greedy step's embedding gather + rotation rows / arg-max + bookkeeping,
-// exactly as gemv3_body does for bf16 weights (round 6: config 5's step is 129 launches too)
-template <int NST, int CH, int STEP>
-__device__ __forceinline__ void gemv3_f8_body(const GemvF8P& p, int units_per_wave, int wpw, unsigned char* smem, float* red, const GemvStepP* sp) {
-  constexpr int CHUNKS = NST * CH * 64;                 // 16-byte weight chunks per row (K = 16 * CHUNKS)
-  constexpr int XCH = CHUNKS * 2;                       // 16-byte x chunks
-  constexpr int XC = (XCH + 255) / 256;
-  u32x4_t* xs = (u32x4_t*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool silu = p.epi == P3V_EPI_SILU_MUL, has_res = p.epi == P3V_EPI_RESID_BF16;
-  const int u_begin = wave < wpw ? min(p.units, (blockIdx.x * wpw + wave) * units_per_wave) : p.units;   // (wpw: see p3v_gemv_wpw)
-  const int u_end = min(p.units, u_begin + units_per_wave);
-  const int n_st = (u_end - u_begin) * NST;
-
-  u32x4_t xv[XC], gv[XC];
-  const bf16_t* xrow[1] = {p.x};
-  if (STEP == STEP_BEGIN) {
-    int id = sp->tok[0];                                // (uniform: a scalar load)
-    id = id < 0 ? 0 : (id >= sp->vocab ? sp->vocab - 1 : id);
-    xrow[0] = sp->table + (size_t)id * (XCH * 8);
-  }
-#pragma unroll
-  for (int k = 0; k < XC; ++k) {
-    const int c = min(tid + k * 256, XCH - 1);
-    xv[k] = ((const u32x4_t*)xrow[0])[c];
-    gv[k] = p.norm_w ? ((const u32x4_t*)p.norm_w)[c] : (u32x4_t){0, 0, 0, 0};
-  }
-  u32x4_t wbuf[2][2][CH];
-  uint32_t rbuf[2];
-  float sbuf[2][2];
-  auto issue = [&](int gs, auto bufc) {
-    constexpr int buf = decltype(bufc)::value;
-    const int u = min(u_begin + gs / NST, p.units - 1), s = gs % NST;
-    const int r0 = silu ? u : 2 * u, r1 = silu ? u + p.N : min(2 * u + 1, p.N - 1);
-    const u32x4_t* w0 = (const u32x4_t*)(p.W + (size_t)r0 * (CHUNKS * 16)) + s * CH * 64 + lane;
-    const u32x4_t* w1 = (const u32x4_t*)(p.W + (size_t)r1 * (CHUNKS * 16)) + s * CH * 64 + lane;
+// ---------------------------------------------------------------- M = 1 streaming: what gemv_stream_body needs to know about e4m3
+// a lane load is 16 bytes = 16 weights, meeting two 16-byte x chunks; the row's fp32 scale travels with the stage and multiplies the sum
+struct GemvF8 {
+  typedef GemvF8P P;
+  static constexpr int WPL = 16, MAX_MT = 1;
+  static constexpr bool XSUM = false;
+  template <int CH> struct Stage { u32x4_t w[2][CH]; float scale[2]; };
+  static int wpc() { return p3v_tuning().gemv_f8_wpc; }   // (a stage is half the bytes of the bf16 kernel's: twice the waves keep as many in flight; 8: 1.321, 16: 1.301, 24: 1.333 ms/step)
+  static __device__ __forceinline__ void mark(int) {}
+  template <int K, int CH>
+  static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
+    const u32x4_t* w0 = (const u32x4_t*)(p.W + (size_t)r0 * K) + c0;
+    const u32x4_t* w1 = (const u32x4_t*)(p.W + (size_t)r1 * K) + c0;
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
-      wbuf[buf][0][j] = __builtin_nontemporal_load(w0 + j * 64);
-      wbuf[buf][1][j] = __builtin_nontemporal_load(w1 + j * 64);
+      st.w[0][j] = __builtin_nontemporal_load(w0 + j * 64);
+      st.w[1][j] = __builtin_nontemporal_load(w1 + j * 64);
     }
-    rbuf[buf] = has_res ? *(const uint32_t*)(p.resid + 2 * u) : 0u;
-    sbuf[buf][0] = p.wscale[r0];
-    sbuf[buf][1] = p.wscale[r1];
-  };
-  if (n_st > 0) issue(0, IC0{});
-
-  float r = 1.f;
-  if (p.norm_w) {
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < XC; ++k)
-      if (tid + k * 256 < XCH) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const float a = bf16lo(xv[k][j]), b = bf16hi(xv[k][j]); ss += a * a + b * b; }
-      }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    r = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)(CHUNKS * 16) + p.eps);
+    st.scale[0] = p.wscale[r0];
+    st.scale[1] = p.wscale[r1];
   }
-#pragma unroll
-  for (int k = 0; k < XC; ++k) {
-    const int c = tid + k * 256;
-    if (c < XCH) {
-      u32x4_t o = xv[k];
-      if (p.norm_w) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          o[j] = rms_pair(xv[k][j], r, gv[k][j]);
-      }
-      xs[c] = o;
-    }
+  template <int CH>
+  static __device__ __forceinline__ void dot(const Stage<CH>& st, int j, const u32x4_t* x, const float*, int c, float& a0, float& a1) {
+    const u32x4_t xa = x[2 * c], xb = x[2 * c + 1];
+    a0 = dot16_f8(st.w[0][j], xa, xb, a0);
+    a1 = dot16_f8(st.w[1][j], xa, xb, a1);
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  float a0 = 0.f, a1 = 0.f;
-  ArgMaxVI best[1] = {ArgMaxVI{-INFINITY, 0x7fffffff}};      // STEP_END: this wave's arg-max candidate (lane 0's copy counts)
-  auto compute = [&](int gs, auto bufc) {
-    constexpr int buf = decltype(bufc)::value;
-    const int s = gs % NST;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int c = (s * CH + j) * 64 + lane;
-      const u32x4_t xa = xs[2 * c], xb = xs[2 * c + 1];
-      a0 = dot16_f8(wbuf[buf][0][j], xa, xb, a0);
-      a1 = dot16_f8(wbuf[buf][1][j], xa, xb, a1);
-    }
-    if (s == NST - 1) {
-      const int u = u_begin + gs / NST;
-      a0 = wave_sum(a0) * sbuf[buf][0];
-      a1 = wave_sum(a1) * sbuf[buf][1];
-      if (lane == 0) {
-        if (silu) {
-          const float g = bf16_round(a0), up = bf16_round(a1);
-          ((bf16_t*)p.out)[u] = f32_to_bf16(bf16_round(g * bf16_round(1.f / (1.f + __expf(-g)))) * up);
-        } else if (p.epi == P3V_EPI_F32) {
-          ((float*)p.out)[2 * u] = a0;
-          ((float*)p.out)[2 * u + 1] = a1;
-        } else {
-          float v0 = a0, v1 = a1;
-          if (has_res) { v0 = bf16lo(rbuf[buf]) + bf16_round(v0); v1 = bf16hi(rbuf[buf]) + bf16_round(v1); }
-          *(uint32_t*)((bf16_t*)p.out + 2 * u) = pack_bf16x2(v0, v1);
-          if (STEP == STEP_END) {                              // on the values just stored (bf16)
-            amax_take(best[0], bf16_round(v0), 2 * u);
-            if (2 * u + 1 < p.N) amax_take(best[0], bf16_round(v1), 2 * u + 1);
-          }
-        }
-      }
-      a0 = a1 = 0.f;
-    }
-  };
-  int gs = 0;
-  while (gs + 2 < n_st) {
-    issue(gs + 1, IC1{}); compute(gs, IC0{});
-    issue(gs + 2, IC0{}); compute(gs + 1, IC1{});
-    gs += 2;
-  }
-  if (gs + 1 < n_st) { issue(gs + 1, IC1{}); compute(gs, IC0{}); compute(gs + 1, IC1{}); }
-  else if (gs < n_st) compute(gs, IC0{});
-  if (STEP == STEP_BEGIN && blockIdx.x == 0) gemv_step_begin_tail<1>(sp, xrow, 1, XCH, tid);
-  if (STEP == STEP_END) gemv_step_end_tail<1>(sp, best, 1, (int)blockIdx.x, tid);
-}
-
-template <int NST, int CH>
-__global__ void __launch_bounds__(256) k_gemv3_f8(GemvF8P p, int units_per_wave, int wpw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[4];
-  gemv3_f8_body<NST, CH, STEP_NONE>(p, units_per_wave, wpw, smem, red, nullptr);
-}
-
-template <int NST, int CH, int STEP>
-__global__ void __launch_bounds__(256) k_gemv3_f8_step(GemvF8P p, int units_per_wave, int wpw, GemvStepP sp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[4];
-  gemv3_f8_body<NST, CH, STEP>(p, units_per_wave, wpw, smem, red, &sp);
-}
+  template <int CH> static __device__ __forceinline__ float finish(float v, const Stage<CH>& st, int row) { return v * st.scale[row]; }
+};
 
 // ---------------------------------------------------------------- 2 <= M <= 16 through the matrix cores (see k_gemv_mfma)
 // a 16-byte weight load = 16 consecutive k of one row = the A fragments of TWO MFMAs; the MFMA k index is
@@ -447,51 +337,16 @@ extern "C" int p3v_dequant_fp8(const uint8_t* w8, const float* scale, uint16_t* 
   return P3V_OK;
 }
 
-template <int NST, int CH, int STEP = STEP_NONE>
-static int launch_gemv3_f8(const GemvF8P& p, hipStream_t s, const GemvStepP* sp = nullptr) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
-    n_cu = pr.multiProcessorCount;
-  }
-  const int wpc = p3v_tuning().gemv_f8_wpc;   // waves per CU (a stage is half the bytes of the bf16 kernel's: twice the waves keep as many in flight; 8: 1.321, 16: 1.301, 24: 1.333 ms/step)
-  int upw = p3v_cdiv(p.units, n_cu * wpc);
-  if (upw < 1) upw = 1;
-  const int waves = p3v_cdiv(p.units, upw);
-  const int wpw = p3v_gemv_wpw(waves, n_cu, p3v_tuning().gemv_wpw);
-  if constexpr (STEP != STEP_NONE) {
-    if (p3v_cdiv(waves, wpw) > P3V_GEMV_STEP_MAX_WG) return P3V_ERR_UNSUPPORTED;        // (amax_ws holds one candidate per workgroup)
-    hipLaunchKernelGGL((k_gemv3_f8_step<NST, CH, STEP>), dim3(p3v_cdiv(waves, wpw)), dim3(256), (size_t)p.K * 2, s, p, upw, wpw, *sp);
-  } else {
-    hipLaunchKernelGGL((k_gemv3_f8<NST, CH>), dim3(p3v_cdiv(waves, wpw)), dim3(256), (size_t)p.K * 2, s, p, upw, wpw);
-  }
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
 // p3v_gemv_step on e4m3 weights: the first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in
 // (one row, K = 3072 or 8192, no epilogue); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_fp8_step(const p3v_gemv_fp8_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->w_scale || !a->out) return P3V_ERR_ARG;
-  const bool begin = st->tok != nullptr, end = st->next_tok != nullptr;
-  if (begin == end) return P3V_ERR_ARG;                        // exactly one of the two ends
-  if (a->M <= 0 || a->N <= 0 || a->K <= 0) return P3V_ERR_ARG;
-  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192) || a->epilogue != P3V_EPI_NONE) return P3V_ERR_UNSUPPORTED;
-  if (begin) {
-    if (!st->embed_table || !st->x_out || !st->cos_t || !st->sin_t || !st->d_past || !st->cos_out || !st->sin_out || st->vocab <= 0) return P3V_ERR_ARG;
-    if (((uintptr_t)st->embed_table | (uintptr_t)st->x_out) & 15) return P3V_ERR_ARG;
-  } else {
-    if (!a->x || !st->tok_out || !st->history || !st->d_step || !st->d_past || !st->ticket || !st->amax_ws) return P3V_ERR_ARG;
-    if ((uintptr_t)st->amax_ws & 7) return P3V_ERR_ARG;
-  }
+  GemvStepP sp; bool begin;
+  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
   const GemvF8P p = {a->x, a->W, a->w_scale, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
-  const GemvStepP sp = {st->tok, st->embed_table, st->vocab, st->x_out, st->cos_t, st->sin_t, st->d_past, st->cos_out, st->sin_out, st->tab_t,
-                        st->half_dim, st->next_tok, st->tok_out, st->history, st->d_step, st->d_past, st->ticket, st->amax_ws, st->max_steps};
   hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv3_f8<1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv3_f8<1, 3, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv3_f8<2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv3_f8<2, 4, STEP_END>(p, s, &sp);
+  if (a->K == 3072) return begin ? launch_gemv_stream<GemvF8, 1, 1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvF8, 1, 1, 3, STEP_END>(p, s, &sp);
+  return begin ? launch_gemv_stream<GemvF8, 1, 2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvF8, 1, 2, 4, STEP_END>(p, s, &sp);
 }
 
 extern "C" int p3v_gemv_fp8(const p3v_gemv_fp8_args_t* a, void* stream) {
@@ -504,7 +359,7 @@ extern "C" int p3v_gemv_fp8(const p3v_gemv_fp8_args_t* a, void* stream) {
   GemvF8P p = {a->x, a->W, a->w_scale, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
                a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2};
   hipStream_t s = (hipStream_t)stream;
-  if (a->M == 1) return a->K == 3072 ? launch_gemv3_f8<1, 3>(p, s) : launch_gemv3_f8<2, 4>(p, s);
+  if (a->M == 1) return a->K == 3072 ? launch_gemv_stream<GemvF8, 1, 1, 3>(p, s) : launch_gemv_stream<GemvF8, 1, 2, 4>(p, s);
   if (a->M >= 5 && a->M <= 8 && !p3v_tuning().gemv_no_mfma8) {
     const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
     if (a->K == 3072) return silu ? launch_gemv_mfma8_f8<true, 4, 6>(p, s) : launch_gemv_mfma8_f8<false, 4, 6>(p, s);

@@ -10,184 +10,59 @@
 //   SB [N, K/64] u32: scale (bf16) | bias (bf16) << 16.
 // Per 16-weight piece p of a row, with D = sum_k x_k (128 + q_k) and X = sum_k x_k (16 activations, shared by all rows,
 // precomputed in LDS):   contribution = scale * (D - 128 X) + bias * X.
-// Same streaming skeleton as k_gemv3: x (+RMSNorm) staged in LDS, (row pair, stage) pipeline with two register buffers,
-// unconditional loads, branch-free body.  HBM-bound: N*K/2 + N*K/16 bytes per launch.
+// M = 1 runs the streaming GEMV that every weight format shares (gemv_stream_body, p3v_gemv3_body.h) with the GemvQ4 policy below.
+// HBM-bound: N*K/2 + N*K/16 bytes per launch.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "p3v_common.h"
 #include "p3v_dot_q4.h"
-#include "p3v_gemv3_body.h"      // GemvStepP + the step-end helpers shared with the bf16 / e4m3 kernels
+#include "p3v_gemv3_body.h"      // the streaming M = 1 GEMV (IC0 / IC1 come from there too)
 
 struct GemvQ4P {
   const bf16_t* x; const uint32_t* W; const uint32_t* sb; void* out; const bf16_t* resid; const bf16_t* norm_w;
   float eps;
   int M, N, K, epi, units;
 };
-typedef std::integral_constant<int, 0> QC0;
-typedef std::integral_constant<int, 1> QC1;
-// NST stages x NP 16-weight pieces per lane per row: K = NST * NP * 64 * 16
-// STEP (p3v_gemv3_body.h): STEP_BEGIN / STEP_END carry the replayed greedy step's two ends, as gemv3_body does for bf16 weights
-template <int NST, int NP, int STEP>
-__device__ __forceinline__ void gemv3_q4_body(const GemvQ4P& p, int units_per_wave, int wpw, unsigned char* smem, float* red, const GemvStepP* sp) {
-  constexpr int PIECES = NST * NP * 64;                 // 16-weight pieces per row
-  constexpr int K = PIECES * 16, XCH = K / 8;           // 16-byte x chunks
-  constexpr int XC = (XCH + 255) / 256;
-  u32x4_t* xs = (u32x4_t*)smem;                         // [K] bf16 x (normalised)
-  float* xsum = (float*)(smem + K * 2);                 // [PIECES] sum of the 16 activations of a piece
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool silu = p.epi == P3V_EPI_SILU_MUL, has_res = p.epi == P3V_EPI_RESID_BF16;
-  const int u_begin = wave < wpw ? min(p.units, (blockIdx.x * wpw + wave) * units_per_wave) : p.units;   // (wpw: see p3v_gemv_wpw)
-  const int u_end = min(p.units, u_begin + units_per_wave);
-  const int n_st = (u_end - u_begin) * NST;
-
-  u32x4_t xv[XC], gv[XC];
-  const bf16_t* xrow[1] = {p.x};
-  if (STEP == STEP_BEGIN) {
-    int id = sp->tok[0];                                // (uniform: a scalar load)
-    id = id < 0 ? 0 : (id >= sp->vocab ? sp->vocab - 1 : id);
-    xrow[0] = sp->table + (size_t)id * K;
-  }
+// What gemv_stream_body needs to know about the 4-bit layout: a lane load is 8 bytes = one 16-weight piece, meeting two 16-byte x
+// chunks and the piece's activation sum X (XSUM: the body precomputes them in LDS); a piece's scale | bias word travels with it
+struct GemvQ4 {
+  typedef GemvQ4P P;
+  static constexpr int WPL = 16, MAX_MT = 1;
+  static constexpr bool XSUM = true;
+  template <int CH> struct Stage { u32x2_t w[2][CH]; uint32_t sb[2][CH]; };
+  static int wpc() { return p3v_tuning().gemv_q4_wpc; }
+  static __device__ __forceinline__ void mark(int) {}
+  template <int K, int CH>
+  static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
+    const u32x2_t* w0 = (const u32x2_t*)(p.W + (size_t)r0 * (K / 8)) + c0;
+    const u32x2_t* w1 = (const u32x2_t*)(p.W + (size_t)r1 * (K / 8)) + c0;
+    const uint32_t* s0 = p.sb + (size_t)r0 * (K / 64) + (c0 >> 2);
+    const uint32_t* s1 = p.sb + (size_t)r1 * (K / 64) + (c0 >> 2);
 #pragma unroll
-  for (int k = 0; k < XC; ++k) {
-    const int c = min(tid + k * 256, XCH - 1);
-    xv[k] = ((const u32x4_t*)xrow[0])[c];
-    gv[k] = p.norm_w ? ((const u32x4_t*)p.norm_w)[c] : (u32x4_t){0, 0, 0, 0};
-  }
-  u32x2_t wbuf[2][2][NP];
-  uint32_t sbuf[2][2][NP];
-  uint32_t rbuf[2];
-  auto issue = [&](int gs, auto bufc) {
-    constexpr int buf = decltype(bufc)::value;
-    const int u = min(u_begin + gs / NST, p.units - 1), s = gs % NST;
-    const int r0 = silu ? u : 2 * u, r1 = silu ? u + p.N : min(2 * u + 1, p.N - 1);
-    const u32x2_t* w0 = (const u32x2_t*)(p.W + (size_t)r0 * (K / 8)) + s * NP * 64 + lane;
-    const u32x2_t* w1 = (const u32x2_t*)(p.W + (size_t)r1 * (K / 8)) + s * NP * 64 + lane;
-    const uint32_t* s0 = p.sb + (size_t)r0 * (K / 64) + ((s * NP * 64 + lane) >> 2);
-    const uint32_t* s1 = p.sb + (size_t)r1 * (K / 64) + ((s * NP * 64 + lane) >> 2);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      wbuf[buf][0][j] = __builtin_nontemporal_load(w0 + j * 64);
-      wbuf[buf][1][j] = __builtin_nontemporal_load(w1 + j * 64);
-      sbuf[buf][0][j] = s0[j * 16];
-      sbuf[buf][1][j] = s1[j * 16];
-    }
-    rbuf[buf] = has_res ? *(const uint32_t*)(p.resid + 2 * u) : 0u;
-  };
-  if (n_st > 0) issue(0, QC0{});
-
-  float r = 1.f;
-  if (p.norm_w) {
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < XC; ++k)
-      if (tid + k * 256 < XCH) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const float a = bf16lo(xv[k][j]), b = bf16hi(xv[k][j]); ss += a * a + b * b; }
-      }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    r = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + p.eps);
-  }
-#pragma unroll
-  for (int k = 0; k < XC; ++k) {
-    const int c = tid + k * 256;
-    if (c < XCH) {
-      u32x4_t o = xv[k];
-      if (p.norm_w) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          o[j] = rms_pair(xv[k][j], r, gv[k][j]);
-      }
-      xs[c] = o;
+    for (int j = 0; j < CH; ++j) {
+      st.w[0][j] = __builtin_nontemporal_load(w0 + j * 64);
+      st.w[1][j] = __builtin_nontemporal_load(w1 + j * 64);
+      st.sb[0][j] = s0[j * 16];
+      st.sb[1][j] = s1[j * 16];
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  for (int pc = tid; pc < PIECES; pc += 256) {           // X of every piece, from the (rounded) activations the dots see
-    const u32x4_t a = xs[2 * pc], b = xs[2 * pc + 1];
-    float t = 0.f;
+  template <int CH>
+  static __device__ __forceinline__ void dot(const Stage<CH>& st, int j, const u32x4_t* x, const float* xsum, int pc, float& a0, float& a1) {
+    const u32x4_t xa = x[2 * pc], xb = x[2 * pc + 1];
+    const float X = xsum[pc], X128 = 128.f * X;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) t += (bf16lo(a[j]) + bf16hi(a[j])) + (bf16lo(b[j]) + bf16hi(b[j]));
-    xsum[pc] = t;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  float a0 = 0.f, a1 = 0.f;
-  ArgMaxVI best[1] = {ArgMaxVI{-INFINITY, 0x7fffffff}};      // STEP_END: this wave's arg-max candidate (lane 0's copy counts)
-  auto compute = [&](int gs, auto bufc) {
-    constexpr int buf = decltype(bufc)::value;
-    const int s = gs % NST;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      const int pc = (s * NP + j) * 64 + lane;
-      const u32x4_t xa = xs[2 * pc], xb = xs[2 * pc + 1];
-      const float X = xsum[pc], X128 = 128.f * X;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const u32x2_t w = wbuf[buf][h][j];
-        const float D = dot8_q4(w[1], xb, dot8_q4(w[0], xa, 0.f));
-        const uint32_t sb = sbuf[buf][h][j];
-        const float c = bf16lo(sb) * (D - X128) + bf16hi(sb) * X;
-        if (h == 0) a0 += c; else a1 += c;
-      }
+    for (int h = 0; h < 2; ++h) {
+      const u32x2_t w = st.w[h][j];
+      const float D = dot8_q4(w[1], xb, dot8_q4(w[0], xa, 0.f));
+      const uint32_t sb = st.sb[h][j];
+      const float c = bf16lo(sb) * (D - X128) + bf16hi(sb) * X;
+      if (h == 0) a0 += c; else a1 += c;
     }
-    if (s == NST - 1) {
-      const int u = u_begin + gs / NST;
-      a0 = wave_sum(a0);
-      a1 = wave_sum(a1);
-      if (lane == 0) {
-        if (silu) {
-          const float g = bf16_round(a0), up = bf16_round(a1);
-          ((bf16_t*)p.out)[u] = f32_to_bf16(bf16_round(g * bf16_round(1.f / (1.f + __expf(-g)))) * up);
-        } else if (p.epi == P3V_EPI_F32) {
-          ((float*)p.out)[2 * u] = a0;
-          ((float*)p.out)[2 * u + 1] = a1;
-        } else {
-          float v0 = a0, v1 = a1;
-          if (has_res) { v0 = bf16lo(rbuf[buf]) + bf16_round(v0); v1 = bf16hi(rbuf[buf]) + bf16_round(v1); }
-          *(uint32_t*)((bf16_t*)p.out + 2 * u) = pack_bf16x2(v0, v1);
-          if (STEP == STEP_END) {                              // on the values just stored (bf16)
-            amax_take(best[0], bf16_round(v0), 2 * u);
-            if (2 * u + 1 < p.N) amax_take(best[0], bf16_round(v1), 2 * u + 1);
-          }
-        }
-      }
-      a0 = a1 = 0.f;
-    }
-  };
-  int gs = 0;
-  while (gs + 2 < n_st) {
-    issue(gs + 1, QC1{}); compute(gs, QC0{});
-    issue(gs + 2, QC0{}); compute(gs + 1, QC1{});
-    gs += 2;
   }
-  if (gs + 1 < n_st) {
-    issue(gs + 1, QC1{}); compute(gs, QC0{}); compute(gs + 1, QC1{});
-  } else if (gs < n_st) {
-    compute(gs, QC0{});
-  }
-  if (STEP == STEP_BEGIN && blockIdx.x == 0) gemv_step_begin_tail<1>(sp, xrow, 1, XCH, tid);
-  if (STEP == STEP_END) gemv_step_end_tail<1>(sp, best, 1, (int)blockIdx.x, tid);
-}
-
-template <int NST, int NP>
-__global__ void __launch_bounds__(256) k_gemv3_q4(GemvQ4P p, int units_per_wave, int wpw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[4];
-  gemv3_q4_body<NST, NP, STEP_NONE>(p, units_per_wave, wpw, smem, red, nullptr);
-}
-
-template <int NST, int NP, int STEP>
-__global__ void __launch_bounds__(256) k_gemv3_q4_step(GemvQ4P p, int units_per_wave, int wpw, GemvStepP sp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[4];
-  gemv3_q4_body<NST, NP, STEP>(p, units_per_wave, wpw, smem, red, &sp);
-}
+  template <int CH> static __device__ __forceinline__ float finish(float v, const Stage<CH>&, int) { return v; }
+};
 
 // W4 / SB -> bf16 [rows, K] (prefill and batched decode run the bf16 kernels on a dequantised scratch copy)
 __global__ void __launch_bounds__(256) k_dequant_q4(const uint32_t* __restrict__ w, const uint32_t* __restrict__ sb,
@@ -215,51 +90,16 @@ extern "C" int p3v_dequant_q4(const uint32_t* w4, const uint32_t* sb, uint16_t* 
   return P3V_OK;
 }
 
-template <int NST, int NP, int STEP = STEP_NONE>
-static int launch_gemv3_q4(const GemvQ4P& p, hipStream_t s, const GemvStepP* sp = nullptr) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
-    n_cu = pr.multiProcessorCount;
-  }
-  const int wpc = p3v_tuning().gemv_q4_wpc;   // waves per CU
-  int upw = p3v_cdiv(p.units, n_cu * wpc);
-  if (upw < 1) upw = 1;
-  const int waves = p3v_cdiv(p.units, upw);
-  const int wpw = p3v_gemv_wpw(waves, n_cu, p3v_tuning().gemv_wpw);
-  if constexpr (STEP != STEP_NONE) {
-    if (p3v_cdiv(waves, wpw) > P3V_GEMV_STEP_MAX_WG) return P3V_ERR_UNSUPPORTED;        // (amax_ws holds one candidate per workgroup)
-    hipLaunchKernelGGL((k_gemv3_q4_step<NST, NP, STEP>), dim3(p3v_cdiv(waves, wpw)), dim3(256), (size_t)p.K * 2 + (size_t)p.K / 4, s, p, upw, wpw, *sp);
-  } else {
-    hipLaunchKernelGGL((k_gemv3_q4<NST, NP>), dim3(p3v_cdiv(waves, wpw)), dim3(256), (size_t)p.K * 2 + (size_t)p.K / 4, s, p, upw, wpw);
-  }
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
 // p3v_gemv_step on MLX 4-bit weights: the first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in
 // (one row, K = 3072 or 8192, no epilogue); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_q4_step(const p3v_gemv_q4_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->sb || !a->out) return P3V_ERR_ARG;
-  const bool begin = st->tok != nullptr, end = st->next_tok != nullptr;
-  if (begin == end) return P3V_ERR_ARG;                        // exactly one of the two ends
-  if (a->M <= 0 || a->N <= 0 || a->K <= 0) return P3V_ERR_ARG;
-  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192) || a->epilogue != P3V_EPI_NONE) return P3V_ERR_UNSUPPORTED;
-  if (begin) {
-    if (!st->embed_table || !st->x_out || !st->cos_t || !st->sin_t || !st->d_past || !st->cos_out || !st->sin_out || st->vocab <= 0) return P3V_ERR_ARG;
-    if (((uintptr_t)st->embed_table | (uintptr_t)st->x_out) & 15) return P3V_ERR_ARG;
-  } else {
-    if (!a->x || !st->tok_out || !st->history || !st->d_step || !st->d_past || !st->ticket || !st->amax_ws) return P3V_ERR_ARG;
-    if ((uintptr_t)st->amax_ws & 7) return P3V_ERR_ARG;
-  }
+  GemvStepP sp; bool begin;
+  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
   const GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
-  const GemvStepP sp = {st->tok, st->embed_table, st->vocab, st->x_out, st->cos_t, st->sin_t, st->d_past, st->cos_out, st->sin_out, st->tab_t,
-                        st->half_dim, st->next_tok, st->tok_out, st->history, st->d_step, st->d_past, st->ticket, st->amax_ws, st->max_steps};
   hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv3_q4<1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv3_q4<1, 3, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv3_q4<2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv3_q4<2, 4, STEP_END>(p, s, &sp);
+  if (a->K == 3072) return begin ? launch_gemv_stream<GemvQ4, 1, 1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvQ4, 1, 1, 3, STEP_END>(p, s, &sp);
+  return begin ? launch_gemv_stream<GemvQ4, 1, 2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvQ4, 1, 2, 4, STEP_END>(p, s, &sp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -330,13 +170,13 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_rows_q4(RowsQ4P p) {
     sv[slot][st][1] = b1[st * 4];
   };
   auto issue_set = [&](int which, auto slotc) {
-    issue(which, slotc, QC0{});
-    if constexpr (NST > 1) issue(which, slotc, QC1{});
+    issue(which, slotc, IC0{});
+    if constexpr (NST > 1) issue(which, slotc, IC1{});
     if constexpr (NST > 2) issue(which, slotc, QC2{});
     if constexpr (NST > 3) issue(which, slotc, QC3{});
   };
   static_assert(NST <= 4, "unrolled for at most four blocks");
-  issue_set(set, QC0{});
+  issue_set(set, IC0{});
 
   // (The input RMSNorm is NOT fused here: built and measured -- every one of the 192-256 workgroups normalising its own copy of the 2 .. 16
   //  rows costs more than the one p3v_rmsnorm launch it saves: B = 8 at 512 keys 2.39 ms per step fused against 2.13 with the launch.)
@@ -362,7 +202,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_rows_q4(RowsQ4P p) {
   auto do_set = [&](auto refillc) {
     constexpr int slot = 0;
     constexpr bool REFILL = decltype(refillc)::value;
-    const auto slotc = QC0{};
+    const auto slotc = IC0{};
     const int refill = set + stride;
     constexpr int ITEMS = (SILU ? 8 : 16) * 16;                  // (output column, x row) pairs of a set: at most one per thread
     static_assert(ITEMS <= NW * 64, "one epilogue item per thread");
@@ -392,7 +232,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_rows_q4(RowsQ4P p) {
         if constexpr (REFILL) { issue(refill, slotc, stc); __builtin_amdgcn_sched_barrier(0); }   // (pinned: the scheduler otherwise sinks the refills to the end of the set)
       }
     };
-    step(QC0{}); step(QC1{}); step(QC2{}); step(QC3{});
+    step(IC0{}); step(IC1{}); step(QC2{}); step(QC3{});
     float* cp = cpart[par];
 #pragma unroll
     for (int s_ = 0; s_ < 2; ++s_) {
@@ -472,8 +312,8 @@ __global__ void __launch_bounds__(NW * 64) k_gemv8_q4(RowsQ4P p, const bf16_t* n
     sv[slot][st][1] = b1[st * 4];
   };
   auto issue_set = [&](int which, auto slotc) {
-    issue(which, slotc, QC0{});
-    if constexpr (NST > 1) issue(which, slotc, QC1{});
+    issue(which, slotc, IC0{});
+    if constexpr (NST > 1) issue(which, slotc, IC1{});
     if constexpr (NST > 2) issue(which, slotc, QC2{});
     if constexpr (NST > 3) issue(which, slotc, QC3{});
   };
@@ -490,7 +330,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemv8_q4(RowsQ4P p, const bf16_t* n
       for (int m = 0; m < 8; ++m) xv[m][k] = *(const u32x4_t*)(p.x + (size_t)min(m, p.M - 1) * K + k_lo + 8 * c);
       gv[k] = norm_w ? *(const u32x4_t*)(norm_w + k_lo + 8 * c) : (u32x4_t){0, 0, 0, 0};
     }
-    issue_set(set, QC0{});
+    issue_set(set, IC0{});
     float r[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) r[m] = 1.f;
@@ -549,7 +389,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemv8_q4(RowsQ4P p, const bf16_t* n
   auto do_set = [&](auto refillc) {
     constexpr int slot = 0;
     constexpr bool REFILL = decltype(refillc)::value;
-    const auto slotc = QC0{};
+    const auto slotc = IC0{};
     const int refill = set + stride;
     // the residual element of this thread's output goes out BEFORE this set's refills: read in the epilogue it would be the youngest
     // load in flight and its wait (vmcnt(0)) would drain the whole ring at every set
@@ -575,7 +415,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemv8_q4(RowsQ4P p, const bf16_t* n
         if constexpr (REFILL) { issue(refill, slotc, stc); __builtin_amdgcn_sched_barrier(0); }   // (pinned: the scheduler otherwise sinks the refills to the end of the set)
       }
     };
-    step(QC0{}); step(QC1{}); step(QC2{}); step(QC3{});
+    step(IC0{}); step(IC1{}); step(QC2{}); step(QC3{});
     // C[4 (lane >> 4) + e][column 2 m + h']: e = h' and h' + 2 are weight rows 2 (lane >> 4), + 1 over k-half h'; the halves meet by DPP
     float e[2][2] = {{odd ? acc0[1] : acc0[0], odd ? acc0[3] : acc0[2]}, {odd ? acc1[1] : acc1[0], odd ? acc1[3] : acc1[2]}};
 #pragma unroll
@@ -670,5 +510,5 @@ if (a->K == 3072) return silu ? launch_gemv8_q4<true, 4, 3>(q, a->norm_w, a->nor
   GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
                a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2};
   hipStream_t s = (hipStream_t)stream;
-  return a->K == 3072 ? launch_gemv3_q4<1, 3>(p, s) : launch_gemv3_q4<2, 4>(p, s);
+  return a->K == 3072 ? launch_gemv_stream<GemvQ4, 1, 1, 3>(p, s) : launch_gemv_stream<GemvQ4, 1, 2, 4>(p, s);
 }

@@ -1423,6 +1423,49 @@ def test_gemv_q4_and_dequant(ops, N, K, epi, norm):
     close(got, ref, rtol=2 ** -6, atol=3e-2)
 
 
+@pytest.fixture(scope="module")
+def stream_tails_case(ops):
+    """(format, K) -> seeded inputs, 8198 weight rows in that format on the device, and the fp32 reference of
+    resid + bf16(W_dequantised . rms_norm(x)) for all of them (the N of a case takes the first N rows): built once per (format, K),
+    freed with the module."""
+    cache = {}
+
+    def case(fmt, K, rows=8198):
+        if (fmt, K) not in cache:
+            from phi_3_vision_mlx_amd.weights import mlx_dequantize, mlx_quantize, q4_repack
+            x, nw, res = g((1, K), 410), g((K,), 411) * 0.1 + 1, g((1, rows), 412)
+            w = g((rows, K), 413, 1.0 / math.sqrt(K)).cuda()
+            if fmt == "bf16":
+                dev, wd = (w,), w.float()
+            elif fmt == "e4m3":
+                dev = ops.quantize_fp8_rows(w)
+                wd = dev[0].cpu().view(torch.float8_e4m3fn).float() * dev[1].cpu()[:, None]        # exact fp32 dequant
+            else:
+                q = mlx_quantize(w)
+                dev, wd = tuple(t.contiguous() for t in q4_repack(*q)), mlx_dequantize(*q)         # fp32, exact scale*q+bias
+            xin = x.float()
+            xin = ((xin * torch.rsqrt(xin.pow(2).mean(-1, keepdim=True) + 1e-5)).to(BF16) * nw).float()    # mx.fast.rms_norm: two roundings
+            ref = (res.float() + (xin @ wd.cpu().t()).to(BF16).float()).to(BF16)
+            cache[fmt, K] = (x.cuda(), nw.cuda(), res, dev, ref)
+        return cache[fmt, K]
+    yield case
+    cache.clear()
+
+
+@pytest.mark.parametrize("N", [2, 4102, 6144, 8198])
+@pytest.mark.parametrize("K", [3072, 8192])
+@pytest.mark.parametrize("fmt", ["bf16", "e4m3", "q4"])
+def test_gemv_stream_tails(ops, stream_tails_case, fmt, K, N):
+    """The streaming M = 1 GEMV (one body for the three weight formats, csrc/p3v_gemv3_body.h) where its pipeline ends early or
+    raggedly: with the default knobs on 256 CUs these N give a wave 1, 2 or 3 stages (the three tail branches) or a longer run, a last
+    wave with fewer row pairs than the others, and a grid with idle waves.  Residual epilogue + fused RMSNorm, against the fp32 product
+    with the dequantised weights."""
+    x, nw, res, dev, ref = stream_tails_case(fmt, K)
+    fn = {"bf16": ops.gemv, "e4m3": ops.gemv_fp8, "q4": ops.gemv_q4}[fmt]
+    out = fn(x, *(t[:N] for t in dev), ops.EPI_RESID_BF16, resid=res[:, :N].contiguous().cuda(), norm_w=nw, norm_eps=1e-5)
+    close(out, ref[:, :N], rtol=2 ** -6, atol=3e-2 if fmt == "q4" else 2e-2)
+
+
 @pytest.mark.parametrize("M", [2, 5, 8, 15, 16])
 @pytest.mark.parametrize("N,K,epi", [(9216, 3072, "none"), (3072, 3072, "resid"), (8192, 3072, "silu"), (3072, 8192, "resid"), (32064, 3072, "none")])
 def test_gemv_q4_rows_2_to_16(ops, N, K, epi, M):

@@ -1041,7 +1041,7 @@ def test_well_conditioned_4bit_fixture():
     """Round 6: MLX 4-bit group-64 decoder weights (`quantize_model=True, quantize_format="int4"`) at FULL size on the well-conditioned
     checkpoint against the oracle on the exact dequantised values (gen_golden_oracle.q4_wc), BASELINE config 1's 128-token prompt, 16
     greedy steps under two unsearched heads: every recorded logit within 2 % of max |z|, the token exact on every clear step.  The
-    steps run what round 6 built for this format: k_gemv3_q4 with the step's two ends folded in (p3v_gemv_q4_step) and the merge
+    steps run what round 6 built for this format: k_gemv3<GemvQ4, ..> with the step's two ends folded in (p3v_gemv_q4_step) and the merge
     launch that carries the 4-bit o_proj (k_attn_combine_o); the prefill dequantises per projection."""
     from phi_3_vision_mlx_amd.api import load_synthetic
     g = np.load(GOLDEN + "/q4_wc_oracle.npz")

@@ -15,7 +15,7 @@
 #include <vector>
 #include <algorithm>
 #include "p3v_common.h"
-#include "p3v_gemv3_body.h"
+#include "p3v_dot_bf16.h"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
