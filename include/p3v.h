@@ -134,6 +134,30 @@ typedef struct {
 int p3v_gemv_fp8(const p3v_gemv_fp8_args_t* args /* host */, void* stream);
 int p3v_dequant_fp8(const uint8_t* w8, const float* w_scale, uint16_t* out_bf16, int rows, int K, void* stream);
 
+/* ---- bf16 weights as exact 13-bit codes: the B = 1 decode projections stream 13/16 of the bytes and
+ * compute the same bits.  A weight s|e8|m7 is stored as s|q5|m7: q = 0 for +-0, q = e - base + 1 (1 .. 31), one `base` per matrix --
+ * 31 consecutive binades ending at the matrix's largest exponent (real checkpoints keep almost everything within 20 .. 30 binades;
+ * 4 code bits would only hold the synthetic weights).  A matrix with a value below that window, a denormal, Inf or NaN does not fit.
+ * p3v_pack_b13: W [rows, K] bf16 -> `out` (rows * K * 13 / 8 bytes, 16-byte aligned), K = 3072 or 8192, rows even.  The packing follows
+ * the row PAIRS the streaming kernel walks: silu_pairs = 0: rows (2u, 2u + 1); silu_pairs = 1: rows (u, u + rows / 2), the gate / up
+ * pairs of P3V_EPI_SILU_MUL.  info: 4 int32 on the device, written by the launches: [0] status (0 = packed; non-zero = W does not fit
+ * and `out` is undefined), [1] base, [2] / [3] smallest / largest biased exponent of the non-zero weights.  The caller reads info once,
+ * at load time.  p3v_unpack_b13 restores the bf16 rows bit for bit (tests). */
+int p3v_pack_b13(const uint16_t* W, int rows, int K, int silu_pairs, void* out, int32_t* info, void* stream);
+int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pairs, int exp_base, uint16_t* out_bf16, void* stream);
+/* p3v_gemv on packed weights: M = 1 only (P3V_ERR_UNSUPPORTED otherwise: the caller keeps the bf16 copy for more rows), N even,
+ * K = 3072 or 8192, every epilogue and the fused RMSNorm of p3v_gemv; bit-identical to p3v_gemv on the bf16 matrix.
+ * silu_pairs must be what the matrix was packed with and equal (epilogue == P3V_EPI_SILU_MUL). */
+typedef struct {
+  const uint16_t* x; const void* W; void* out;
+  const uint16_t* resid; const uint16_t* norm_w;
+  float norm_eps;
+  int M, N, K;
+  int epilogue;
+  int exp_base, silu_pairs;
+} p3v_gemv_b13_args_t;
+int p3v_gemv_b13(const p3v_gemv_b13_args_t* args /* host */, void* stream);
+
 /* ---- W8A8 projection on the fp8 matrix cores (BASELINE config 5, prompt-sized inputs; the same call sites:
  * QuantizedLinear, phi_3_vision_mlx.py:264,291-305, under `quantize_model=True`).
  *   out[M, N] = epilogue((a_scale[m] * w_scale[n]) * sum_k A8[m,k] * W8[n,k])     A8 [M, lda], W8 [N or 2N, ldw]: e4m3 bytes
@@ -467,6 +491,8 @@ typedef struct {
 int p3v_gemv_step(const p3v_gemv_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
 /* the same on e4m3 weights (config 5: `args` as for p3v_gemv_fp8, one row, no epilogue) */
 int p3v_gemv_fp8_step(const p3v_gemv_fp8_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
+/* the same on 13-bit packed bf16 weights (`args` as for p3v_gemv_b13, silu_pairs = 0) */
+int p3v_gemv_b13_step(const p3v_gemv_b13_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
 /* and on MLX 4-bit group-64 weights (`args` as for p3v_gemv_q4, one row, no epilogue) */
 int p3v_gemv_q4_step(const p3v_gemv_q4_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
 

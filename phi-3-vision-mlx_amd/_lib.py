@@ -54,6 +54,11 @@ class GemvF8Args(C.Structure):
                 ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32)]
 
 
+class GemvB13Args(C.Structure):
+    _fields_ = [("x", vp), ("W", vp), ("out", vp), ("resid", vp), ("norm_w", vp), ("norm_eps", f32),
+                ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("exp_base", i32), ("silu_pairs", i32)]
+
+
 class GemmF8Args(C.Structure):
     _fields_ = [("A", vp), ("a_scale", vp), ("W", vp), ("w_scale", vp), ("out", vp), ("resid", vp),
                 ("M", i32), ("N", i32), ("K", i32), ("lda", i32), ("ldw", i32), ("ldo", i32), ("epilogue", i32)]
@@ -146,6 +151,10 @@ SIGNATURES = {
     "p3v_gemv_q4_step": (i32, [C.POINTER(GemvQ4Args), C.POINTER(GemvStep), vp]),
     "p3v_gemv_fp8": (i32, [C.POINTER(GemvF8Args), vp]),
     "p3v_dequant_fp8": (i32, [vp, vp, vp, i32, i32, vp]),
+    "p3v_pack_b13": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "p3v_unpack_b13": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "p3v_gemv_b13": (i32, [C.POINTER(GemvB13Args), vp]),
+    "p3v_gemv_b13_step": (i32, [C.POINTER(GemvB13Args), C.POINTER(GemvStep), vp]),
     "p3v_gemm_fp8": (i32, [C.POINTER(GemmF8Args), vp]),
     "p3v_quant_fp8_rows": (i32, [vp, vp, f32, vp, vp, i32, i32, vp]),
     "p3v_rope_table": (i32, [vp, vp, f32, vp, vp, i32, i32, vp]),

@@ -1,0 +1,224 @@
+// The B = 1 decode projections on bf16 weights stored as exact 13-bit codes (p3v_dot_b13.h): the streaming GEMV
+// that every weight format shares (gemv_stream_body, p3v_gemv3_body.h) with the GemvB13 policy below -- 13/16 of the bf16 stream's
+// bytes, the same eight weights per lane and lane load, so the same v_dot2c sequence and the same bits out -- plus the load-time
+// pack kernels and the unpack kernel the tests use.
+#include <type_traits>
+
+#include "p3v_common.h"
+#include "p3v_dot_b13.h"
+#include "p3v_dot_bf16.h"
+#include "p3v_gemv3_body.h"
+
+struct GemvB13P {
+  const bf16_t* x; const uint32_t* W; void* out; const bf16_t* resid; const bf16_t* norm_w;
+  float eps;
+  int M, N, K, epi, units;
+  uint32_t cc;                       // ((base - 1) << 7) in both 16-bit halves
+};
+
+// ---------------------------------------------------------------- M = 1 streaming: what gemv_stream_body needs to know about the packing
+// a stage is one container: 1 sign load + CH / 2 nibble loads + CH low-byte loads per lane (10 against 12 at CH = 6, 7 against 8 at CH = 4)
+struct GemvB13 {
+  typedef GemvB13P P;
+  static constexpr int WPL = 8, MAX_MT = 1;
+  static constexpr bool XSUM = false;
+  template <int CH> struct Stage { uint32_t sg[B13<CH>::NS]; u32x4_t nib[CH / 2]; u32x4_t lo[CH]; uint32_t cc; };   // (cc: uniform, rides along for dot)
+  static int wpc() { return p3v_tuning().gemv_wpc; }
+  static __device__ __forceinline__ void mark(int) {}
+  template <int K, int CH>
+  static __device__ __forceinline__ void load(const P& p, int r0, int, int c0, Stage<CH>& st) {
+    typedef B13<CH> L;
+    constexpr int NST = K / (CH * 512);
+    const int u = p.epi == P3V_EPI_SILU_MUL ? r0 : r0 >> 1, lane = c0 & 63, s = (c0 >> 6) / CH;
+    const uint32_t* cp = p.W + (size_t)(u * NST + s) * L::DWORDS;
+    if constexpr (L::NS == 3) {
+      const uint32_t* sp = cp + lane * 3;
+      st.sg[0] = __builtin_nontemporal_load(sp);
+      st.sg[1] = __builtin_nontemporal_load(sp + 1);
+      st.sg[2] = __builtin_nontemporal_load(sp + 2);
+    } else {
+      const u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)cp + lane);
+      st.sg[0] = v[0];
+      st.sg[1] = v[1];
+    }
+    const u32x4_t* np = (const u32x4_t*)(cp + L::NIB_OFF) + lane;
+    const u32x4_t* lp = (const u32x4_t*)(cp + L::LO_OFF) + lane;
+#pragma unroll
+    for (int i = 0; i < CH / 2; ++i) st.nib[i] = __builtin_nontemporal_load(np + i * 64);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) st.lo[j] = __builtin_nontemporal_load(lp + j * 64);
+    st.cc = p.cc;
+  }
+  template <int CH>
+  static __device__ __forceinline__ u32x4_t weights(const Stage<CH>& st, int j, int row) {
+    typedef B13<CH> L;
+    return b13_decode8(st.lo[j][2 * row], st.lo[j][2 * row + 1], st.nib[j >> 1][(j & 1) * 2 + row],
+                       st.sg[L::sign_word(row, j, 0)] << L::sign_shift(row, j, 0), st.sg[L::sign_word(row, j, 1)] << L::sign_shift(row, j, 1), st.cc);
+  }
+  template <int CH>
+  static __device__ __forceinline__ void dot(const Stage<CH>& st, int j, const u32x4_t* x, const float*, int c, float& a0, float& a1) {
+    const u32x4_t xa = x[c];
+    a0 = dot8(weights(st, j, 0), xa, a0);
+    a1 = dot8(weights(st, j, 1), xa, a1);
+  }
+  template <int CH> static __device__ __forceinline__ float finish(float v, const Stage<CH>&, int) { return v; }
+};
+
+// ---------------------------------------------------------------- pack (load time) / unpack (tests)
+// info[4]: [0] status (0 = packed, non-zero = the matrix does not fit and `out` holds nothing), [1] base, [2] / [3] smallest / largest
+// biased exponent of the non-zero weights.  Pass 1 finds the range and flags denormals, Inf and NaN; pass 2 packs one container per lane.
+#define B13_BAD_VALUE 1
+#define B13_BAD_RANGE 2
+
+__global__ void k_b13_init(int32_t* info) { info[0] = 0; info[1] = 1; info[2] = 255; info[3] = 0; }
+
+__global__ void __launch_bounds__(256) k_b13_range(const u32x4_t* __restrict__ W, long chunks, int32_t* info) {
+  int emin = 255, emax = 0, bad = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long)gridDim.x * 256) {
+    const u32x4_t w = W[i];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const uint32_t h = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu, e = (h >> 7) & 0xffu, m = h & 0x7fu;
+      if (e == 255u || (e == 0u && m != 0u)) bad = 1;               // Inf / NaN, denormal
+      if (e != 0u) { emin = min(emin, (int)e); emax = max(emax, (int)e); }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    emin = min(emin, __shfl_xor(emin, off, 64));
+    emax = max(emax, __shfl_xor(emax, off, 64));
+    bad |= __shfl_xor(bad, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(info + 2, emin);
+    atomicMax(info + 3, emax);
+    if (bad) atomicOr(info, B13_BAD_VALUE);
+  }
+}
+
+template <int CH>
+__global__ void __launch_bounds__(256) k_b13_pack(const u32x4_t* __restrict__ W, uint32_t* __restrict__ out, int32_t* info, int rows, int nst,
+                                                  int silu_pairs, long n_lanes) {
+  typedef B13<CH> L;
+  const int emin = info[2], emax = info[3];
+  const int base = max(1, emax - 30);                     // the window's 31 binades end at the largest exponent
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t == 0) {
+    info[1] = base;
+    if (emin < base) atomicOr(info, B13_BAD_RANGE);
+  }
+  if (t >= n_lanes || emin < base) return;
+  const long ci = t >> 6;
+  const int lane = (int)(t & 63), u = (int)(ci / nst), s = (int)(ci % nst), xch = nst * CH * 64;
+  const int r[2] = {silu_pairs ? u : 2 * u, silu_pairs ? u + rows / 2 : 2 * u + 1};
+  uint32_t sg[L::NS] = {};
+  u32x4_t nib[CH / 2], lo[CH];
+#pragma unroll
+  for (int i = 0; i < CH / 2; ++i) nib[i] = (u32x4_t){0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < CH; ++j) lo[j] = (u32x4_t){0, 0, 0, 0};
+#pragma unroll
+  for (int row = 0; row < 2; ++row)
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      const u32x4_t w = W[(size_t)r[row] * xch + (s * CH + j) * 64 + lane];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t h = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu, e = (h >> 7) & 0xffu, m = h & 0x7fu, sign = h >> 15;
+        const uint32_t q = e == 0u ? 0u : (e - (uint32_t)base + 1u) & 31u;
+        const int half = k >> 2, b = k & 3;
+        lo[j][2 * row + half] |= (((q & 1u) << 7) | m) << (8 * b);
+        nib[j >> 1][(j & 1) * 2 + row] |= (q >> 1) << (4 * (2 * b + half));
+        sg[L::sign_word(row, j, half)] |= sign << (8 * b + 7 - L::sign_shift(row, j, half));
+      }
+    }
+  uint32_t* cp = out + (size_t)ci * L::DWORDS;
+#pragma unroll
+  for (int i = 0; i < L::NS; ++i) cp[lane * L::NS + i] = sg[i];
+#pragma unroll
+  for (int i = 0; i < CH / 2; ++i) ((u32x4_t*)(cp + L::NIB_OFF))[i * 64 + lane] = nib[i];
+#pragma unroll
+  for (int j = 0; j < CH; ++j) ((u32x4_t*)(cp + L::LO_OFF))[j * 64 + lane] = lo[j];
+}
+
+// the GEMV's own loads and decode (GemvB13::load / weights), written back as bf16 rows
+template <int K, int CH>
+__global__ void __launch_bounds__(256) k_b13_unpack(GemvB13P p, u32x4_t* __restrict__ out, int rows, long n_lanes) {
+  constexpr int NST = K / (CH * 512);
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_lanes) return;
+  const long ci = t >> 6;
+  const int lane = (int)(t & 63), u = (int)(ci / NST), s = (int)(ci % NST);
+  const bool silu = p.epi == P3V_EPI_SILU_MUL;
+  const int r[2] = {silu ? u : 2 * u, silu ? u + rows / 2 : 2 * u + 1};
+  GemvB13::Stage<CH> st;
+  GemvB13::load<K, CH>(p, r[0], r[1], s * CH * 64 + lane, st);
+#pragma unroll
+  for (int row = 0; row < 2; ++row)
+#pragma unroll
+    for (int j = 0; j < CH; ++j) out[(size_t)r[row] * (K / 8) + (s * CH + j) * 64 + lane] = GemvB13::weights(st, j, row);
+}
+
+static bool b13_shape_ok(int rows, int K) { return rows > 0 && rows % 2 == 0 && (K == 3072 || K == 8192); }
+static uint32_t b13_cc(int base) { const uint32_t c = (uint32_t)(base - 1) << 7; return c | (c << 16); }
+
+extern "C" int p3v_pack_b13(const uint16_t* W, int rows, int K, int silu_pairs, void* out, int32_t* info, void* stream) {
+  if (!W || !out || !info) return P3V_ERR_ARG;
+  if (!b13_shape_ok(rows, K)) return P3V_ERR_UNSUPPORTED;
+  if (((uintptr_t)W | (uintptr_t)out) & 15) return P3V_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long chunks = (long)rows * (K / 8), n_lanes = chunks / (K == 3072 ? 12 : 8);   // a lane packs 2 rows x CH chunks
+  hipLaunchKernelGGL(k_b13_init, dim3(1), dim3(1), 0, s, info);
+  hipLaunchKernelGGL(k_b13_range, dim3(min(4096, p3v_cdiv(chunks, 256))), dim3(256), 0, s, (const u32x4_t*)W, chunks, info);
+  if (K == 3072) hipLaunchKernelGGL(k_b13_pack<6>, dim3(p3v_cdiv(n_lanes, 256)), dim3(256), 0, s, (const u32x4_t*)W, (uint32_t*)out, info, rows, 1, silu_pairs, n_lanes);
+  else hipLaunchKernelGGL(k_b13_pack<4>, dim3(p3v_cdiv(n_lanes, 256)), dim3(256), 0, s, (const u32x4_t*)W, (uint32_t*)out, info, rows, 4, silu_pairs, n_lanes);
+  P3V_CHECK_LAUNCH();
+  return P3V_OK;
+}
+
+extern "C" int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pairs, int exp_base, uint16_t* out, void* stream) {
+  if (!packed || !out || exp_base < 1 || exp_base > 224) return P3V_ERR_ARG;
+  if (!b13_shape_ok(rows, K)) return P3V_ERR_UNSUPPORTED;
+  if (((uintptr_t)packed | (uintptr_t)out) & 15) return P3V_ERR_ARG;
+  GemvB13P p = {nullptr, (const uint32_t*)packed, nullptr, nullptr, nullptr, 0.f, 1, rows, K, silu_pairs ? P3V_EPI_SILU_MUL : P3V_EPI_NONE, rows / 2, b13_cc(exp_base)};
+  const long n_lanes = (long)rows * (K / 8) / (K == 3072 ? 12 : 8);
+  hipStream_t s = (hipStream_t)stream;
+  if (K == 3072) hipLaunchKernelGGL((k_b13_unpack<3072, 6>), dim3(p3v_cdiv(n_lanes, 256)), dim3(256), 0, s, p, (u32x4_t*)out, rows, n_lanes);
+  else hipLaunchKernelGGL((k_b13_unpack<8192, 4>), dim3(p3v_cdiv(n_lanes, 256)), dim3(256), 0, s, p, (u32x4_t*)out, rows, n_lanes);
+  P3V_CHECK_LAUNCH();
+  return P3V_OK;
+}
+
+// ---------------------------------------------------------------- entry points: the twins of p3v_gemv_fp8 / p3v_gemv_fp8_step, one row only
+static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p) {
+  if (a->M <= 0 || a->N <= 0) return P3V_ERR_ARG;
+  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192)) return P3V_ERR_UNSUPPORTED;
+  if (a->exp_base < 1 || a->exp_base > 224 || ((uintptr_t)a->W & 15)) return P3V_ERR_ARG;
+  if ((a->silu_pairs != 0) != (a->epilogue == P3V_EPI_SILU_MUL)) return P3V_ERR_ARG;   // the row pairing is part of the packing
+  p = {a->x, (const uint32_t*)a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
+       a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2, b13_cc(a->exp_base)};
+  return P3V_OK;
+}
+
+extern "C" int p3v_gemv_b13_step(const p3v_gemv_b13_args_t* a, const p3v_gemv_step_t* st, void* stream) {
+  if (!a || !st || !a->W || !a->out) return P3V_ERR_ARG;
+  GemvStepP sp; bool begin;
+  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
+  GemvB13P p;
+  if (const int rc = b13_params(a, p)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->K == 3072) return begin ? launch_gemv_stream<GemvB13, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13, 1, 1, 6, STEP_END>(p, s, &sp);
+  return begin ? launch_gemv_stream<GemvB13, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13, 1, 4, 4, STEP_END>(p, s, &sp);
+}
+
+extern "C" int p3v_gemv_b13(const p3v_gemv_b13_args_t* a, void* stream) {
+  if (!a || !a->x || !a->W || !a->out) return P3V_ERR_ARG;
+  if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && a->epilogue != P3V_EPI_SILU_MUL &&
+      a->epilogue != P3V_EPI_F32)
+    return P3V_ERR_UNSUPPORTED;
+  if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
+  GemvB13P p;
+  if (const int rc = b13_params(a, p)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  return a->K == 3072 ? launch_gemv_stream<GemvB13, 1, 1, 6>(p, s) : launch_gemv_stream<GemvB13, 1, 4, 4>(p, s);
+}

@@ -227,6 +227,9 @@ class Phi3VModel:
         if self.w4 and not hasattr(self, "_deq"):
             n_max = max(v[0].shape[0] * v[0].shape[1] * 8 for v in self.w4.values())
             self._deq = torch.empty(n_max, dtype=BF16, device=self.device)  # one dequantised matrix (prefill GEMM scratch)
+        self.w13 = {}                                # weight key -> ops.PackedB13: what the one-row decode projections stream
+        if os.environ.get("P3V_PACK13", "1") != "0":
+            self._pack_decoder_b13()
         if self.vision:
             self._prep_vision()
 
@@ -239,6 +242,44 @@ class Phi3VModel:
             self.w8[k] = ops.quantize_fp8_rows(self.w.pop(k))
         n_max = max(v[0].shape[0] * v[0].shape[1] for v in self.w8.values())
         self._deq = torch.empty(n_max, dtype=BF16, device=self.device)      # one dequantised matrix (prefill GEMM scratch)
+
+    # ------------------------------------------------------------------ 13-bit packed bf16 weights (B = 1 decode)
+    @_on_device
+    def _pack_decoder_b13(self):
+        """A second, exact copy of every bf16 qkv / gate_up / down projection and of lm_head as 13-bit codes:
+        the one-row decode projections stream it instead -- 13/16 of the bytes, the same bits out.  `self.w` keeps the bf16 matrices
+        (prefill, batched decode, adapters and the fused attention + o_proj launch read them).  A matrix that does not fit the format
+        (ops.pack_b13 answers None) or whose K is not 3072 / 8192 is simply not in the dict and stays on bf16."""
+        for k, v in self.w.items():
+            if k != "lm_head.weight" and not (k.startswith("model.layers.") and k.endswith(("qkv_proj.weight", "gate_up_proj.weight", "down_proj.weight"))):
+                continue
+            if v.dim() != 2 or v.shape[1] not in (3072, 8192) or v.shape[0] % 2:
+                continue
+            pk = ops.pack_b13(v, silu_pairs=k.endswith("gate_up_proj.weight"))
+            if pk is not None:
+                self.w13[k] = pk
+
+    def _packed(self, key):
+        """The packed copy of self.w[key], or None: there is none, or the bf16 matrix was replaced or written to since it was made
+        (the copy is then dropped: that matrix runs on bf16 from here on).  This is looked at where a launch is ISSUED -- eager calls and
+        graph captures; a step that is already captured keeps replaying the copy it was captured with, so whoever changes decoder
+        weights of a live model calls `repack_b13`."""
+        pk = self.w13.get(key)
+        if pk is not None and not pk.current(self.w.get(key)):
+            del self.w13[key]
+            self.epoch += 1
+            return None
+        return pk
+
+    def repack_b13(self):
+        """After decoder weights were replaced or written to: drop every packed copy and every captured step that may stream one, and
+        pack again from `self.w` as it stands (nothing if P3V_PACK13=0)."""
+        self.w13.clear()
+        self.epoch += 1
+        for st in list(self._states):
+            st.graphs.clear()
+        if os.environ.get("P3V_PACK13", "1") != "0":
+            self._pack_decoder_b13()
 
     # ------------------------------------------------------------------ LoRA adapters (use_adapter=True)
     def set_adapters(self, adapters):
@@ -405,6 +446,9 @@ class Phi3VModel:
         eps = self.cfg.rms_norm_eps
         M, K = x.shape
         q, q4 = self.w8.get(key), self.w4.get(key)
+        pk = self._packed(key) if M == 1 else None
+        if pk is not None and pk.silu_pairs == (epilogue == EPI_SILU_MUL):      # (an adapted gate_up runs with a plain epilogue: bf16)
+            return ops.gemv_b13(x, pk, epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
         skinny = M <= 8 or (M <= ops.GEMV_MAX_M and K % 512 == 0)
         if skinny and M > 8 and q is None and q4 is None and K % 64 == 0 and self.w[key].shape[0] % 64 == 0:
             # 9 .. 16 rows on bf16 weights: the 64-row tiles of the weight-streaming GEMM (p3v_gemm_skinny.hip) beat the 16-row MFMA
@@ -946,6 +990,8 @@ class Phi3VModel:
             if i == 0 and step_begin is not None:               # replayed greedy step: the embedding gather + rotation-row staging
                 sb = step_begin                                 # ride in this projection's prologue when the library takes the shape
                 w_fold = w.get(k_w) if k_w in w else (self.w8.get(k_w) or self.w4.get(k_w))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
+                if B == 1 and self._packed(k_w) is not None:
+                    w_fold = self.w13[k_w]                      # one row: the 13-bit packed copy of the bf16 matrix
                 if not (w_fold is not None and k_w not in self.adapters and k_w not in self._bank and os.environ.get("P3V_STEP_FOLD", "1") != "0"
                         and ops.gemv_step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"], sb["sin_o"],
                                                 w_fold, w[p + "input_layernorm.weight"], eps, qkv)):
@@ -1080,6 +1126,8 @@ class Phi3VModel:
         end = (g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
         if not sampled:
             w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
+            if st.B == 1 and self._packed(head) is not None:
+                w_fold = self.w13[head]                         # one row: the 13-bit packed copy of the bf16 matrix
             if (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
                     and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
                 return self._logprobs_tail(st, g) if logprobs else None

@@ -6,6 +6,7 @@ Each op names the MLX call site of the reference it replaces.
 """
 import contextlib
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -321,6 +322,60 @@ def gemv_fp8(x, w8, w_scale, epilogue=EPI_NONE, resid=None, norm_w=None, norm_ep
     return out
 
 
+class PackedB13:
+    """A bf16 matrix [rows, K] as exact 13-bit codes (include/p3v.h: p3v_pack_b13): `data` u8 [rows, K * 13 / 8] in the container layout
+    of the streaming GEMV, `base` the matrix's exponent base, `silu_pairs` the row pairing it was packed for (gate / up rows of
+    EPI_SILU_MUL, or neighbouring rows for every other epilogue); `src` / `version` a weak reference to the tensor it was made from and
+    that tensor's in-place modification count then (`current` says whether the copy still stands for a given tensor)."""
+    __slots__ = ("data", "base", "rows", "K", "silu_pairs", "src", "version")
+
+    def __init__(self, data, base, rows, K, silu_pairs, src=None):
+        self.data, self.base, self.rows, self.K, self.silu_pairs = data, int(base), int(rows), int(K), bool(silu_pairs)
+        self.src, self.version = (weakref.ref(src) if src is not None else None), (src._version if src is not None else 0)
+
+    def current(self, w):
+        return w is not None and self.src is not None and w is self.src() and w._version == self.version
+
+
+def pack_b13(w, silu_pairs=False):
+    """bf16 [rows, K] -> PackedB13, or None when the matrix does not fit the format (a value more than 30 binades below its largest,
+    a denormal, Inf or NaN): the caller then keeps the bf16 matrix.  Load-time weight prep: reads the verdict back (one sync)."""
+    _chk(w, BF16, "w")
+    rows, K = w.shape
+    if K not in (3072, 8192) or rows % 2:
+        return None
+    data = torch.empty((rows, K * 13 // 8), dtype=torch.uint8, device=w.device)
+    info = torch.empty(4, dtype=I32, device=w.device)
+    L.check(L.lib().p3v_pack_b13(_p(w), rows, K, int(bool(silu_pairs)), _p(data), _p(info), _stream()), "pack_b13")
+    status, base = info.tolist()[:2]
+    return None if status else PackedB13(data, base, rows, K, silu_pairs, src=w)
+
+
+def unpack_b13(pk, out=None):
+    """PackedB13 -> the bf16 matrix, bit for bit."""
+    out = torch.empty((pk.rows, pk.K), dtype=BF16, device=pk.data.device) if out is None else out
+    L.check(L.lib().p3v_unpack_b13(_p(pk.data), pk.rows, pk.K, int(pk.silu_pairs), pk.base, _p(out), _stream()), "unpack_b13")
+    return out
+
+
+def _b13_args(x, pk, out, resid, norm_w, norm_eps, M, epilogue):
+    N = pk.rows // 2 if epilogue == EPI_SILU_MUL else pk.rows
+    return L.GemvB13Args(_p(x), _p(pk.data), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, pk.K, epilogue, pk.base, int(pk.silu_pairs))
+
+
+def gemv_b13(x, pk, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, out=None):
+    """`gemv` on 13-bit packed bf16 weights: one row of x, 13/16 of the streamed bytes, the same bits out."""
+    _chk(x, BF16, "x")
+    M, K = x.shape
+    if K != pk.K:
+        raise ValueError(f"gemv_b13: x has {K} columns, the packed matrix {pk.K}")
+    if out is None:
+        out = torch.empty((M, pk.rows // 2 if epilogue == EPI_SILU_MUL else pk.rows), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
+    args = _b13_args(x, pk, out, resid, norm_w, norm_eps, M, epilogue)
+    L.check(L.lib().p3v_gemv_b13(C.byref(args), _stream()), "gemv_b13")
+    return out
+
+
 def dequant_fp8(w8, w_scale, out=None):
     """fp8 rows -> bf16 (scratch for the prefill GEMM)."""
     N, K = w8.shape
@@ -625,7 +680,12 @@ def gemv_step_begin(tok, table, x_out, cos_t, sin_t, d_past, cos_out, sin_out, w
     B, tab_t, half = tok.numel(), cos_t.shape[-2], cos_t.shape[-1]
     st = L.GemvStep(_p(tok), _p(table), table.shape[0], _p(x_out), _p(cos_t), _p(sin_t), _p(cos_out), _p(sin_out), tab_t, half,
                     None, None, None, None, None, None, 0, _p(d_past))
-    if isinstance(w, tuple) and w[0].dtype == I32:              # (4-bit weights, scale | bias words): p3v_gemv_q4_step
+    if isinstance(w, PackedB13):                                # 13-bit packed bf16 weights: p3v_gemv_b13_step
+        if table.shape[1] != w.K or x_out.shape[-1] != w.K:
+            raise ValueError(f"gemv_step_begin: table / x_out rows of {table.shape[1]} / {x_out.shape[-1]} columns, the packed matrix {w.K}")
+        args = _b13_args(None, w, out, None, norm_w, norm_eps, B, EPI_NONE)
+        rc = L.lib().p3v_gemv_b13_step(C.byref(args), C.byref(st), _stream())
+    elif isinstance(w, tuple) and w[0].dtype == I32:            # (4-bit weights, scale | bias words): p3v_gemv_q4_step
         w4, sb = w
         _chk(sb, I32, "sb")
         args = L.GemvQ4Args(None, _p(w4), _p(sb), _p(out), None, _p(norm_w), float(norm_eps), B, w4.shape[0], w4.shape[1] * 8, EPI_NONE)
@@ -654,7 +714,12 @@ def gemv_step_end(x, w, norm_w, norm_eps, out, next_tok, tok, history, d_step, d
     M, K = x.shape
     st = L.GemvStep(None, None, 0, None, None, None, None, None, 0, 0,
                     _p(next_tok), _p(tok), _p(history), _p(d_step), _p(ticket), _p(amax_ws), history.shape[1], _p(d_past))
-    if isinstance(w, tuple) and w[0].dtype == I32:              # (4-bit weights, scale | bias words)
+    if isinstance(w, PackedB13):                                # 13-bit packed bf16 weights
+        if K != w.K:
+            raise ValueError(f"gemv_step_end: x has {K} columns, the packed matrix {w.K}")
+        args = _b13_args(x, w, out, None, norm_w, norm_eps, M, EPI_NONE)
+        rc = L.lib().p3v_gemv_b13_step(C.byref(args), C.byref(st), _stream())
+    elif isinstance(w, tuple) and w[0].dtype == I32:            # (4-bit weights, scale | bias words)
         w4, sb = w
         _chk(sb, I32, "sb")
         args = L.GemvQ4Args(_p(x), _p(w4), _p(sb), _p(out), None, _p(norm_w), float(norm_eps), M, w4.shape[0], K, EPI_NONE)
