@@ -157,6 +157,11 @@ typedef struct {
   int exp_base, silu_pairs;
 } p3v_gemv_b13_args_t;
 int p3v_gemv_b13(const p3v_gemv_b13_args_t* args /* host */, void* stream);
+/* How p3v_gemv_b13 / p3v_gemv_b13_step cut a launch of N outputs (as in `args`) on `n_cu` compute units at the current knobs
+ * (gemv_b13_wpc, gemv_wpw; the end fold of p3v_gemv_b13_step runs at gemv_b13_wpc_end instead) -- the launcher's own arithmetic, callable without a GPU.  out[0] row pairs per wave, out[1] waves that
+ * take rows (wave i: row pairs [i * out[0], (i + 1) * out[0]), cut at the end), out[2] row-streaming waves per 4-wave workgroup,
+ * out[3] workgroups. */
+int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out /* host, 4 ints */);
 
 /* ---- W8A8 projection on the fp8 matrix cores (BASELINE config 5, prompt-sized inputs; the same call sites:
  * QuantizedLinear, phi_3_vision_mlx.py:264,291-305, under `quantize_model=True`).

@@ -154,6 +154,7 @@ SIGNATURES = {
     "p3v_pack_b13": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "p3v_unpack_b13": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "p3v_gemv_b13": (i32, [C.POINTER(GemvB13Args), vp]),
+    "p3v_gemv_b13_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
     "p3v_gemv_b13_step": (i32, [C.POINTER(GemvB13Args), C.POINTER(GemvStep), vp]),
     "p3v_gemm_fp8": (i32, [C.POINTER(GemmF8Args), vp]),
     "p3v_quant_fp8_rows": (i32, [vp, vp, f32, vp, vp, i32, i32, vp]),

@@ -136,18 +136,18 @@ static int launch_gemv(const GemvP& p, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // Streaming variant for the B=1 decode shapes (M <= 4; K = 3072 or 8192, compile-time): gemv_stream_body (p3v_gemv3_body.h) on
 // bf16 weights -- a lane load is 16 bytes = 8 weights, nothing travels with a stage, the sum of a row is its result.
-#ifdef P3V_GEMV_TIMING                                         // tools/gemv_timeline.py: 100 MHz stamps per wave (entry, exit)
-__device__ long long p3v_gemv_tbuf[4096 * 2];
+#ifdef P3V_GEMV_TIMING                                         // tools/gemv_timeline.py: 100 MHz stamps per wave (entry, exit, first dot)
+__device__ long long p3v_gemv_tbuf[4096 * 3];
 extern "C" int p3v_gemv_timing_read(long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(p3v_gemv_tbuf), sizeof(long long) * n) == hipSuccess ? 0 : -1;
 }
-#define GMARK(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) p3v_gemv_tbuf[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (k)] = wall_clock64(); } while (0)
+#define GMARK(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) p3v_gemv_tbuf[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 3 + (k)] = wall_clock64(); } while (0)
 #else
 #define GMARK(k)
 #endif
 struct GemvBf16 {
   typedef GemvP P;
-  static constexpr int WPL = 8, MAX_MT = 4;
+  static constexpr int WPL = 8, MAX_MT = 4, MIN_WG = 1;
   static constexpr bool XSUM = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; };
   static int wpc() { return p3v_tuning().gemv_wpc; }

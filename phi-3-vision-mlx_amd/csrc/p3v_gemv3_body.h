@@ -8,7 +8,10 @@
 //   load        requests a Stage, in the order that format's stream wants;  dot: folds lane load j of both rows into the two
 //               accumulators from the activations in LDS;  finish: applied to a row's sum after wave_sum (the e4m3 row scale)
 //   XSUM        the 4-bit form needs the sum of every 16 activations: one more pass over LDS between staging and streaming
-//   wpc         the format's waves-per-CU tuning knob;  mark: timing stamp hook (tools/gemv_timeline.py, bf16 only)
+//   wpc         the format's waves-per-CU tuning knob;  mark: timing stamp hook (tools/gemv_timeline.py: bf16 and the 13-bit codes;
+//               0 entry, 1 exit, 2 first dot)
+//   MIN_WG      workgroups per CU the kernels are compiled to fit (__launch_bounds__): 1 = whatever the registers allow; a format
+//               that asks for more also supplies wpc_end, the waves per CU of its STEP_END launch, which keeps the default bound
 // (fo_project, the o_proj stage of the fused attention launches in p3v_attention.hip, repeats this arithmetic from the p3v_dot_*.h
 // helpers; it does not share the body.  Two fused launches that did were removed in round 4: DESIGN.md section 3.1.)
 #pragma once
@@ -251,6 +254,7 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
   }
 
   // ---- 4. pipeline
+  F::mark(2);
   float a0[MT], a1[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m) a0[m] = a1[m] = 0.f;
@@ -318,15 +322,28 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
 }
 
 template <class F, int MT, int NST, int CH>
-__global__ void __launch_bounds__(256) k_gemv3(typename F::P p, int units_per_wave, int wpw) {
+__global__ void __launch_bounds__(256, F::MIN_WG) k_gemv3(typename F::P p, int units_per_wave, int wpw) {
   F::mark(0);
   gemv_stream_body<F, MT, NST, CH, STEP_NONE>(p, units_per_wave, wpw, nullptr);
   F::mark(1);
 }
 
+// (the arg-max tail of STEP_END does not fit the registers of a MIN_WG > 1 bound without scratch: it keeps the default)
 template <class F, int MT, int NST, int CH, int STEP>
-__global__ void __launch_bounds__(256) k_gemv3_step(typename F::P p, int units_per_wave, int wpw, GemvStepP sp) {
+__global__ void __launch_bounds__(256, STEP == STEP_END ? 1 : F::MIN_WG) k_gemv3_step(typename F::P p, int units_per_wave, int wpw, GemvStepP sp) {
   gemv_stream_body<F, MT, NST, CH, STEP>(p, units_per_wave, wpw, &sp);
+}
+
+// How a launch of `units` row pairs is cut up, for the launcher and for p3v_gemv_b13_plan alike: row pairs per wave, waves that take
+// rows, row-streaming waves per 4-wave workgroup.  Wave i owns row pairs [i * upw, (i + 1) * upw), cut at `units`.
+struct GemvPlan { int upw, waves, wpw; };
+static inline GemvPlan gemv_stream_plan(int units, int n_cu, int wpc, int forced_wpw) {
+  GemvPlan g;
+  g.upw = p3v_cdiv(units, (long)n_cu * (wpc < 1 ? 1 : wpc));
+  if (g.upw < 1) g.upw = 1;
+  g.waves = p3v_cdiv(units, g.upw);
+  g.wpw = p3v_gemv_wpw(g.waves, n_cu, forced_wpw);        // 4 or 3 row-streaming waves per workgroup
+  return g;
 }
 
 template <class F, int MT, int NST, int CH, int STEP = STEP_NONE>
@@ -338,10 +355,10 @@ static int launch_gemv_stream(const typename F::P& p, hipStream_t s, const GemvS
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
     n_cu = pr.multiProcessorCount;
   }
-  int upw = p3v_cdiv(p.units, n_cu * F::wpc());          // row pairs per wave
-  if (upw < 1) upw = 1;
-  const int waves = p3v_cdiv(p.units, upw);
-  const int wpw = p3v_gemv_wpw(waves, n_cu, p3v_tuning().gemv_wpw);   // 4 or 3 row-streaming waves per workgroup
+  int wpc = F::wpc();
+  if constexpr (STEP == STEP_END && F::MIN_WG > 1) wpc = F::wpc_end();   // (that kernel is not bounded to MIN_WG workgroups a CU)
+  const GemvPlan g = gemv_stream_plan(p.units, n_cu, wpc, p3v_tuning().gemv_wpw);
+  const int upw = g.upw, waves = g.waves, wpw = g.wpw;
   constexpr size_t K = (size_t)NST * CH * 64 * F::WPL, lds = MT * K * 2 + (F::XSUM ? K / 4 : 0);   // x as bf16 (+ the piece sums)
   if constexpr (lds > 48 * 1024) {                       // (bf16, four x rows of K = 8192)
     static bool attr_set = false;

@@ -18,13 +18,25 @@ struct GemvB13P {
 
 // ---------------------------------------------------------------- M = 1 streaming: what gemv_stream_body needs to know about the packing
 // a stage is one container: 1 sign load + CH / 2 nibble loads + CH low-byte loads per lane (10 against 12 at CH = 6, 7 against 8 at CH = 4)
+#ifdef P3V_GEMV_TIMING                                         // tools/gemv_timeline.py: 100 MHz stamps per wave (entry, exit, first dot)
+__device__ long long p3v_gemv_b13_tbuf[4096 * 3];
+extern "C" int p3v_gemv_b13_timing_read(long long* out, int n) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(p3v_gemv_b13_tbuf), sizeof(long long) * n) == hipSuccess ? 0 : -1;
+}
+#define B13MARK(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) p3v_gemv_b13_tbuf[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 3 + (k)] = wall_clock64(); } while (0)
+#else
+#define B13MARK(k)
+#endif
 struct GemvB13 {
   typedef GemvB13P P;
-  static constexpr int WPL = 8, MAX_MT = 1;
+  static constexpr int WPL = 8, MAX_MT = 1, MIN_WG = 4;
   static constexpr bool XSUM = false;
+  // 4 workgroups a CU (at most 128 VGPRs): the decode's ~2.6 VALU operations per weight want the fourth wave of a SIMD, and
+  // gemv_b13_wpc = 16 puts it there (gate_up: 4096 waves, all resident)
   template <int CH> struct Stage { uint32_t sg[B13<CH>::NS]; u32x4_t nib[CH / 2]; u32x4_t lo[CH]; uint32_t cc; };   // (cc: uniform, rides along for dot)
-  static int wpc() { return p3v_tuning().gemv_wpc; }
-  static __device__ __forceinline__ void mark(int) {}
+  static int wpc() { return p3v_tuning().gemv_b13_wpc; }
+  static int wpc_end() { return p3v_tuning().gemv_b13_wpc_end; }   // the vocabulary head's fold: 131 VGPRs, 16 waves a CU would not be resident
+  static __device__ __forceinline__ void mark(int k) { B13MARK(k); }
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int, int c0, Stage<CH>& st) {
     typedef B13<CH> L;
@@ -197,6 +209,14 @@ static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p) {
   if ((a->silu_pairs != 0) != (a->epilogue == P3V_EPI_SILU_MUL)) return P3V_ERR_ARG;   // the row pairing is part of the packing
   p = {a->x, (const uint32_t*)a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
        a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2, b13_cc(a->exp_base)};
+  return P3V_OK;
+}
+
+extern "C" int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out) {
+  if (!out || N <= 0 || n_cu <= 0) return P3V_ERR_ARG;
+  if (N % 2 || (K != 3072 && K != 8192)) return P3V_ERR_UNSUPPORTED;
+  const GemvPlan g = gemv_stream_plan(epilogue == P3V_EPI_SILU_MUL ? N : N / 2, n_cu, GemvB13::wpc(), p3v_tuning().gemv_wpw);
+  out[0] = g.upw; out[1] = g.waves; out[2] = g.wpw; out[3] = p3v_cdiv(g.waves, g.wpw);
   return P3V_OK;
 }
 

@@ -25,7 +25,7 @@ struct GemvF8P {
 // a lane load is 16 bytes = 16 weights, meeting two 16-byte x chunks; the row's fp32 scale travels with the stage and multiplies the sum
 struct GemvF8 {
   typedef GemvF8P P;
-  static constexpr int WPL = 16, MAX_MT = 1;
+  static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
   static constexpr bool XSUM = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; float scale[2]; };
   static int wpc() { return p3v_tuning().gemv_f8_wpc; }   // (a stage is half the bytes of the bf16 kernel's: twice the waves keep as many in flight; 8: 1.321, 16: 1.301, 24: 1.333 ms/step)

@@ -29,7 +29,7 @@ struct GemvQ4P {
 // chunks and the piece's activation sum X (XSUM: the body precomputes them in LDS); a piece's scale | bias word travels with it
 struct GemvQ4 {
   typedef GemvQ4P P;
-  static constexpr int WPL = 16, MAX_MT = 1;
+  static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
   static constexpr bool XSUM = true;
   template <int CH> struct Stage { u32x2_t w[2][CH]; uint32_t sb[2][CH]; };
   static int wpc() { return p3v_tuning().gemv_q4_wpc; }

@@ -376,6 +376,14 @@ def gemv_b13(x, pk, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, ou
     return out
 
 
+def gemv_b13_plan(N, K, epilogue, n_cu):
+    """(row pairs per wave, waves that take rows, row-streaming waves per workgroup, workgroups) of a `gemv_b13` launch at the current
+    knobs.  Host arithmetic only (include/p3v.h: p3v_gemv_b13_plan)."""
+    out = (C.c_int32 * 4)()
+    L.check(L.lib().p3v_gemv_b13_plan(int(N), int(K), int(epilogue), int(n_cu), out), "gemv_b13_plan")
+    return tuple(out)
+
+
 def dequant_fp8(w8, w_scale, out=None):
     """fp8 rows -> bf16 (scratch for the prefill GEMM)."""
     N, K = w8.shape
