@@ -573,6 +573,42 @@ int p3v_logprobs(const uint16_t* logits, int64_t row_stride, const int32_t* toke
 int p3v_logprobs_step(const uint16_t* logits, const int32_t* next_tok, const int32_t* want, const int32_t* d_step,
                       p3v_logprob_t* records, int B, int n, int max_steps, void* stream);
 
+/* ---- repetition / presence / frequency penalties and logit_bias: added after round 6, no version change.
+ * Per-row state on the device, so a captured step adjusts its logits with no host input: a record, a table seen[0..n) of uint32
+ * (bit 31: the token occurs in the row's prompt; bits 0..30: how often the row has emitted it, below 2^31) and an optional table
+ * bias[0..n) of fp32.  The rule, for one row of bf16 logits l[0..n) -> the adjusted row l'[0..n), a second buffer:
+ *   0. flags & 1 == 0 (an inactive row): l' is a byte copy of l (NaN payloads and -0 kept); seen is neither read nor written.
+ *   1. a = f32(l_i), c = seen_i & 0x7fffffff, s = (seen_i != 0).
+ *   2. repetition (the HF / vLLM convention, prompt and output): if s and repetition != 1: a = (a > 0) ? a / repetition
+ *      : a * repetition (IEEE fp32, correctly rounded).
+ *   3. frequency (output only): a = a - fl32(frequency * (float)c): two separately rounded fp32 operations, no FMA.
+ *   4. presence (output only): if c > 0: a = a - presence.
+ *   5. bias: if flags & 2 (and a bias table was passed): a = a + bias_i.  A -inf bias bans the token.
+ *   6. l'_i = bf16_rne(a).  A NaN stays a NaN (its payload is not specified): the sampler then reports -1, as it does today.
+ * Every operation is ONE correctly rounded fp32 operation in a fixed order: fp32 arithmetic on the host reproduces every bit
+ * (penalties.reference_adjust).  The raw logits are not touched: p3v_logprobs* keep describing the RAW distribution, the sampler
+ * (p3v_sample / p3v_sample_step_end) reads l', so temperature, top-k and top-p apply after the penalties and a T = 0 row takes
+ * the arg-max of l' by p3v_argmax's rule. */
+#define P3V_PENALTY_ACTIVE 1
+#define P3V_PENALTY_BIAS 2
+typedef struct { float repetition, frequency, presence; int32_t flags; } p3v_penalty_row_t;   /* 16 bytes */
+/* seen[r, id] |= 1 << 31 (as_prompt != 0) or += 1 (otherwise) for id = ids[r, first[r] .. first[r] + count[r]) (row r of `ids` at
+ * ids + r * ids_stride, of `seen` at seen + r * seen_stride; the run is cut to the row: first[r] < 0 skips it, the count ends at
+ * ids_stride); ids outside [0, n) are skipped (image slots, the -1 of a failed step).  clear != 0 zeroes the `rows` rows first,
+ * ordered before the scatter.  Duplicates and equal ids in one row are fine (32-bit vector atomics).  rows >= 1, n >= 1,
+ * ids_stride >= 0, seen_stride >= n; P3V_ERR_ARG otherwise or for a null pointer. */
+int p3v_penalty_note(uint32_t* seen, int64_t seen_stride, const int32_t* ids, int64_t ids_stride, const int32_t* first,
+                     const int32_t* count, int rows, int n, int as_prompt, int clear, void* stream);
+/* out[r] = the rule on logits row r.  fed != NULL: BEFORE reading, seen[r, fed[r]] += 1 when fed[r] lies in [0, n) and the row is
+ * active (the token this step was fed = the token the row emitted last; a count stays at 2^31 - 1 once there), done by the one
+ * thread that owns that index: no atomics, no second launch.  bias may be NULL (step 5 is then skipped for every row).  Every
+ * pointer is device memory, so the call is capturable.  Rows whose four bases are 16-byte aligned move 16 bytes per access,
+ * others (and the tail n % 8) go element by element.  1 <= rows <= 65535, n >= 1, every stride >= n, out != logits;
+ * P3V_ERR_ARG otherwise or for a null logits / rows_params / seen / out. */
+int p3v_penalize(const uint16_t* logits, int64_t row_stride, const p3v_penalty_row_t* rows_params, uint32_t* seen,
+                 int64_t seen_stride, const float* bias /* may be NULL */, int64_t bias_stride, const int32_t* fed /* may be NULL */,
+                 uint16_t* out, int64_t out_stride, int rows, int n, void* stream);
+
 /* ---- prompt prefix cache: KV block copy at any column phase (added after round 6, no version change).
  * One job copies tokens [t0_src, t0_src + n_tok) of batch row b_src of a source cache to tokens [t0_dst, t0_dst + n_tok) of
  * batch row b_dst of a destination cache, for ALL nl layers and nkv heads; up to P3V_KV_COPY_MAX_JOBS jobs share ONE launch

@@ -112,6 +112,15 @@ class LogprobRecord(C.Structure):
 LOGPROB_WORDS = C.sizeof(LogprobRecord) // 4     # 20
 
 
+class PenaltyRow(C.Structure):
+    """p3v_penalty_row_t: one row's penalties and flags (include/p3v.h)."""
+    _fields_ = [("repetition", f32), ("frequency", f32), ("presence", f32), ("flags", C.c_int32)]
+
+
+PENALTY_WORDS = C.sizeof(PenaltyRow) // 4        # 4
+PENALTY_ACTIVE, PENALTY_BIAS = 1, 2              # P3V_PENALTY_ACTIVE, P3V_PENALTY_BIAS
+
+
 class KvCopyJob(C.Structure):
     """p3v_kv_copy_job_t: one row's token run, source -> destination (include/p3v.h)."""
     _fields_ = [("k_src", vp), ("v_src", vp), ("k_dst", vp), ("v_dst", vp),
@@ -196,6 +205,8 @@ SIGNATURES = {
     "p3v_sample_step_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_logprobs": (i32, [vp, i64, vp, vp, vp, i32, i32, vp]),
     "p3v_logprobs_step": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p3v_penalty_note": (i32, [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),     # added after round 6, no version change
+    "p3v_penalize": (i32, [vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, vp]),   # added after round 6, no version change
     "p3v_spec_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p3v_spec_end": (i32, [vp, C.POINTER(SpecState), i32, i32, vp]),
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),

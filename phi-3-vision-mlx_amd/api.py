@@ -31,6 +31,7 @@ import torch
 from . import ops as model_ops
 from . import sampling as sampling_mod
 from . import logprobs as logprobs_mod
+from . import penalties as penalties_mod
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
@@ -310,7 +311,7 @@ def _last_logits(logits):
 
 
 def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None, sampling=None,
-                logprobs=None):
+                logprobs=None, penalties=None):
     """The decode loop of `_generate` (reference phi_3_vision_mlx.py:390-398): `n_steps` greedy steps after the prefill token,
     every token handed to the streamer and the stoppers in order, stops as the reference stops.
 
@@ -327,7 +328,13 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     logprobs: a logprobs.Collector -- the loop then drives the replay that ends in the log-probability launch
     (model.logprob_step / sample_logprob_step: the same step plus one launch) and hands the collector every step's records
     right after the streamer got its tokens.  The one-step-ahead loop reads them from the capture's pinned `records` buffer
-    behind the event that guards `history`: no sync and no copy of their own.  None: the replays and launches of today."""
+    behind the event that guards `history`: no sync and no copy of their own.  None: the replays and launches of today.
+
+    penalties: {"prompt_ids", "pad"} of a state whose rows carry penalty records (model.set_penalties, done by the caller with
+    the prefill token drawn from the adjusted prefill logits) -- the loop then drives the PENALISED replay for every step
+    (model.penal_step / penal_logprob_step: each step counts the token it is fed), greedy rows under greedy sampling records.
+    If the loop re-plans after a failed step, the rows' tables are rebuilt from the prompt and the tokens fed so far rather than
+    trusted.  None: the replays and launches of today."""
     graph_step = getattr(model, "greedy_step", None)
     records = None
     if sampling is not None:
@@ -344,6 +351,12 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             model.set_logprobs(cache[0].state, logprobs.wants)
         else:                                                       # an eager model: one eager launch per step
             want_dev = torch.tensor(logprobs.wants, dtype=torch.int32, device=token.device)
+    if penalties is not None:
+        if graph_step is None or not hasattr(model, "penal_step"):
+            raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
+        if sampling is None:                                        # the penalised tail is the sampled one: greedy records
+            model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
+        graph_step = model.penal_step if logprobs is None else model.penal_logprob_step
 
     def slot(g_):
         """the pinned records of the replay just enqueued ([B, 20], valid once the step has run)"""
@@ -396,12 +409,15 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             raise _StepFailed(f"device step failed: NaN logits (token ids {rows})")
         taken[:] = rows
         n_done += 1
+        if penalties is not None:
+            delivered.append(list(rows))
         streamer(rows)
         if p[3] is not None:
             logprobs.add(p[3])
         return token_stopper(rows)
     st = cache[0].state
     token0 = token.clone()                                          # (the caller's tensor may be the step's own output buffer)
+    delivered = []                                                  # (penalties) every step's tokens, for a rebuild of the tables
     degraded = False
     i = 0
     while True:
@@ -450,6 +466,12 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             token = torch.tensor(taken, dtype=torch.int32, device=token0.device).view(-1, 1) if n_done else token0
             if records is not None:                                 # the draw index rewinds with the offset: step n_done draws n_done + 1
                 model.set_sampling(st, sampling_mod.pack(sampling, counter=1 + n_done))
+            if penalties is not None:
+                # the tables may hold the dropped steps' counts: rebuild them from the prompt and the tokens FED so far (steps
+                # 0 .. n_done - 1 were fed the prefill token and the first n_done - 1 delivered ones; the next step counts its own)
+                fed = ([_rows(token0)] + delivered)[:n_done]
+                model.rebuild_penalties(st, penalties["prompt_ids"], np.asarray(fed, dtype=np.int32).T if n_done else None,
+                                        0, penalties.get("pad"))
             print("[phi3v] a decode step timed out in the fused attention + o_proj launch (is another process using this GPU?): "
                   "continuing with separate launches", file=sys.stderr)
 
@@ -555,7 +577,8 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
-              speculate=0, spec_info=None, logprobs=None, logprob_info=None):
+              speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
+              frequency_penalty=0.0, logit_bias=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -566,12 +589,21 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     of prompts ignores it (counted as a bypass).  logprobs: None (off: today's path, launch for launch), an int N in 0..8, or one
     such value per prompt -- every generated token's log-probability under the RAW logits, its rank and the N most likely
     tokens (include/p3v.h: p3v_logprob_t); logprob_info (a dict) receives token_ids / token_logprobs / ranks / top_logprobs,
-    each a list per prompt (None for a prompt that did not ask) with one entry per token handed to the streamer."""
+    each a list per prompt (None for a prompt that did not ask) with one entry per token handed to the streamer.
+    repetition_penalty (> 0; 1 = off; over prompt and output, the HF / vLLM convention), presence_penalty and frequency_penalty
+    (0 = off; over the output), each a scalar or a per-prompt list, and logit_bias ({token id: bias} for every prompt, or one
+    mapping / None per prompt; -inf bans a token): the rule of include/p3v.h above p3v_penalty_row_t, applied to every step's
+    logits BEFORE temperature, top-k and top-p (a greedy row takes the arg-max of the adjusted row); log-probabilities stay
+    those of the raw logits.  The defaults are today's path, launch for launch; under speculate they raise."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     B = len(prompt) if isinstance(prompt, list) else 1
     lp_wants = logprobs_mod.wants(logprobs, B)                  # (checked before anything runs)
     logprobs_mod.refuse_speculation(lp_wants, speculate)
+    pen = penalties_mod.rows(B, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                             getattr(getattr(model, "cfg", None), "vocab_size", None))
+    pen = None if penalties_mod.off(pen) else pen
+    penalties_mod.refuse_speculation(pen, speculate)
     kw_adapter = {}
     if adapter is not None:
         from .engine import _check_adapter, adapter_list
@@ -598,10 +630,21 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         logits, cache = _prefill_with_store(model, prefix_cache, dict_input, digests, max_tokens, kw_adapter, isinstance(prompt, list))
     else:
         logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter)
+    first, pen_state = logits[:, -1, :], None
+    if pen is not None:                                         # records + prompt bits first: the prefill token is penalised too
+        if not hasattr(model, "set_penalties"):
+            raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
+        ids2 = np.asarray(dict_input["input_ids"])
+        ids2 = ids2[None] if ids2.ndim == 1 else ids2
+        pad = (np.asarray(mask).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if mask is not None else None
+        pen_state = dict(prompt_ids=ids2, pad=pad)
+        model.set_penalties(cache[0].state, penalties_mod.pack(pen), ids2, 0,
+                            bias=penalties_mod.bias_table(pen, logits.shape[-1]), pad=pad)
+        first = model.penalized_logits(cache[0].state, logits)
     if sampled is None:
-        token = model_ops.argmax(_last_logits(logits))[:, None]
+        token = model_ops.argmax(first.contiguous())[:, None]
     else:                                                       # draw 0 of every row: from the prefill logits
-        token = model_ops.sample(logits[:, -1, :], sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
+        token = model_ops.sample(first, sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
     streamer(_rows(token))                                      # D2H copy = the per-token sync the reference has (mx.eval)
     collector = None
     if lp_wants is not None:                                    # the first token's record: from the prefill logits
@@ -614,6 +657,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         speculative_loop(model, dict_input["input_ids"], token, cache, max_tokens - 1, speculate, streamer, token_stopper, stats)
         if spec_info is not None:
             spec_info.update(stats)
+    elif pen_state is not None:
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
+                    logprobs=collector, penalties=pen_state)
     elif sampled is None:
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, logprobs=collector)
     else:
@@ -640,21 +686,26 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
 def generate(prompt, images=None, preload=None, blind_model=False, quantize_model=False, quantize_cache=False,
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
-             prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None):
+             prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
+             presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
     """reference phi_3_vision_mlx.py:1324-1374, plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
-    log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`)."""
+    log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`) and the penalties on tokens already seen
+    (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     lp_wants = logprobs_mod.wants(logprobs, len(prompt) if isinstance(prompt, list) else 1)   # before a model is loaded or run
     logprobs_mod.refuse_speculation(lp_wants, speculate)
+    penalties_mod.refuse_speculation(penalties_mod.rows(len(prompt) if isinstance(prompt, list) else 1, repetition_penalty,
+                                                        presence_penalty, frequency_penalty, logit_bias), speculate)
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
                      top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache, speculate=speculate,
-                     spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info)
+                     spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info, repetition_penalty=repetition_penalty,
+                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)
 
 
 # ----------------------------------------------------------------------------- score

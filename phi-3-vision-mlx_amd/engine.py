@@ -64,9 +64,9 @@ def _set_device(device):
 
 class Request:
     __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
-                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records")
+                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties")
 
-    def __init__(self, inputs, max_tokens, sampling=None, adapter=None, logprobs=None):
+    def __init__(self, inputs, max_tokens, sampling=None, adapter=None, logprobs=None, penalties=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
         # prompt prefix cache (engine with a store only; `cache_args` puts them beside the inputs): digests of the request's source
         # images, whether its prompt may be captured, an explicit capture length; `cached_tokens`: prompt tokens restored from the
@@ -79,6 +79,7 @@ class Request:
         self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
         self.logprobs = logprobs                                 # None (off) or N in 0..8: one record per token in `logprob_records`
         self.logprob_records = []                                # (logprobs.unpack dicts, aligned with `tokens`)
+        self.penalties = penalties                               # None (off) or one (repetition, frequency, presence, bias) tuple
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
         self.tokens, self.row, self.error = [], None, None
         self.cancelled, self.blocked_at = False, None
@@ -141,9 +142,14 @@ class ContinuousEngine:
         as `cache_args` does (so it travels through a router or a fleet too) -- every token of the request then comes with its
         log-probability under the raw logits, its rank and the N most likely tokens (include/p3v.h: p3v_logprob_t) in
         `logprob_records`, aligned with `tokens`.  While no active request asks, the engine replays exactly what it replays
-        without the feature."""
+        without the feature.
+        Penalties and logit_bias: `submit(penalty_args(inputs, repetition_penalty=, presence_penalty=, frequency_penalty=,
+        logit_bias=), ...)` puts them beside the inputs in the same way -- the request's row then has its logits adjusted by the
+        rule of include/p3v.h (p3v_penalty_row_t) before its token is drawn, from its first token on, whoever shares the
+        batch; rows that did not ask pass through bit for bit.  While no active request asks, nothing of it runs."""
         try:
             want = _check_logprobs(requested_logprobs(inputs))
+            pen = _check_penalties(requested_penalties(inputs), getattr(getattr(self.model, "cfg", None), "vocab_size", None))
             rec = _sampling_row(sampling)
             _check_adapter(adapter, self.adapter_names())
             _check_prefix_args(inputs)
@@ -151,7 +157,7 @@ class ContinuousEngine:
             r = Request(inputs, max_tokens)
             r.fail(e)
             return r
-        r = Request(inputs, max_tokens, rec, adapter, want)
+        r = Request(inputs, max_tokens, rec, adapter, want, pen)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -172,6 +178,8 @@ class ContinuousEngine:
             self.st.pad_len[r.row:r.row + 1].fill_(self.window)  # every key masked: the row idles at zero cost of correctness
             if r.logprobs is not None:
                 self.model.set_logprobs(self.st, [-1], r.row)    # the row's next occupant costs the launch one early exit
+            if r.penalties is not None:
+                self.model.clear_penalties(self.st, r.row, 1)    # ... and is not penalised by this one's record
         r.done.set()
 
     _finish = _release
@@ -255,7 +263,23 @@ class ContinuousEngine:
         if self.adapter_names():
             # the rows' adapters (None -> -1: a refilled row must not keep its last occupant's) BEFORE their prefill reads them
             self.model.set_row_adapters(st, [r.adapter for r in group], row0)
-        if any(r.sampling is not None for r in group):
+        penalized = any(r.penalties is not None for r in group)
+        if not penalized and getattr(st, "penalty", None) is not None:
+            self.model.clear_penalties(st, row0, n)              # a penalised request had these rows before: inactive now
+        if penalized:
+            # the rows' records and prompt bits BEFORE the first token is drawn: it comes from the adjusted prefill logits, under
+            # the group's sampling records (greedy members: temperature 0 = the arg-max of the adjusted row)
+            from . import penalties as penalties_mod
+            prows = [r.penalties or penalties_mod.INACTIVE for r in group]
+            ids2 = np.asarray(inputs["input_ids"])
+            ids2 = ids2[None] if ids2.ndim == 1 else ids2
+            pad = (np.asarray(inputs["mask"]).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if "mask" in inputs else None
+            self.model.set_penalties(st, penalties_mod.pack(prows), ids2, row0,
+                                     bias=penalties_mod.bias_table(prows, self.model.cfg.vocab_size), pad=pad)
+            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
+            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
+            toks = self.model.sample_logits(st, self.model.penalized_logits(st, logits, row0), row0)
+        elif any(r.sampling is not None for r in group):
             # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
             _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
@@ -359,6 +383,8 @@ class ContinuousEngine:
                     del r.logprob_records[:]
                 if getattr(self.st, "logprob_want", None) is not None and any(r.logprobs is not None for r in group):
                     self.model.set_logprobs(self.st, [-1] * n, row0)
+                if getattr(self.st, "penalty", None) is not None and any(r.penalties is not None for r in group):
+                    self.model.clear_penalties(self.st, row0, n)
                 if n == 1:
                     group[0].fail(e)
                     continue
@@ -383,6 +409,11 @@ class ContinuousEngine:
         g = self.model.decode_graph(self.st)
         # the sampled replay while any active row samples (its greedy rows take the arg-max there too), the greedy one otherwise
         replay = self.model.sample_step if any(r.sampling is not None for r in active) else self.model.greedy_step
+        # the penalised replay while any active row is penalised (a penalised row is active from its prefill to its release, so
+        # every one of its steps counts the token it is fed; the other rows' logits pass through bit for bit)
+        penalized = any(r.penalties is not None for r in active)
+        if penalized:
+            replay = self.model.penal_step
         scored = any(r.logprobs is not None for r in active)
         if scored:
             # ... followed by the log-probability launch while any active row wants records (the others: one early exit each).
@@ -390,6 +421,8 @@ class ContinuousEngine:
             # they have as many slots as `history` (made with the first scored replay): a long-lived state starts the counter
             # afresh when the slots have run out, whether or not the record buffer exists yet.
             replay = self.model.sample_logprob_step if any(r.sampling is not None for r in active) else self.model.logprob_step
+            if penalized:
+                replay = self.model.penal_logprob_step
             if g.get("n_replays", 0) >= g["history"].shape[1]:
                 self.model.restart_history(self.st)
         _, tok = replay(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
@@ -439,8 +472,9 @@ class ContinuousEngine:
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)
+                 logprobs=None, penalties=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
+                              penalties)
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
@@ -486,6 +520,36 @@ def adapter_list(adapter, n):
     return list(adapter)
 
 
+PENALTY_ARGS = "penalties"          # key of a request's penalty settings inside its `inputs` (no model call forwards it)
+
+
+def penalty_args(inputs, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
+    """A copy of a B = 1 `processor(...)` result that carries the request's penalties and logit_bias (ContinuousEngine.submit) as
+    one plain dict, so it travels through a router or a fleet as `logprob_args` does.  The processor's own result is not
+    touched; `submit` checks the values (penalties.request_row)."""
+    return dict(inputs, **{PENALTY_ARGS: dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                               frequency_penalty=frequency_penalty, logit_bias=logit_bias)})
+
+
+def requested_penalties(inputs):
+    return inputs.get(PENALTY_ARGS) if isinstance(inputs, dict) else None
+
+
+def _check_penalties(d, vocab=None):
+    """submit's penalty dict -> None (off) or the checked (repetition, frequency, presence, bias) tuple; ValueError names the value."""
+    from .penalties import request_row
+    return request_row(d, vocab)
+
+
+def penalties_list(penalties, n):
+    """`penalties` argument of a text-level call (None, one dict for every prompt, or one dict / None per prompt) -> a list."""
+    if penalties is None or isinstance(penalties, dict):
+        return [penalties] * n
+    if len(penalties) != n:
+        raise ValueError(f"penalties: {len(penalties)} values for {n} prompts")
+    return list(penalties)
+
+
 LOGPROB_ARGS = "logprobs"           # key of a request's `logprobs` value inside its `inputs` (no model call forwards it)
 
 
@@ -528,7 +592,8 @@ def _check_prefix_args(inputs):
             raise ValueError(f"prefix_len must be a positive integer, got {prefix_len!r}")
 
 
-def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None, logprobs=None):
+def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None, logprobs=None,
+            penalties=None):
     """submit with only the keywords in use (an engine-like object without them keeps working for plain requests); the prefix-cache
     arguments, when one of them is in use, ride beside the inputs (`cache_args`), and so does `logprobs` (`logprob_args`)."""
     kw = {}
@@ -540,6 +605,8 @@ def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, c
         kw["adapter"] = adapter
     if logprobs is not None:
         inputs = logprob_args(inputs, logprobs)
+    if penalties is not None:
+        inputs = dict(inputs, **{PENALTY_ARGS: dict(penalties)})
     return engine.submit(inputs, max_tokens, **kw)
 
 
@@ -570,12 +637,13 @@ def has_prefix_cache(engine):
 
 
 def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None,
-                   logprobs=None):
+                   logprobs=None, penalties=None):
     """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt.
     cache_prompt: None / True (the prompt may be captured by the engine's prefix store) or False.  info: a dict that receives
     "cached_tokens" (one count per prompt) and, when a prompt asked for them, "logprobs" (per prompt: logprobs.entry of its
     records -- token_ids / token_logprobs / ranks / top_logprobs over the tokens of the returned text -- or None).
-    logprobs: None, N in 0..8, or one such value per prompt."""
+    logprobs: None, N in 0..8, or one such value per prompt.  penalties: None, one {"repetition_penalty", "presence_penalty",
+    "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     images = images if images is not None else [None] * len(prompts)
@@ -583,6 +651,7 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
         raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
     adapters = adapter_list(adapter, len(prompts))
     lps = logprobs_list(logprobs, len(prompts))
+    pens = penalties_list(penalties, len(prompts))
     reqs = []
     for i, (p, im) in enumerate(zip(prompts, images)):
         text, imgs = api._apply_chat_template(p, im, False)
@@ -592,7 +661,7 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
             digests = image_digests(imgs)
         inputs = processor(text, imgs) if imgs is not None else processor(text)
         reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt,
-                            logprobs=lps[i]))
+                            logprobs=lps[i], penalties=pens[i]))
     out, kept = [], []
     try:
         for r in reqs:
@@ -652,5 +721,6 @@ class RegimeRouter:
                 stop_event.wait(idle_sleep)
 
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)
+                 logprobs=None, penalties=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
+                              penalties)

@@ -16,7 +16,8 @@ one receiver thread per source takes them in order).  RCCL is not involved; the 
 import threading
 import time
 
-from .engine import Request, _check_adapter, _check_logprobs, _generate_text, _submit, requested_logprobs
+from .engine import (Request, _check_adapter, _check_logprobs, _check_penalties, _generate_text, _submit, requested_logprobs,
+                     requested_penalties)
 
 _ERRORS = {"ValueError": ValueError, "TimeoutError": TimeoutError, "TypeError": TypeError}   # what the HTTP handler tells apart
 
@@ -89,10 +90,12 @@ class EngineFleet:
     def submit(self, inputs, max_tokens, sampling=None, adapter=None):
         """Prefix-cache arguments (`engine.cache_args`) travel inside `inputs` to whichever rank takes the request (one store per
         engine; no cache-affinity routing: the least-loaded rank wins as before).  So does `logprobs` (`engine.logprob_args`);
-        the records come back with the tokens."""
+        the records come back with the tokens.  Penalties and logit_bias (`engine.penalty_args`) ride there too; a bad value is
+        refused here, on rank 0."""
         try:
             _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
             logprobs = _check_logprobs(requested_logprobs(inputs))   # nor does a bad N
+            _check_penalties(requested_penalties(inputs))        # nor a bad penalty or bias (the vocabulary bound: the rank's engine)
         except ValueError as e:
             h = Request(inputs, max_tokens)
             h.fail(e)
@@ -162,8 +165,9 @@ class EngineFleet:
         self.engine.serve_forever(stop_event, idle_sleep)
 
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs)
+                 logprobs=None, penalties=None):
+        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
+                              penalties)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""

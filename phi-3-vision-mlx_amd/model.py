@@ -119,6 +119,13 @@ class CacheState:
         lives with `shared`: the leases of a captured-prefill entry share their captures, which bake its address in."""
         return self.shared.get("logprob_want")
 
+    @property
+    def penalty(self):
+        """The penalty state (model.set_penalties): a dict of the rows' records (int32 [B, 4]), their `seen` table (int32 [B, n]:
+        the uint32 words of the rule), the adjusted-logits buffer (bf16 [B, n]) and, once a request brought one, the bias table
+        (fp32 [B, n]) -- or None before the first penalised request.  With `shared`, as the want-table is."""
+        return self.shared.get("penalty")
+
     def rows_view(self, rows, offset, S):
         """Batch rows `rows` (a slice) as a cache of their own at `offset`, for a prompt of S tokens (model.prefill_slot): the same
         buffers sliced, no captured graphs, none of the slot state's roles (slots, serving, sampling records; the caller names the
@@ -1111,7 +1118,7 @@ class Phi3VModel:
         g["d_step"].zero_()                                      # the warm-up run counted as a step
         return g
 
-    def _decode_step(self, st, g, sampled=False, logprobs=False):
+    def _decode_step(self, st, g, sampled=False, logprobs=False, penalized=False):
         """The launches of one decode step over the loop state `g` of a greedy capture: the layers, then the step's tail -- final
         norm + lm_head + arg-max + bookkeeping, or with sampled=True each row's token drawn under its record (`set_sampling`)
         where the greedy step has its arg-max.
@@ -1119,7 +1126,10 @@ class Phi3VModel:
         (B = 1 on bf16, e4m3 or 4-bit weights: ops.gemv_step_begin / gemv_step_end; 129 launches per step instead of 131); the
         sampled tail always goes through `_proj` (every weight format, adapters honoured).
         logprobs=True: ONE more launch behind that tail, whichever it is -- the record of each row's emitted token
-        (p3v_logprobs_step) into the pinned `records` buffer; it reads the logits and the loop state and changes neither."""
+        (p3v_logprobs_step) into the pinned `records` buffer; it reads the logits and the loop state and changes neither.
+        penalized=True (a sampled tail): ONE more launch between lm_head and the tail -- p3v_penalize counts the token this step
+        was fed into the rows' `seen` table and writes the adjusted rows to the penalty state's second buffer, which the tail
+        draws from (a T = 0 row: its arg-max); `logits` stays raw, for the caller and for the log-probability launch."""
         cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
         self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
                      step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
@@ -1132,7 +1142,11 @@ class Phi3VModel:
                     and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
                 return self._logprobs_tail(st, g) if logprobs else None
         self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output)
-        if sampled:
+        if penalized:
+            pen = st.penalty
+            ops.penalize(g["logits"], pen["rows"], pen["seen"], pen["bias"], g["tok"], out=pen["adj"])
+            ops.sample_step_end(pen["adj"], st.sample_rows, *end)
+        elif sampled:
             ops.sample_step_end(g["logits"], st.sample_rows, *end)
         else:
             ops.step_end(g["logits"], *end)
@@ -1145,8 +1159,8 @@ class Phi3VModel:
     def _replay(self, token, cache, which):
         """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy), "sample_graph" (a
         second capture over the same loop state, built on first use -- after the token and the cache length are in place, which
-        its warm-up run reads), or "logprob_graph" / "sample_logprob_graph" (either step followed by the log-probability launch,
-        built the same way).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
+        its warm-up run reads), "logprob_graph" / "sample_logprob_graph" (either step followed by the log-probability launch,
+        built the same way), or "penal_graph" / "penal_logprob_graph" (the sampled step on penalised logits).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
         st = cache[0].state
         if st.offset + 1 > st.T:
             raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
@@ -1156,8 +1170,10 @@ class Phi3VModel:
         if g.get("synced_offset") != st.offset:
             g["d_past"].fill_(st.offset)
         if which != "graph" and which not in g:
-            g[which] = self._build_sample_graph(st, g, sampled=which in ("sample_graph", "sample_logprob_graph"),
-                                                logprobs=which in ("logprob_graph", "sample_logprob_graph"))
+            penalized = which in ("penal_graph", "penal_logprob_graph")
+            g[which] = self._build_sample_graph(st, g, sampled=penalized or which in ("sample_graph", "sample_logprob_graph"),
+                                                logprobs=which in ("logprob_graph", "sample_logprob_graph", "penal_logprob_graph"),
+                                                penalized=penalized)
         g[which].launch()
         g["n_replays"] = g.get("n_replays", 0) + 1              # replay r, greedy or sampled, wrote its token to history[:, r - 1] (while it fits)
         st.offset += 1
@@ -1361,26 +1377,121 @@ class Phi3VModel:
             raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
         return self._replay(token, cache, "sample_graph")
 
-    def _build_sample_graph(self, st, g, sampled=True, logprobs=False):
+    def _build_sample_graph(self, st, g, sampled=True, logprobs=False, penalized=False):
         """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
         through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
         The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it.
         The two log-probability captures are made here as well: sampled=False keeps the greedy step as `_decode_step` runs it
         (the folded tail included), logprobs=True appends p3v_logprobs_step; their records land in a pinned buffer beside
-        `history`, made with the first of them."""
+        `history`, made with the first of them.  penalized=True: the sampled step with p3v_penalize in front of its tail; the
+        warm-up run's count of the fed token is taken back with the rest."""
         torch.cuda.synchronize()
         if logprobs and "records" not in g:
             g["records"] = torch.zeros((st.B, g["history"].shape[1], ops.L.LOGPROB_WORDS), dtype=I32).pin_memory()
         saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
         saved_rows = st.sample_rows.clone() if sampled else None
-        ws = g["gemm_ws_" + ("sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
-        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs), ws)
+        saved_seen = st.penalty["seen"].clone() if penalized else None
+        ws = g["gemm_ws_" + ("penalized" if penalized else "sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
+        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs, penalized=penalized), ws)
         for k, v in saved.items():
             g[k].copy_(v)
         if sampled:
             st.sample_rows.copy_(saved_rows)
+        if penalized:
+            st.penalty["seen"].copy_(saved_seen)
         torch.cuda.synchronize()
         return graph
+
+    # ------------------------------------------------------------------ penalties and logit_bias (include/p3v.h: p3v_penalty_row_t)
+    @staticmethod
+    def _drop_penalty_captures(st):
+        g = st.graphs.get("greedy")
+        for k in ("penal_graph", "penal_logprob_graph"):
+            if g is not None:
+                g.pop(k, None)
+
+    @_on_device
+    def set_penalties(self, st, records, prompt_ids, row0=0, bias=None, pad=None):
+        """Give rows row0 .. row0+n-1 of a state their penalty records (penalties.pack: int32 [n, 4] on the host) and start their
+        `seen` rows from their prompts: prompt_ids (int [n, S] on the host; pad: per-row count of left-padding ids to skip, None =
+        0) are noted with p3v_penalty_note(clear=1, as_prompt=1) -- ids outside the vocabulary (image slots) are skipped.
+        bias: fp32 [n, vocab] on the host (penalties.bias_table) or None.  The first call makes the state's `seen` table and the
+        adjusted-logits buffer ([B, vocab] each) and greedy sampling records where the state has none (the penalised step's tail
+        is the sampled one); the first call WITH a bias makes the [B, vocab] bias table -- captures made before it baked a null
+        pointer in and are dropped.  One H2D copy per operand and one scatter, outside any graph."""
+        V, dev = self.cfg.vocab_size, self.device
+        n = records.shape[0]
+        pen = st.penalty
+        if pen is None or pen["seen"].shape[0] != st.B:
+            pen = st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
+                                              seen=torch.zeros((st.B, V), dtype=I32, device=dev),
+                                              adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
+            self._drop_penalty_captures(st)
+        if st.sample_rows is None:
+            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))   # (all rows greedy: temperature 0)
+        if bias is not None:
+            if pen["bias"] is None:
+                pen["bias"] = torch.zeros((st.B, V), dtype=F32, device=dev)
+                self._drop_penalty_captures(st)
+            pen["bias"][row0:row0 + n].copy_(torch.as_tensor(np.ascontiguousarray(bias, dtype=np.float32)).view(n, V))
+        pen["rows"][row0:row0 + n].copy_(records)
+        self.rebuild_penalties(st, prompt_ids, None, row0, pad)
+
+    @_on_device
+    def rebuild_penalties(self, st, prompt_ids, emitted, row0=0, pad=None):
+        """Rebuild the `seen` rows row0 .. row0+n-1 from scratch -- wherever a step may be repeated or a state re-planned, instead
+        of replaying increments: the prompts with clear=1, as_prompt=1, then `emitted` (int [n, m] on the host, or None: the
+        tokens the rows have been FED so far, i.e. everything they emitted but the newest) with as_prompt=0."""
+        pen, dev = st.penalty, self.device
+        ids = np.asarray(prompt_ids)
+        ids = (ids[None] if ids.ndim == 1 else ids).astype(np.int32)
+        n, S = ids.shape
+        first = np.zeros(n, dtype=np.int32) if pad is None else np.asarray(pad, dtype=np.int32).reshape(n)
+        seen = pen["seen"][row0:row0 + n]
+        ops.penalty_note(seen, torch.from_numpy(np.ascontiguousarray(ids)).to(dev), torch.from_numpy(first).to(dev),
+                         torch.from_numpy((S - first).astype(np.int32)).to(dev), as_prompt=True, clear=True)
+        if emitted is not None:
+            em = np.asarray(emitted).astype(np.int32).reshape(n, -1)
+            if em.shape[1]:
+                ops.penalty_note(seen, torch.from_numpy(np.ascontiguousarray(em)).to(dev), torch.zeros((n,), dtype=I32, device=dev),
+                                 torch.full((n,), em.shape[1], dtype=I32, device=dev), as_prompt=False)
+
+    @_on_device
+    def clear_penalties(self, st, row0=0, n=None):
+        """Rows row0 .. row0+n-1 (default: to the end) become inactive: the penalised step copies their logits through."""
+        if st.penalty is not None:
+            st.penalty["rows"][row0:None if n is None else row0 + n].zero_()
+
+    @_on_device
+    def penalized_logits(self, st, logits, row0=0):
+        """The adjusted rows of rows row0 .. row0+n-1's logits ([n, L, V] or [n, V]: the last position) under their records --
+        the eager form, for the token drawn from the PREFILL logits: nothing is fed, nothing is counted.  bf16 [n, V], a new
+        tensor; `logits` is not written."""
+        pen = st.penalty
+        if pen is None:
+            raise RuntimeError("penalized_logits: no penalty state on this state (model.set_penalties)")
+        last = logits[:, -1, :] if logits.dim() == 3 else logits
+        rows = slice(row0, row0 + last.shape[0])
+        return ops.penalize(last, pen["rows"][rows], pen["seen"][rows], None if pen["bias"] is None else pen["bias"][rows])
+
+    @_on_device
+    def penal_step(self, token, cache):
+        """One decode step on PENALISED logits through its captured graph (built on first use over the greedy capture's loop
+        state): lm_head, p3v_penalize (which counts the fed token), then the sampled tail on the adjusted rows.  A state with
+        active penalties takes this replay for EVERY step: each step counts the token it is fed.  Returns (raw logits [B,1,V],
+        next_token [B,1])."""
+        st = cache[0].state
+        if st.penalty is None or st.sample_rows is None:
+            raise RuntimeError("penal_step: no penalty state on this state (model.set_penalties)")
+        return self._replay(token, cache, "penal_graph")
+
+    @_on_device
+    def penal_logprob_step(self, token, cache):
+        """`penal_step` followed by the log-probability launch -- on the RAW logits."""
+        st = cache[0].state
+        if st.penalty is None or st.sample_rows is None or st.logprob_want is None:
+            raise RuntimeError("penal_logprob_step: needs a penalty state and a want-table (set_penalties, set_logprobs)")
+        return self._replay(token, cache, "penal_logprob_graph")
 
     # ------------------------------------------------------------------ token log-probabilities (include/p3v.h: p3v_logprob_t)
     @_on_device

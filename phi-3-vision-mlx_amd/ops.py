@@ -835,6 +835,57 @@ def logprobs_step(logits, next_tok, want, d_step, records):
                                       _stream()), "logprobs_step")
 
 
+def _rows2d(t, dtype, name, rows=None, n=None):
+    """A [rows, n] device view with unit stride along n (rows may be strided) -> its row stride in elements."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a device tensor (the hot path has no CPU fallback)")
+    if t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected {dtype} [rows, n] with unit stride along n")
+    if (rows is not None and t.shape[0] != rows) or (n is not None and t.shape[1] != n):
+        raise ValueError(f"{name}: expected [{rows}, {n}], got {tuple(t.shape)}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))   # (a one-row tensor's row stride is arbitrary: never used)
+
+
+def _chk_i32_vec(t, rows, name):
+    _chk(t, I32, name)
+    if t.shape != (rows,):
+        raise ValueError(f"{name}: expected int32 [{rows}], got {tuple(t.shape)}")
+
+
+def penalty_note(seen, ids, first, count, as_prompt, clear=False):
+    """Build the penalty table from token ids (include/p3v.h: p3v_penalty_note): seen int32 [rows, n] (the uint32 words of the
+    rule), ids int32 [rows, m]; row r notes ids[r, first[r] : first[r] + count[r]] -- bit 31 with as_prompt, one count each
+    otherwise; ids outside [0, n) are skipped.  clear: the rows are zeroed first.  One scatter launch (two with clear)."""
+    rows, n = seen.shape
+    s_stride = _rows2d(seen, I32, "seen")
+    i_stride = _rows2d(ids, I32, "ids", rows)
+    _chk_i32_vec(first, rows, "first"), _chk_i32_vec(count, rows, "count")
+    L.check(L.lib().p3v_penalty_note(_p(seen), s_stride, _p(ids), i_stride, _p(first), _p(count), rows, n, int(bool(as_prompt)),
+                                     int(bool(clear)), _stream()), "penalty_note")
+
+
+def penalize(logits2d, rows_params, seen, bias=None, fed=None, out=None):
+    """The penalty rule (include/p3v.h: p3v_penalize) on bf16 rows: out[r] = the adjusted row r under record r (int32 [rows, 4],
+    penalties.pack), its seen table row (int32 [rows, n]) and, with `bias` (fp32 [rows, n]), its bias row.  fed (int32 [rows]):
+    the token each row was fed this step, counted into `seen` before the row is adjusted.  The logits are not written; returns
+    `out` (bf16 [rows, n], made when None).  Every operand may have strided rows."""
+    rows, n = logits2d.shape
+    l_stride = _rows2d(logits2d, BF16, "logits")
+    s_stride = _rows2d(seen, I32, "seen", rows, n)
+    b_stride = 0 if bias is None else _rows2d(bias, F32, "bias", rows, n)
+    _chk(rows_params, I32, "rows_params")
+    if rows_params.shape != (rows, L.PENALTY_WORDS):
+        raise ValueError(f"rows_params: expected int32 [{rows}, {L.PENALTY_WORDS}] records (penalties.pack), got {tuple(rows_params.shape)}")
+    if fed is not None:
+        _chk_i32_vec(fed, rows, "fed")
+    if out is None:
+        out = torch.empty((rows, n), dtype=BF16, device=logits2d.device)
+    o_stride = _rows2d(out, BF16, "out", rows, n)
+    L.check(L.lib().p3v_penalize(_p(logits2d), l_stride, _p(rows_params), _p(seen), s_stride, _p(bias), b_stride, _p(fed), _p(out),
+                                 o_stride, rows, n, _stream()), "penalize")
+    return out
+
+
 def spec_state(g, n_max, n_min):
     """p3v_spec_state_t over the loop-state buffers of a speculative capture (model._build_spec_graph)."""
     _chk(g["tok"], I32, "tok"), _chk(g["ctx"], I32, "ctx"), _chk(g["ctl"], I32, "ctl"), _chk(g["amax"], I32, "amax")

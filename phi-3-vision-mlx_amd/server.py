@@ -22,6 +22,12 @@
      "tokens" (the decoded pieces), "token_logprobs", "ranks" and "top_logprobs" (per token a list of {"id", "token", "logprob"});
      non-finite values travel as null.  A bool, a string or a value outside 0 .. 8 -> 400 naming the range; so does an explicit
      "speculate" > 0 next to it, and the batch-sharded path.  Merged requests keep their own N.)
+    (extension: "repetition_penalty" (> 0; 1 = off; prompt and output, the HF / vLLM convention), "presence_penalty" and
+     "frequency_penalty" (0 = off; output only) and "logit_bias": {"<token id>": bias} (string keys, as JSON has them; a bias of
+     -Infinity -- or any value <= -1e30 -- bans the token) -- one setting per request, applied to every prompt of it: the rule
+     of include/p3v.h (p3v_penalty_row_t) on each step's logits before temperature / top-k / top-p.  "logprobs" stay those of
+     the raw logits.  A bad value -> 400 with the reason; so does an explicit "speculate" > 0 next to them, and the
+     batch-sharded path.  Honoured on the one-request, the merged and the --continuous path; merged requests keep their own.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -54,10 +60,12 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs", "penalties")
 
-    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None):
+    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
+                 penalties=None):
         self.logprobs = logprobs                # None, or one N per prompt
+        self.penalties = penalties              # None, or one penalty dict per prompt
         self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
         self.adapter = adapter                  # None, or one name / None per prompt
         self.speculate, self.info = speculate, info             # draft rows per verify step (0 = off), the caller's statistics dict
@@ -154,6 +162,42 @@ def parse_logprobs(request, n_prompts):
         raise ValueError(f"logprobs must be a single integer 0 .. 8 (or null), got {type(v).__name__}")
     want = check(v)
     return None if want == OFF else [want] * n_prompts
+
+
+PENALTY_BAN = -1e30                             # a logit_bias at or below this bans the token (JSON has no -Infinity)
+
+
+def vocab_of(engine):
+    """The vocabulary size behind a backend (the bound of logit_bias keys), or None when it does not say."""
+    v = getattr(engine, "vocab_size", None)
+    if v is not None:
+        return int(v)
+    inner = getattr(engine, "engine", engine)
+    for e in getattr(inner, "engines", None) or [getattr(inner, "engine", inner)]:
+        v = getattr(getattr(getattr(e, "model", None), "cfg", None), "vocab_size", None)
+        if v is not None:
+            return int(v)
+    return None
+
+
+def parse_penalties(request, n_prompts, vocab=None):
+    """The "repetition_penalty", "presence_penalty", "frequency_penalty" and "logit_bias" fields of a request body -> None (all
+    absent, null or at their defaults) or one checked dict per prompt (the same for each).  ValueError (-> 400) with the reason
+    (penalties.rows) on a value of the wrong type or range, a logit_bias that is no object, a key that is no token id below
+    `vocab`, or a bias that is NaN or +inf."""
+    from . import penalties as penalties_mod
+    d = {k: request[k] for k in penalties_mod.FIELDS if request.get(k) is not None}
+    if not d:
+        return None
+    lb = d.get("logit_bias")
+    if lb is not None:
+        if not isinstance(lb, dict):
+            raise ValueError(f"logit_bias must be an object of token id -> bias, got {type(lb).__name__}")
+        d["logit_bias"] = {k: (float("-inf") if isinstance(v, (int, float)) and not isinstance(v, bool) and v <= PENALTY_BAN else v)
+                           for k, v in lb.items()}
+    if penalties_mod.request_row(d, vocab) is None:
+        return None
+    return [d] * n_prompts
 
 
 def token_decoder(engine):
@@ -276,7 +320,8 @@ class EngineQueue:
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
                  length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=(), speculate=False,
-                 speculate_default=0, decode_fn=None):
+                 speculate_default=0, decode_fn=None, vocab_size=None):
+        self.vocab_size = vocab_size                            # bound of a request's logit_bias keys (None: checked by generate_fn)
         self.decode_fn = decode_fn                              # token id -> text piece (the "tokens" of a logprobs response)
         # speculate: generate_fn takes `speculate=K, spec_info=dict` (one prompt, greedy); never with merge (B > 1 batches)
         self.speculate, self.speculate_default = bool(speculate) and not merge, int(speculate_default)
@@ -293,8 +338,10 @@ class EngineQueue:
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info, logprobs)
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
+               penalties=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info, logprobs,
+                   penalties)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -354,6 +401,8 @@ class EngineQueue:
                 if any(j.logprobs is not None for j in group):  # every row keeps its own request's N (None: that row is off)
                     lp_info = {}
                     kw.update(logprobs=[w for j in group for w in (j.logprobs or [None] * len(j.prompts))], logprob_info=lp_info)
+                if any(j.penalties is not None for j in group):  # every row keeps its own request's penalties (None: none)
+                    kw["penalties"] = [d for j in group for d in (j.penalties or [None] * len(j.prompts))]
                 if first.speculate:                             # (one prompt, never merged: self.speculate excludes merge)
                     stats = {}
                     out = self.generate_fn(flat, first.max_tokens, first.images, speculate=first.speculate, spec_info=stats, **kw)
@@ -429,7 +478,16 @@ def make_handler(engine, image_policy=None):
                 cache_prompt = parse_cache_prompt(request)
                 speculate = parse_speculate(request, len(prompts), engine, sampling)
                 logprobs = parse_logprobs(request, len(prompts))
+                penalties = parse_penalties(request, len(prompts), vocab_of(engine))
                 sharded = getattr(engine, "sharded_fn", None)
+                if penalties is not None and speculate:
+                    if "speculate" in request:
+                        raise ValueError("penalties and logit_bias are not available under speculative decoding (a verify step "
+                                         "scores several tokens per replay against one table); send speculate 0")
+                    speculate = 0                               # (the server-wide default steps aside)
+                if penalties is not None and sharded is not None and sharded(prompts, images):
+                    raise ValueError("penalties and logit_bias are not available on the batch-sharded path (image requests and "
+                                     "process groups of the queue server); run the server with --continuous, or send none")
                 if logprobs is not None and speculate:
                     if "speculate" in request:
                         raise ValueError("logprobs are not available under speculative decoding (a verify step emits several "
@@ -454,12 +512,14 @@ def make_handler(engine, image_policy=None):
                 return
             info = None
             try:
-                if logprobs is not None:
-                    info = {}
-                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
+                if logprobs is not None or penalties is not None:
+                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("logprobs", logprobs),
+                                            ("penalties", penalties)) if v is not None}
+                    if logprobs is not None or prefix_counters(engine) is not None:
+                        info = kw["info"] = {}
                     if prefix_counters(engine) is not None and cache_prompt is not None:
                         kw["cache_prompt"] = cache_prompt
-                    responses = engine.submit(prompts, max_tokens, images, logprobs=logprobs, info=info, **kw)
+                    responses = engine.submit(prompts, max_tokens, images, **kw)
                 elif speculate:
                     info = {}
                     kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
@@ -537,11 +597,14 @@ class ContinuousBackend:
             return out
         return counters
 
-    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None):
+    def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None,
+               penalties=None):
         mt = max(1, min(int(max_tokens), self.max_tokens_cap))
         kw = {} if adapter is None else {"adapter": adapter}
         if logprobs is not None:
             kw["logprobs"] = logprobs
+        if penalties is not None:
+            kw["penalties"] = penalties
         if cache_prompt is not None:
             kw["cache_prompt"] = cache_prompt
         if info is not None:
@@ -605,13 +668,16 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return images is not None or (dist.is_available() and dist.is_initialized())
 
     def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
-                    logprob_info=None):
+                    logprob_info=None, penalties=None):
         import torch.distributed as dist
         if speculate:                                                # (one prompt, greedy, no image: the handler saw to it)
             return generate(prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, speculate=speculate, spec_info=spec_info,
                             **({} if adapter is None else {"adapter": adapter[0]}))
-        if sampling is not None or adapter is not None or logprobs is not None:   # (the handler kept these requests off the sharded path)
+        if sampling is not None or adapter is not None or logprobs is not None or penalties is not None:   # (the handler kept these requests off the sharded path)
             kw = {} if sampling is None else {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
+            if penalties is not None:                                # one value per row; a row that asked for nothing: the defaults
+                for f, dflt in (("repetition_penalty", 1.0), ("presence_penalty", 0.0), ("frequency_penalty", 0.0), ("logit_bias", None)):
+                    kw[f] = [dflt if d is None or d.get(f) is None else d[f] for d in penalties]
             if logprobs is not None:
                 kw.update(logprobs=logprobs, logprob_info=logprob_info)
             if adapter is not None:
@@ -630,7 +696,8 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
 
     httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
                           image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True,
-                          speculate_default=speculate, decode_fn=lambda i: processor.tokenizer.decode([int(i)]))
+                          speculate_default=speculate, decode_fn=lambda i: processor.tokenizer.decode([int(i)]),
+                          vocab_size=getattr(getattr(preload[0], "cfg", None), "vocab_size", None))
     print(f"Starting server on port {port}")
     try:
         httpd.serve_forever()
