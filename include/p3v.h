@@ -634,6 +634,40 @@ typedef struct {
 } p3v_kv_copy_job_t;
 int p3v_kv_copy(const p3v_kv_copy_job_t* jobs /* host */, int n_jobs, int nl, int nkv, int hd, int elem_size, void* stream);
 
+/* ---- n completions per prompt: KV fork, one source row to many rows (added after round 6, no version change).
+ * The rule of a family of n completions of ONE prompt (api.generate(n=, best_of=), engine.n_args, the server's "n"):
+ *   Prefill: the prompt is prefilled ONCE, into one batch row.  K is stored rotated by logical position and every row of a
+ *   slot state keeps its own position table and pad_len, so the prompt's K/V rows are valid in any row at the same columns:
+ *   the other n - 1 rows become continuations of the first by copying its K/V columns [pad, offset), its cos / sin table
+ *   rows and its pad_len.
+ *   Seeds: a scalar seed s gives completion j the seed (s + j) mod 2^64 (sampling.rows's batch rule); a list of n seeds is
+ *   used as given; no seed draws 64 random bits once.  Every completion's draw 0 reads the ONE prefill logits row, draw i
+ *   its own row of step i: each completion is the B = 1 request with its seed, on the batched step's logits.
+ *   best_of = m (n <= m <= 16): m completions are generated and the n with the largest sum of RAW-logit token
+ *   log-probabilities through the first EOS are returned, best first; ties go to the lower index (logprobs.rank_best_of).
+ * p3v_kv_fork copies tokens [t0_src, t0_src + n_tok) of batch row b_src of the source cache to tokens
+ * [t0_dst, t0_dst + n_tok) of EVERY row b_dst[0 .. n_dst) of the destination cache, all nl layers and nkv heads in ONE launch:
+ * K, V^T and (all four or none) the fp32 scale rows of the int8 cache, in p3v_kv_copy's layouts.  Every 16-byte piece of
+ * the source is loaded once and stored n_dst times (plain vector stores).  The destination may be another allocation (a B = 1
+ * state forked into a B = n one) or the SAME tensors with B_src == B_dst and T_src == T_dst (rows of one slot state).
+ * Both uses keep the run in the same columns, so only EQUAL 16-byte phase is implemented:
+ * (v_src + t0_src * es) % 16 == (v_dst + t0_dst * es) % 16 with T_src * es and T_dst * es multiples of 16; anything else is
+ * P3V_ERR_UNSUPPORTED with nothing launched (p3v_kv_copy takes any phase pair).  The destination is written inside its runs
+ * ONLY and the source is read inside its runs only.
+ * P3V_ERR_ARG, nothing launched: null / misaligned pointers (K bases 16 bytes, V^T bases elem_size, scales 4), n_dst
+ * outside 1..P3V_KV_FORK_MAX_DST, elem_size other than 1 / 2, hd * elem_size not a multiple of 16, a row index outside its
+ * B, a run that leaves its row, two equal destination rows, the same tensors with a destination row equal to b_src, two
+ * different views that share memory (refused outright, as p3v_kv_copy does).  These are checked first; then n_tok = 0 is an
+ * empty job: P3V_OK at any phase; then the phase. */
+#define P3V_KV_FORK_MAX_DST 15
+typedef struct {
+  const void* k_src; const void* v_src; void* k_dst; void* v_dst;
+  const float* ks_src; const float* vs_src; float* ks_dst; float* vs_dst;   /* all four or none (int8 cache) */
+  int32_t B_src, b_src, T_src, t0_src, B_dst, T_dst, t0_dst, n_tok, n_dst;
+  int32_t b_dst[P3V_KV_FORK_MAX_DST];
+} p3v_kv_fork_t;
+int p3v_kv_fork(const p3v_kv_fork_t* job /* host */, int nl, int nkv, int hd, int elem_size, void* stream);
+
 /* ---- speculative greedy decoding (B = 1): prompt-lookup drafts, one verify step per replay (added after round 6, no
  * version change).  The rule (speculate.py states it once more in plain Python; the kernels are held to it exactly):
  *   State of one sequence: ctx[0..n) -- every token id so far, prompt included; the newest token ctx[n-1] is not yet in

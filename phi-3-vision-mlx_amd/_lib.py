@@ -129,6 +129,18 @@ class KvCopyJob(C.Structure):
                 ("B_dst", i32), ("b_dst", i32), ("T_dst", i32), ("t0_dst", i32), ("n_tok", i32)]
 
 
+KV_FORK_MAX_DST = 15                             # P3V_KV_FORK_MAX_DST
+
+
+class KvFork(C.Structure):
+    """p3v_kv_fork_t: one row's token run to the same-phase columns of n_dst rows (include/p3v.h)."""
+    _fields_ = [("k_src", vp), ("v_src", vp), ("k_dst", vp), ("v_dst", vp),
+                ("ks_src", vp), ("vs_src", vp), ("ks_dst", vp), ("vs_dst", vp),
+                ("B_src", i32), ("b_src", i32), ("T_src", i32), ("t0_src", i32),
+                ("B_dst", i32), ("T_dst", i32), ("t0_dst", i32), ("n_tok", i32), ("n_dst", i32),
+                ("b_dst", i32 * KV_FORK_MAX_DST)]
+
+
 class SpecState(C.Structure):
     """p3v_spec_state_t: the loop state of the speculative greedy step (include/p3v.h)."""
     _fields_ = [("tok", vp), ("ctx", vp), ("ctl", vp), ("amax", vp), ("ticket", vp),
@@ -211,6 +223,7 @@ SIGNATURES = {
     "p3v_spec_end": (i32, [vp, C.POINTER(SpecState), i32, i32, vp]),
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "p3v_kv_copy": (i32, [C.POINTER(KvCopyJob), i32, i32, i32, i32, i32, vp]),
+    "p3v_kv_fork": (i32, [C.POINTER(KvFork), i32, i32, i32, i32, vp]),                   # added after round 6, no version change
     "p3v_graph_begin": (i32, [vp]),
     "p3v_graph_end": (i32, [vp, C.POINTER(vp)]),
     "p3v_graph_launch": (i32, [vp, vp]),

@@ -32,6 +32,7 @@ from . import ops as model_ops
 from . import sampling as sampling_mod
 from . import logprobs as logprobs_mod
 from . import penalties as penalties_mod
+from . import parallel as parallel_mod
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
@@ -578,7 +579,7 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
               speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
-              frequency_penalty=0.0, logit_bias=None):
+              frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -594,12 +595,33 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     (0 = off; over the output), each a scalar or a per-prompt list, and logit_bias ({token id: bias} for every prompt, or one
     mapping / None per prompt; -inf bans a token): the rule of include/p3v.h above p3v_penalty_row_t, applied to every step's
     logits BEFORE temperature, top-k and top-p (a greedy row takes the arg-max of the adjusted row); log-probabilities stay
-    those of the raw logits.  The defaults are today's path, launch for launch; under speculate they raise."""
+    those of the raw logits.  The defaults are today's path, launch for launch; under speculate they raise.
+    n (1..16; ONE prompt, with or without images) completions of the prompt, returned as a list of n strings: the prompt is
+    prefilled ONCE, its B = 1 state forked into a B = m state (model.fork_state: one p3v_kv_fork launch), the m first tokens
+    drawn from the one prefill logits row, and the batched loop runs on the m rows (include/p3v.h above p3v_kv_fork_t).
+    seed=s gives completion j the seed (s + j) mod 2^64; every per-row argument (temperature, top_k, top_p, seed, logprobs, the
+    penalties, logit_bias) is a scalar or one value per GENERATED completion.  At temperature 0 the n completions are equal.
+    best_of=m (n <= m <= 16): m completions are generated and the n with the largest cumulative raw-logit log-probability
+    through the first EOS are returned, best first, ties to the lower index (logprobs.rank_best_of); logprob_info then
+    describes the n returned ones, and family_info (a dict) receives "chosen" (their indices among the m) and "seeds".
+    n == 1 without best_of (or best_of 1) is today's path, launch for launch."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
-    B = len(prompt) if isinstance(prompt, list) else 1
+    n, fam = parallel_mod.check(n, best_of)
+    if fam > 1:                                                 # (n == 1: the model is not asked anything here)
+        cfg_ = getattr(model, "cfg", None)
+        why = parallel_mod.refusal(fam, isinstance(prompt, list), speculate,
+                                   getattr(cfg_, "use_quantized_cache", False) and getattr(cfg_, "cache_format", "int8") == "mlx4",
+                                   hasattr(model, "fork_state") and hasattr(model, "sample_step"))
+        if why:
+            raise ValueError(why)
+    fam = fam if fam > 1 else 0                                 # rows of the family; 0: the plain path
+    B = fam or (len(prompt) if isinstance(prompt, list) else 1)
     lp_wants = logprobs_mod.wants(logprobs, B)                  # (checked before anything runs)
     logprobs_mod.refuse_speculation(lp_wants, speculate)
+    lp_asked = lp_wants
+    if fam > n:                                                 # best_of ranks on every row's records: N = 0 where nobody asked
+        lp_wants = [0 if w == logprobs_mod.OFF else w for w in (lp_wants or [logprobs_mod.OFF] * fam)]
     pen = penalties_mod.rows(B, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
                              getattr(getattr(model, "cfg", None), "vocab_size", None))
     pen = None if penalties_mod.off(pen) else pen
@@ -607,7 +629,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     kw_adapter = {}
     if adapter is not None:
         from .engine import _check_adapter, adapter_list
-        names = adapter_list(adapter, B)
+        if fam and not isinstance(adapter, str):
+            raise ValueError("n > 1: one adapter name for the family (the prompt is prefilled once, under one adapter)")
+        names = adapter_list(adapter, 1 if fam else B)
         for a in names:
             _check_adapter(a, list(getattr(model, "adapter_names", None) or []))
         kw_adapter = {"row_adapters": names}
@@ -619,17 +643,24 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     logit_stopper = LogitStopper(max_tokens, early_stop)
     streamer = Streamer(processor, stream, mute)
     digests = None
-    if prefix_cache is not None and B == 1 and images is not None:
+    if prefix_cache is not None and not isinstance(prompt, list) and images is not None:   # (a family is ONE prompt too: B = fam there)
         from .prefix import image_digests                       # of the source images, next to the processor call
         digests = image_digests(images)
     dict_input = processor(prompt, images)
     mask, pids = dict_input.get("mask", None), dict_input.get("pids", None)
-    token_stopper = TokenStopper(processor, dict_input["input_ids"].shape[0])
+    token_stopper = TokenStopper(processor, fam or dict_input["input_ids"].shape[0])
     tic = Tic()
     if prefix_cache is not None:
         logits, cache = _prefill_with_store(model, prefix_cache, dict_input, digests, max_tokens, kw_adapter, isinstance(prompt, list))
     else:
         logits, cache = model(**dict_input, max_tokens=max_tokens, **kw_adapter)
+    if fam:
+        # ONE prefill behind us: its state forked into `fam` rows (another allocation; the B = 1 state is dropped here), its
+        # one logits row repeated -- every row's draw 0 reads it under the row's own record
+        cache = model.fork_state(cache[0].state, fam)
+        if adapter is not None:
+            model.set_row_adapters(cache[0].state, [adapter] * fam)
+        logits = logits[:, -1:, :].expand(fam, -1, -1).contiguous()
     first, pen_state = logits[:, -1, :], None
     if pen is not None:                                         # records + prompt bits first: the prefill token is penalised too
         if not hasattr(model, "set_penalties"):
@@ -637,6 +668,8 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         ids2 = np.asarray(dict_input["input_ids"])
         ids2 = ids2[None] if ids2.ndim == 1 else ids2
         pad = (np.asarray(mask).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if mask is not None else None
+        if fam:                                                 # every row of the family starts from the prompt's bits
+            ids2, pad = np.repeat(ids2, fam, axis=0), (None if pad is None else np.repeat(pad, fam))
         pen_state = dict(prompt_ids=ids2, pad=pad)
         model.set_penalties(cache[0].state, penalties_mod.pack(pen), ids2, 0,
                             bias=penalties_mod.bias_table(pen, logits.shape[-1]), pad=pad)
@@ -666,8 +699,15 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
                     logprobs=collector)
     result, gen_len = streamer.end()
-    if collector is not None and logprob_info is not None:
-        logprob_info.update(collector.result())
+    chosen = list(range(fam or B))
+    if fam > n:                                                 # best_of: the n best of the m rows, by their own records
+        chosen = logprobs_mod.rank_best_of([[r["token"] for r in rs] for rs in collector.rows],
+                                           [[r["logprob"] for r in rs] for rs in collector.rows], n, ID_EOS)
+        result = [result[j] for j in chosen]
+    if family_info is not None:
+        family_info.update(chosen=chosen, seeds=[rows[j][3] for j in chosen])
+    if collector is not None and logprob_info is not None and lp_asked is not None:
+        logprob_info.update(logprobs_mod.result([collector.rows[j] if lp_asked[j] != logprobs_mod.OFF else None for j in chosen]))
     gen_time = tic()
     prompt_len = dict_input["input_ids"].size
     prompt_tps = prompt_len / prompt_time
@@ -687,17 +727,23 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
              prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
-             presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
-    """reference phi_3_vision_mlx.py:1324-1374, plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
+             presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None):
+    """reference phi_3_vision_mlx.py:1324-1374, plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
+    strings, see `_generate`), plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
     log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`) and the penalties on tokens already seen
     (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
-    lp_wants = logprobs_mod.wants(logprobs, len(prompt) if isinstance(prompt, list) else 1)   # before a model is loaded or run
+    n, fam = parallel_mod.check(n, best_of)                      # before a model is loaded or run
+    why = parallel_mod.refusal(fam, isinstance(prompt, list), speculate)
+    if why:
+        raise ValueError(why)
+    B = fam if fam > 1 else len(prompt) if isinstance(prompt, list) else 1
+    lp_wants = logprobs_mod.wants(logprobs, B)
     logprobs_mod.refuse_speculation(lp_wants, speculate)
-    penalties_mod.refuse_speculation(penalties_mod.rows(len(prompt) if isinstance(prompt, list) else 1, repetition_penalty,
+    penalties_mod.refuse_speculation(penalties_mod.rows(B, repetition_penalty,
                                                         presence_penalty, frequency_penalty, logit_bias), speculate)
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
@@ -705,7 +751,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
                      verbose=verbose, return_tps=return_tps, early_stop=early_stop, stream=stream, temperature=temperature,
                      top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache, speculate=speculate,
                      spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info, repetition_penalty=repetition_penalty,
-                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)
+                     presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
+                     **({} if (n, best_of, family_info) == (1, None, None) else dict(n=n, best_of=best_of, family_info=family_info)))
 
 
 # ----------------------------------------------------------------------------- score

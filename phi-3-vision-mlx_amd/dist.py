@@ -234,8 +234,10 @@ def _all_max(value, group=None):
 
 
 def generate_sharded(prompts, images=None, preload=None, max_tokens=512, group=None, max_batch=8, apply_chat_template=True,
-                     return_tokens=False):
+                     return_tokens=False, n=1, best_of=None):
     """Batched `generate()` over all ranks -- BASELINE config 4 (mixed image + text requests).
+    n / best_of: accepted so that a caller's request is refused by name -- this path runs one row per prompt, a family of
+    n > 1 completions (api._generate(n=...)) raises ValueError before anything is broadcast.
 
     `prompts`: list of str.  `images`: None, or a list with one entry (an image / path / URL as `generate` takes it, or
     None) per prompt.  Rank 0's request table is broadcast (`broadcast_requests`: text + decoded RGB pixels as one uint8 tensor, ~340 KB per 336x336 image);
@@ -248,12 +250,16 @@ def generate_sharded(prompts, images=None, preload=None, max_tokens=512, group=N
     Returns the full list of texts (or token lists) on every rank."""
     from . import api
     from .processor import collate_requests
+    from . import parallel
+    why = parallel.refusal(parallel.check(n, best_of)[1], sharded=True)
+    if why:
+        raise ValueError(why)
     rank, world = _world(group)
     prompts, images = broadcast_requests(list(prompts), list(images) if images is not None else None, group=group)
-    n = len(prompts)
-    images = images if images is not None else [None] * n
+    n_req = len(prompts)                                        # (`n` is the caller's completions-per-prompt, refused above)
+    images = images if images is not None else [None] * n_req
     model, processor = preload
-    idx = shard_indices(n, rank, world)
+    idx = shard_indices(n_req, rank, world)
     reqs = []
     for i in idx:
         if apply_chat_template:
@@ -265,7 +271,7 @@ def generate_sharded(prompts, images=None, preload=None, max_tokens=512, group=N
     local = []
     for c in range(0, len(reqs), max_batch):
         local += generate_requests(model, processor, reqs[c:c + max_batch], max_tokens, return_tokens, width=width)
-    return gather_results(idx, local, n, group)
+    return gather_results(idx, local, n_req, group)
 
 
 class _SlotCache:

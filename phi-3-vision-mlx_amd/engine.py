@@ -64,7 +64,8 @@ def _set_device(device):
 
 class Request:
     __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
-                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties")
+                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties",
+                 "family", "members", "completions", "family_done", "n", "asked_logprobs")
 
     def __init__(self, inputs, max_tokens, sampling=None, adapter=None, logprobs=None, penalties=None):
         self.inputs, self.max_tokens = inputs, int(max_tokens)
@@ -84,14 +85,61 @@ class Request:
         self.tokens, self.row, self.error = [], None, None
         self.cancelled, self.blocked_at = False, None
         self.done = threading.Event()
+        # n completions per prompt (`n_args`): a plain request is its own family of one.  The HEAD of a family (family is self)
+        # lists the m generated requests in `members` (itself first) and the n returned ones in `completions` (for best_of:
+        # ranked, set when `family_done` is); every member has its own tokens / logprob_records / error / done
+        self.family, self.members, self.completions, self.family_done, self.n = None, [self], [self], self.done, 1
+        self.asked_logprobs = logprobs                           # what the CLIENT asked (best_of scores every member at N >= 0)
 
     def cancel(self):
-        """The waiter gave up (timeout, client gone): the engine drops the request at its next step."""
+        """The waiter gave up (timeout, client gone): the engine drops the request at its next step.  A cancelled head cancels
+        its family."""
         self.cancelled = True
+        if self.family is self:
+            for r in self.members[1:]:
+                r.cancelled = True
 
     def fail(self, error):
-        self.error = error
-        self.done.set()
+        """A head fails with every member that has not finished (refused at submit, a failed prefill, a dead engine)."""
+        for r in (self.members if self.family is self else [self]):
+            if r is self or not r.done.is_set():
+                r.error = error
+                r.done.set()
+        self.settle()
+
+    def settle(self):
+        """After `done` was set: the last member to finish ranks the family (best_of) and sets the head's `family_done`."""
+        head = self.family
+        if head is None or head.family_done.is_set() or not all(r.done.is_set() for r in head.members):
+            return
+        if head.completions is None and len(head.members) <= head.n:
+            head.completions = list(head.members)                # (a remote head that failed before its completions arrived)
+        if head.completions is None:
+            from .logprobs import rank_best_of
+            ok = [r.error is None for r in head.members]
+            order = rank_best_of([r.tokens if g else None for r, g in zip(head.members, ok)],
+                                 [[x["logprob"] for x in r.logprob_records] if g else None for r, g in zip(head.members, ok)],
+                                 head.n, ID_EOS)
+            head.completions = [head.members[j] for j in order]
+        head.family_done.set()
+
+
+def make_family(head, n, m):
+    """Turn a fresh Request into the head of a family of m generated rows, n of them returned: member j is the same request
+    under the seed (s + j) mod 2^64 (a greedy head: m greedy members).  best_of (m > n): every member is scored (N = 0 where
+    the client asked for nothing), `completions` waits for the ranking."""
+    from .parallel import seeds
+    head.family, head.n, head.family_done = head, n, threading.Event()
+    want = head.logprobs if m == n or head.logprobs is not None else 0
+    head.logprobs = want
+    ss = [None] * m if head.sampling is None else seeds(head.sampling[3], m)
+    for j in range(1, m):
+        r = Request(head.inputs, head.max_tokens, None if head.sampling is None else head.sampling[:3] + (ss[j],), head.adapter, want,
+                    head.penalties)
+        r.family, r.asked_logprobs = head, head.asked_logprobs
+        head.members.append(r)
+    head.completions = list(head.members) if m == n else None
+    return head
 
 
 class ContinuousEngine:
@@ -146,18 +194,33 @@ class ContinuousEngine:
         Penalties and logit_bias: `submit(penalty_args(inputs, repetition_penalty=, presence_penalty=, frequency_penalty=,
         logit_bias=), ...)` puts them beside the inputs in the same way -- the request's row then has its logits adjusted by the
         rule of include/p3v.h (p3v_penalty_row_t) before its token is drawn, from its first token on, whoever shares the
-        batch; rows that did not ask pass through bit for bit.  While no active request asks, nothing of it runs."""
+        batch; rows that did not ask pass through bit for bit.  While no active request asks, nothing of it runs.
+        n completions: `submit(n_args(inputs, n, best_of=None), ...)` puts the count beside the inputs in the same way, so the
+        whole family travels to ONE engine.  The handle is then the family's HEAD: `.completions` lists the n returned
+        Requests (head first; under best_of the n best of the m generated, best first, once `.family_done` is set), each with
+        its own tokens / logprob_records / error / done.  The prompt is prefilled once into one free row and forked into m - 1
+        others (model.fork_rows); member j samples under the seed (s + j) mod 2^64.  A family is admitted all or nothing
+        (m free rows, not necessarily adjacent); m > slots fails the handle here.  Without `n_args` nothing changes."""
         try:
             want = _check_logprobs(requested_logprobs(inputs))
             pen = _check_penalties(requested_penalties(inputs), getattr(getattr(self.model, "cfg", None), "vocab_size", None))
             rec = _sampling_row(sampling)
             _check_adapter(adapter, self.adapter_names())
             _check_prefix_args(inputs)
+            n, m = _check_n(requested_n(inputs))
+            if m > 1:
+                why = _family_refusal(m, self.st)
+                if why:
+                    raise ValueError(why)
+                if m > self.slots:
+                    raise ValueError(f"n > slots: a family of {m} completions needs {m} rows at once, this engine has {self.slots} slots")
         except ValueError as e:
             r = Request(inputs, max_tokens)
             r.fail(e)
             return r
         r = Request(inputs, max_tokens, rec, adapter, want, pen)
+        if m > 1:
+            make_family(r, n, m)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -181,17 +244,19 @@ class ContinuousEngine:
             if r.penalties is not None:
                 self.model.clear_penalties(self.st, r.row, 1)    # ... and is not penalised by this one's record
         r.done.set()
+        r.settle()                                               # (the last member of a family sets its head's family_done)
 
     _finish = _release
 
     def _fail_all(self, error):
         with self.lock:
             waiting, self.waiting = list(self.waiting), collections.deque()
-        for r in self._active() + waiting:
+        for r in self._active() + [x for h in waiting for x in h.members]:   # (a waiting head: its whole family)
             r.error = error
             if r.row is not None and self.rows[r.row] is r:
                 self.rows[r.row] = None
             r.done.set()
+            r.settle()
 
     def _recover(self, error):
         """A step raised: fail everybody now, then rebuild the slot state + graph (or die loudly)."""
@@ -219,11 +284,15 @@ class ContinuousEngine:
             ws.view(torch.int32).fill_(-1)
 
     def _pick(self):
-        """FIFO admission with bounded overtaking (under the lock).  Returns (requests to prefill, their free rows)."""
+        """FIFO admission with bounded overtaking (under the lock).  Returns (requests to prefill, their free rows).  The head of
+        a family counts as its m rows, all or nothing: one that fits the column but not the free rows waits under the same
+        patience rule as a request that does not fit the column."""
         st = self.st
         for r in self.waiting:
             if r.cancelled:
-                r.done.set()
+                for x in r.members:
+                    x.done.set()
+                r.settle()
         self.waiting = collections.deque(r for r in self.waiting if not r.cancelled)
         if not self.waiting:
             return [], []
@@ -235,13 +304,15 @@ class ContinuousEngine:
             head = first[0]
             st.offset = max(r.S for r in first if r.S == head.S or r.S + head.max_tokens <= self.window)
         free = [i for i, r in enumerate(self.rows) if r is None]
-        admit, keep, draining = [], collections.deque(), False
+        admit, keep, draining, used = [], collections.deque(), False, 0
         for r in self.waiting:
             fits = r.S <= st.offset and st.offset + r.max_tokens <= self.window
-            if not draining and fits and len(admit) < len(free):
+            need = len(r.members)
+            if not draining and fits and used + need <= len(free):
                 admit.append(r)
+                used += need
                 continue
-            if not fits and not draining:
+            if (not fits or need > 1) and not draining:
                 if r.blocked_at is None:
                     r.blocked_at = self.steps
                 draining = self.steps - r.blocked_at >= self.patience       # nobody newer gets in: the engine drains for r
@@ -313,6 +384,63 @@ class ContinuousEngine:
             if t == ID_EOS or len(r.tokens) >= r.max_tokens:
                 self._release(r)
 
+    def _prefill_family(self, head, rows, busy):
+        """n completions of one prompt: every row gets its records first (adapter, penalties and prompt bits, sampling with its
+        own seed and draw counter 0, log-probability want), the prompt is prefilled ONCE into rows[0] -- with a prefix hit or
+        a capture, as any single request -- and forked into the other rows (model.fork_rows: their K/V columns, position
+        tables and pad_len); then every row's first token is drawn from the ONE prefill logits row under its own record.  The
+        rows need not be adjacent: every setter is called per row."""
+        st, model, members = self.st, self.model, head.members
+        g = model.decode_graph(st)
+        for r, row in zip(members, rows):
+            r.row = row
+        row0, inputs = rows[0], head.inputs
+        hit, head.hit = head.hit, None
+        kw_prefix = {} if hit is None else {"prefix": hit}
+        if self.adapter_names():
+            for row in rows:
+                model.set_row_adapters(st, [head.adapter], row)
+        penalized, sampled, scored = head.penalties is not None, head.sampling is not None, head.logprobs is not None
+        if not penalized and getattr(st, "penalty", None) is not None:
+            for row in rows:
+                model.clear_penalties(st, row, 1)
+        if penalized:
+            from . import penalties as penalties_mod
+            ids2 = np.asarray(inputs["input_ids"]).reshape(1, -1)
+            bias = penalties_mod.bias_table([head.penalties], model.cfg.vocab_size)
+            for row in rows:
+                model.set_penalties(st, penalties_mod.pack([head.penalties]), ids2, row, bias=bias)
+        if sampled or penalized or getattr(st, "sample_rows", None) is not None:
+            for r in members:                                    # (greedy family on a state with records: greedy records, counters reset)
+                model.set_sampling(st, _pack([r.sampling or _GREEDY], counter=0), r.row)
+        if sampled or penalized or scored:
+            toks0, logits = model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
+        else:
+            toks0, logits = model.prefill_slot(st, row0, inputs, **kw_prefix), None
+        model.fork_rows(st, row0, rows[1:], pad=st.offset - head.S)
+        if sampled or penalized:
+            toks = torch.cat([model.sample_logits(st, model.penalized_logits(st, logits, r.row) if penalized else logits, r.row)
+                              for r in members]).reshape(-1)
+        else:
+            toks = toks0.reshape(-1)[:1].expand(len(members))    # greedy: the one arg-max serves every row
+        first = toks.tolist()
+        if min(first) < 0:
+            raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
+        if scored:
+            for r, t in zip(members, toks):
+                model.set_logprobs(st, [r.logprobs], r.row)
+                r.logprob_records.append(_unpack_records(model.logprobs_of(st, logits, t.reshape(1), r.row))[0])
+        if hit is not None:
+            head.cached_tokens = int(hit[1])
+        self._capture([head])                                    # (after the NaN check: a poisoned row is never captured)
+        for r, t in zip(members, first):
+            g["tok"][r.row:r.row + 1].fill_(t)
+            self.rows[r.row] = r
+            self.joined_mid_flight += int(busy)
+            r.tokens.append(t)
+            if t == ID_EOS or len(r.tokens) >= r.max_tokens:
+                self._release(r)
+
     # ---- prompt prefix cache
     def _prefix_key(self, adapter=None):
         """The store key of a row of this engine with that adapter, or None when its cache can neither be captured nor restored
@@ -362,8 +490,25 @@ class ContinuousEngine:
         # requests of nearly equal length that get ADJACENT free rows are prefilled as one left-padded group (one pass over
         # the weights instead of one per request; dist.GROUP_PAD bounds the padding a request may carry)
         from .dist import GROUP_PAD
-        admit.sort(key=lambda r: -r.S)
         free.sort()
+        for head in [r for r in admit if len(r.members) > 1]:   # a family: prefilled alone into its first row, forked into the rest
+            rows, free = free[:len(head.members)], free[len(head.members):]
+            try:
+                self._prefill_family(head, rows, busy)
+            except Exception as e:                              # noqa: BLE001 -- a failed prefill releases every row of the family
+                for x in head.members:
+                    if x.row is not None:
+                        if self.rows[x.row] is x:
+                            self.rows[x.row] = None
+                        self.st.pad_len[x.row:x.row + 1].fill_(self.window)
+                        if getattr(self.st, "logprob_want", None) is not None and x.logprobs is not None:
+                            self.model.set_logprobs(self.st, [-1], x.row)
+                        if getattr(self.st, "penalty", None) is not None and x.penalties is not None:
+                            self.model.clear_penalties(self.st, x.row, 1)
+                    del x.logprob_records[:], x.tokens[:]
+                head.fail(e)
+        admit = [r for r in admit if len(r.members) == 1]
+        admit.sort(key=lambda r: -r.S)
         while admit:
             run = 1
             while run < len(free) and free[run] == free[0] + run:
@@ -472,9 +617,9 @@ class ContinuousEngine:
 
     # ---- convenience: text in, text out (what the HTTP handler calls)
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None):
+                 logprobs=None, penalties=None, n=None, best_of=None):
         return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties)
+                              penalties, n, best_of)
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
@@ -563,6 +708,36 @@ def requested_logprobs(inputs):
     return inputs.get(LOGPROB_ARGS) if isinstance(inputs, dict) else None
 
 
+N_ARGS = "n_completions"            # key of a request's {"n", "best_of"} inside its `inputs` (no model call forwards it)
+
+
+def n_args(inputs, n, best_of=None):
+    """A copy of a B = 1 `processor(...)` result that carries the number of completions asked of it (ContinuousEngine.submit:
+    n in 1..16, best_of None or n..16), beside the inputs as `cache_args` / `logprob_args` / `penalty_args` put theirs -- so a
+    router or a fleet hands the WHOLE family to one engine.  The processor's own result is not touched; `submit` checks the
+    values."""
+    return dict(inputs, **{N_ARGS: {"n": n, "best_of": best_of}})
+
+
+def requested_n(inputs):
+    return inputs.get(N_ARGS) if isinstance(inputs, dict) else None
+
+
+def _check_n(d):
+    """submit's n-args -> (n, m): n returned of m generated; (1, 1) without them.  ValueError names the limit."""
+    from .parallel import check
+    if d is None:
+        return 1, 1
+    if not isinstance(d, dict) or set(d) - {"n", "best_of"}:
+        raise ValueError(f"{N_ARGS} must be what engine.n_args makes")
+    return check(d.get("n", 1), d.get("best_of"))
+
+
+def _family_refusal(m, st):
+    from .parallel import refusal
+    return refusal(m, mlx4=bool(getattr(st, "mlx4", False)))
+
+
 PREFIX_ARGS = "prefix_cache_args"   # key of a request's prefix-cache arguments inside its `inputs` (no model call forwards it)
 
 
@@ -593,10 +768,13 @@ def _check_prefix_args(inputs):
 
 
 def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None, logprobs=None,
-            penalties=None):
+            penalties=None, n=None, best_of=None):
     """submit with only the keywords in use (an engine-like object without them keeps working for plain requests); the prefix-cache
-    arguments, when one of them is in use, ride beside the inputs (`cache_args`), and so does `logprobs` (`logprob_args`)."""
+    arguments, when one of them is in use, ride beside the inputs (`cache_args`), and so do `logprobs` (`logprob_args`) and a
+    family's `n` / `best_of` (`n_args`)."""
     kw = {}
+    if (n, best_of) not in ((None, None), (1, None)):
+        inputs = n_args(inputs, 1 if n is None else n, best_of)
     if image_digests is not None or prefix_len is not None or (cache_prompt is not None and not cache_prompt):
         inputs = cache_args(inputs, image_digests, True if cache_prompt is None else bool(cache_prompt), prefix_len)
     if sampling is not None:
@@ -637,15 +815,24 @@ def has_prefix_cache(engine):
 
 
 def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None,
-                   logprobs=None, penalties=None):
-    """sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt.
+                   logprobs=None, penalties=None, n=None, best_of=None):
+    """n / best_of (one prompt only): n completions of it from one prefill (`n_args`) -- the result is then the list of the n
+    returned texts, info gains "seeds" (one per returned completion, when sampled) and its "logprobs" has one entry per
+    returned completion.
+    sampling: None, or one settings dict per prompt (engine.submit); adapter: None, a name, or one name / None per prompt.
     cache_prompt: None / True (the prompt may be captured by the engine's prefix store) or False.  info: a dict that receives
     "cached_tokens" (one count per prompt) and, when a prompt asked for them, "logprobs" (per prompt: logprobs.entry of its
     records -- token_ids / token_logprobs / ranks / top_logprobs over the tokens of the returned text -- or None).
     logprobs: None, N in 0..8, or one such value per prompt.  penalties: None, one {"repetition_penalty", "presence_penalty",
     "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt."""
     from . import api
+    from .parallel import check, refusal
+    batched = not isinstance(prompts, str) and len(prompts) != 1
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+    fam = check(n, best_of)[1] > 1
+    why = refusal(check(n, best_of)[1], batched=batched)
+    if why:
+        raise ValueError(why)
     images = images if images is not None else [None] * len(prompts)
     if sampling is not None and len(sampling) != len(prompts):
         raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
@@ -661,9 +848,17 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
             digests = image_digests(imgs)
         inputs = processor(text, imgs) if imgs is not None else processor(text)
         reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt,
-                            logprobs=lps[i], penalties=pens[i]))
+                            logprobs=lps[i], penalties=pens[i], **(dict(n=n, best_of=best_of) if fam else {})))
     out, kept = [], []
+    heads = reqs
     try:
+        if fam:                                                 # one prompt: wait for its family, answer with the returned completions
+            head = reqs[0]
+            if not head.family_done.wait(timeout):
+                raise TimeoutError("engine did not finish the request in time")
+            if not head.completions:                            # (a remote family that failed before its completions arrived)
+                raise head.error or RuntimeError("the family returned no completion")
+            reqs, lps = list(head.completions), lps * len(head.completions)
         for r in reqs:
             if not r.done.wait(timeout):
                 raise TimeoutError("engine did not finish the request in time")
@@ -673,14 +868,16 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
             kept.append(ids)
             out.append(processor.tokenizer.decode(ids))
         if info is not None:
-            info["cached_tokens"] = [int(getattr(r, "cached_tokens", 0)) for r in reqs]
+            info["cached_tokens"] = [int(getattr(r, "cached_tokens", 0)) for r in heads]
+            if fam and all(r.sampling is not None for r in reqs):
+                info["seeds"] = [int(r.sampling[3]) for r in reqs]
             if any(w is not None for w in lps):
                 from .logprobs import entry
                 info["logprobs"] = [None if w is None else entry(list(r.logprob_records)[:len(ids_out)])
                                     for w, r, ids_out in zip(lps, reqs, kept)]
     except BaseException:
-        for r in reqs:                                          # nobody is waiting for these any more: free their slots
-            if not r.done.is_set():
+        for r in heads:                                         # nobody is waiting for these any more: free their slots (a head: its family's)
+            if not getattr(r, "family_done", r.done).is_set():
                 r.cancel()
         raise
     return out
@@ -721,6 +918,6 @@ class RegimeRouter:
                 stop_event.wait(idle_sleep)
 
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None):
+                 logprobs=None, penalties=None, n=None, best_of=None):
         return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties)
+                              penalties, n, best_of)

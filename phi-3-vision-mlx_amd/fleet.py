@@ -16,8 +16,8 @@ one receiver thread per source takes them in order).  RCCL is not involved; the 
 import threading
 import time
 
-from .engine import (Request, _check_adapter, _check_logprobs, _check_penalties, _generate_text, _submit, requested_logprobs,
-                     requested_penalties)
+from .engine import (Request, _check_adapter, _check_logprobs, _check_n, _check_penalties, _generate_text, _submit, make_family,
+                     requested_logprobs, requested_n, requested_penalties)
 
 _ERRORS = {"ValueError": ValueError, "TimeoutError": TimeoutError, "TypeError": TypeError}   # what the HTTP handler tells apart
 
@@ -91,11 +91,13 @@ class EngineFleet:
         """Prefix-cache arguments (`engine.cache_args`) travel inside `inputs` to whichever rank takes the request (one store per
         engine; no cache-affinity routing: the least-loaded rank wins as before).  So does `logprobs` (`engine.logprob_args`);
         the records come back with the tokens.  Penalties and logit_bias (`engine.penalty_args`) ride there too; a bad value is
-        refused here, on rank 0."""
+        refused here, on rank 0.  A family of n completions (`engine.n_args`) goes to ONE rank as one request: its engine
+        prefills once and forks; the returned completions come back in one message and fill the head's `completions`."""
         try:
             _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
             logprobs = _check_logprobs(requested_logprobs(inputs))   # nor does a bad N
             _check_penalties(requested_penalties(inputs))        # nor a bad penalty or bias (the vocabulary bound: the rank's engine)
+            n, m = _check_n(requested_n(inputs))                 # nor a bad n / best_of
         except ValueError as e:
             h = Request(inputs, max_tokens)
             h.fail(e)
@@ -110,6 +112,8 @@ class EngineFleet:
                 self.local.append(h)
                 return h
             h = RemoteRequest(inputs, max_tokens, logprobs=logprobs)
+            if m > 1:                                            # the head of a remote family: `completions` arrive with the result
+                h.family, h.n, h.family_done, h.completions = h, n, threading.Event(), None
             h.fleet, h.rank, h.rid = self, dst, self.next_id
             self.next_id += 1
             self.pending[h.rid] = h
@@ -141,10 +145,22 @@ class EngineFleet:
                 continue
             h.tokens = list(tokens)
             h.logprob_records = list(msg[4]) if len(msg) > 4 else []
+            if h.family is h:
+                # the returned completions, in order (tokens, error, records, sampling record): the head stands for the first
+                h.completions = []
+                for i, (toks, cerr, recs, samp) in enumerate(msg[5] if len(msg) > 5 and err is None else []):
+                    c = h if i == 0 else Request(h.inputs, h.max_tokens)
+                    c.tokens, c.logprob_records, c.sampling = list(toks), list(recs), samp
+                    c.error = None if cerr is None else _ERRORS.get(cerr[0], RuntimeError)(f"rank {rank}: {cerr[1]}")
+                    h.completions.append(c)
+                    c.done.set()
+                h.members = list(h.completions) or [h]
             if err is None:
                 h.done.set()
+                h.family_done.set()
             else:
                 h.fail(_ERRORS.get(err[0], RuntimeError)(f"rank {rank}: {err[1]}"))
+                h.family_done.set()
         with self.lock:                                          # the worker is gone: nobody will answer what it still held,
             self.load[rank] = 1 << 30                            # and nothing more goes there
             lost = [h for h in self.pending.values() if h.rank == rank]
@@ -165,9 +181,9 @@ class EngineFleet:
         self.engine.serve_forever(stop_event, idle_sleep)
 
     def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None):
+                 logprobs=None, penalties=None, n=None, best_of=None):
         return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties)
+                              penalties, n, best_of)
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""
@@ -195,14 +211,21 @@ def worker(engine, groups, poll_s=0.002):
     def completions():
         while True:
             with lock:
-                done = [(rid, h) for rid, h in live.items() if h.done.is_set()]
+                done = [(rid, h) for rid, h in live.items() if h.family_done.is_set()]   # (a plain request: its own `done`)
                 for rid, _ in done:
                     del live[rid]
                 idle = not live
             for rid, h in done:
                 err = None if h.error is None else (type(h.error).__name__, str(h.error))
                 recs = list(getattr(h, "logprob_records", None) or [])
-                _send(("done", rid, [int(t) for t in h.tokens], err) + ((recs,) if recs else ()), 0, up)
+                fam = ()
+                if h.family is h and h.completions:
+                    # a family: its RETURNED completions travel in the same message, each with its own error -- as on rank 0, a
+                    # generated member that failed and was not returned (best_of ranks it last) fails nobody
+                    err = None
+                    fam = (recs, [([int(t) for t in c.tokens], None if c.error is None else (type(c.error).__name__, str(c.error)),
+                                   list(c.logprob_records) if c.asked_logprobs is not None else [], c.sampling) for c in h.completions])
+                _send(("done", rid, [int(t) for t in h.tokens], err) + (fam or ((recs,) if recs else ())), 0, up)
             if closing.is_set() and idle and not done:
                 _send(("bye",), 0, up)                            # from THIS thread: the only sender on `up`, so the size / payload
                 return                                           # pairs of two messages can never interleave
@@ -229,7 +252,9 @@ def worker(engine, groups, poll_s=0.002):
     with lock:
         left = list(live.values())
     for h in left:
-        if not h.done.is_set():
-            h.fail(RuntimeError("worker stopped"))
+        if not h.family_done.is_set():                           # (a family: every member still running, whether or not its head is)
+            for r in h.members:
+                if not r.done.is_set():
+                    r.fail(RuntimeError("worker stopped"))
     closing.set()
     reporter.join()

@@ -90,6 +90,29 @@ def result(per_prompt):
     return out
 
 
+def cumulative(token_ids, token_logprobs, eos_id):
+    """One completion's best_of score: the sum of its tokens' RAW-logit log-probabilities through the first `eos_id`
+    (included); what follows an EOS is not text and does not count.  None (a completion without records), an empty list,
+    a NaN or a -inf entry: -inf."""
+    if token_ids is None or token_logprobs is None or len(token_ids) == 0:
+        return -math.inf
+    ids = list(token_ids)
+    stop = ids.index(eos_id) + 1 if eos_id is not None and eos_id in ids else len(ids)
+    lps = list(token_logprobs)[:stop]
+    if len(lps) < stop or any(x is None or math.isnan(x) for x in lps):
+        return -math.inf
+    return float(math.fsum(lps))
+
+
+def rank_best_of(token_ids, token_logprobs, n, eos_id=None):
+    """best_of: the indices of the n completions with the largest `cumulative` score, best first; ties go to the lower
+    index (a stable sort on the negated score).  token_ids / token_logprobs: one list (or None) per generated completion."""
+    scores = [cumulative(i, l, eos_id) for i, l in zip(token_ids, token_logprobs)]
+    if not 1 <= n <= len(scores):
+        raise ValueError(f"best_of: {n} completions out of {len(scores)}")
+    return sorted(range(len(scores)), key=lambda j: -scores[j])[:n]
+
+
 def finite_or_none(x):
     """JSON has no NaN / Infinity: non-finite values travel as null."""
     return float(x) if x is not None and math.isfinite(x) else None

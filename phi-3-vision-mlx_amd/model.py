@@ -820,6 +820,60 @@ class Phi3VModel:
         ops.kv_copy([(src, row, pad, tuple(t.unsqueeze(1) for t in kv), 0, 0, P)])
         return kv
 
+    # ------------------------------------------------------------------ n completions per prompt (include/p3v.h: p3v_kv_fork_t)
+    @_on_device
+    def fork_rows(self, st, src_row, dst_rows, pad=None):
+        """Make rows `dst_rows` of a slot state exact continuations of row `src_row` at st.offset: its K/V columns
+        [pad, st.offset) (ops.kv_fork: one launch, every piece of the source read once), its cos / sin table rows and its
+        pad_len (`pad`: the source row's pad_len where the caller knows it on the host; None reads it back).  K is stored rotated by logical position, so the columns are valid in any row.  NOT copied -- their setters
+        take a row range and the caller sets them: sampling records, the penalty record / `seen` row / bias, the
+        log-probability want-table entry, the row's adapter."""
+        if st.mlx4:
+            raise ValueError('cache_format="mlx4" states are never forked: n > 1 completions need the bf16 or the int8 cache')
+        dst_rows = [int(r) for r in dst_rows]
+        src_row = int(src_row)
+        if not dst_rows:
+            return
+        if not 0 <= src_row < st.B or any(not 0 <= r < st.B for r in dst_rows) or src_row in dst_rows or len(set(dst_rows)) != len(dst_rows):
+            raise ValueError(f"fork_rows: {dst_rows} must be distinct rows of the state's {st.B}, none of them the source row {src_row}")
+        if st.pad_len is None:
+            raise ValueError("fork_rows: a slot state (per-row pad_len and position tables)")
+        kv = self._state_kv(st)
+        pad = int(st.pad_len[src_row].item()) if pad is None else int(pad)
+        if not 0 <= pad <= st.Tp:
+            raise ValueError(f"fork_rows: pad {pad} is outside the state's {st.Tp} columns")
+        idx = torch.tensor(dst_rows, dtype=torch.int64, device=self.device)
+        for i in range(0, len(dst_rows), ops.L.KV_FORK_MAX_DST):
+            ops.kv_fork(kv, src_row, pad, kv, dst_rows[i:i + ops.L.KV_FORK_MAX_DST], pad, max(st.offset - pad, 0))
+        st.cos.index_copy_(0, idx, st.cos[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
+        st.sin.index_copy_(0, idx, st.sin[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
+        st.pad_len.index_fill_(0, idx, pad)
+
+    @_on_device
+    def fork_state(self, st1, n):
+        """The B = 1 state of a finished prefill as a NEW B = n state of the same geometry whose n rows all continue that
+        prompt (api._generate(n=...)): another allocation, K/V columns [0, offset) through ONE ops.kv_fork launch with n
+        destination rows, position tables and pad_len replicated, offset and epoch carried over, captures not.  Returns the
+        new state's cache list; the B = 1 state is left as it was (the caller drops it: n + 1 copies of the prompt are held
+        only between this call's two ends)."""
+        n = int(n)
+        if st1.B != 1 or not 1 <= n <= ops.L.KV_FORK_MAX_DST + 1:
+            raise ValueError(f"fork_state: a B = 1 state into 1..{ops.L.KV_FORK_MAX_DST + 1} rows, got B = {st1.B}, n = {n}")
+        if st1.mlx4:
+            raise ValueError('cache_format="mlx4" states are never forked: n > 1 completions need the bf16 or the int8 cache')
+        st = CacheState(self.cfg, n, st1.S, st1.T - st1.S, self.device)
+        assert (st.T, st.Tp) == (st1.T, st1.Tp)
+        self._states.add(st)
+        src, dst = self._state_kv(st1), self._state_kv(st)
+        rows = list(range(n))
+        ops.kv_fork(src, 0, 0, dst, rows[:ops.L.KV_FORK_MAX_DST], 0, st1.offset)
+        if n > ops.L.KV_FORK_MAX_DST:                            # the 16th row: a second launch
+            ops.kv_fork(src, 0, 0, dst, rows[ops.L.KV_FORK_MAX_DST:], 0, st1.offset)
+        st.cos, st.sin = st1.cos.expand(n, -1, -1).contiguous(), st1.sin.expand(n, -1, -1).contiguous()
+        st.pad_len = None if st1.pad_len is None else st1.pad_len.expand(n).contiguous()
+        st.offset, st.epoch, st.serving = st1.offset, st1.epoch, st1.serving
+        return [LayerCache(st, i) for i in range(self.cfg.num_hidden_layers)]
+
     @_on_device
     def decode_graph(self, st):
         """The captured greedy step of a state (built on first use): its `tok` / `next_tok` / `d_past` device buffers."""

@@ -596,6 +596,49 @@ def kv_copy(jobs):
     L.check(L.lib().p3v_kv_copy(recs, len(jobs), nl, nkv, hd, 2 if dt == BF16 else 1, _stream()), "kv_copy")
 
 
+def _kv_side(side, what):
+    """(nl, B, nkv, T, hd, dtype) of one side of a KV move: (k, vt) bf16 or (k8, v8t, k_scale, v_scale)."""
+    if len(side) not in (2, 4):
+        raise ValueError(f"{what}: a cache is (k, vt) or (k8, v8t, k_scale, v_scale)")
+    dt = side[0].dtype
+    if dt not in (BF16, torch.uint8) or (dt == BF16) != (len(side) == 2):
+        raise TypeError(f"{what}: bf16 (k, vt) or uint8 codes with scales, got {dt} with {len(side)} tensors")
+    _chk(side[0], dt, "k"), _chk(side[1], dt, "vt")
+    nl, B, nkv, T, hd = side[0].shape
+    if tuple(side[1].shape) != (nl, B, nkv, hd, T):
+        raise ValueError(f"{what}: V^T must be [nl, B, nkv, hd, T] of its K [nl, B, nkv, T, hd]")
+    for sc in side[2:]:
+        _chk(sc, F32, "scale")
+        if tuple(sc.shape) != (nl, B, nkv, T):
+            raise ValueError(f"{what}: scale rows must be [nl, B, nkv, T]")
+    return nl, B, nkv, T, hd, dt
+
+
+def kv_fork(src, b_src, t0_src, dst, b_dst, t0_dst, n_tok):
+    """n completions of one prompt (p3v_kv_fork): tokens [t0_src, +n_tok) of batch row b_src of `src` go to tokens
+    [t0_dst, +n_tok) of EVERY row in `b_dst` (1..KV_FORK_MAX_DST distinct rows) of `dst`, all layers and heads in one launch;
+    each piece of the source is read once.  src / dst as in `kv_copy`; `dst` may be `src` itself (rows of one state, none
+    of them b_src).  Equal 16-byte phase of the two runs only: anything else raises (kv_copy takes any phase pair)."""
+    b_dst = [int(b) for b in b_dst]
+    if not 1 <= len(b_dst) <= L.KV_FORK_MAX_DST:
+        raise ValueError(f"kv_fork: 1..{L.KV_FORK_MAX_DST} destination rows per launch, got {len(b_dst)}")
+    if len(src) != len(dst):
+        raise ValueError("kv_fork: the same kind of cache on both sides")
+    nl, B_s, nkv, T_s, hd, dt = _kv_side(src, "kv_fork")
+    g = _kv_side(dst, "kv_fork")
+    if (g[0], g[2], g[4], g[5]) != (nl, nkv, hd, dt):
+        raise ValueError("kv_fork: both caches have the same layers, heads, head size and element type")
+    rec = L.KvFork()
+    rec.k_src, rec.v_src, rec.k_dst, rec.v_dst = _p(src[0]), _p(src[1]), _p(dst[0]), _p(dst[1])
+    if len(src) == 4:
+        rec.ks_src, rec.vs_src, rec.ks_dst, rec.vs_dst = _p(src[2]), _p(src[3]), _p(dst[2]), _p(dst[3])
+    rec.B_src, rec.b_src, rec.T_src, rec.t0_src = B_s, int(b_src), T_s, int(t0_src)
+    rec.B_dst, rec.T_dst, rec.t0_dst, rec.n_tok, rec.n_dst = g[1], g[3], int(t0_dst), int(n_tok), len(b_dst)
+    for i, b in enumerate(b_dst):
+        rec.b_dst[i] = b
+    L.check(L.lib().p3v_kv_fork(rec, nl, nkv, hd, 2 if dt == BF16 else 1, _stream()), "kv_fork")
+
+
 def attention_decode_q8(qkv, cos_new, sin_new, rope_bstride, k8, v8t, k_scale, v_scale, out, B, Lq, nh, nkv, hd, scale, past,
                         cache_t, ws, n_split, pad_len=None, d_past=None, merge_in_launch=False, o_proj_w8=None, o_proj_scale=None,
                         o_proj_x=None, o_rearm=None):

@@ -28,6 +28,13 @@
      of include/p3v.h (p3v_penalty_row_t) on each step's logits before temperature / top-k / top-p.  "logprobs" stay those of
      the raw logits.  A bad value -> 400 with the reason; so does an explicit "speculate" > 0 next to them, and the
      batch-sharded path.  Honoured on the one-request, the merged and the --continuous path; merged requests keep their own.)
+    (extension: "n": 1 .. 16 completions of ONE prompt (a string), and "best_of": n .. 16 -- the prompt is prefilled once, its
+     K/V forked into the other rows (include/p3v.h: p3v_kv_fork_t), and "responses" has n entries; "best_of" generates that many
+     and returns the n with the largest cumulative raw-logit log-probability, best first.  A sampled request's "seeds" has
+     one entry per response -- completion j of seed s runs under (s + j) mod 2^64 -- and posting a returned seed alone with
+     "n": 1 reproduces its text; "logprobs" has one object per response.  At temperature 0 the n responses are equal.  A bad
+     value, a list of prompts with n > 1, a server started with --merge, or an explicit "speculate" > 0 beside n > 1 -> 400
+     with the reason.  Served by the one-request path and by --continuous; without "n" a response is byte for byte today's.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -60,10 +67,12 @@ MODEL_NAME = "phi-3-vision"
 
 
 class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs", "penalties")
+    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs", "penalties",
+                 "n", "best_of")
 
     def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
-                 penalties=None):
+                 penalties=None, n=None, best_of=None):
+        self.n, self.best_of = n, best_of       # None, or a family: n completions of the one prompt (never merged)
         self.logprobs = logprobs                # None, or one N per prompt
         self.penalties = penalties              # None, or one penalty dict per prompt
         self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
@@ -162,6 +171,24 @@ def parse_logprobs(request, n_prompts):
         raise ValueError(f"logprobs must be a single integer 0 .. 8 (or null), got {type(v).__name__}")
     want = check(v)
     return None if want == OFF else [want] * n_prompts
+
+
+def parse_n(request, prompts, engine, speculate_explicit=False):
+    """The "n" and "best_of" fields of a request body -> None (absent, or n = 1 without best_of > 1: today's request) or
+    (n, best_of).  ValueError (-> 400) naming the limit on a bad type or range, and for more than one completion wherever a
+    family does not run: a list of prompts, the merging queue, an explicit "speculate" > 0."""
+    from .parallel import check, refusal
+    if request.get("n") is None and request.get("best_of") is None:
+        return None
+    n, m = check(request.get("n", 1), request.get("best_of"))
+    if m <= 1:
+        return None
+    why = refusal(m, batched=len(prompts) != 1 or isinstance(request.get("prompt"), list), speculate=speculate_explicit)
+    if why is None and getattr(engine, "merge", False):
+        why = "n > 1: not on a server started with --merge (a family is one prompt's rows, never merged with other requests)"
+    if why:
+        raise ValueError(why)
+    return n, request.get("best_of")
 
 
 PENALTY_BAN = -1e30                             # a logit_bias at or below this bans the token (JSON has no -Infinity)
@@ -339,9 +366,9 @@ class EngineQueue:
         self.thread.start()
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
-               penalties=None):
+               penalties=None, n=None, best_of=None):
         job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info, logprobs,
-                   penalties)
+                   penalties, n, best_of)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -364,7 +391,7 @@ class EngineQueue:
         """merge=False: `first` alone.  merge=True: plus every queued job with the same max_tokens that fits and keeps the
         RoPE regime of each member unchanged, waiting at most `window_s` for stragglers."""
         group, n, held = [first], len(first.prompts), []
-        if not self.merge or first.images is not None or first.adapter is not None:   # image / adapter requests are never merged
+        if not self.merge or first.images is not None or first.adapter is not None or first.n is not None:   # image / adapter requests and families are never merged
             return group
         regime = self._regime(first.prompts, first.max_tokens)
         while n < self.max_batch:
@@ -375,7 +402,7 @@ class EngineQueue:
             if job is None:
                 self.jobs.put(None)
                 break
-            if job.images is None and job.adapter is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
+            if job.n is None and job.images is None and job.adapter is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
                     and self._regime(job.prompts, job.max_tokens) == regime and (job.sampling is None) == (first.sampling is None):
                 group.append(job)
                 n += len(job.prompts)
@@ -403,7 +430,18 @@ class EngineQueue:
                     kw.update(logprobs=[w for j in group for w in (j.logprobs or [None] * len(j.prompts))], logprob_info=lp_info)
                 if any(j.penalties is not None for j in group):  # every row keeps its own request's penalties (None: none)
                     kw["penalties"] = [d for j in group for d in (j.penalties or [None] * len(j.prompts))]
-                if first.speculate:                             # (one prompt, never merged: self.speculate excludes merge)
+                if first.n is not None:                         # a family: ONE prompt, n texts back (one prefill, forked)
+                    fam = {}
+                    if first.sampling is not None:
+                        kw["sampling"] = first.sampling
+                    out = self.generate_fn(flat, first.max_tokens, first.images, n=first.n, best_of=first.best_of, family_info=fam, **kw)
+                    if first.info is not None and first.sampling is not None:
+                        first.info["seeds"] = [int(x) for x in fam.get("seeds", [])]
+                    out = [out] if isinstance(out, str) else list(out)
+                    if len(out) != first.n:
+                        raise RuntimeError(f"generate returned {len(out)} texts for n = {first.n}")
+                    flat = out                                  # (one result per completion from here on)
+                elif first.speculate:                           # (one prompt, never merged: self.speculate excludes merge)
                     stats = {}
                     out = self.generate_fn(flat, first.max_tokens, first.images, speculate=first.speculate, spec_info=stats, **kw)
                     if first.info is not None:
@@ -422,11 +460,12 @@ class EngineQueue:
                 self.batches.append(len(flat))
                 i = 0
                 for j in group:
-                    j.result = out[i:i + len(j.prompts)]
+                    k = len(j.prompts) if j.n is None else j.n  # (a family: its one prompt has n results)
+                    j.result = out[i:i + k]
                     if j.logprobs is not None and j.info is not None:
-                        j.info["logprobs"] = [None if lp_info["token_ids"][b] is None else {k: lp_info[k][b] for k in lp_info}
-                                              for b in range(i, i + len(j.prompts))]
-                    i += len(j.prompts)
+                        j.info["logprobs"] = [None if lp_info["token_ids"][b] is None else {k_: lp_info[k_][b] for k_ in lp_info}
+                                              for b in range(i, i + k)]
+                    i += k
             except Exception as e:              # noqa: BLE001 -- reported to every waiting request
                 for j in group:
                     j.error = e
@@ -477,9 +516,12 @@ def make_handler(engine, image_policy=None):
                 adapter = parse_adapter(request, len(prompts), known_adapters(engine))
                 cache_prompt = parse_cache_prompt(request)
                 speculate = parse_speculate(request, len(prompts), engine, sampling)
+                family = parse_n(request, prompts, engine, bool(speculate) and "speculate" in request)
+                if family is not None:
+                    speculate = 0                               # (the server-wide default steps aside)
                 logprobs = parse_logprobs(request, len(prompts))
                 penalties = parse_penalties(request, len(prompts), vocab_of(engine))
-                sharded = getattr(engine, "sharded_fn", None)
+                sharded = None if family is not None else getattr(engine, "sharded_fn", None)   # (a family runs api.generate, images too)
                 if penalties is not None and speculate:
                     if "speculate" in request:
                         raise ValueError("penalties and logit_bias are not available under speculative decoding (a verify step "
@@ -512,7 +554,14 @@ def make_handler(engine, image_policy=None):
                 return
             info = None
             try:
-                if logprobs is not None or penalties is not None:
+                if family is not None:
+                    info = {}
+                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("logprobs", logprobs),
+                                            ("penalties", penalties)) if v is not None}
+                    if prefix_counters(engine) is not None and cache_prompt is not None:
+                        kw["cache_prompt"] = cache_prompt
+                    responses = engine.submit(prompts, max_tokens, images, info=info, n=family[0], best_of=family[1], **kw)
+                elif logprobs is not None or penalties is not None:
                     kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("logprobs", logprobs),
                                             ("penalties", penalties)) if v is not None}
                     if logprobs is not None or prefix_counters(engine) is not None:
@@ -540,15 +589,15 @@ def make_handler(engine, image_policy=None):
                 return
             out = {"model": MODEL_NAME, "responses": responses}
             if sampling is not None:
-                out["seeds"] = [r["seed"] for r in sampling]
+                out["seeds"] = [r["seed"] for r in sampling] if family is None else list(info.get("seeds", []))
             if speculate:
                 out["speculation"] = info.get("speculation", {"steps": 0, "drafted": 0, "accepted": 0})
-            elif info is not None and (logprobs is None or prefix_counters(engine) is not None):
+            elif info is not None and (prefix_counters(engine) is not None or (logprobs is None and family is None)):
                 out["cached_tokens"] = list(info.get("cached_tokens", [0] * len(prompts)))
             if logprobs is not None:
                 from .api import ID_EOS
                 decode = token_decoder(engine)
-                out["logprobs"] = [format_logprobs(e, decode, ID_EOS) for e in info.get("logprobs") or [None] * len(prompts)]
+                out["logprobs"] = [format_logprobs(e, decode, ID_EOS) for e in info.get("logprobs") or [None] * len(responses)]
             self._send(200, out)
 
         def log_message(self, *args):           # quiet
@@ -598,9 +647,12 @@ class ContinuousBackend:
         return counters
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None,
-               penalties=None):
+               penalties=None, n=None, best_of=None):
         mt = max(1, min(int(max_tokens), self.max_tokens_cap))
         kw = {} if adapter is None else {"adapter": adapter}
+        if n is not None:                                        # a family: one prompt (a string for the engine), n texts back
+            kw.update(n=n, best_of=best_of)
+            prompts = prompts[0] if not isinstance(prompts, str) and len(prompts) == 1 else prompts
         if logprobs is not None:
             kw["logprobs"] = logprobs
         if penalties is not None:
@@ -668,8 +720,18 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return images is not None or (dist.is_available() and dist.is_initialized())
 
     def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
-                    logprob_info=None, penalties=None):
+                    logprob_info=None, penalties=None, n=None, best_of=None, family_info=None):
         import torch.distributed as dist
+        if n is not None:                                            # a family: one prompt (image or not), prefilled once, n texts
+            kw = {} if sampling is None else {f: sampling[0][f] for f in SAMPLING_FIELDS}
+            if penalties is not None and penalties[0] is not None:
+                kw.update({f: penalties[0][f] for f in penalties[0] if penalties[0].get(f) is not None})
+            if logprobs is not None:
+                kw.update(logprobs=logprobs[0], logprob_info=logprob_info)
+            if adapter is not None:
+                kw["adapter"] = adapter[0]
+            return generate(prompts[0], images=None if images is None else images[0], preload=preload, max_tokens=max_tokens, verbose=False,
+                            n=n, best_of=best_of, family_info=family_info, **kw)
         if speculate:                                                # (one prompt, greedy, no image: the handler saw to it)
             return generate(prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, speculate=speculate, spec_info=spec_info,
                             **({} if adapter is None else {"adapter": adapter[0]}))
