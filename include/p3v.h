@@ -308,6 +308,38 @@ int p3v_attention_decode_can_fuse_oproj(int B, int L, int n_heads, int hd, int n
  * one tile-only workgroup, projection units ride on the last workgroup of every other CU.  Returns P3V_ERR_UNSUPPORTED for shapes
  * the placement does not cover (the launch then uses the (split, head) grid).  Host-only, no GPU needed: tests/test_abi.py. */
 int p3v_attention_decode_fused_role(int wg, int n_heads, int n_split, int o_n, int map, int* out4);
+/* ---- shared-prefix decode attention: p3v_attention_decode for L == 1 on the bf16 cache, plus a FAMILY TABLE that names the rows
+ * whose caches are identical up to a column (the rows p3v_kv_fork filled from one prefill).  The prompt keys of a family are read
+ * once, from its leader's cache, for all of its members; `out` and the caches come out bit for bit as with a table of single rows.
+ * `family`: DEVICE memory, int32 [B, P3V_FAMILY_INTS], read by the kernel when it runs (a captured launch follows a rewritten table).
+ * Row b = {lead, share_end, member[P3V_FAMILY_MAX]}:
+ *   lead       the row whose cache the shared keys are read from; lead == b for a leader and for a single row;
+ *   share_end  caches of the family are identical in columns [pad, share_end); share_end <= past; the same on every row of a family
+ *              (0 on a single row);
+ *   member[]   on a leader's row: the rows of its family, the leader included, each once, in any order, unused entries -1.
+ *              Ignored on a follower's row.  A single row lists itself or nothing.
+ * With chunk = round_up_64(ceil(cache_t / n_split)), the launcher's keys per split, split s of row b is SHARED iff b's family has
+ * at least two members and (s + 1) * chunk <= share_end.  A shared split is computed by the leader's workgroup alone: keys from the
+ * leader's cache, member j's own rotated query and own pad_len[member j], member j's partial written to ITS workspace record; the
+ * followers' workgroups of that split fetch nothing and write nothing.  Every other split -- the one that contains share_end, all
+ * later ones, all splits of single rows -- runs as in p3v_attention_decode: own cache, own new position appended at `past`.
+ * So for a FOLLOWER columns [0, floor(share_end / chunk) * chunk) of its own cache are dead positions in the sense above: they must
+ * hold finite values, and the output does not depend on them.  Nothing outside column `past` of the caches is written.
+ * Same arguments, workspace and sentinel rule as p3v_attention_decode; the partials are merged by its merge launch.
+ * P3V_ERR_UNSUPPORTED, nothing written, nothing launched: L != 1, hd != 96, a non-null o_proj_w, merge_in_launch != 0, and -- read
+ * from `family_host`, the HOST's copy of the table, when it is not NULL -- a lead or a member outside [0, B), more than
+ * P3V_FAMILY_MAX rows naming one leader, a share_end beyond `past` when d_past is NULL.  P3V_ERR_ARG for a host copy that
+ * contradicts itself (a leader that follows another row, a row missing from or twice in its leader's list, a listed row that names
+ * another leader, two share_end in one family) and for null / misaligned pointers.  family_host == NULL skips those checks (a
+ * table the host has validated before, e.g. while a step is being captured); the kernel then still reads no row outside [0, B): an
+ * entry out of range names nobody, and share_end counts up to `past` at most.
+ * An unvalidated table that contradicts itself (a follower its leader does not list, a leader with one member, ...) yields
+ * UNDEFINED OUTPUT for the rows involved -- typically NaN: the follower's workspace record stays at the sentinel -- and nothing worse.
+ * (tests/test_attn_family_gpu.py pins out / cache bit equality against the all-singles table and the unread follower columns.) */
+#define P3V_FAMILY_MAX 16                       /* members of one family: P3V_KV_FORK_MAX_DST + the source row */
+#define P3V_FAMILY_INTS (2 + P3V_FAMILY_MAX)
+int p3v_attention_decode_family(const p3v_attn_decode_args_t* args /* host */, const int32_t* family /* device */,
+                                const int32_t* family_host /* host or NULL */, void* stream);
 /* cos/sin rows of positions [past, past+L) of each batch row ([B, tab_t, half] tables) -> [B, L, half] */
 int p3v_stage_rope(const float* cos_t, const float* sin_t, int past, const int32_t* d_past,
                    float* cos_out, float* sin_out, int B, int L, int tab_t, int half_dim, void* stream);

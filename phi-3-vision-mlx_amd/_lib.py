@@ -130,6 +130,7 @@ class KvCopyJob(C.Structure):
 
 
 KV_FORK_MAX_DST = 15                             # P3V_KV_FORK_MAX_DST
+FAMILY_MAX, FAMILY_INTS = 16, 18                 # P3V_FAMILY_MAX, P3V_FAMILY_INTS: rows of p3v_attention_decode_family's table
 
 
 class KvFork(C.Structure):
@@ -184,6 +185,7 @@ SIGNATURES = {
     "p3v_attention": (i32, [C.POINTER(AttnArgs), vp]),
     "p3v_attention_decode": (i32, [C.POINTER(AttnDecArgs), vp]),
     "p3v_attention_decode_can_fuse_oproj": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "p3v_attention_decode_family": (i32, [C.POINTER(AttnDecArgs), vp, vp, vp]),          # added after round 6, no version change
     "p3v_attention_decode_fused_role": (i32, [i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "p3v_kv_quantize": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "p3v_kv_dequantize": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -579,7 +579,7 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
               speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
-              frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None):
+              frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None, share_prefix=False):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -604,10 +604,18 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     best_of=m (n <= m <= 16): m completions are generated and the n with the largest cumulative raw-logit log-probability
     through the first EOS are returned, best first, ties to the lower index (logprobs.rank_best_of); logprob_info then
     describes the n returned ones, and family_info (a dict) receives "chosen" (their indices among the m) and "seeds".
-    n == 1 without best_of (or best_of 1) is today's path, launch for launch."""
+    n == 1 without best_of (or best_of 1) is today's path, launch for launch.
+    share_prefix=True (bf16 KV cache): the m rows of the family are registered as one (model.fork_state(share=True)) and every
+    decode step reads the prompt's K/V once for all of them (include/p3v.h: p3v_attention_decode_family) instead of m times;
+    the copies are made all the same.  On a bf16 cache without a family (n == 1, no best_of) it is accepted and does nothing; on a model whose
+    cache is int8 or mlx4 it raises whatever n is (the option cannot be honoured there, and says so before anything runs).  False -- the default -- allocates, launches and captures nothing that was not there before."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     n, fam = parallel_mod.check(n, best_of)
+    if share_prefix:
+        why = model.family_refusal() if hasattr(model, "family_refusal") else "share_prefix needs the device model (this model class has no family table)"
+        if why:
+            raise ValueError(why)
     if fam > 1:                                                 # (n == 1: the model is not asked anything here)
         cfg_ = getattr(model, "cfg", None)
         why = parallel_mod.refusal(fam, isinstance(prompt, list), speculate,
@@ -657,7 +665,7 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     if fam:
         # ONE prefill behind us: its state forked into `fam` rows (another allocation; the B = 1 state is dropped here), its
         # one logits row repeated -- every row's draw 0 reads it under the row's own record
-        cache = model.fork_state(cache[0].state, fam)
+        cache = model.fork_state(cache[0].state, fam, **({"share": True} if share_prefix else {}))
         if adapter is not None:
             model.set_row_adapters(cache[0].state, [adapter] * fam)
         logits = logits[:, -1:, :].expand(fam, -1, -1).contiguous()
@@ -727,13 +735,15 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
              use_adapter=False, max_tokens=512, verbose=True, return_tps=False, early_stop=False, stream=True,
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
              prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
-             presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None):
+             presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None,
+             share_prefix=False):
     """reference phi_3_vision_mlx.py:1324-1374, plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
     strings, see `_generate`), plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
     log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`) and the penalties on tokens already seen
-    (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`."""
+    (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`, and
+    `share_prefix` (the n rows of a family read their prompt's K/V once per decode step, see `_generate`)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     n, fam = parallel_mod.check(n, best_of)                      # before a model is loaded or run
@@ -752,7 +762,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
                      top_k=top_k, top_p=top_p, seed=seed, adapter=adapter, prefix_cache=prefix_cache, speculate=speculate,
                      spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info, repetition_penalty=repetition_penalty,
                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
-                     **({} if (n, best_of, family_info) == (1, None, None) else dict(n=n, best_of=best_of, family_info=family_info)))
+                     **({} if (n, best_of, family_info) == (1, None, None) else dict(n=n, best_of=best_of, family_info=family_info)),
+                     **({"share_prefix": True} if share_prefix else {}))
 
 
 # ----------------------------------------------------------------------------- score

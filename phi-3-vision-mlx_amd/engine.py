@@ -143,8 +143,16 @@ def make_family(head, n, m):
 
 
 class ContinuousEngine:
-    def __init__(self, model, processor, slots=8, window=ROPE_WINDOW, patience=64, prefix_cache=None):
+    def __init__(self, model, processor, slots=8, window=ROPE_WINDOW, patience=64, prefix_cache=None, share_prefix=False):
         self.model, self.processor, self.slots, self.window, self.patience = model, processor, slots, window, patience
+        # share_prefix: the rows of a family (n_args) read their prompt's K/V once per decode step (model.set_families); off --
+        # the default -- nothing of it is allocated, launched or captured
+        self.share_prefix = bool(share_prefix)
+        if self.share_prefix:
+            why = model.family_refusal() if hasattr(model, "family_refusal") else None
+            if why:
+                raise ValueError(why)
+        self.families = []                                       # [(rows, share_end)], leader first: what the state's table holds
         self.prefix_cache = prefix_cache                         # prefix.PrefixCache or None (off: every path as without the feature)
         self.long_rope = window > ROPE_WINDOW
         self.rows = [None] * slots                               # row -> active Request
@@ -161,6 +169,9 @@ class ContinuousEngine:
         self.model.serving = True                               # (the owner is a server: model.py)
         self.st.serving = True                                  # long-lived: the split-KV merge must not lean on dispatch order (model._split_plan)
         self.cache = [type("L", (), {"state": self.st})()]      # greedy_step reads cache[0].state
+        self.families = []
+        if self.share_prefix:                                   # the table BEFORE the step is captured: the capture then follows it
+            self.model.set_families(self.st, [], create=True)
 
     # ---- request side (any thread)
     def accepts(self, S, max_tokens):
@@ -235,8 +246,18 @@ class ContinuousEngine:
     def _active(self):
         return [r for r in self.rows if r is not None]
 
+    def _leave_family(self, rows):
+        """Rows stop being members BEFORE anything may rewrite them (a refill, a scrub, a rewound column): no table entry names
+        a freed row as `lead`.  A leader that leaves hands over to the next member, a family of one is cleared."""
+        from .parallel import families_without
+        rows = [r for r in rows if r is not None]
+        if self.share_prefix and any(r in members for members, _ in self.families for r in rows):
+            self.families = families_without(self.families, rows)
+            self.model.set_families(self.st, self.families)
+
     def _release(self, r):
         if r.row is not None and self.rows[r.row] is r:
+            self._leave_family([r.row])
             self.rows[r.row] = None
             self.st.pad_len[r.row:r.row + 1].fill_(self.window)  # every key masked: the row idles at zero cost of correctness
             if r.logprobs is not None:
@@ -257,6 +278,7 @@ class ContinuousEngine:
                 self.rows[r.row] = None
             r.done.set()
             r.settle()
+        self.families = []                                       # (the state is rebuilt, or the engine is down)
 
     def _recover(self, error):
         """A step raised: fail everybody now, then rebuild the slot state + graph (or die loudly)."""
@@ -418,6 +440,10 @@ class ContinuousEngine:
         else:
             toks0, logits = model.prefill_slot(st, row0, inputs, **kw_prefix), None
         model.fork_rows(st, row0, rows[1:], pad=st.offset - head.S)
+        if self.share_prefix:                                   # columns [pad, offset) of the rows are identical from here on
+            from .parallel import families_without
+            self.families = families_without(self.families, rows) + [(tuple(rows), int(st.offset))]
+            model.set_families(st, self.families)
         if sampled or penalized:
             toks = torch.cat([model.sample_logits(st, model.penalized_logits(st, logits, r.row) if penalized else logits, r.row)
                               for r in members]).reshape(-1)
@@ -496,6 +522,7 @@ class ContinuousEngine:
             try:
                 self._prefill_family(head, rows, busy)
             except Exception as e:                              # noqa: BLE001 -- a failed prefill releases every row of the family
+                self._leave_family([x.row for x in head.members])
                 for x in head.members:
                     if x.row is not None:
                         if self.rows[x.row] is x:

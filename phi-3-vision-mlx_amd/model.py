@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .parallel import families_without, family_pays, family_table
 from .config import head_dim, is_vision, rope_scaling_factor
 from .weights import Q4Weight, mlx_quantize, q4_repack
 from .ops import (BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_QGELU, EPI_BIAS_RESID_F32, EPI_NONE, EPI_PATCH,
@@ -112,6 +113,11 @@ class CacheState:
         self.fresh_rows = False                                 # a rows_view whose columns left of its offset hold nothing its rows may see
         self.row_adapter = None                                 # adapter bank: int32 [B] slot per row, made on first use (model._state_rows)
         self.sample_rows = None                                 # sampling records int32 [B, 6] (model.set_sampling)
+        # shared-prefix decode (model.set_families): the device table int32 [B, 18] of ops.attention_decode_family, made on first
+        # use -- from then on the state's L = 1 steps take that launch, whatever the table holds --, the host's copy of it and the
+        # families it was built from [(rows, share_end)]
+        self.family = self.family_host = None
+        self.families = []
 
     @property
     def logprob_want(self):
@@ -140,6 +146,8 @@ class CacheState:
         view.serving = False
         view.row_adapter = None
         view.sample_rows = None
+        view.family = view.family_host = None                   # (the table is the whole state's: a view's rows are single rows)
+        view.families = []
         view.mlx4 = False                                       # (the view carries k / v alone, never the 4-bit prompt codes)
         view.cos = self.cos[rows]
         view.sin = self.sin[rows]
@@ -822,12 +830,14 @@ class Phi3VModel:
 
     # ------------------------------------------------------------------ n completions per prompt (include/p3v.h: p3v_kv_fork_t)
     @_on_device
-    def fork_rows(self, st, src_row, dst_rows, pad=None):
+    def fork_rows(self, st, src_row, dst_rows, pad=None, share=False):
         """Make rows `dst_rows` of a slot state exact continuations of row `src_row` at st.offset: its K/V columns
         [pad, st.offset) (ops.kv_fork: one launch, every piece of the source read once), its cos / sin table rows and its
         pad_len (`pad`: the source row's pad_len where the caller knows it on the host; None reads it back).  K is stored rotated by logical position, so the columns are valid in any row.  NOT copied -- their setters
         take a row range and the caller sets them: sampling records, the penalty record / `seen` row / bias, the
-        log-probability want-table entry, the row's adapter."""
+        log-probability want-table entry, the row's adapter.
+        share: also register the source and destination rows as a family that shares columns [pad, st.offset)
+        (`set_families`; the rows leave whatever family they were in).  The copies are made all the same."""
         if st.mlx4:
             raise ValueError('cache_format="mlx4" states are never forked: n > 1 completions need the bf16 or the int8 cache')
         dst_rows = [int(r) for r in dst_rows]
@@ -848,14 +858,19 @@ class Phi3VModel:
         st.cos.index_copy_(0, idx, st.cos[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
         st.sin.index_copy_(0, idx, st.sin[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
         st.pad_len.index_fill_(0, idx, pad)
+        if share:
+            rows = (src_row, *dst_rows)
+            self.set_families(st, families_without(st.families, rows) + [(rows, st.offset)])
 
     @_on_device
-    def fork_state(self, st1, n):
+    def fork_state(self, st1, n, share=False):
         """The B = 1 state of a finished prefill as a NEW B = n state of the same geometry whose n rows all continue that
         prompt (api._generate(n=...)): another allocation, K/V columns [0, offset) through ONE ops.kv_fork launch with n
         destination rows, position tables and pad_len replicated, offset and epoch carried over, captures not.  Returns the
         new state's cache list; the B = 1 state is left as it was (the caller drops it: n + 1 copies of the prompt are held
-        only between this call's two ends)."""
+        only between this call's two ends).  share: the n rows are registered as one family sharing columns [0, offset)
+        (`set_families`): decode steps of the new state read the prompt's K/V once -- where that pays (parallel.family_pays);
+        a smaller family gets the plain state."""
         n = int(n)
         if st1.B != 1 or not 1 <= n <= ops.L.KV_FORK_MAX_DST + 1:
             raise ValueError(f"fork_state: a B = 1 state into 1..{ops.L.KV_FORK_MAX_DST + 1} rows, got B = {st1.B}, n = {n}")
@@ -872,7 +887,53 @@ class Phi3VModel:
         st.cos, st.sin = st1.cos.expand(n, -1, -1).contiguous(), st1.sin.expand(n, -1, -1).contiguous()
         st.pad_len = None if st1.pad_len is None else st1.pad_len.expand(n).contiguous()
         st.offset, st.epoch, st.serving = st1.offset, st1.epoch, st1.serving
+        if share and family_pays(n, st.offset):                 # (below the break-even the state has no table: the plain plan)
+            self.set_families(st, [(tuple(rows), st.offset)])
         return [LayerCache(st, i) for i in range(self.cfg.num_hidden_layers)]
+
+    # ------------------------------------------------------------------ shared-prefix decode (include/p3v.h: p3v_attention_decode_family)
+    def family_refusal(self, st=None):
+        """Why this model / state cannot share a prefix between rows, or None: the family launch reads the bf16 cache."""
+        quantized = bool(getattr(self.cfg, "use_quantized_cache", False)) if st is None else (st.quantized or st.mlx4)
+        if quantized:
+            fmt = getattr(self.cfg, "cache_format", "int8") if st is None else ("mlx4" if st.mlx4 else "int8")
+            return f"share_prefix needs the bf16 KV cache: the shared-prefix attention has no {fmt} form (quantize_cache=True)"
+        return None
+
+    @_on_device
+    def set_families(self, st, families, create=False):
+        """Name the rows of `st` whose caches are identical up to a column: families = [(rows, share_end), ...], the leader -- the
+        row whose copy is read -- first; [] clears the table.  Decode steps (L = 1, no beams) of a state that has a table go
+        through ops.attention_decode_family, which reads columns [0, floor(share_end / chunk) * chunk) of a family once, from its
+        leader; those columns of the other members are then dead positions (finite, otherwise ignored).  The table is made on
+        first use and lives on the device: this call is one host-to-device copy, and a step captured AFTER the table was made
+        follows it without a new capture.  A state that already holds a captured step and no table is refused (ValueError: its
+        capture would keep the plain launch beside eager steps on the family launch); a long-lived state makes the table first,
+        with create=True and no families.  Nothing here drops a capture.
+        Families below the measured break-even (parallel.family_pays: few rows x few shared keys) stay single rows, and make no
+        table where there is none; `st.families` lists the registered ones.  The caller keeps the contract: no row is rewritten
+        below share_end while it is in a family."""
+        families = [(tuple(int(r) for r in rows), int(se)) for rows, se in families]
+        if st.family is None and not families and not create:
+            return
+        why = self.family_refusal(st)
+        if why:
+            raise ValueError(why)
+        family_table(st.B, families)                            # (every family is checked, also those left out below)
+        if any(se > st.offset for rows, se in families if len(rows) > 1):
+            raise ValueError(f"set_families: share_end beyond the cache length {st.offset}")
+        families = [f for f in families if len(f[0]) > 1 and family_pays(len(f[0]), f[1])]   # below the break-even: single rows
+        if st.family is None and not families and not create:
+            return
+        tab = torch.from_numpy(family_table(st.B, families))
+        if st.family is None:
+            if st.graphs:                                       # a step captured without a table keeps the plain launch: two plans on one state
+                raise ValueError("set_families: the state already holds a captured step; make the table before the first capture "
+                                 "(set_families(st, [], create=True))")
+            st.family = torch.empty((st.B, ops.L.FAMILY_INTS), dtype=I32, device=self.device)
+        st.family.copy_(tab)
+        st.family_host = tab
+        st.families = families
 
     @_on_device
     def decode_graph(self, st):
@@ -896,7 +957,7 @@ class Phi3VModel:
         return g
 
     # ------------------------------------------------------------------ decoder stack
-    def _plan(self, st, B, L, fuse_o, captured=False):
+    def _plan(self, st, B, L, fuse_o, captured=False, family=True):
         """The buffers and the attention plan of a pass over B x L rows of a state.  fuse_o: also plan the fused attention + o_proj
         launch (_plan_fused_oproj; it sets bufs["fuse_o"]).  captured:
         the plan is for a captured step, which reads the cache length from the device -- it carries the step's staging rows for the
@@ -905,7 +966,11 @@ class Phi3VModel:
         bufs = self._alloc_bufs(B, L)
         # split plan from the cache CAPACITY, eager or captured: same kernel, same split boundaries -> eager and replayed steps
         # agree bit for bit
-        self._split_plan(bufs, B, L, st.Tp, st.quantized, serving=st.serving or self.serving)
+        if family and L == 1 and st.family is not None and B == st.B and not st.quantized and not st.mlx4:
+            self._family_plan(bufs, B, st.Tp)                   # a state with a family table: ops.attention_decode_family, no fused o_proj
+            fuse_o = False
+        else:
+            self._split_plan(bufs, B, L, st.Tp, st.quantized, serving=st.serving or self.serving)
         if captured:
             bufs["past_lb"] = -1 if st.slots else int(st.offset)
             bufs["rope_cos"] = torch.empty((B, L, self.hd // 2), dtype=F32, device=self.device)
@@ -1002,6 +1067,22 @@ class Phi3VModel:
                 fused = False
             bufs["attn_merge"] = bool(fused)
 
+    FAMILY_CHUNK = 256
+
+    def _family_plan(self, bufs, B, T):
+        """Split plan of the shared-prefix decode attention.  A family's whole splits below share_end are read once, by its
+        leader, and the up-to-one-chunk remainder by every member, so the chunk is small and fixed: 256 keys (four tiles of the
+        one-wave kernel per split), as many splits as the workspace and the merge launch take (128; longer caches get longer
+chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 keys, shared step, n = 4 / n = 8
+        (profiles/share_prefix_step_time.txt): 64 keys 2.4306 / 2.8538 ms, 128 keys 2.2363 / 2.4925 ms, 256 keys 2.1288 /
+        2.4102 ms -- fewer, longer single-wave workgroups and half the partials to merge outweigh the longer remainder.
+        FAMILY_CHUNK is the target (tools/share_step_time.py sets it on its model to time the alternatives)."""
+        nh, hd = self.cfg.num_attention_heads, self.hd
+        keys = int(self.FAMILY_CHUNK)
+        n_split = max(1, min(128, -(-T // keys)))
+        bufs["n_split"], bufs["attn_merge"], bufs["family"] = n_split, False, True
+        bufs["ws"] = ops.attention_ws(B, 1, nh, hd, n_split, self.device)
+
     def _layers(self, x, st, B, L, past, n_beam, bufs=None, d_past=None, last_only=False, step_begin=None):
         """Phi3DecoderLayer stack (phi.py:473-485).  `d_past` (device int32) makes every
         position-dependent kernel read the cache length from HBM -> graph-replayable.
@@ -1015,7 +1096,7 @@ class Phi3VModel:
         scale = hd ** -0.5
         decode = L <= ops.L.DECODE_MAX_L                        # decode-shaped rows: one fused attention launch (+ merge) per layer
         if bufs is None:
-            bufs = self._plan(st, B, L, fuse_o=decode and n_beam == 1)
+            bufs = self._plan(st, B, L, fuse_o=decode and n_beam == 1, family=n_beam == 1)
         q, o, qkv, a, h, n_split, ws = (bufs[k] for k in ("q", "o", "qkv", "a", "h", "n_split", "ws"))
         fuse_o, attn_merge = bufs.get("fuse_o", False), bufs.get("attn_merge", False)
         if decode and d_past is not None:                       # graph replay: rotation rows staged once per step by the caller
@@ -1089,6 +1170,10 @@ class Phi3VModel:
                 ops.attention(q, o, B, L, nh, nkv, hd, scale, True, k_new=k_new, v_new=v_new, new_t=Lp, past=past,
                               k_past=st.k[i], v_past=st.v[i], past_t=st.Tp, past_div=n_beam, pad_len=st.pad_len,
                               pad_div=n_beam, ws=ws, n_split=n_split)
+            elif decode and bufs.get("family"):                 # a state with a family table: its prompts' K/V read once per family
+                ops.attention_decode_family(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, nh, nkv, hd, scale,
+                                            past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split, st.family,
+                                            family_host=st.family_host, pad_len=st.pad_len, d_past=d_past)
             elif decode:
                 kw_o = {}
                 if fuse_o:                                      # (o_proj on bf16 or 4-bit weights)

@@ -523,6 +523,33 @@ def attention_decode(qkv, cos_new, sin_new, rope_bstride, k_cache, v_cache, out,
     return out
 
 
+def attention_family_chunk(cache_t, n_split):
+    """Keys per split of the decode attention launchers: the unit in which `attention_decode_family` shares a prefix."""
+    return (-(-cache_t // n_split) + 63) & ~63
+
+
+def attention_decode_family(qkv, cos_new, sin_new, rope_bstride, k_cache, v_cache, out, B, nh, nkv, hd, scale, past, cache_t, ws,
+                            n_split, family, family_host=None, pad_len=None, d_past=None, Lq=1, merge_in_launch=False, o_proj_w=None):
+    """`attention_decode` for one new token per row, reading the prompt keys of every family of `family` once (include/p3v.h:
+    p3v_attention_decode_family).  family: int32 [B, 18] on the device, {lead, share_end, member[16]} per row; family_host: the
+    same table on the host (a CPU int32 tensor) for the library to check before it launches, or None.  Lq, merge_in_launch and
+    o_proj_w exist to be refused: the library takes Lq == 1, the separate merge launch and no fused o_proj."""
+    _chk(family, I32, "family")
+    if tuple(family.shape) != (B, L.FAMILY_INTS):
+        raise ValueError(f"family table must be [{B}, {L.FAMILY_INTS}], got {tuple(family.shape)}")
+    host = None
+    if family_host is not None:
+        if family_host.is_cuda or family_host.dtype != torch.int32 or not family_host.is_contiguous() or \
+                tuple(family_host.shape) != (B, L.FAMILY_INTS):
+            raise ValueError(f"family_host must be a contiguous CPU int32 [{B}, {L.FAMILY_INTS}] tensor")
+        host = family_host.data_ptr()
+    args = L.AttnDecArgs(_p(qkv), _p(cos_new), _p(sin_new), _p(k_cache), _p(v_cache), _p(out), _p(pad_len), _p(d_past), _p(ws),
+                         B, Lq, nh, nkv, hd, int(past), cache_t, rope_bstride, n_split, float(scale), int(bool(merge_in_launch)),
+                         _p(o_proj_w), None, None, 0, None)
+    L.check(L.lib().p3v_attention_decode_family(C.byref(args), _p(family), host, _stream()), "attention_decode_family")
+    return out
+
+
 def kv_quantize(k, vt, k8, v8t, k_scale, v_scale, t0, n_tok):
     """bf16 K [B,nkv,Ts,hd] / V^T [B,nkv,hd,Ts] rows [t0,t0+n) -> offset-binary u8 caches + per-token scales."""
     B, nkv, src_t, hd = k.shape
