@@ -37,12 +37,19 @@ into the model changes.
 
 Cost model: a row reads the cache columns [0, column) whatever its own length (static split ranges), so a short request
 that joins late pays for the padding it attends over with zero weight; the weights (7.4 GB/step) are shared by all rows.
+
+A request's options are ONE record (request.RequestOptions): `submit` reads it from its arguments and from what rides beside the
+inputs (`cache_args`, `logprob_args`, `penalty_args`, `n_args`), checks it once, and the Request keeps the checked values.
 """
 import collections
+import dataclasses
 import threading
 
 import numpy as np
 import torch
+
+from .request import (LOGPROB_ARGS, N_ARGS, PENALTY_ARGS, PREFIX_ARGS, RequestOptions, _check_adapter, adapter_list,  # noqa: F401
+                      carry, options_per_prompt, requested_logprobs, requested_n, requested_penalties)
 
 ID_EOS = 32007
 ROPE_WINDOW = 4096            # original_max_position_embeddings: the short / long factor boundary (phi.py:492)
@@ -65,22 +72,19 @@ def _set_device(device):
 class Request:
     __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
                  "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties",
-                 "family", "members", "completions", "family_done", "n", "asked_logprobs")
+                 "family", "members", "completions", "family_done", "n", "asked_logprobs", "opts")
 
-    def __init__(self, inputs, max_tokens, sampling=None, adapter=None, logprobs=None, penalties=None):
+    def __init__(self, inputs, max_tokens, opts=None, **fields):
+        """opts: the request's CHECKED options record (request.RequestOptions; `fields` replace single values of it).  `step()`
+        reads them every step, so they are plain attributes: sampling, adapter, logprobs (one record per token in
+        `logprob_records`), penalties, and for an engine with a prefix store image_digests, cache_prompt and prefix_len."""
         self.inputs, self.max_tokens = inputs, int(max_tokens)
-        # prompt prefix cache (engine with a store only; `cache_args` puts them beside the inputs): digests of the request's source
-        # images, whether its prompt may be captured, an explicit capture length; `cached_tokens`: prompt tokens restored from the
-        # store instead of computed
-        pa = inputs.get(PREFIX_ARGS) if isinstance(inputs, dict) else None
-        pa = pa if isinstance(pa, dict) else {}
-        self.image_digests, self.cache_prompt, self.prefix_len = pa.get("image_digests"), bool(pa.get("cache_prompt", True)), pa.get("prefix_len")
-        self.cached_tokens, self.hit = 0, None
-        self.adapter = adapter                                   # None (the base model) or the name of an adapter of the model's bank
-        self.sampling = sampling                                 # None (greedy) or one (temperature, top_k, top_p, seed) tuple
-        self.logprobs = logprobs                                 # None (off) or N in 0..8: one record per token in `logprob_records`
+        self.opts = opts = dataclasses.replace(opts or RequestOptions(), **fields)
+        for f in ("sampling", "adapter", "logprobs", "penalties", "image_digests", "prefix_len"):
+            setattr(self, f, getattr(opts, f))
+        self.cache_prompt = bool(opts.cache_prompt)
+        self.cached_tokens, self.hit = 0, None                   # prompt tokens restored from the prefix store instead of computed
         self.logprob_records = []                                # (logprobs.unpack dicts, aligned with `tokens`)
-        self.penalties = penalties                               # None (off) or one (repetition, frequency, presence, bias) tuple
         self.S = int(np.asarray(inputs["input_ids"]).shape[-1])
         self.tokens, self.row, self.error = [], None, None
         self.cancelled, self.blocked_at = False, None
@@ -89,7 +93,7 @@ class Request:
         # lists the m generated requests in `members` (itself first) and the n returned ones in `completions` (for best_of:
         # ranked, set when `family_done` is); every member has its own tokens / logprob_records / error / done
         self.family, self.members, self.completions, self.family_done, self.n = None, [self], [self], self.done, 1
-        self.asked_logprobs = logprobs                           # what the CLIENT asked (best_of scores every member at N >= 0)
+        self.asked_logprobs = self.logprobs                      # what the CLIENT asked (best_of scores every member at N >= 0)
 
     def cancel(self):
         """The waiter gave up (timeout, client gone): the engine drops the request at its next step.  A cancelled head cancels
@@ -134,12 +138,19 @@ def make_family(head, n, m):
     head.logprobs = want
     ss = [None] * m if head.sampling is None else seeds(head.sampling[3], m)
     for j in range(1, m):
-        r = Request(head.inputs, head.max_tokens, None if head.sampling is None else head.sampling[:3] + (ss[j],), head.adapter, want,
-                    head.penalties)
+        r = Request(head.inputs, head.max_tokens, head.opts, logprobs=want,
+                    sampling=None if head.sampling is None else head.sampling[:3] + (ss[j],))
         r.family, r.asked_logprobs = head, head.asked_logprobs
         head.members.append(r)
     head.completions = list(head.members) if m == n else None
     return head
+
+
+def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
+             logprobs=None, penalties=None, n=None, best_of=None):
+    """Text in, text out (what the HTTP backend calls): the `generate` of ContinuousEngine, RegimeRouter and fleet.EngineFleet."""
+    return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
+                          penalties, n, best_of)
 
 
 class ContinuousEngine:
@@ -212,26 +223,23 @@ class ContinuousEngine:
         its own tokens / logprob_records / error / done.  The prompt is prefilled once into one free row and forked into m - 1
         others (model.fork_rows); member j samples under the seed (s + j) mod 2^64.  A family is admitted all or nothing
         (m free rows, not necessarily adjacent); m > slots fails the handle here.  Without `n_args` nothing changes."""
+        from .parallel import refusal
         try:
-            want = _check_logprobs(requested_logprobs(inputs))
-            pen = _check_penalties(requested_penalties(inputs), getattr(getattr(self.model, "cfg", None), "vocab_size", None))
-            rec = _sampling_row(sampling)
-            _check_adapter(adapter, self.adapter_names())
-            _check_prefix_args(inputs)
-            n, m = _check_n(requested_n(inputs))
-            if m > 1:
-                why = _family_refusal(m, self.st)
-                if why:
-                    raise ValueError(why)
-                if m > self.slots:
-                    raise ValueError(f"n > slots: a family of {m} completions needs {m} rows at once, this engine has {self.slots} slots")
+            opts = RequestOptions.read(inputs, sampling, adapter).checked(
+                self.adapter_names(), getattr(getattr(self.model, "cfg", None), "vocab_size", None), inputs)
+            m = opts.m
+            why = refusal(m, mlx4=bool(getattr(self.st, "mlx4", False)))
+            if why:
+                raise ValueError(why)
+            if m > self.slots:
+                raise ValueError(f"n > slots: a family of {m} completions needs {m} rows at once, this engine has {self.slots} slots")
         except ValueError as e:
             r = Request(inputs, max_tokens)
             r.fail(e)
             return r
-        r = Request(inputs, max_tokens, rec, adapter, want, pen)
+        r = Request(inputs, max_tokens, opts)
         if m > 1:
-            make_family(r, n, m)
+            make_family(r, opts.n, m)
         if self.dead is not None:
             r.fail(RuntimeError(f"engine is down: {self.dead!r}"))
         elif not self.accepts(r.S, r.max_tokens):
@@ -642,21 +650,10 @@ class ContinuousEngine:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    # ---- convenience: text in, text out (what the HTTP handler calls)
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None, n=None, best_of=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties, n, best_of)
+    generate = generate
 
 
 _GREEDY = (0.0, 0, 1.0, 0)
-
-
-def _check_logprobs(logprobs):
-    """submit's `logprobs` -> None (off) or the checked N; ValueError names the range."""
-    from .logprobs import OFF, check
-    want = check(logprobs)
-    return None if want == OFF else want
 
 
 def _unpack_records(words):
@@ -664,168 +661,29 @@ def _unpack_records(words):
     return unpack(words)
 
 
-def logprobs_list(logprobs, n):
-    """`logprobs` argument of a text-level call -> one checked value / None per prompt."""
-    from .logprobs import OFF, wants
-    w = wants(logprobs, n)
-    return [None] * n if w is None else [None if x == OFF else x for x in w]
-
-
-def _check_adapter(adapter, known):
-    if adapter is None:
-        return
-    if not isinstance(adapter, str):
-        raise ValueError(f"adapter must be a name (string) or None, got {type(adapter).__name__}; known adapters: {known}")
-    if adapter not in known:
-        raise ValueError(f"unknown adapter {adapter!r}; known adapters: {known}")
-
-
-def adapter_list(adapter, n):
-    """`adapter` argument of a text-level call -> one name / None per prompt: a name (or None) serves every prompt, a list gives
-    one per prompt."""
-    if adapter is None or isinstance(adapter, str):
-        return [adapter] * n
-    if not isinstance(adapter, (list, tuple)):
-        raise ValueError(f"adapter must be a name, None, or a list of one per prompt, got {type(adapter).__name__}")
-    if len(adapter) != n:
-        raise ValueError(f"adapter: {len(adapter)} names for {n} prompts")
-    return list(adapter)
-
-
-PENALTY_ARGS = "penalties"          # key of a request's penalty settings inside its `inputs` (no model call forwards it)
-
-
+# What rides beside a request's inputs (request.py has the keys, their one reader and their one writer).  Each helper returns a
+# COPY of a B = 1 `processor(...)` result with one carrier added, so the option travels through a router or a fleet with the
+# inputs; the processor's own result is not touched, and `submit` checks the values.
 def penalty_args(inputs, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
-    """A copy of a B = 1 `processor(...)` result that carries the request's penalties and logit_bias (ContinuousEngine.submit) as
-    one plain dict, so it travels through a router or a fleet as `logprob_args` does.  The processor's own result is not
-    touched; `submit` checks the values (penalties.request_row)."""
-    return dict(inputs, **{PENALTY_ARGS: dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                               frequency_penalty=frequency_penalty, logit_bias=logit_bias)})
-
-
-def requested_penalties(inputs):
-    return inputs.get(PENALTY_ARGS) if isinstance(inputs, dict) else None
-
-
-def _check_penalties(d, vocab=None):
-    """submit's penalty dict -> None (off) or the checked (repetition, frequency, presence, bias) tuple; ValueError names the value."""
-    from .penalties import request_row
-    return request_row(d, vocab)
-
-
-def penalties_list(penalties, n):
-    """`penalties` argument of a text-level call (None, one dict for every prompt, or one dict / None per prompt) -> a list."""
-    if penalties is None or isinstance(penalties, dict):
-        return [penalties] * n
-    if len(penalties) != n:
-        raise ValueError(f"penalties: {len(penalties)} values for {n} prompts")
-    return list(penalties)
-
-
-LOGPROB_ARGS = "logprobs"           # key of a request's `logprobs` value inside its `inputs` (no model call forwards it)
+    """... the request's penalties and logit_bias, as one plain dict (penalties.request_row checks it)."""
+    return carry(inputs, PENALTY_ARGS, RequestOptions(penalties=dict(
+        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)))
 
 
 def logprob_args(inputs, logprobs):
-    """A copy of a B = 1 `processor(...)` result that carries the request's `logprobs` (None, or N in 0..8: ContinuousEngine.submit).
-    The processor's own result is not touched; `submit` checks the value."""
-    return dict(inputs, **{LOGPROB_ARGS: logprobs})
-
-
-def requested_logprobs(inputs):
-    return inputs.get(LOGPROB_ARGS) if isinstance(inputs, dict) else None
-
-
-N_ARGS = "n_completions"            # key of a request's {"n", "best_of"} inside its `inputs` (no model call forwards it)
+    """... the request's `logprobs`: None, or N in 0..8."""
+    return carry(inputs, LOGPROB_ARGS, RequestOptions(logprobs=logprobs))
 
 
 def n_args(inputs, n, best_of=None):
-    """A copy of a B = 1 `processor(...)` result that carries the number of completions asked of it (ContinuousEngine.submit:
-    n in 1..16, best_of None or n..16), beside the inputs as `cache_args` / `logprob_args` / `penalty_args` put theirs -- so a
-    router or a fleet hands the WHOLE family to one engine.  The processor's own result is not touched; `submit` checks the
-    values."""
-    return dict(inputs, **{N_ARGS: {"n": n, "best_of": best_of}})
-
-
-def requested_n(inputs):
-    return inputs.get(N_ARGS) if isinstance(inputs, dict) else None
-
-
-def _check_n(d):
-    """submit's n-args -> (n, m): n returned of m generated; (1, 1) without them.  ValueError names the limit."""
-    from .parallel import check
-    if d is None:
-        return 1, 1
-    if not isinstance(d, dict) or set(d) - {"n", "best_of"}:
-        raise ValueError(f"{N_ARGS} must be what engine.n_args makes")
-    return check(d.get("n", 1), d.get("best_of"))
-
-
-def _family_refusal(m, st):
-    from .parallel import refusal
-    return refusal(m, mlx4=bool(getattr(st, "mlx4", False)))
-
-
-PREFIX_ARGS = "prefix_cache_args"   # key of a request's prefix-cache arguments inside its `inputs` (no model call forwards it)
+    """... the number of completions asked of it (n in 1..16, best_of None or n..16): a router or a fleet hands the WHOLE family
+    to one engine."""
+    return carry(inputs, N_ARGS, RequestOptions(n=n, best_of=best_of))
 
 
 def cache_args(inputs, image_digests=None, cache_prompt=True, prefix_len=None):
-    """A copy of a B = 1 `processor(...)` result that carries the request's prefix-cache arguments (ContinuousEngine.submit).
-    The processor's own result is not touched; `submit` checks the values."""
-    return dict(inputs, **{PREFIX_ARGS: {"image_digests": image_digests, "cache_prompt": cache_prompt, "prefix_len": prefix_len}})
-
-
-def _check_prefix_args(inputs):
-    pa = inputs.get(PREFIX_ARGS) if isinstance(inputs, dict) else None
-    if pa is None:
-        return
-    if not isinstance(pa, dict) or set(pa) - {"image_digests", "cache_prompt", "prefix_len"}:
-        raise ValueError(f"{PREFIX_ARGS} must be what engine.cache_args makes")
-    image_digests, prefix_len = pa.get("image_digests"), pa.get("prefix_len")
-    if not isinstance(pa.get("cache_prompt", True), bool):
-        raise ValueError("cache_prompt must be True or False")
-    if image_digests is not None:
-        if isinstance(image_digests, (str, bytes)) or not all(isinstance(d, str) and d for d in image_digests):
-            raise ValueError("image_digests must be a list of non-empty strings, one per image")
-        n_img = 0 if inputs.get("image_sizes") is None else len(np.asarray(inputs["image_sizes"]))
-        if len(image_digests) != n_img:
-            raise ValueError(f"image_digests: {len(image_digests)} digests for {n_img} images")
-    if prefix_len is not None:
-        if isinstance(prefix_len, bool) or not isinstance(prefix_len, (int, np.integer)) or prefix_len < 1:
-            raise ValueError(f"prefix_len must be a positive integer, got {prefix_len!r}")
-
-
-def _submit(engine, inputs, max_tokens, sampling, adapter, image_digests=None, cache_prompt=None, prefix_len=None, logprobs=None,
-            penalties=None, n=None, best_of=None):
-    """submit with only the keywords in use (an engine-like object without them keeps working for plain requests); the prefix-cache
-    arguments, when one of them is in use, ride beside the inputs (`cache_args`), and so do `logprobs` (`logprob_args`) and a
-    family's `n` / `best_of` (`n_args`)."""
-    kw = {}
-    if (n, best_of) not in ((None, None), (1, None)):
-        inputs = n_args(inputs, 1 if n is None else n, best_of)
-    if image_digests is not None or prefix_len is not None or (cache_prompt is not None and not cache_prompt):
-        inputs = cache_args(inputs, image_digests, True if cache_prompt is None else bool(cache_prompt), prefix_len)
-    if sampling is not None:
-        kw["sampling"] = sampling
-    if adapter is not None:
-        kw["adapter"] = adapter
-    if logprobs is not None:
-        inputs = logprob_args(inputs, logprobs)
-    if penalties is not None:
-        inputs = dict(inputs, **{PENALTY_ARGS: dict(penalties)})
-    return engine.submit(inputs, max_tokens, **kw)
-
-
-def _sampling_row(sampling):
-    """submit's `sampling` dict -> one checked (temperature, top_k, top_p, seed) tuple; None stays None (greedy)."""
-    if sampling is None:
-        return None
-    if isinstance(sampling, tuple):
-        sampling = dict(zip(("temperature", "top_k", "top_p", "seed"), sampling))
-    unknown = set(sampling) - {"temperature", "top_k", "top_p", "seed"}
-    if unknown:
-        raise ValueError(f"unknown sampling settings {sorted(unknown)}")
-    from .sampling import rows
-    return rows(1, sampling.get("temperature", 0.0), sampling.get("top_k", 0), sampling.get("top_p", 1.0), sampling.get("seed"))[0]
+    """... the request's prefix-cache arguments."""
+    return carry(inputs, PREFIX_ARGS, RequestOptions(image_digests=image_digests, cache_prompt=cache_prompt, prefix_len=prefix_len))
 
 
 def _pack(rows_, counter=0):
@@ -833,12 +691,19 @@ def _pack(rows_, counter=0):
     return pack(rows_, counter)
 
 
+def leaf_engines(front):
+    """The ContinuousEngines behind a server backend, a fleet (rank 0's own), a router, or an engine itself."""
+    inner = getattr(front, "engine", None)
+    behind = [inner] if inner is not None else list(getattr(front, "engines", None) or ())
+    if not behind:
+        yield front
+    for e in behind:
+        yield from leaf_engines(e)
+
+
 def has_prefix_cache(engine):
     """Does this engine (or any engine behind a router / fleet) carry a prefix store?"""
-    if getattr(engine, "prefix_cache", None) is not None:
-        return True
-    inner = list(getattr(engine, "engines", ()) or ()) + [e for e in (getattr(engine, "engine", None),) if e is not None]
-    return any(has_prefix_cache(e) for e in inner)
+    return any(getattr(e, "prefix_cache", None) is not None for e in leaf_engines(engine))
 
 
 def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None,
@@ -853,29 +718,17 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
     logprobs: None, N in 0..8, or one such value per prompt.  penalties: None, one {"repetition_penalty", "presence_penalty",
     "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt."""
     from . import api
-    from .parallel import check, refusal
-    batched = not isinstance(prompts, str) and len(prompts) != 1
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
-    fam = check(n, best_of)[1] > 1
-    why = refusal(check(n, best_of)[1], batched=batched)
-    if why:
-        raise ValueError(why)
+    opts = options_per_prompt(len(prompts), sampling, adapter, logprobs, penalties, cache_prompt, n, best_of)
+    fam, lps = opts[0].m > 1, [o.logprobs for o in opts]
     images = images if images is not None else [None] * len(prompts)
-    if sampling is not None and len(sampling) != len(prompts):
-        raise ValueError(f"sampling: {len(sampling)} records for {len(prompts)} prompts")
-    adapters = adapter_list(adapter, len(prompts))
-    lps = logprobs_list(logprobs, len(prompts))
-    pens = penalties_list(penalties, len(prompts))
     reqs = []
-    for i, (p, im) in enumerate(zip(prompts, images)):
+    for o, p, im in zip(opts, prompts, images):
         text, imgs = api._apply_chat_template(p, im, False)
-        digests = None
         if imgs is not None and has_prefix_cache(engine):       # of the decoded source images, before the processor runs
             from .prefix import image_digests
-            digests = image_digests(imgs)
-        inputs = processor(text, imgs) if imgs is not None else processor(text)
-        reqs.append(_submit(engine, inputs, max_tokens, None if sampling is None else sampling[i], adapters[i], digests, cache_prompt,
-                            logprobs=lps[i], penalties=pens[i], **(dict(n=n, best_of=best_of) if fam else {})))
+            o = dataclasses.replace(o, image_digests=image_digests(imgs))
+        reqs.append(o.send(engine, processor(text, imgs) if imgs is not None else processor(text), max_tokens))
     out, kept = [], []
     heads = reqs
     try:
@@ -926,7 +779,7 @@ class RegimeRouter:
         S = int(np.asarray(inputs["input_ids"]).shape[-1])
         for e in self.engines:
             if e.accepts(S, int(max_tokens)):
-                return _submit(e, inputs, max_tokens, sampling, adapter)    # (`cache_args` / `logprob_args` inputs pass through as they are)
+                return RequestOptions(sampling=sampling, adapter=adapter).send(e, inputs, max_tokens)   # (what rides beside the inputs passes through as it is)
         r = Request(inputs, max_tokens)
         r.fail(ValueError(f"prompt {S} + max_tokens {max_tokens} fits no engine window"))
         return r
@@ -944,7 +797,4 @@ class RegimeRouter:
             if not self.safe_step() and not self.waiting:
                 stop_event.wait(idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None, n=None, best_of=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties, n, best_of)
+    generate = generate

@@ -16,8 +16,7 @@ one receiver thread per source takes them in order).  RCCL is not involved; the 
 import threading
 import time
 
-from .engine import (Request, _check_adapter, _check_logprobs, _check_n, _check_penalties, _generate_text, _submit, make_family,
-                     requested_logprobs, requested_n, requested_penalties)
+from .engine import Request, RequestOptions, generate
 
 _ERRORS = {"ValueError": ValueError, "TimeoutError": TimeoutError, "TypeError": TypeError}   # what the HTTP handler tells apart
 
@@ -93,11 +92,8 @@ class EngineFleet:
         the records come back with the tokens.  Penalties and logit_bias (`engine.penalty_args`) ride there too; a bad value is
         refused here, on rank 0.  A family of n completions (`engine.n_args`) goes to ONE rank as one request: its engine
         prefills once and forks; the returned completions come back in one message and fill the head's `completions`."""
-        try:
-            _check_adapter(adapter, self.adapter_names())        # an unknown name never leaves rank 0
-            logprobs = _check_logprobs(requested_logprobs(inputs))   # nor does a bad N
-            _check_penalties(requested_penalties(inputs))        # nor a bad penalty or bias (the vocabulary bound: the rank's engine)
-            n, m = _check_n(requested_n(inputs))                 # nor a bad n / best_of
+        try:                                                     # a bad value never leaves rank 0 (the vocabulary bound: the rank's engine)
+            opts = RequestOptions.read(inputs, sampling, adapter).checked(self.adapter_names(), None, inputs)
         except ValueError as e:
             h = Request(inputs, max_tokens)
             h.fail(e)
@@ -108,12 +104,12 @@ class EngineFleet:
             dst = min(range(self.world), key=lambda r: (loads[r], r))
             self.sent[dst] += 1
             if dst == 0:
-                h = _submit(self.engine, inputs, max_tokens, sampling, adapter)
+                h = RequestOptions(sampling=sampling, adapter=adapter).send(self.engine, inputs, max_tokens)
                 self.local.append(h)
                 return h
-            h = RemoteRequest(inputs, max_tokens, logprobs=logprobs)
-            if m > 1:                                            # the head of a remote family: `completions` arrive with the result
-                h.family, h.n, h.family_done, h.completions = h, n, threading.Event(), None
+            h = RemoteRequest(inputs, max_tokens, logprobs=opts.logprobs)
+            if opts.m > 1:                                       # the head of a remote family: `completions` arrive with the result
+                h.family, h.n, h.family_done, h.completions = h, opts.n, threading.Event(), None
             h.fleet, h.rank, h.rid = self, dst, self.next_id
             self.next_id += 1
             self.pending[h.rid] = h
@@ -180,10 +176,7 @@ class EngineFleet:
     def serve_forever(self, stop_event, idle_sleep=0.002):
         self.engine.serve_forever(stop_event, idle_sleep)
 
-    def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-                 logprobs=None, penalties=None, n=None, best_of=None):
-        return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                              penalties, n, best_of)
+    generate = generate
 
     def close(self, timeout=10.0):
         """Tell every worker to stop (each answers "bye" once its engine thread is down)."""
@@ -239,7 +232,7 @@ def worker(engine, groups, poll_s=0.002):
         if msg[0] == "stop":
             break
         if msg[0] == "submit":
-            h = _submit(engine, msg[2], msg[3], msg[4], msg[5] if len(msg) > 5 else None)
+            h = RequestOptions(sampling=msg[4], adapter=msg[5] if len(msg) > 5 else None).send(engine, msg[2], msg[3])
             with lock:
                 live[msg[1]] = h
         elif msg[0] == "cancel":

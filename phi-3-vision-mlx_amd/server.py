@@ -55,6 +55,10 @@ gets 500.
 `--continuous` replaces the queue by `engine.ContinuousEngine`: requests are prefilled into free batch rows between the
 decode steps of the rows already generating and leave at their own EOS / budget (no request waits for a batch to drain).
 
+Which keywords a request hands to a backend, to the engine and to a queued job is said once, by `in_use`; where an option cannot
+run (under speculation, on the batch-sharded path), by the `REFUSALS` table; how a queued group becomes `api.generate` keywords,
+by `generate_kwargs`.
+
     python -m phi_3_vision_mlx_amd.server --port 8000 [--synthetic] [--blind] [--merge | --continuous]
 """
 import json
@@ -66,17 +70,33 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 MODEL_NAME = "phi-3-vision"
 
 
-class _Job:
-    __slots__ = ("prompts", "max_tokens", "images", "done", "result", "error", "sampling", "adapter", "speculate", "info", "logprobs", "penalties",
-                 "n", "best_of")
+def in_use(sampling=None, adapter=None, logprobs=None, penalties=None, n=None, best_of=None, speculate=0, cache_prompt=None, info=None):
+    """The keywords of the options a request really uses -- what the handler passes to a backend's `submit`, what
+    ContinuousBackend passes to the engine's `generate`, and what a queued job keeps.  The rules, stated once:
 
-    def __init__(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
-                 penalties=None, n=None, best_of=None):
-        self.n, self.best_of = n, best_of       # None, or a family: n completions of the one prompt (never merged)
-        self.logprobs = logprobs                # None, or one N per prompt
-        self.penalties = penalties              # None, or one penalty dict per prompt
-        self.prompts, self.max_tokens, self.images, self.sampling = prompts, max_tokens, images, sampling
-        self.adapter = adapter                  # None, or one name / None per prompt
+      * a plain request passes no keyword at all (a backend that knows nothing of an option keeps serving plain requests);
+        `images` is positional, and only when not None;
+      * sampling, adapter, logprobs and penalties are present only when not None;
+      * n and best_of (both) are present only for a family -- m > 1 rows; the caller passes n=None otherwise;
+      * speculate is present only when K > 0;
+      * cache_prompt is present only when not None, and the handler passes it on only to a backend with a prefix store;
+      * info (the dict a backend reports into) is present only when not None; the handler makes one exactly when the request is
+        a family, asks for logprobs, speculates (K > 0), or the backend has a prefix store."""
+    kw = {k: v for k, v in (("sampling", sampling), ("adapter", adapter), ("logprobs", logprobs), ("penalties", penalties),
+                            ("cache_prompt", cache_prompt), ("info", info)) if v is not None}
+    if n is not None:
+        kw.update(n=n, best_of=best_of)
+    if speculate:
+        kw["speculate"] = speculate
+    return kw
+
+
+class _Job:
+    __slots__ = ("prompts", "max_tokens", "images", "opts", "speculate", "info", "done", "result", "error")
+
+    def __init__(self, prompts, max_tokens, images=None, opts=None, speculate=0, info=None):
+        self.prompts, self.max_tokens, self.images = prompts, max_tokens, images
+        self.opts = opts or {}                  # `in_use` of the request: per-prompt lists; n, best_of: a family (never merged)
         self.speculate, self.info = speculate, info             # draft rows per verify step (0 = off), the caller's statistics dict
         self.done, self.result, self.error = threading.Event(), None, None
 
@@ -198,15 +218,10 @@ PENALTY_BAN = -1e30                             # a logit_bias at or below this 
 
 def vocab_of(engine):
     """The vocabulary size behind a backend (the bound of logit_bias keys), or None when it does not say."""
-    v = getattr(engine, "vocab_size", None)
-    if v is not None:
-        return int(v)
-    inner = getattr(engine, "engine", engine)
-    for e in getattr(inner, "engines", None) or [getattr(inner, "engine", inner)]:
-        v = getattr(getattr(getattr(e, "model", None), "cfg", None), "vocab_size", None)
-        if v is not None:
-            return int(v)
-    return None
+    from .engine import leaf_engines
+    sizes = [getattr(engine, "vocab_size", None)] + [getattr(getattr(getattr(e, "model", None), "cfg", None), "vocab_size", None)
+                                                     for e in leaf_engines(engine)]
+    return next((int(v) for v in sizes if v is not None), None)
 
 
 def parse_penalties(request, n_prompts, vocab=None):
@@ -231,11 +246,11 @@ def parse_penalties(request, n_prompts, vocab=None):
 
 def token_decoder(engine):
     """id -> text piece for the "tokens" of a logprobs response: the backend's `decode_fn`, or its tokenizer; None without one."""
+    from .engine import leaf_engines
     fn = getattr(engine, "decode_fn", None)
     if fn is not None:
         return fn
-    inner = getattr(engine, "engine", engine)
-    tok = getattr(getattr(inner, "processor", None), "tokenizer", None)
+    tok = getattr(getattr(next(leaf_engines(engine)), "processor", None), "tokenizer", None)
     return None if tok is None else (lambda i: tok.decode([int(i)]))
 
 
@@ -370,8 +385,8 @@ class EngineQueue:
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
                penalties=None, n=None, best_of=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, sampling, adapter, speculate, info, logprobs,
-                   penalties, n, best_of)
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, in_use(sampling, adapter, logprobs, penalties, n, best_of),
+                   speculate, info)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -393,8 +408,10 @@ class EngineQueue:
     def _collect(self, first):
         """merge=False: `first` alone.  merge=True: plus every queued job with the same max_tokens that fits and keeps the
         RoPE regime of each member unchanged, waiting at most `window_s` for stragglers."""
+        def alone(job):                         # image / adapter requests and families are never merged
+            return job.images is not None or "adapter" in job.opts or "n" in job.opts
         group, n, held = [first], len(first.prompts), []
-        if not self.merge or first.images is not None or first.adapter is not None or first.n is not None:   # image / adapter requests and families are never merged
+        if not self.merge or alone(first):
             return group
         regime = self._regime(first.prompts, first.max_tokens)
         while n < self.max_batch:
@@ -405,8 +422,8 @@ class EngineQueue:
             if job is None:
                 self.jobs.put(None)
                 break
-            if job.n is None and job.images is None and job.adapter is None and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
-                    and self._regime(job.prompts, job.max_tokens) == regime and (job.sampling is None) == (first.sampling is None):
+            if not alone(job) and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
+                    and self._regime(job.prompts, job.max_tokens) == regime and ("sampling" in job.opts) == ("sampling" in first.opts):
                 group.append(job)
                 n += len(job.prompts)
             else:
@@ -426,46 +443,43 @@ class EngineQueue:
             group = self._collect(first)
             flat = [p for j in group for p in j.prompts]
             try:
-                kw = {} if first.adapter is None else {"adapter": first.adapter}
-                lp_info = None
-                if any(j.logprobs is not None for j in group):  # every row keeps its own request's N (None: that row is off)
-                    lp_info = {}
-                    kw.update(logprobs=[w for j in group for w in (j.logprobs or [None] * len(j.prompts))], logprob_info=lp_info)
-                if any(j.penalties is not None for j in group):  # every row keeps its own request's penalties (None: none)
-                    kw["penalties"] = [d for j in group for d in (j.penalties or [None] * len(j.prompts))]
-                if first.n is not None:                         # a family: ONE prompt, n texts back (one prefill, forked)
-                    fam = {}
-                    if first.sampling is not None:
-                        kw["sampling"] = first.sampling
-                    out = self.generate_fn(flat, first.max_tokens, first.images, n=first.n, best_of=first.best_of, family_info=fam, **kw)
-                    if first.info is not None and first.sampling is not None:
-                        first.info["seeds"] = [int(x) for x in fam.get("seeds", [])]
+                # ONE call for the group.  `images` is positional unless the call is plain (no keyword, no image: a plain
+                # `generate_fn(prompts, max_tokens)` keeps serving plain requests).  adapter, n, best_of: the first job's (such jobs
+                # are never merged).  logprobs / penalties / sampling: one value per row of the group, None for the rows of a job
+                # that did not ask (sampled jobs merge only with sampled jobs).  Each statistics dict comes in with what fills it;
+                # speculate: one greedy prompt, never a family, never merged (self.speculate excludes merge).
+                opts, fam = first.opts, "n" in first.opts
+                spec = 0 if fam else first.speculate
+                kw = {k: opts[k] for k in ("adapter", "n", "best_of") if k in opts}
+                for k in ("logprobs", "penalties") + (() if spec else ("sampling",)):
+                    if any(k in j.opts for j in group):
+                        kw[k] = [v for j in group for v in (j.opts.get(k) or [None] * len(j.prompts))]
+                lp_info, fam_info, stats = {}, {}, {}
+                if "logprobs" in kw:
+                    kw["logprob_info"] = lp_info
+                if fam:
+                    kw["family_info"] = fam_info
+                if spec:
+                    kw.update(speculate=spec, spec_info=stats)
+                out = self.generate_fn(flat, first.max_tokens, *([first.images] if kw or first.images is not None else []), **kw)
+                if fam:                                         # ONE prompt, n texts back (one prefill, forked)
+                    if first.info is not None and "sampling" in opts:
+                        first.info["seeds"] = [int(x) for x in fam_info.get("seeds", [])]
                     out = [out] if isinstance(out, str) else list(out)
-                    if len(out) != first.n:
-                        raise RuntimeError(f"generate returned {len(out)} texts for n = {first.n}")
+                    if len(out) != opts["n"]:
+                        raise RuntimeError(f"generate returned {len(out)} texts for n = {opts['n']}")
                     flat = out                                  # (one result per completion from here on)
-                elif first.speculate:                           # (one prompt, never merged: self.speculate excludes merge)
-                    stats = {}
-                    out = self.generate_fn(flat, first.max_tokens, first.images, speculate=first.speculate, spec_info=stats, **kw)
-                    if first.info is not None:
-                        first.info["speculation"] = {k: int(stats.get(k, 0)) for k in ("steps", "drafted", "accepted")}
-                elif first.sampling is not None:                  # (sampled jobs merge only with sampled jobs: one record per row)
-                    out = self.generate_fn(flat, first.max_tokens, first.images, sampling=[r for j in group for r in j.sampling], **kw)
-                elif kw:
-                    out = self.generate_fn(flat, first.max_tokens, first.images, **kw)
-                elif first.images is None:
-                    out = self.generate_fn(flat, first.max_tokens)
-                else:
-                    out = self.generate_fn(flat, first.max_tokens, first.images)
+                if spec and first.info is not None:
+                    first.info["speculation"] = {k: int(stats.get(k, 0)) for k in ("steps", "drafted", "accepted")}
                 out = [out] if isinstance(out, str) else list(out)
                 if len(out) != len(flat):
                     raise RuntimeError(f"generate returned {len(out)} texts for {len(flat)} prompts")
                 self.batches.append(len(flat))
                 i = 0
                 for j in group:
-                    k = len(j.prompts) if j.n is None else j.n  # (a family: its one prompt has n results)
+                    k = j.opts.get("n", len(j.prompts))          # (a family: its one prompt has n results)
                     j.result = out[i:i + k]
-                    if j.logprobs is not None and j.info is not None:
+                    if "logprobs" in j.opts and j.info is not None:
                         j.info["logprobs"] = [None if lp_info["token_ids"][b] is None else {k_: lp_info[k_][b] for k_ in lp_info}
                                               for b in range(i, i + k)]
                     i += k
@@ -474,6 +488,23 @@ class EngineQueue:
                     j.error = e
             for j in group:
                 j.done.set()
+
+
+# Where an option cannot run, in the order it is checked: (option present, where -- "speculate": the request speculates (K > 0),
+# "sharded": it is bound for the batch-sharded path --, the 400's text, refused only for an explicit "speculate" field?).  Where only
+# the explicit field is refused, a server-wide --speculate default steps aside silently (speculate becomes 0).
+_SHARDED = " on the batch-sharded path (image requests and process groups of the queue server)"
+REFUSALS = (
+    ("penalties", "speculate", "penalties and logit_bias are not available under speculative decoding (a verify step scores several "
+     "tokens per replay against one table); send speculate 0", True),
+    ("penalties", "sharded", f"penalties and logit_bias are not available{_SHARDED}; run the server with --continuous, or send none", False),
+    ("logprobs", "speculate", "logprobs are not available under speculative decoding (a verify step emits several tokens per replay); "
+     "send speculate 0", True),
+    ("logprobs", "sharded", f"logprobs are not available{_SHARDED}; run the server with --continuous, or send no logprobs", False),
+    ("speculate", "sharded", f"speculative decoding is not available{_SHARDED}", True),
+    ("sampling", "sharded", f"sampling is not available{_SHARDED}; run the server with --continuous to sample, or send temperature 0", False),
+    ("adapter", "sharded", f"adapters are not available{_SHARDED}; run the server with --continuous, or send no adapter", False),
+)
 
 
 def make_handler(engine, image_policy=None):
@@ -525,68 +556,22 @@ def make_handler(engine, image_policy=None):
                 logprobs = parse_logprobs(request, len(prompts))
                 penalties = parse_penalties(request, len(prompts), vocab_of(engine))
                 sharded = None if family is not None else getattr(engine, "sharded_fn", None)   # (a family runs api.generate, images too)
-                if penalties is not None and speculate:
-                    if "speculate" in request:
-                        raise ValueError("penalties and logit_bias are not available under speculative decoding (a verify step "
-                                         "scores several tokens per replay against one table); send speculate 0")
+                asked = {"sampling": sampling, "adapter": adapter, "logprobs": logprobs, "penalties": penalties}
+                for option, where, message, explicit_only in REFUSALS:      # in order: the first that fails answers
+                    present = speculate if option == "speculate" else asked[option] is not None
+                    if not present or not (speculate if where == "speculate" else sharded is not None and sharded(prompts, images)):
+                        continue
+                    if not explicit_only or "speculate" in request:
+                        raise ValueError(message)
                     speculate = 0                               # (the server-wide default steps aside)
-                if penalties is not None and sharded is not None and sharded(prompts, images):
-                    raise ValueError("penalties and logit_bias are not available on the batch-sharded path (image requests and "
-                                     "process groups of the queue server); run the server with --continuous, or send none")
-                if logprobs is not None and speculate:
-                    if "speculate" in request:
-                        raise ValueError("logprobs are not available under speculative decoding (a verify step emits several "
-                                         "tokens per replay); send speculate 0")
-                    speculate = 0                               # (the server-wide default steps aside)
-                if logprobs is not None and sharded is not None and sharded(prompts, images):
-                    raise ValueError("logprobs are not available on the batch-sharded path (image requests and process groups of "
-                                     "the queue server); run the server with --continuous, or send no logprobs")
-                if speculate and sharded is not None and sharded(prompts, images):
-                    if "speculate" in request:
-                        raise ValueError("speculative decoding is not available on the batch-sharded path (image requests and "
-                                         "process groups of the queue server)")
-                    speculate = 0
-                if sampling is not None and sharded is not None and sharded(prompts, images):
-                    raise ValueError("sampling is not available on the batch-sharded path (image requests and process groups of "
-                                     "the queue server); run the server with --continuous to sample, or send temperature 0")
-                if adapter is not None and sharded is not None and sharded(prompts, images):
-                    raise ValueError("adapters are not available on the batch-sharded path (image requests and process groups of "
-                                     "the queue server); run the server with --continuous, or send no adapter")
             except (ValueError, TypeError, AttributeError, OSError) as e:
                 self._send(400, {"error": str(e)})
                 return
-            info = None
+            store = prefix_counters(engine) is not None         # a backend with a prefix store reports what each prompt reused
+            info = {} if family is not None or logprobs is not None or speculate or store else None
             try:
-                if family is not None:
-                    info = {}
-                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("logprobs", logprobs),
-                                            ("penalties", penalties)) if v is not None}
-                    if prefix_counters(engine) is not None and cache_prompt is not None:
-                        kw["cache_prompt"] = cache_prompt
-                    responses = engine.submit(prompts, max_tokens, images, info=info, n=family[0], best_of=family[1], **kw)
-                elif logprobs is not None or penalties is not None:
-                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("logprobs", logprobs),
-                                            ("penalties", penalties)) if v is not None}
-                    if logprobs is not None or prefix_counters(engine) is not None:
-                        info = kw["info"] = {}
-                    if prefix_counters(engine) is not None and cache_prompt is not None:
-                        kw["cache_prompt"] = cache_prompt
-                    responses = engine.submit(prompts, max_tokens, images, **kw)
-                elif speculate:
-                    info = {}
-                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling)) if v is not None}
-                    responses = engine.submit(prompts, max_tokens, images, speculate=speculate, info=info, **kw)
-                elif prefix_counters(engine) is not None:         # a backend with a prefix store: it reports what each prompt reused
-                    info = {}
-                    kw = {k: v for k, v in (("adapter", adapter), ("sampling", sampling), ("cache_prompt", cache_prompt)) if v is not None}
-                    responses = engine.submit(prompts, max_tokens, images, info=info, **kw)
-                elif adapter is not None:
-                    kw = {"adapter": adapter} if sampling is None else {"adapter": adapter, "sampling": sampling}
-                    responses = engine.submit(prompts, max_tokens, images, **kw)
-                elif sampling is not None:
-                    responses = engine.submit(prompts, max_tokens, images, sampling=sampling)
-                else:
-                    responses = engine.submit(prompts, max_tokens, images) if images is not None else engine.submit(prompts, max_tokens)
+                kw = in_use(sampling, adapter, logprobs, penalties, *(family or (None, None)), speculate, cache_prompt if store else None, info)
+                responses = engine.submit(prompts, max_tokens, *([images] if images is not None else []), **kw)
             except Exception as e:              # noqa: BLE001
                 self._send(500, {"error": f"{type(e).__name__}: {e}"})
                 return
@@ -630,9 +615,8 @@ class ContinuousBackend:
         return known_adapters(self.engine)
 
     def _stores(self):
-        # (the engines of a router, the engine itself, or a fleet's own engine)
-        engines = getattr(self.engine, "engines", None) or [getattr(self.engine, "engine", self.engine)]
-        return [e.prefix_cache for e in engines if getattr(e, "prefix_cache", None) is not None]
+        from .engine import leaf_engines
+        return [e.prefix_cache for e in leaf_engines(self.engine) if getattr(e, "prefix_cache", None) is not None]
 
     @property
     def prefix_counters(self):
@@ -651,22 +635,10 @@ class ContinuousBackend:
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None,
                penalties=None, n=None, best_of=None):
-        mt = max(1, min(int(max_tokens), self.max_tokens_cap))
-        kw = {} if adapter is None else {"adapter": adapter}
-        if n is not None:                                        # a family: one prompt (a string for the engine), n texts back
-            kw.update(n=n, best_of=best_of)
-            prompts = prompts[0] if not isinstance(prompts, str) and len(prompts) == 1 else prompts
-        if logprobs is not None:
-            kw["logprobs"] = logprobs
-        if penalties is not None:
-            kw["penalties"] = penalties
-        if cache_prompt is not None:
-            kw["cache_prompt"] = cache_prompt
-        if info is not None:
-            kw["info"] = info
-        if sampling is None:
-            return self.engine.generate(prompts, images, mt, self.timeout_s, **kw)
-        return self.engine.generate(prompts, images, mt, self.timeout_s, sampling=sampling, **kw)
+        kw = in_use(sampling, adapter, logprobs, penalties, n, best_of, 0, cache_prompt, info)
+        if "n" in kw and not isinstance(prompts, str) and len(prompts) == 1:
+            prompts = prompts[0]                                 # a family: one prompt (a string for the engine), n texts back
+        return self.engine.generate(prompts, images, max(1, min(int(max_tokens), self.max_tokens_cap)), self.timeout_s, **kw)
 
     def close(self):
         self.stop.set()
@@ -676,6 +648,33 @@ class ContinuousBackend:
 def serve_continuous(engine, port=8000, host="127.0.0.1", image_policy=None, **kw):
     backend = ContinuousBackend(engine, **kw)
     return ThreadingHTTPServer((host, port), make_handler(backend, image_policy)), backend
+
+
+def generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, n_prompts):
+    """The per-row lists a queued group carries (EngineQueue._run) -> the keywords of `api.generate` for them.  A family (n is
+    not None: one prompt) takes scalars -- its sampling record's fields, the penalty fields it gave, its N, its adapter --, n and
+    best_of.  A speculating request (one greedy prompt) takes `speculate` and its adapter.  Any other request takes one value per
+    row (a single prompt: its adapter as a name), a row that asked for no penalty the defaults."""
+    fam = n is not None
+    if speculate and not fam:
+        sampling = logprobs = penalties = None
+    kw = {}
+    if sampling is not None:
+        kw.update({f: sampling[0][f] if fam else [r[f] for r in sampling] for f in SAMPLING_FIELDS})
+    if penalties is not None and fam:
+        kw.update({f: v for f, v in (penalties[0] or {}).items() if v is not None})
+    elif penalties is not None:
+        for f, dflt in (("repetition_penalty", 1.0), ("presence_penalty", 0.0), ("frequency_penalty", 0.0), ("logit_bias", None)):
+            kw[f] = [dflt if d is None or d.get(f) is None else d[f] for d in penalties]
+    if logprobs is not None:
+        kw["logprobs"] = logprobs[0] if fam else logprobs
+    if adapter is not None:
+        kw["adapter"] = adapter if n_prompts > 1 else adapter[0]
+    if fam:
+        kw.update(n=n, best_of=best_of)
+    elif speculate:
+        kw["speculate"] = speculate
+    return kw
 
 
 def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=False, host="127.0.0.1", image_policy=None,
@@ -728,36 +727,21 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
     def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
                     logprob_info=None, penalties=None, n=None, best_of=None, family_info=None):
         import torch.distributed as dist
+        kw = generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, len(prompts))
+        if "logprobs" in kw:
+            kw["logprob_info"] = logprob_info
+        if "speculate" in kw:
+            kw["spec_info"] = spec_info
         if n is not None:                                            # a family: one prompt (image or not), prefilled once, n texts
-            kw = {} if sampling is None else {f: sampling[0][f] for f in SAMPLING_FIELDS}
-            if penalties is not None and penalties[0] is not None:
-                kw.update({f: penalties[0][f] for f in penalties[0] if penalties[0].get(f) is not None})
-            if logprobs is not None:
-                kw.update(logprobs=logprobs[0], logprob_info=logprob_info)
-            if adapter is not None:
-                kw["adapter"] = adapter[0]
-            return generate(prompts[0], images=None if images is None else images[0], preload=preload, max_tokens=max_tokens, verbose=False,
-                            n=n, best_of=best_of, family_info=family_info, **kw, **({"share_prefix": True} if share_prefix else {}))
-        if speculate:                                                # (one prompt, greedy, no image: the handler saw to it)
-            return generate(prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, speculate=speculate, spec_info=spec_info,
-                            **({} if adapter is None else {"adapter": adapter[0]}))
-        if sampling is not None or adapter is not None or logprobs is not None or penalties is not None:   # (the handler kept these requests off the sharded path)
-            kw = {} if sampling is None else {f: [r[f] for r in sampling] for f in SAMPLING_FIELDS}
-            if penalties is not None:                                # one value per row; a row that asked for nothing: the defaults
-                for f, dflt in (("repetition_penalty", 1.0), ("presence_penalty", 0.0), ("frequency_penalty", 0.0), ("logit_bias", None)):
-                    kw[f] = [dflt if d is None or d.get(f) is None else d[f] for d in penalties]
-            if logprobs is not None:
-                kw.update(logprobs=logprobs, logprob_info=logprob_info)
-            if adapter is not None:
-                kw["adapter"] = adapter if len(prompts) > 1 else adapter[0]
-            return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, **kw)
-        if images is not None or (dist.is_available() and dist.is_initialized() and len(prompts) > 1):
+            kw.update(images=None if images is None else images[0], family_info=family_info, **({"share_prefix": True} if share_prefix else {}))
+        elif not kw and (images is not None or (dist.is_available() and dist.is_initialized() and len(prompts) > 1)):
             # mixed image + text requests -- and text-only batches whenever a process group exists -- go through the
-            # batch-sharded path (dist.py: one left-padded batch per rank; world size 1 = this GPU alone)
+            # batch-sharded path (dist.py: one left-padded batch per rank; world size 1 = this GPU alone); the handler kept
+            # every request with an option off it
             from .dist import generate_sharded
             return generate_sharded(prompts, images if images is not None else [None] * len(prompts), preload=preload,
                                     max_tokens=max_tokens)
-        return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False)
+        return generate(prompts if len(prompts) > 1 else prompts[0], preload=preload, max_tokens=max_tokens, verbose=False, **kw)
 
     def length_fn(prompt):
         return len(processor.tokenizer(_apply_chat_template(prompt, None, False)[0]).input_ids)
