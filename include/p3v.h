@@ -641,6 +641,41 @@ int p3v_penalize(const uint16_t* logits, int64_t row_stride, const p3v_penalty_r
                  int64_t seen_stride, const float* bias /* may be NULL */, int64_t bias_stride, const int32_t* fed /* may be NULL */,
                  uint16_t* out, int64_t out_stride, int rows, int n, void* stream);
 
+/* ---- guided decoding: a regular expression (or a choice list) walked on the device; added after round 6, no version change.
+ * A GUIDE is a DFA over bytes: states 1..S, S <= P3V_GUIDE_MAX_STATES; state 0 is dead, state 1 the start; delta[s][b] a uint16
+ * table, accept[s] a uint8 table.  The host guarantees that every state 1..S can reach an accepting state and has checked, against
+ * the vocabulary table, that every state either accepts or allows at least one token (guide.check).
+ * A VOCABULARY TABLE, one per processor, device-resident, built once: tok_off uint32 [n + 1] and tok_bytes uint8 [n_bytes], the
+ * byte string of token i at tok_bytes[tok_off[i] .. tok_off[i + 1]); specials, image-slot ids and unused ids are empty.
+ * PER-ROW STATE: a 16-byte record {flags, n_states, state, reserved} (state == P3V_GUIDE_DONE after EOS) and the row's own table
+ * region, delta [rows, 256, 256] uint16 and accept [rows, 256] uint8, both dense: row r's tables at delta + r * 65536 and
+ * accept + r * 256.  Admitting a request copies at most 128 KB into its row's region; there is no bank.
+ * walk(s, bytes): s = delta[s][b] for each byte b in order, stopping at 0; an entry above n_states counts as 0.
+ * The rule, for one row of bf16 logits, IN PLACE (in a step: the penalty state's adjusted rows, never the raw logits):
+ *   0. flags & 1 == 0 (an inactive row): the row is not touched (NaN payloads kept); the record is neither read further nor written.
+ *   1. fed != NULL and the row is active and not DONE: if fed[r] == eos the state becomes DONE; else if fed[r] lies in [0, n) and
+ *      has bytes, state = walk(state, bytes(fed[r])); otherwise the state is unchanged.  BEFORE masking, as p3v_penalize counts
+ *      the token the step was fed.  A fed token the guide bans leaves state 0, which step 4 reads as DONE.
+ *   2. token i is allowed iff -- i == eos: the state is DONE, or accept[state] != 0; any other i: the state is not DONE, the token
+ *      has bytes and walk(state, bytes(i)) != 0.
+ *   3. a banned position is overwritten with bf16 -inf (0xFF80) whatever it held; an allowed position is not stored to.
+ *   4. a record that points outside its tables -- n_states outside 1..255, or a state outside {-1, 1..n_states} -- is treated as
+ *      DONE (only EOS allowed) and is not written.  Whatever a record holds, nothing outside the row's region and the
+ *      vocabulary table is read; a token whose offsets do not lie in [0, n_bytes] in order counts as one without bytes.
+ * No atomics, plain vector stores, no allocation; every pointer is device memory, so the call is capturable.  One workgroup per
+ * row: the state is stored by one thread behind the barrier that follows every thread's read of it.  guide.reference_mask
+ * (NumPy) gives every output bit and every state. */
+#define P3V_GUIDE_MAX_STATES 255
+#define P3V_GUIDE_ACTIVE 1
+#define P3V_GUIDE_DONE (-1)
+typedef struct { int32_t flags, n_states, state, reserved; } p3v_guide_row_t;   /* 16 bytes */
+/* eos: the EOS id (a launch argument; outside [0, n) there is no EOS position).  fed may be NULL (the first token, drawn from the
+ * prefill logits: nothing is walked).  1 <= rows <= 65535, n >= 1, row_stride >= n, 0 <= n_bytes < 2^32, delta 16-byte aligned;
+ * P3V_ERR_ARG otherwise or for a null pointer other than fed, nothing launched. */
+int p3v_guide_mask(uint16_t* logits, int64_t row_stride, p3v_guide_row_t* rows_state, const uint16_t* delta, const uint8_t* accept,
+                   const uint32_t* tok_off, const uint8_t* tok_bytes, int64_t n_bytes, const int32_t* fed /* may be NULL */,
+                   int eos, int rows, int n, void* stream);
+
 /* ---- prompt prefix cache: KV block copy at any column phase (added after round 6, no version change).
  * One job copies tokens [t0_src, t0_src + n_tok) of batch row b_src of a source cache to tokens [t0_dst, t0_dst + n_tok) of
  * batch row b_dst of a destination cache, for ALL nl layers and nkv heads; up to P3V_KV_COPY_MAX_JOBS jobs share ONE launch

@@ -121,6 +121,15 @@ PENALTY_WORDS = C.sizeof(PenaltyRow) // 4        # 4
 PENALTY_ACTIVE, PENALTY_BIAS = 1, 2              # P3V_PENALTY_ACTIVE, P3V_PENALTY_BIAS
 
 
+class GuideRow(C.Structure):
+    """p3v_guide_row_t: one row's guide record (include/p3v.h)."""
+    _fields_ = [("flags", C.c_int32), ("n_states", C.c_int32), ("state", C.c_int32), ("reserved", C.c_int32)]
+
+
+GUIDE_WORDS = C.sizeof(GuideRow) // 4            # 4
+GUIDE_MAX_STATES, GUIDE_ACTIVE, GUIDE_DONE = 255, 1, -1     # P3V_GUIDE_MAX_STATES, P3V_GUIDE_ACTIVE, P3V_GUIDE_DONE
+
+
 class KvCopyJob(C.Structure):
     """p3v_kv_copy_job_t: one row's token run, source -> destination (include/p3v.h)."""
     _fields_ = [("k_src", vp), ("v_src", vp), ("k_dst", vp), ("v_dst", vp),
@@ -221,6 +230,7 @@ SIGNATURES = {
     "p3v_logprobs_step": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p3v_penalty_note": (i32, [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),     # added after round 6, no version change
     "p3v_penalize": (i32, [vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, vp]),   # added after round 6, no version change
+    "p3v_guide_mask": (i32, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32, vp]),   # added after round 6, no version change
     "p3v_spec_begin": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p3v_spec_end": (i32, [vp, C.POINTER(SpecState), i32, i32, vp]),
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),

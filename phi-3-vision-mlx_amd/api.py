@@ -32,6 +32,7 @@ from . import ops as model_ops
 from . import sampling as sampling_mod
 from . import logprobs as logprobs_mod
 from . import penalties as penalties_mod
+from . import guide as guide_mod
 from . import parallel as parallel_mod
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
@@ -312,7 +313,7 @@ def _last_logits(logits):
 
 
 def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_stopper=None, mask=None, pids=None, sampling=None,
-                logprobs=None, penalties=None):
+                logprobs=None, penalties=None, guides=None):
     """The decode loop of `_generate` (reference phi_3_vision_mlx.py:390-398): `n_steps` greedy steps after the prefill token,
     every token handed to the streamer and the stoppers in order, stops as the reference stops.
 
@@ -335,7 +336,12 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     the prefill token drawn from the adjusted prefill logits) -- the loop then drives the PENALISED replay for every step
     (model.penal_step / penal_logprob_step: each step counts the token it is fed), greedy rows under greedy sampling records.
     If the loop re-plans after a failed step, the rows' tables are rebuilt from the prompt and the tokens fed so far rather than
-    trusted.  None: the replays and launches of today."""
+    trusted.  None: the replays and launches of today.
+
+    guides: {"dfas", "table", "eos"} of a state whose rows carry guide records (model.set_guides, done by the caller with the
+    prefill token drawn from the masked prefill logits) -- the loop then drives the GUIDED replay for every step
+    (model.guide_step / guide_logprob_step: the penalised step plus p3v_guide_mask, which walks the token it is fed).  After a
+    re-plan the rows' states are rebuilt by walking the tokens fed so far.  None: the replays and launches of today."""
     graph_step = getattr(model, "greedy_step", None)
     records = None
     if sampling is not None:
@@ -358,6 +364,12 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
         if sampling is None:                                        # the penalised tail is the sampled one: greedy records
             model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
         graph_step = model.penal_step if logprobs is None else model.penal_logprob_step
+    if guides is not None:
+        if graph_step is None or not hasattr(model, "guide_step"):
+            raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
+        if sampling is None and penalties is None:                  # the guided tail is the sampled one: greedy records
+            model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
+        graph_step = model.guide_step if logprobs is None else model.guide_logprob_step
 
     def slot(g_):
         """the pinned records of the replay just enqueued ([B, 20], valid once the step has run)"""
@@ -410,7 +422,7 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             raise _StepFailed(f"device step failed: NaN logits (token ids {rows})")
         taken[:] = rows
         n_done += 1
-        if penalties is not None:
+        if penalties is not None or guides is not None:
             delivered.append(list(rows))
         streamer(rows)
         if p[3] is not None:
@@ -473,6 +485,11 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
                 fed = ([_rows(token0)] + delivered)[:n_done]
                 model.rebuild_penalties(st, penalties["prompt_ids"], np.asarray(fed, dtype=np.int32).T if n_done else None,
                                         0, penalties.get("pad"))
+            if guides is not None:                                  # the states may hold the dropped steps' walks: walk again
+                fed = ([_rows(token0)] + delivered)[:n_done]
+                model.set_guides(st, guides["dfas"], 0, states=[
+                    guide_mod.replay_state(d, guides["table"], [f[b] for f in fed], guides["eos"])
+                    for b, d in enumerate(guides["dfas"])])
             print("[phi3v] a decode step timed out in the fused attention + o_proj launch (is another process using this GPU?): "
                   "continuing with separate launches", file=sys.stderr)
 
@@ -579,7 +596,8 @@ def _prefill_with_store(model, store, dict_input, digests, max_tokens, kw_adapte
 def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=True, return_tps=False, early_stop=False,
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
               speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
-              frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None, share_prefix=False):
+              frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None, share_prefix=False,
+              guided_regex=None, guided_choice=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -608,7 +626,15 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     share_prefix=True (bf16 KV cache): the m rows of the family are registered as one (model.fork_state(share=True)) and every
     decode step reads the prompt's K/V once for all of them (include/p3v.h: p3v_attention_decode_family) instead of m times;
     the copies are made all the same.  On a bf16 cache without a family (n == 1, no best_of) it is accepted and does nothing; on a model whose
-    cache is int8 or mlx4 it raises whatever n is (the option cannot be honoured there, and says so before anything runs).  False -- the default -- allocates, launches and captures nothing that was not there before."""
+    cache is int8 or mlx4 it raises whatever n is (the option cannot be honoured there, and says so before anything runs).  False -- the default -- allocates, launches and captures nothing that was not there before.
+    guided_regex (a pattern of guide.py's subset) or guided_choice (a non-empty list of strings): the output's UTF-8 bytes up
+    to EOS must full-match it -- one value for every prompt, or a list of one value / None per prompt (a per-prompt list of
+    choices is a list of lists); both for one prompt raise.  The guide is compiled to a byte-level DFA on the host and walked on
+    the device (include/p3v.h: p3v_guide_mask): every step bans, in the penalised logits, the tokens whose bytes the row's
+    state does not allow, and allows EOS exactly in accepting states; the sampler then draws as usual and `logprobs` stay those
+    of the raw logits.  With n / best_of every completion walks its own state.  max_tokens can still cut the output before
+    the pattern completes.  None -- the default -- launches, allocates and captures nothing that was not there before; under
+    speculate a guide raises."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     n, fam = parallel_mod.check(n, best_of)
@@ -634,6 +660,17 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
                              getattr(getattr(model, "cfg", None), "vocab_size", None))
     pen = None if penalties_mod.off(pen) else pen
     penalties_mod.refuse_speculation(pen, speculate)
+    guides = guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice)
+    guide_mod.refuse_speculation(guides, speculate)
+    guide_state = None
+    if guides is not None:                                      # compiled and checked against the vocabulary before anything runs
+        if not hasattr(model, "set_guides"):
+            raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
+        table = guide_mod.vocab_for(processor.tokenizer, model.cfg.vocab_size)
+        for d in guides:
+            if d is not None:
+                guide_mod.checked(d, table, ID_EOS)
+        guide_state = dict(dfas=guides * fam if fam else guides, table=table, eos=ID_EOS)
     kw_adapter = {}
     if adapter is not None:
         from .engine import _check_adapter, adapter_list
@@ -682,6 +719,10 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         model.set_penalties(cache[0].state, penalties_mod.pack(pen), ids2, 0,
                             bias=penalties_mod.bias_table(pen, logits.shape[-1]), pad=pad)
         first = model.penalized_logits(cache[0].state, logits)
+    if guide_state is not None:                                 # behind the penalties: the mask works on the adjusted rows
+        model.set_guide_vocab(guide_state["table"], guide_state["eos"])
+        model.set_guides(cache[0].state, guide_state["dfas"])
+        first = model.guided_logits(cache[0].state, first)
     if sampled is None:
         token = model_ops.argmax(first.contiguous())[:, None]
     else:                                                       # draw 0 of every row: from the prefill logits
@@ -698,6 +739,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         speculative_loop(model, dict_input["input_ids"], token, cache, max_tokens - 1, speculate, streamer, token_stopper, stats)
         if spec_info is not None:
             spec_info.update(stats)
+    elif guide_state is not None:
+        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
+                    logprobs=collector, penalties=pen_state, guides=guide_state)
     elif pen_state is not None:
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
                     logprobs=collector, penalties=pen_state)
@@ -736,14 +780,15 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
              prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
              presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None,
-             share_prefix=False):
+             share_prefix=False, guided_regex=None, guided_choice=None):
     """reference phi_3_vision_mlx.py:1324-1374, plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
     strings, see `_generate`), plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
     log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`) and the penalties on tokens already seen
     (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`, and
-    `share_prefix` (the n rows of a family read their prompt's K/V once per decode step, see `_generate`)."""
+    `share_prefix` (the n rows of a family read their prompt's K/V once per decode step, see `_generate`), and guided decoding
+    (`guided_regex`, `guided_choice`: the output full-matches a regular expression or is one of a list, see `_generate`)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     n, fam = parallel_mod.check(n, best_of)                      # before a model is loaded or run
@@ -755,6 +800,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
     logprobs_mod.refuse_speculation(lp_wants, speculate)
     penalties_mod.refuse_speculation(penalties_mod.rows(B, repetition_penalty,
                                                         presence_penalty, frequency_penalty, logit_bias), speculate)
+    guide_mod.refuse_speculation(guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice),
+                                 speculate)                     # (a bad pattern raises here, before a model is loaded)
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
@@ -763,7 +810,9 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
                      spec_info=spec_info, logprobs=logprobs, logprob_info=logprob_info, repetition_penalty=repetition_penalty,
                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias,
                      **({} if (n, best_of, family_info) == (1, None, None) else dict(n=n, best_of=best_of, family_info=family_info)),
-                     **({"share_prefix": True} if share_prefix else {}))
+                     **({"share_prefix": True} if share_prefix else {}),
+                     **({} if guided_regex is None and guided_choice is None else
+                        dict(guided_regex=guided_regex, guided_choice=guided_choice)))
 
 
 # ----------------------------------------------------------------------------- score

@@ -48,7 +48,7 @@ import threading
 import numpy as np
 import torch
 
-from .request import (LOGPROB_ARGS, N_ARGS, PENALTY_ARGS, PREFIX_ARGS, RequestOptions, _check_adapter, adapter_list,  # noqa: F401
+from .request import (GUIDE_ARGS, LOGPROB_ARGS, N_ARGS, PENALTY_ARGS, PREFIX_ARGS, RequestOptions, _check_adapter, adapter_list,  # noqa: F401
                       carry, options_per_prompt, requested_logprobs, requested_n, requested_penalties)
 
 ID_EOS = 32007
@@ -71,7 +71,7 @@ def _set_device(device):
 
 class Request:
     __slots__ = ("inputs", "max_tokens", "tokens", "done", "row", "error", "S", "cancelled", "blocked_at", "sampling", "adapter",
-                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties",
+                 "image_digests", "cache_prompt", "prefix_len", "cached_tokens", "hit", "logprobs", "logprob_records", "penalties", "guide",
                  "family", "members", "completions", "family_done", "n", "asked_logprobs", "opts")
 
     def __init__(self, inputs, max_tokens, opts=None, **fields):
@@ -80,7 +80,7 @@ class Request:
         `logprob_records`), penalties, and for an engine with a prefix store image_digests, cache_prompt and prefix_len."""
         self.inputs, self.max_tokens = inputs, int(max_tokens)
         self.opts = opts = dataclasses.replace(opts or RequestOptions(), **fields)
-        for f in ("sampling", "adapter", "logprobs", "penalties", "image_digests", "prefix_len"):
+        for f in ("sampling", "adapter", "logprobs", "penalties", "guide", "image_digests", "prefix_len"):
             setattr(self, f, getattr(opts, f))
         self.cache_prompt = bool(opts.cache_prompt)
         self.cached_tokens, self.hit = 0, None                   # prompt tokens restored from the prefix store instead of computed
@@ -147,10 +147,10 @@ def make_family(head, n, m):
 
 
 def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
-             logprobs=None, penalties=None, n=None, best_of=None):
+             logprobs=None, penalties=None, n=None, best_of=None, guide=None):
     """Text in, text out (what the HTTP backend calls): the `generate` of ContinuousEngine, RegimeRouter and fleet.EngineFleet."""
     return _generate_text(self, self.processor, prompts, images, max_tokens, timeout, sampling, adapter, cache_prompt, info, logprobs,
-                          penalties, n, best_of)
+                          penalties, n, best_of, **({} if guide is None else {"guide": guide}))
 
 
 class ContinuousEngine:
@@ -217,6 +217,11 @@ class ContinuousEngine:
         logit_bias=), ...)` puts them beside the inputs in the same way -- the request's row then has its logits adjusted by the
         rule of include/p3v.h (p3v_penalty_row_t) before its token is drawn, from its first token on, whoever shares the
         batch; rows that did not ask pass through bit for bit.  While no active request asks, nothing of it runs.
+        Guided decoding: `submit(guide_args(inputs, regex=pattern), ...)` or `guide_args(inputs, choice=[...])` puts the request's
+        guide beside the inputs in the same way; it is compiled and checked against the vocabulary HERE, so a bad pattern fails
+        the handle at once.  The request's row then has its penalised logits masked by the rule of include/p3v.h
+        (p3v_guide_row_t) before its token is drawn, from its first token on; a refilled row starts from its own start state.
+        While no active request asks, nothing of it runs.
         n completions: `submit(n_args(inputs, n, best_of=None), ...)` puts the count beside the inputs in the same way, so the
         whole family travels to ONE engine.  The handle is then the family's HEAD: `.completions` lists the n returned
         Requests (head first; under best_of the n best of the m generated, best first, once `.family_done` is set), each with
@@ -227,6 +232,9 @@ class ContinuousEngine:
         try:
             opts = RequestOptions.read(inputs, sampling, adapter).checked(
                 self.adapter_names(), getattr(getattr(self.model, "cfg", None), "vocab_size", None), inputs)
+            if opts.guide is not None:                          # ... and can this vocabulary spell it?
+                from . import guide as guide_mod
+                guide_mod.checked(opts.guide, guide_mod.vocab_for(self.processor.tokenizer, self.model.cfg.vocab_size), ID_EOS)
             m = opts.m
             why = refusal(m, mlx4=bool(getattr(self.st, "mlx4", False)))
             if why:
@@ -272,6 +280,8 @@ class ContinuousEngine:
                 self.model.set_logprobs(self.st, [-1], r.row)    # the row's next occupant costs the launch one early exit
             if r.penalties is not None:
                 self.model.clear_penalties(self.st, r.row, 1)    # ... and is not penalised by this one's record
+            if r.guide is not None:
+                self.model.clear_guides(self.st, r.row, 1)       # ... nor masked by this one's guide
         r.done.set()
         r.settle()                                               # (the last member of a family sets its head's family_done)
 
@@ -303,6 +313,12 @@ class ContinuousEngine:
         except Exception as e:                                  # noqa: BLE001
             self.dead = e
             self._fail_all(RuntimeError(f"engine is down: {e!r}"))
+
+    def _set_guides(self, guides, row0):
+        """The rows' guides (None: an inactive record) at their start states; the vocabulary table goes to the model once."""
+        from . import guide as guide_mod
+        self.model.set_guide_vocab(guide_mod.vocab_for(self.processor.tokenizer, self.model.cfg.vocab_size), ID_EOS)
+        self.model.set_guides(self.st, guides, row0)
 
     def _rearm_workspace(self):
         """The in-launch split-KV merge expects an all-sentinel workspace (ops.attention_ws); after a poisoned step a late
@@ -367,6 +383,12 @@ class ContinuousEngine:
         penalized = any(r.penalties is not None for r in group)
         if not penalized and getattr(st, "penalty", None) is not None:
             self.model.clear_penalties(st, row0, n)              # a penalised request had these rows before: inactive now
+        guided = any(r.guide is not None for r in group)
+        if not guided and getattr(st, "guide", None) is not None:
+            self.model.clear_guides(st, row0, n)                 # a guided request had these rows before: inactive now
+        if guided:                                               # the rows' regions and start states BEFORE the first token is drawn
+            self._set_guides([r.guide for r in group], row0)
+        mask = (lambda lg: self.model.guided_logits(st, lg, row0)) if guided else (lambda lg: lg)
         if penalized:
             # the rows' records and prompt bits BEFORE the first token is drawn: it comes from the adjusted prefill logits, under
             # the group's sampling records (greedy members: temperature 0 = the arg-max of the adjusted row)
@@ -379,7 +401,11 @@ class ContinuousEngine:
                                      bias=penalties_mod.bias_table(prows, self.model.cfg.vocab_size), pad=pad)
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
             _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-            toks = self.model.sample_logits(st, self.model.penalized_logits(st, logits, row0), row0)
+            toks = self.model.sample_logits(st, mask(self.model.penalized_logits(st, logits, row0)), row0)
+        elif guided:                                             # the masked prefill logits, under the group's sampling records
+            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
+            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
+            toks = self.model.sample_logits(st, mask(logits), row0)
         elif any(r.sampling is not None for r in group):
             # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
@@ -440,10 +466,16 @@ class ContinuousEngine:
             bias = penalties_mod.bias_table([head.penalties], model.cfg.vocab_size)
             for row in rows:
                 model.set_penalties(st, penalties_mod.pack([head.penalties]), ids2, row, bias=bias)
-        if sampled or penalized or getattr(st, "sample_rows", None) is not None:
+        guided = head.guide is not None
+        if not guided and getattr(st, "guide", None) is not None:
+            for row in rows:
+                model.clear_guides(st, row, 1)
+        if guided:                                              # the leader's row; fork_rows hands region and start state to the others
+            self._set_guides([head.guide], row0)
+        if sampled or penalized or guided or getattr(st, "sample_rows", None) is not None:
             for r in members:                                    # (greedy family on a state with records: greedy records, counters reset)
                 model.set_sampling(st, _pack([r.sampling or _GREEDY], counter=0), r.row)
-        if sampled or penalized or scored:
+        if sampled or penalized or scored or guided:
             toks0, logits = model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
         else:
             toks0, logits = model.prefill_slot(st, row0, inputs, **kw_prefix), None
@@ -452,9 +484,11 @@ class ContinuousEngine:
             from .parallel import families_without
             self.families = families_without(self.families, rows) + [(tuple(rows), int(st.offset))]
             model.set_families(st, self.families)
-        if sampled or penalized:
-            toks = torch.cat([model.sample_logits(st, model.penalized_logits(st, logits, r.row) if penalized else logits, r.row)
-                              for r in members]).reshape(-1)
+        if sampled or penalized or guided:
+            def first_row(r):
+                lg = model.penalized_logits(st, logits, r.row) if penalized else logits
+                return model.guided_logits(st, lg, r.row) if guided else lg
+            toks = torch.cat([model.sample_logits(st, first_row(r), r.row) for r in members]).reshape(-1)
         else:
             toks = toks0.reshape(-1)[:1].expand(len(members))    # greedy: the one arg-max serves every row
         first = toks.tolist()
@@ -540,6 +574,8 @@ class ContinuousEngine:
                             self.model.set_logprobs(self.st, [-1], x.row)
                         if getattr(self.st, "penalty", None) is not None and x.penalties is not None:
                             self.model.clear_penalties(self.st, x.row, 1)
+                        if getattr(self.st, "guide", None) is not None and x.guide is not None:
+                            self.model.clear_guides(self.st, x.row, 1)
                     del x.logprob_records[:], x.tokens[:]
                 head.fail(e)
         admit = [r for r in admit if len(r.members) == 1]
@@ -565,6 +601,8 @@ class ContinuousEngine:
                     self.model.set_logprobs(self.st, [-1] * n, row0)
                 if getattr(self.st, "penalty", None) is not None and any(r.penalties is not None for r in group):
                     self.model.clear_penalties(self.st, row0, n)
+                if getattr(self.st, "guide", None) is not None and any(r.guide is not None for r in group):
+                    self.model.clear_guides(self.st, row0, n)
                 if n == 1:
                     group[0].fail(e)
                     continue
@@ -594,6 +632,10 @@ class ContinuousEngine:
         penalized = any(r.penalties is not None for r in active)
         if penalized:
             replay = self.model.penal_step
+        # the guided replay while any active row is guided: the penalised step plus the mask (rows without a guide are not touched)
+        guided = any(r.guide is not None for r in active)
+        if guided:
+            replay = self.model.guide_step
         scored = any(r.logprobs is not None for r in active)
         if scored:
             # ... followed by the log-probability launch while any active row wants records (the others: one early exit each).
@@ -603,6 +645,8 @@ class ContinuousEngine:
             replay = self.model.sample_logprob_step if any(r.sampling is not None for r in active) else self.model.logprob_step
             if penalized:
                 replay = self.model.penal_logprob_step
+            if guided:
+                replay = self.model.guide_logprob_step
             if g.get("n_replays", 0) >= g["history"].shape[1]:
                 self.model.restart_history(self.st)
         _, tok = replay(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
@@ -670,6 +714,15 @@ def penalty_args(inputs, repetition_penalty=1.0, presence_penalty=0.0, frequency
         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)))
 
 
+def guide_args(inputs, regex=None, choice=None):
+    """... the request's guide: a regular expression or a choice list (one of them; guide.py compiles and checks it at submit)."""
+    if regex is not None and choice is not None:
+        raise ValueError("guided_regex and guided_choice exclude each other: give one per prompt")
+    if regex is None and choice is None:
+        return inputs
+    return carry(inputs, GUIDE_ARGS, RequestOptions(guide={"regex": regex} if regex is not None else {"choice": list(choice)}))
+
+
 def logprob_args(inputs, logprobs):
     """... the request's `logprobs`: None, or N in 0..8."""
     return carry(inputs, LOGPROB_ARGS, RequestOptions(logprobs=logprobs))
@@ -707,7 +760,7 @@ def has_prefix_cache(engine):
 
 
 def _generate_text(engine, processor, prompts, images, max_tokens, timeout, sampling=None, adapter=None, cache_prompt=None, info=None,
-                   logprobs=None, penalties=None, n=None, best_of=None):
+                   logprobs=None, penalties=None, n=None, best_of=None, guide=None):
     """n / best_of (one prompt only): n completions of it from one prefill (`n_args`) -- the result is then the list of the n
     returned texts, info gains "seeds" (one per returned completion, when sampled) and its "logprobs" has one entry per
     returned completion.
@@ -716,10 +769,12 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
     "cached_tokens" (one count per prompt) and, when a prompt asked for them, "logprobs" (per prompt: logprobs.entry of its
     records -- token_ids / token_logprobs / ranks / top_logprobs over the tokens of the returned text -- or None).
     logprobs: None, N in 0..8, or one such value per prompt.  penalties: None, one {"repetition_penalty", "presence_penalty",
-    "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt."""
+    "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt.  guide: None, one {"regex": pattern} /
+    {"choice": [strings]} dict for every prompt, or one dict / None per prompt."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
-    opts = options_per_prompt(len(prompts), sampling, adapter, logprobs, penalties, cache_prompt, n, best_of)
+    opts = options_per_prompt(len(prompts), sampling, adapter, logprobs, penalties, cache_prompt, n, best_of,
+                              **({} if guide is None else {"guide": guide}))
     fam, lps = opts[0].m > 1, [o.logprobs for o in opts]
     images = images if images is not None else [None] * len(prompts)
     reqs = []

@@ -132,6 +132,13 @@ class CacheState:
         (fp32 [B, n]) -- or None before the first penalised request.  With `shared`, as the want-table is."""
         return self.shared.get("penalty")
 
+    @property
+    def guide(self):
+        """The guide state (model.set_guides): a dict of the rows' records (int32 [B, 4]) and their table regions (`delta` int16
+        [B, 256, 256]: the uint16 entries; `accept` uint8 [B, 256]) -- or None before the first guided request.  With `shared`,
+        as the penalty state is."""
+        return self.shared.get("guide")
+
     def rows_view(self, rows, offset, S):
         """Batch rows `rows` (a slice) as a cache of their own at `offset`, for a prompt of S tokens (model.prefill_slot): the same
         buffers sliced, no captured graphs, none of the slot state's roles (slots, serving, sampling records; the caller names the
@@ -835,7 +842,8 @@ class Phi3VModel:
         [pad, st.offset) (ops.kv_fork: one launch, every piece of the source read once), its cos / sin table rows and its
         pad_len (`pad`: the source row's pad_len where the caller knows it on the host; None reads it back).  K is stored rotated by logical position, so the columns are valid in any row.  NOT copied -- their setters
         take a row range and the caller sets them: sampling records, the penalty record / `seen` row / bias, the
-        log-probability want-table entry, the row's adapter.
+        log-probability want-table entry, the row's adapter.  A state with guides: the destination rows get the source row's
+        guide region and its record at the START state (an inactive source row makes inactive copies).
         share: also register the source and destination rows as a family that shares columns [pad, st.offset)
         (`set_families`; the rows leave whatever family they were in).  The copies are made all the same."""
         if st.mlx4:
@@ -858,6 +866,14 @@ class Phi3VModel:
         st.cos.index_copy_(0, idx, st.cos[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
         st.sin.index_copy_(0, idx, st.sin[src_row:src_row + 1].expand(len(dst_rows), -1, -1))
         st.pad_len.index_fill_(0, idx, pad)
+        gd = st.guide
+        if gd is not None:                                      # the leader's guide region, at its start state
+            k = len(dst_rows)
+            gd["delta"].index_copy_(0, idx, gd["delta"][src_row:src_row + 1].expand(k, -1, -1))
+            gd["accept"].index_copy_(0, idx, gd["accept"][src_row:src_row + 1].expand(k, -1))
+            rec = gd["rows"][src_row:src_row + 1].clone()
+            rec[:, 2] = 1
+            gd["rows"].index_copy_(0, idx, rec.expand(k, -1))
         if share:
             rows = (src_row, *dst_rows)
             self.set_families(st, families_without(st.families, rows) + [(rows, st.offset)])
@@ -1257,7 +1273,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         g["d_step"].zero_()                                      # the warm-up run counted as a step
         return g
 
-    def _decode_step(self, st, g, sampled=False, logprobs=False, penalized=False):
+    def _decode_step(self, st, g, sampled=False, logprobs=False, penalized=False, guided=False):
         """The launches of one decode step over the loop state `g` of a greedy capture: the layers, then the step's tail -- final
         norm + lm_head + arg-max + bookkeeping, or with sampled=True each row's token drawn under its record (`set_sampling`)
         where the greedy step has its arg-max.
@@ -1268,7 +1284,9 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         (p3v_logprobs_step) into the pinned `records` buffer; it reads the logits and the loop state and changes neither.
         penalized=True (a sampled tail): ONE more launch between lm_head and the tail -- p3v_penalize counts the token this step
         was fed into the rows' `seen` table and writes the adjusted rows to the penalty state's second buffer, which the tail
-        draws from (a T = 0 row: its arg-max); `logits` stays raw, for the caller and for the log-probability launch."""
+        draws from (a T = 0 row: its arg-max); `logits` stays raw, for the caller and for the log-probability launch.
+        guided=True (a penalised step): ONE more launch between p3v_penalize and the tail -- p3v_guide_mask walks the token this
+        step was fed through each guided row's DFA and bans, in the adjusted rows, what the new state does not allow."""
         cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
         self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
                      step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
@@ -1284,6 +1302,8 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         if penalized:
             pen = st.penalty
             ops.penalize(g["logits"], pen["rows"], pen["seen"], pen["bias"], g["tok"], out=pen["adj"])
+            if guided:
+                self._guide_mask(pen["adj"], st.guide, slice(0, st.B), g["tok"])
             ops.sample_step_end(pen["adj"], st.sample_rows, *end)
         elif sampled:
             ops.sample_step_end(g["logits"], st.sample_rows, *end)
@@ -1299,7 +1319,8 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy), "sample_graph" (a
         second capture over the same loop state, built on first use -- after the token and the cache length are in place, which
         its warm-up run reads), "logprob_graph" / "sample_logprob_graph" (either step followed by the log-probability launch,
-        built the same way), or "penal_graph" / "penal_logprob_graph" (the sampled step on penalised logits).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
+        built the same way), "penal_graph" / "penal_logprob_graph" (the sampled step on penalised logits) or "guide_graph" /
+        "guide_logprob_graph" (the penalised step with the guide mask in front of its tail).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
         st = cache[0].state
         if st.offset + 1 > st.T:
             raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
@@ -1309,10 +1330,12 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         if g.get("synced_offset") != st.offset:
             g["d_past"].fill_(st.offset)
         if which != "graph" and which not in g:
-            penalized = which in ("penal_graph", "penal_logprob_graph")
+            guided = which in ("guide_graph", "guide_logprob_graph")
+            penalized = guided or which in ("penal_graph", "penal_logprob_graph")
             g[which] = self._build_sample_graph(st, g, sampled=penalized or which in ("sample_graph", "sample_logprob_graph"),
-                                                logprobs=which in ("logprob_graph", "sample_logprob_graph", "penal_logprob_graph"),
-                                                penalized=penalized)
+                                                logprobs=which in ("logprob_graph", "sample_logprob_graph", "penal_logprob_graph",
+                                                                   "guide_logprob_graph"),
+                                                penalized=penalized, **({"guided": True} if guided else {}))
         g[which].launch()
         g["n_replays"] = g.get("n_replays", 0) + 1              # replay r, greedy or sampled, wrote its token to history[:, r - 1] (while it fits)
         st.offset += 1
@@ -1516,28 +1539,33 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
             raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
         return self._replay(token, cache, "sample_graph")
 
-    def _build_sample_graph(self, st, g, sampled=True, logprobs=False, penalized=False):
+    def _build_sample_graph(self, st, g, sampled=True, logprobs=False, penalized=False, guided=False):
         """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
         through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
         The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it.
         The two log-probability captures are made here as well: sampled=False keeps the greedy step as `_decode_step` runs it
         (the folded tail included), logprobs=True appends p3v_logprobs_step; their records land in a pinned buffer beside
         `history`, made with the first of them.  penalized=True: the sampled step with p3v_penalize in front of its tail; the
-        warm-up run's count of the fed token is taken back with the rest."""
+        warm-up run's count of the fed token is taken back with the rest.  guided=True: the penalised step with p3v_guide_mask
+        behind p3v_penalize; the warm-up run's walk of the fed token is taken back too."""
         torch.cuda.synchronize()
         if logprobs and "records" not in g:
             g["records"] = torch.zeros((st.B, g["history"].shape[1], ops.L.LOGPROB_WORDS), dtype=I32).pin_memory()
         saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
         saved_rows = st.sample_rows.clone() if sampled else None
         saved_seen = st.penalty["seen"].clone() if penalized else None
-        ws = g["gemm_ws_" + ("penalized" if penalized else "sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
-        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs, penalized=penalized), ws)
+        saved_guide = st.guide["rows"].clone() if guided else None
+        ws = g["gemm_ws_" + ("guided" if guided else "penalized" if penalized else "sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
+        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs, penalized=penalized,
+                                                        **({"guided": True} if guided else {})), ws)
         for k, v in saved.items():
             g[k].copy_(v)
         if sampled:
             st.sample_rows.copy_(saved_rows)
         if penalized:
             st.penalty["seen"].copy_(saved_seen)
+        if guided:
+            st.guide["rows"].copy_(saved_guide)
         torch.cuda.synchronize()
         return graph
 
@@ -1545,7 +1573,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
     @staticmethod
     def _drop_penalty_captures(st):
         g = st.graphs.get("greedy")
-        for k in ("penal_graph", "penal_logprob_graph"):
+        for k in ("penal_graph", "penal_logprob_graph", "guide_graph", "guide_logprob_graph"):   # (the guided step is a penalised one)
             if g is not None:
                 g.pop(k, None)
 
@@ -1631,6 +1659,112 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         if st.penalty is None or st.sample_rows is None or st.logprob_want is None:
             raise RuntimeError("penal_logprob_step: needs a penalty state and a want-table (set_penalties, set_logprobs)")
         return self._replay(token, cache, "penal_logprob_graph")
+
+    # ------------------------------------------------------------------ guided decoding (include/p3v.h: p3v_guide_row_t, guide.py)
+    @staticmethod
+    def _drop_guide_captures(st):
+        g = st.graphs.get("greedy")
+        for k in ("guide_graph", "guide_logprob_graph"):
+            if g is not None:
+                g.pop(k, None)
+
+    @_on_device
+    def set_guide_vocab(self, table, eos):
+        """The vocabulary table of guided decoding (guide.token_bytes: one per processor) as device tensors, made once, and the
+        EOS id the mask is launched with.  A different table replaces the old one; captures that baked the old pointers in are
+        dropped with their states' guide state."""
+        cur = getattr(self, "_guide_vocab", None)
+        if cur is not None and cur["table"] is table and cur["eos"] == int(eos):
+            return
+        if table.n < self.cfg.vocab_size:
+            raise ValueError(f"set_guide_vocab: the table covers {table.n} ids, the model's vocabulary holds {self.cfg.vocab_size}")
+        if cur is not None:
+            for st in list(self._states):
+                if st.guide is not None:
+                    self._drop_guide_captures(st)
+        dev = self.device
+        self._guide_vocab = dict(table=table, eos=int(eos), n_bytes=table.n_bytes,
+                                 tok_off=torch.from_numpy(table.tok_off.view(np.int32).copy()).to(dev),
+                                 tok_bytes=torch.from_numpy(table.tok_bytes.copy()).to(dev))
+
+    def _guide_mask(self, rows2d, gd, rows, fed):
+        v = self._guide_vocab
+        return ops.guide_mask(rows2d, gd["rows"][rows], gd["delta"][rows], gd["accept"][rows], v["tok_off"], v["tok_bytes"], v["eos"],
+                              fed=fed, n_bytes=v["n_bytes"])
+
+    @_on_device
+    def set_guides(self, st, guides, row0=0, states=None):
+        """Give rows row0 .. row0+n-1 of a state their guides (guide.Dfa, or None for a row without one): each row's table
+        region (at most 128 KB) and its record, at the start state -- or at states[i] (rebuilding a row after a re-plan).  The
+        first call makes the state's guide state (records [B, 4], delta [B, 256, 256], accept [B, 256]) and, where the state has
+        none, the penalty state and greedy sampling records, as `set_penalties` does: the guided step is the penalised one with
+        one more launch.  One H2D copy per operand, outside any graph.  Needs `set_guide_vocab`."""
+        from . import guide as guide_mod
+        if getattr(self, "_guide_vocab", None) is None:
+            raise RuntimeError("set_guides: no vocabulary table on this model (model.set_guide_vocab)")
+        dev, n = self.device, len(guides)
+        if row0 < 0 or row0 + n > st.B:
+            raise ValueError(f"set_guides: rows {row0} .. {row0 + n - 1} are outside the state's {st.B}")
+        gd = st.guide
+        if gd is None or gd["rows"].shape[0] != st.B:
+            gd = st.shared["guide"] = dict(rows=torch.zeros((st.B, ops.L.GUIDE_WORDS), dtype=I32, device=dev),
+                                           delta=torch.zeros((st.B, 256, 256), dtype=torch.int16, device=dev),
+                                           accept=torch.zeros((st.B, 256), dtype=torch.uint8, device=dev))
+            self._drop_guide_captures(st)
+        if st.penalty is None or st.penalty["seen"].shape[0] != st.B:
+            V = self.cfg.vocab_size                             # (every row inactive: p3v_penalize copies the logits through)
+            st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
+                                        seen=torch.zeros((st.B, V), dtype=I32, device=dev),
+                                        adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
+            self._drop_penalty_captures(st)
+        if st.sample_rows is None:
+            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))
+        recs = []
+        for i, dfa in enumerate(guides):
+            recs.append(guide_mod.record(dfa, 1 if states is None else states[i]))
+            if dfa is None:
+                continue
+            S1 = dfa.n_states + 1
+            gd["delta"][row0 + i, :S1].copy_(torch.from_numpy(dfa.delta.view(np.int16)))
+            gd["accept"][row0 + i, :S1].copy_(torch.from_numpy(dfa.accept))
+        if n:
+            gd["rows"][row0:row0 + n].copy_(torch.tensor(recs, dtype=I32))
+
+    @_on_device
+    def clear_guides(self, st, row0=0, n=None):
+        """Rows row0 .. row0+n-1 (default: to the end) become inactive: the guided step does not touch them."""
+        if st.guide is not None:
+            st.guide["rows"][row0:None if n is None else row0 + n].zero_()
+
+    @_on_device
+    def guided_logits(self, st, logits, row0=0):
+        """The masked rows of rows row0 .. row0+n-1 -- the eager form, for the token drawn from the PREFILL logits ([n, L, V] or
+        [n, V]: the last position; after `penalized_logits` where the rows are penalised): nothing is fed, no state moves.
+        bf16 [n, V], a new tensor; `logits` is not written."""
+        gd = st.guide
+        if gd is None:
+            raise RuntimeError("guided_logits: no guide state on this state (model.set_guides)")
+        last = (logits[:, -1, :] if logits.dim() == 3 else logits).clone()
+        return self._guide_mask(last, gd, slice(row0, row0 + last.shape[0]), None)
+
+    @_on_device
+    def guide_step(self, token, cache):
+        """One decode step on penalised AND guided logits through its captured graph (built on first use over the greedy
+        capture's loop state): lm_head, p3v_penalize, p3v_guide_mask (which walks the fed token), then the sampled tail on the
+        adjusted rows.  A state with active guides takes this replay for EVERY step.  Returns (raw logits [B,1,V], next_token
+        [B,1])."""
+        st = cache[0].state
+        if st.guide is None or st.penalty is None or st.sample_rows is None:
+            raise RuntimeError("guide_step: no guide state on this state (model.set_guides)")
+        return self._replay(token, cache, "guide_graph")
+
+    @_on_device
+    def guide_logprob_step(self, token, cache):
+        """`guide_step` followed by the log-probability launch -- on the RAW logits."""
+        st = cache[0].state
+        if st.guide is None or st.penalty is None or st.sample_rows is None or st.logprob_want is None:
+            raise RuntimeError("guide_logprob_step: needs a guide state and a want-table (set_guides, set_logprobs)")
+        return self._replay(token, cache, "guide_logprob_graph")
 
     # ------------------------------------------------------------------ token log-probabilities (include/p3v.h: p3v_logprob_t)
     @_on_device

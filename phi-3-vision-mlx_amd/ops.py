@@ -956,6 +956,30 @@ def penalize(logits2d, rows_params, seen, bias=None, fed=None, out=None):
     return out
 
 
+def guide_mask(logits2d, rows_state, delta, accept, tok_off, tok_bytes, eos, fed=None, n_bytes=None):
+    """The guide rule (include/p3v.h: p3v_guide_mask) IN PLACE on bf16 rows [rows, n] (rows may be strided): row r under its
+    record rows_state[r] (int32 [rows, 4]) and its table region delta[r] (int16 [rows, 256, 256]: the uint16 entries) / accept[r]
+    (uint8 [rows, 256]); tok_off int32 [>= n + 1] (the uint32 offsets) and tok_bytes uint8: the vocabulary table; fed (int32
+    [rows]): the token each row was fed this step, walked before the row is masked.  One launch; returns `logits2d`."""
+    rows, n = logits2d.shape
+    l_stride = _rows2d(logits2d, BF16, "logits")
+    _chk(rows_state, I32, "rows_state"), _chk(delta, torch.int16, "delta"), _chk(accept, torch.uint8, "accept")
+    _chk(tok_off, I32, "tok_off"), _chk(tok_bytes, torch.uint8, "tok_bytes")
+    if rows_state.shape != (rows, L.GUIDE_WORDS) or delta.shape != (rows, 256, 256) or accept.shape != (rows, 256):
+        raise ValueError(f"guide_mask: expected records [{rows}, {L.GUIDE_WORDS}], delta [{rows}, 256, 256] and accept [{rows}, 256], "
+                         f"got {tuple(rows_state.shape)}, {tuple(delta.shape)}, {tuple(accept.shape)}")
+    if tok_off.dim() != 1 or tok_off.numel() < n + 1 or tok_bytes.dim() != 1 or tok_bytes.numel() < 1:
+        raise ValueError(f"guide_mask: the vocabulary table covers {tok_off.numel() - 1} ids, the rows hold {n}")
+    n_bytes = tok_bytes.numel() if n_bytes is None else int(n_bytes)
+    if not 0 <= n_bytes <= tok_bytes.numel():
+        raise ValueError(f"guide_mask: n_bytes {n_bytes} lies outside tok_bytes ({tok_bytes.numel()} bytes)")
+    if fed is not None:
+        _chk_i32_vec(fed, rows, "fed")
+    L.check(L.lib().p3v_guide_mask(_p(logits2d), l_stride, _p(rows_state), _p(delta), _p(accept), _p(tok_off), _p(tok_bytes),
+                                   n_bytes, _p(fed), int(eos), rows, n, _stream()), "guide_mask")
+    return logits2d
+
+
 def spec_state(g, n_max, n_min):
     """p3v_spec_state_t over the loop-state buffers of a speculative capture (model._build_spec_graph)."""
     _chk(g["tok"], I32, "tok"), _chk(g["ctx"], I32, "ctx"), _chk(g["ctl"], I32, "ctl"), _chk(g["amax"], I32, "amax")

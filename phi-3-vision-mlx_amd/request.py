@@ -13,6 +13,7 @@ PREFIX_ARGS = "prefix_cache_args"   # keys of a request's options inside its `in
 LOGPROB_ARGS = "logprobs"
 PENALTY_ARGS = "penalties"
 N_ARGS = "n_completions"
+GUIDE_ARGS = "guide"
 
 
 @dataclasses.dataclass(frozen=True)
@@ -24,6 +25,7 @@ class RequestOptions:
     adapter: object = None          # None (the base model) or the name of an adapter of the model's bank
     logprobs: object = None         # None (off) or N in 0..8
     penalties: object = None        # None (off) or {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"}
+    guide: object = None            # None (off) or {"regex": pattern} / {"choice": [strings]}; checked: the compiled guide.Dfa
     n: object = 1                   # completions returned ...
     best_of: object = None          # ... of this many generated (None: n)
     image_digests: object = None    # prefix cache: one prefix.image_digest per source image
@@ -44,7 +46,8 @@ class RequestOptions:
             if d is not None and (not isinstance(d, dict) or set(d) - set(names)):
                 raise ValueError(f"{key} must be what engine.{maker} makes")
             fields.update({k: d[k] for k in names if d is not None and k in d})
-        return cls(sampling=sampling, adapter=adapter, logprobs=requested_logprobs(inputs), penalties=requested_penalties(inputs), **fields)
+        return cls(sampling=sampling, adapter=adapter, logprobs=requested_logprobs(inputs), penalties=requested_penalties(inputs),
+                   guide=requested_guide(inputs), **fields)
 
     def checked(self, adapters, vocab=None, inputs=None):
         """The normalised record, or the ValueError that names the bad value.  adapters: the names the model's bank knows;
@@ -54,11 +57,13 @@ class RequestOptions:
         from .penalties import request_row
         want = logprobs_mod.check(self.logprobs)
         pen = request_row(self.penalties, vocab)
+        from .guide import Dfa, request_guide
+        dfa = self.guide if isinstance(self.guide, Dfa) else request_guide(self.guide)   # (compiled here: a bad pattern is a ValueError)
         rec = _sampling_row(self.sampling)
         _check_adapter(self.adapter, adapters)
         self._check_prefix(inputs)
         n, m = check(self.n, self.best_of)
-        return dataclasses.replace(self, sampling=rec, logprobs=None if want == logprobs_mod.OFF else want, penalties=pen, n=n,
+        return dataclasses.replace(self, sampling=rec, logprobs=None if want == logprobs_mod.OFF else want, penalties=pen, guide=dfa, n=n,
                                    best_of=None if self.best_of is None else m)
 
     def _check_prefix(self, inputs):
@@ -91,6 +96,7 @@ CARRIERS = {
                   lambda o: {"image_digests": o.image_digests, "cache_prompt": o.cache_prompt, "prefix_len": o.prefix_len}),
     LOGPROB_ARGS: (lambda o: o.logprobs is not None, lambda o: o.logprobs),
     PENALTY_ARGS: (lambda o: o.penalties is not None, lambda o: dict(o.penalties)),
+    GUIDE_ARGS: (lambda o: o.guide is not None, lambda o: dict(o.guide)),
 }
 
 
@@ -104,6 +110,7 @@ def _requested(key):
 
 
 requested_logprobs, requested_penalties, requested_n = _requested(LOGPROB_ARGS), _requested(PENALTY_ARGS), _requested(N_ARGS)
+requested_guide = _requested(GUIDE_ARGS)
 
 
 def _sampling_row(sampling):
@@ -140,10 +147,12 @@ def adapter_list(adapter, n):
     return list(adapter)
 
 
-def options_per_prompt(n_prompts, sampling=None, adapter=None, logprobs=None, penalties=None, cache_prompt=None, n=None, best_of=None):
+def options_per_prompt(n_prompts, sampling=None, adapter=None, logprobs=None, penalties=None, cache_prompt=None, n=None, best_of=None,
+                       guide=None):
     """The arguments of a text-level call -> one record per prompt.  sampling: None or one settings dict per prompt; adapter: None,
     a name, or one name / None per prompt; logprobs: None, N, or one value per prompt; penalties: None, one dict for every prompt,
-    or one dict / None per prompt; n / best_of: a family, of one prompt only.  ValueError for a list of the wrong length."""
+    or one dict / None per prompt; n / best_of: a family, of one prompt only; guide: None, one {"regex"} / {"choice"} dict for every
+    prompt, or one dict / None per prompt.  ValueError for a list of the wrong length."""
     from .logprobs import OFF, wants
     from .parallel import check, refusal
     m = check(n, best_of)[1]
@@ -158,7 +167,11 @@ def options_per_prompt(n_prompts, sampling=None, adapter=None, logprobs=None, pe
         penalties = [penalties] * n_prompts
     elif len(penalties) != n_prompts:
         raise ValueError(f"penalties: {len(penalties)} values for {n_prompts} prompts")
+    if guide is None or isinstance(guide, dict):
+        guide = [guide] * n_prompts
+    elif len(guide) != n_prompts:
+        raise ValueError(f"guide: {len(guide)} values for {n_prompts} prompts")
     family = {"n": 1 if n is None else n, "best_of": best_of} if m > 1 else {}
     return [RequestOptions(sampling=None if sampling is None else sampling[i], adapter=adapter[i],
-                           logprobs=None if w is None or w[i] == OFF else w[i], penalties=penalties[i],
+                           logprobs=None if w is None or w[i] == OFF else w[i], penalties=penalties[i], guide=guide[i],
                            cache_prompt=True if cache_prompt is None else bool(cache_prompt), **family) for i in range(n_prompts)]

@@ -28,6 +28,12 @@
      of include/p3v.h (p3v_penalty_row_t) on each step's logits before temperature / top-k / top-p.  "logprobs" stay those of
      the raw logits.  A bad value -> 400 with the reason; so does an explicit "speculate" > 0 next to them, and the
      batch-sharded path.  Honoured on the one-request, the merged and the --continuous path; merged requests keep their own.)
+    (extension: "guided_regex": a pattern (guide.py's subset), or "guided_choice": a non-empty list of strings -- one of them per
+     request, applied to every prompt of it: the generated text up to EOS full-matches it (its UTF-8 bytes; a `▁` of a
+     sentencepiece vocabulary counts as a space); "max_tokens" can still cut it short.  The guide is a byte-level DFA walked on
+     the device (include/p3v.h: p3v_guide_row_t).  A bad type, an unsupported construct or more than 255 states -> 400 with the
+     reason; so does an explicit "speculate" > 0 next to it, and the batch-sharded path.  Honoured on the one-request, the
+     merged and the --continuous path; merged requests keep their own.)
     (extension: "n": 1 .. 16 completions of ONE prompt (a string), and "best_of": n .. 16 -- the prompt is prefilled once, its
      K/V forked into the other rows (include/p3v.h: p3v_kv_fork_t), and "responses" has n entries; "best_of" generates that many
      and returns the n with the largest cumulative raw-logit log-probability, best first.  A sampled request's "seeds" has
@@ -70,20 +76,21 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 MODEL_NAME = "phi-3-vision"
 
 
-def in_use(sampling=None, adapter=None, logprobs=None, penalties=None, n=None, best_of=None, speculate=0, cache_prompt=None, info=None):
+def in_use(sampling=None, adapter=None, logprobs=None, penalties=None, n=None, best_of=None, speculate=0, cache_prompt=None, info=None,
+           guide=None):
     """The keywords of the options a request really uses -- what the handler passes to a backend's `submit`, what
     ContinuousBackend passes to the engine's `generate`, and what a queued job keeps.  The rules, stated once:
 
       * a plain request passes no keyword at all (a backend that knows nothing of an option keeps serving plain requests);
         `images` is positional, and only when not None;
-      * sampling, adapter, logprobs and penalties are present only when not None;
+      * sampling, adapter, logprobs, penalties and guide are present only when not None;
       * n and best_of (both) are present only for a family -- m > 1 rows; the caller passes n=None otherwise;
       * speculate is present only when K > 0;
       * cache_prompt is present only when not None, and the handler passes it on only to a backend with a prefix store;
       * info (the dict a backend reports into) is present only when not None; the handler makes one exactly when the request is
         a family, asks for logprobs, speculates (K > 0), or the backend has a prefix store."""
     kw = {k: v for k, v in (("sampling", sampling), ("adapter", adapter), ("logprobs", logprobs), ("penalties", penalties),
-                            ("cache_prompt", cache_prompt), ("info", info)) if v is not None}
+                            ("cache_prompt", cache_prompt), ("info", info), ("guide", guide)) if v is not None}
     if n is not None:
         kw.update(n=n, best_of=best_of)
     if speculate:
@@ -244,6 +251,26 @@ def parse_penalties(request, n_prompts, vocab=None):
     return [d] * n_prompts
 
 
+def parse_guide(request, n_prompts):
+    """The "guided_regex" (a string) and "guided_choice" (a non-empty list of strings) fields of a request body -> None (both
+    absent or null) or one {"regex": pattern} / {"choice": [...]} dict per prompt (the same for each).  ValueError (-> 400) with
+    the reason on a wrong type, both at once, an unsupported construct or more than 255 states: the guide is compiled here (the
+    compiled form is cached by pattern, so the backend's own compilation is a look-up)."""
+    from . import guide as guide_mod
+    regex, choice = request.get("guided_regex"), request.get("guided_choice")
+    if regex is None and choice is None:
+        return None
+    if regex is not None and choice is not None:
+        raise ValueError("guided_regex and guided_choice exclude each other: send one")
+    if regex is not None and not isinstance(regex, str):
+        raise ValueError(f"guided_regex must be a string, got {type(regex).__name__}")
+    if choice is not None and (not isinstance(choice, list) or not choice or not all(isinstance(c, str) for c in choice)):
+        raise ValueError("guided_choice must be a non-empty list of strings")
+    d = {"regex": regex} if regex is not None else {"choice": list(choice)}
+    guide_mod.request_guide(d)
+    return [d] * n_prompts
+
+
 def token_decoder(engine):
     """id -> text piece for the "tokens" of a logprobs response: the backend's `decode_fn`, or its tokenizer; None without one."""
     from .engine import leaf_engines
@@ -384,9 +411,9 @@ class EngineQueue:
         self.thread.start()
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
-               penalties=None, n=None, best_of=None):
-        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images, in_use(sampling, adapter, logprobs, penalties, n, best_of),
-                   speculate, info)
+               penalties=None, n=None, best_of=None, guide=None):
+        job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images,
+                   in_use(sampling, adapter, logprobs, penalties, n, best_of, guide=guide), speculate, info)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -451,7 +478,7 @@ class EngineQueue:
                 opts, fam = first.opts, "n" in first.opts
                 spec = 0 if fam else first.speculate
                 kw = {k: opts[k] for k in ("adapter", "n", "best_of") if k in opts}
-                for k in ("logprobs", "penalties") + (() if spec else ("sampling",)):
+                for k in ("logprobs", "penalties", "guide") + (() if spec else ("sampling",)):
                     if any(k in j.opts for j in group):
                         kw[k] = [v for j in group for v in (j.opts.get(k) or [None] * len(j.prompts))]
                 lp_info, fam_info, stats = {}, {}, {}
@@ -498,6 +525,9 @@ REFUSALS = (
     ("penalties", "speculate", "penalties and logit_bias are not available under speculative decoding (a verify step scores several "
      "tokens per replay against one table); send speculate 0", True),
     ("penalties", "sharded", f"penalties and logit_bias are not available{_SHARDED}; run the server with --continuous, or send none", False),
+    ("guide", "speculate", "guided decoding is not available under speculative decoding (a verify step scores several tokens per "
+     "replay against one guide state); send speculate 0", True),
+    ("guide", "sharded", f"guided decoding is not available{_SHARDED}; run the server with --continuous, or send no guide", False),
     ("logprobs", "speculate", "logprobs are not available under speculative decoding (a verify step emits several tokens per replay); "
      "send speculate 0", True),
     ("logprobs", "sharded", f"logprobs are not available{_SHARDED}; run the server with --continuous, or send no logprobs", False),
@@ -555,8 +585,9 @@ def make_handler(engine, image_policy=None):
                     speculate = 0                               # (the server-wide default steps aside)
                 logprobs = parse_logprobs(request, len(prompts))
                 penalties = parse_penalties(request, len(prompts), vocab_of(engine))
+                guide = parse_guide(request, len(prompts))
                 sharded = None if family is not None else getattr(engine, "sharded_fn", None)   # (a family runs api.generate, images too)
-                asked = {"sampling": sampling, "adapter": adapter, "logprobs": logprobs, "penalties": penalties}
+                asked = {"sampling": sampling, "adapter": adapter, "logprobs": logprobs, "penalties": penalties, "guide": guide}
                 for option, where, message, explicit_only in REFUSALS:      # in order: the first that fails answers
                     present = speculate if option == "speculate" else asked[option] is not None
                     if not present or not (speculate if where == "speculate" else sharded is not None and sharded(prompts, images)):
@@ -570,7 +601,8 @@ def make_handler(engine, image_policy=None):
             store = prefix_counters(engine) is not None         # a backend with a prefix store reports what each prompt reused
             info = {} if family is not None or logprobs is not None or speculate or store else None
             try:
-                kw = in_use(sampling, adapter, logprobs, penalties, *(family or (None, None)), speculate, cache_prompt if store else None, info)
+                kw = in_use(sampling, adapter, logprobs, penalties, *(family or (None, None)), speculate, cache_prompt if store else None, info,
+                            guide=guide)
                 responses = engine.submit(prompts, max_tokens, *([images] if images is not None else []), **kw)
             except Exception as e:              # noqa: BLE001
                 self._send(500, {"error": f"{type(e).__name__}: {e}"})
@@ -634,8 +666,8 @@ class ContinuousBackend:
         return counters
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, cache_prompt=None, info=None, logprobs=None,
-               penalties=None, n=None, best_of=None):
-        kw = in_use(sampling, adapter, logprobs, penalties, n, best_of, 0, cache_prompt, info)
+               penalties=None, n=None, best_of=None, guide=None):
+        kw = in_use(sampling, adapter, logprobs, penalties, n, best_of, 0, cache_prompt, info, guide=guide)
         if "n" in kw and not isinstance(prompts, str) and len(prompts) == 1:
             prompts = prompts[0]                                 # a family: one prompt (a string for the engine), n texts back
         return self.engine.generate(prompts, images, max(1, min(int(max_tokens), self.max_tokens_cap)), self.timeout_s, **kw)
@@ -650,15 +682,21 @@ def serve_continuous(engine, port=8000, host="127.0.0.1", image_policy=None, **k
     return ThreadingHTTPServer((host, port), make_handler(backend, image_policy)), backend
 
 
-def generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, n_prompts):
+def generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, n_prompts, guide=None):
     """The per-row lists a queued group carries (EngineQueue._run) -> the keywords of `api.generate` for them.  A family (n is
     not None: one prompt) takes scalars -- its sampling record's fields, the penalty fields it gave, its N, its adapter --, n and
     best_of.  A speculating request (one greedy prompt) takes `speculate` and its adapter.  Any other request takes one value per
-    row (a single prompt: its adapter as a name), a row that asked for no penalty the defaults."""
+    row (a single prompt: its adapter as a name), a row that asked for no penalty the defaults.  guide: the rows' {"regex"} /
+    {"choice"} dicts (None for a row without one) -> `guided_regex` / `guided_choice`, one value per row."""
     fam = n is not None
     if speculate and not fam:
-        sampling = logprobs = penalties = None
+        sampling = logprobs = penalties = guide = None
     kw = {}
+    if guide is not None and any(d is not None for d in guide):
+        for f in ("regex", "choice"):
+            vals = [None if d is None else d.get(f) for d in guide]
+            if any(v is not None for v in vals):
+                kw["guided_" + f] = vals[0] if fam else vals
     if sampling is not None:
         kw.update({f: sampling[0][f] if fam else [r[f] for r in sampling] for f in SAMPLING_FIELDS})
     if penalties is not None and fam:
@@ -725,9 +763,9 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return images is not None or (dist.is_available() and dist.is_initialized())
 
     def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
-                    logprob_info=None, penalties=None, n=None, best_of=None, family_info=None):
+                    logprob_info=None, penalties=None, n=None, best_of=None, family_info=None, guide=None):
         import torch.distributed as dist
-        kw = generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, len(prompts))
+        kw = generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, len(prompts), guide)
         if "logprobs" in kw:
             kw["logprob_info"] = logprob_info
         if "speculate" in kw:
