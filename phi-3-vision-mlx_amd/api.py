@@ -34,6 +34,7 @@ from . import logprobs as logprobs_mod
 from . import penalties as penalties_mod
 from . import guide as guide_mod
 from . import parallel as parallel_mod
+from .steps import kind_for
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
@@ -342,34 +343,27 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     prefill token drawn from the masked prefill logits) -- the loop then drives the GUIDED replay for every step
     (model.guide_step / guide_logprob_step: the penalised step plus p3v_guide_mask, which walks the token it is fed).  After a
     re-plan the rows' states are rebuilt by walking the tokens fed so far.  None: the replays and launches of today."""
-    graph_step = getattr(model, "greedy_step", None)
-    records = None
+    # the ONE kind of step the arguments ask for (steps.py); an eager model class has none of its methods: the reference's loop
+    kind = kind_for(sampling is not None, penalties is not None, guides is not None, logprobs is not None)
+    graph_step = getattr(model, kind.method, None)
+    if penalties is not None and (graph_step is None or not hasattr(model, "penal_step")):
+        raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
+    if guides is not None and (graph_step is None or not hasattr(model, "guide_step")):
+        raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
+    records = want_dev = None
     if sampling is not None:
         records = sampling_mod.pack(sampling, counter=1)
-        graph_step = getattr(model, "sample_step", None)
         if graph_step is not None:
             model.set_sampling(cache[0].state, records)
         else:                                                       # an eager model: the records ride with the loop
             records = records.to(token.device)
-    want_dev = None
     if logprobs is not None:
         if graph_step is not None:
-            graph_step = getattr(model, "logprob_step" if sampling is None else "sample_logprob_step")
             model.set_logprobs(cache[0].state, logprobs.wants)
         else:                                                       # an eager model: one eager launch per step
             want_dev = torch.tensor(logprobs.wants, dtype=torch.int32, device=token.device)
-    if penalties is not None:
-        if graph_step is None or not hasattr(model, "penal_step"):
-            raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
-        if sampling is None:                                        # the penalised tail is the sampled one: greedy records
-            model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
-        graph_step = model.penal_step if logprobs is None else model.penal_logprob_step
-    if guides is not None:
-        if graph_step is None or not hasattr(model, "guide_step"):
-            raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
-        if sampling is None and penalties is None:                  # the guided tail is the sampled one: greedy records
-            model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
-        graph_step = model.guide_step if logprobs is None else model.guide_logprob_step
+    if kind.sampled and sampling is None:                           # the penalised / guided tail is the sampled one: greedy records
+        model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
 
     def slot(g_):
         """the pinned records of the replay just enqueued ([B, 20], valid once the step has run)"""
@@ -739,17 +733,9 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         speculative_loop(model, dict_input["input_ids"], token, cache, max_tokens - 1, speculate, streamer, token_stopper, stats)
         if spec_info is not None:
             spec_info.update(stats)
-    elif guide_state is not None:
-        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
-                    logprobs=collector, penalties=pen_state, guides=guide_state)
-    elif pen_state is not None:
-        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
-                    logprobs=collector, penalties=pen_state)
-    elif sampled is None:
-        greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, logprobs=collector)
     else:
         greedy_loop(model, token, cache, max_tokens - 1, streamer, token_stopper, logit_stopper, mask, pids, sampling=sampled,
-                    logprobs=collector)
+                    logprobs=collector, penalties=pen_state, guides=guide_state)
     result, gen_len = streamer.end()
     chosen = list(range(fam or B))
     if fam > n:                                                 # best_of: the n best of the m rows, by their own records

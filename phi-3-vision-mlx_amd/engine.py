@@ -48,6 +48,7 @@ import threading
 import numpy as np
 import torch
 
+from .steps import kind_for
 from .request import (GUIDE_ARGS, LOGPROB_ARGS, N_ARGS, PENALTY_ARGS, PREFIX_ARGS, RequestOptions, _check_adapter, adapter_list,  # noqa: F401
                       carry, options_per_prompt, requested_logprobs, requested_n, requested_penalties)
 
@@ -276,16 +277,39 @@ class ContinuousEngine:
             self._leave_family([r.row])
             self.rows[r.row] = None
             self.st.pad_len[r.row:r.row + 1].fill_(self.window)  # every key masked: the row idles at zero cost of correctness
-            if r.logprobs is not None:
-                self.model.set_logprobs(self.st, [-1], r.row)    # the row's next occupant costs the launch one early exit
-            if r.penalties is not None:
-                self.model.clear_penalties(self.st, r.row, 1)    # ... and is not penalised by this one's record
-            if r.guide is not None:
-                self.model.clear_guides(self.st, r.row, 1)       # ... nor masked by this one's guide
+            self._options_over(r.row, [r])
         r.done.set()
         r.settle()                                               # (the last member of a family sets its head's family_done)
 
     _finish = _release
+
+    def _options_over(self, row0, reqs, if_made=False):
+        """Rows row0 .. row0+n-1 stop carrying the options of the requests that held them: a row's next occupant costs the
+        log-probability launch one early exit, and is neither penalised by this one's record nor masked by its guide.  Each
+        table is touched only if one of the requests used it; if_made (a failed prefill, which may have stopped before a table
+        was made): and only if the state has it."""
+        st, n = self.st, len(reqs)
+        for field, table, end in (("logprobs", "logprob_want", lambda: self.model.set_logprobs(st, [-1] * n, row0)),
+                                  ("penalties", "penalty", lambda: self.model.clear_penalties(st, row0, n)),
+                                  ("guide", "guide", lambda: self.model.clear_guides(st, row0, n))):
+            if any(getattr(r, field) is not None for r in reqs) and not (if_made and getattr(st, table, None) is None):
+                end()
+
+    def _vacate(self, table, clear, spans):
+        """Newcomers that do not use an option take rows (spans: [(row0, n)]) whose previous occupant may have: where the state
+        has that option's table, the rows' records become inactive."""
+        if getattr(self.st, table, None) is not None:
+            for row0, n in spans:
+                getattr(self.model, clear)(self.st, row0, n)
+
+    def _first_tokens(self, logits, row0, penalized, guided):
+        """The first token of rows row0 .. row0+n-1, drawn from prefill logits under the rows' sampling records (a greedy row:
+        temperature 0 = the arg-max): of the adjusted rows if penalised, behind the guide mask if guided."""
+        if penalized:
+            logits = self.model.penalized_logits(self.st, logits, row0)
+        if guided:
+            logits = self.model.guided_logits(self.st, logits, row0)
+        return self.model.sample_logits(self.st, logits, row0)
 
     def _fail_all(self, error):
         with self.lock:
@@ -380,18 +404,16 @@ class ContinuousEngine:
         if self.adapter_names():
             # the rows' adapters (None -> -1: a refilled row must not keep its last occupant's) BEFORE their prefill reads them
             self.model.set_row_adapters(st, [r.adapter for r in group], row0)
-        penalized = any(r.penalties is not None for r in group)
-        if not penalized and getattr(st, "penalty", None) is not None:
-            self.model.clear_penalties(st, row0, n)              # a penalised request had these rows before: inactive now
-        guided = any(r.guide is not None for r in group)
-        if not guided and getattr(st, "guide", None) is not None:
-            self.model.clear_guides(st, row0, n)                 # a guided request had these rows before: inactive now
+        sampled, penalized, guided, scored = (any(getattr(r, f) is not None for r in group)
+                                              for f in ("sampling", "penalties", "guide", "logprobs"))
+        if not penalized:
+            self._vacate("penalty", "clear_penalties", [(row0, n)])
+        if not guided:
+            self._vacate("guide", "clear_guides", [(row0, n)])
         if guided:                                               # the rows' regions and start states BEFORE the first token is drawn
             self._set_guides([r.guide for r in group], row0)
-        mask = (lambda lg: self.model.guided_logits(st, lg, row0)) if guided else (lambda lg: lg)
         if penalized:
-            # the rows' records and prompt bits BEFORE the first token is drawn: it comes from the adjusted prefill logits, under
-            # the group's sampling records (greedy members: temperature 0 = the arg-max of the adjusted row)
+            # the rows' records and prompt bits BEFORE the first token is drawn: it comes from the adjusted prefill logits
             from . import penalties as penalties_mod
             prows = [r.penalties or penalties_mod.INACTIVE for r in group]
             ids2 = np.asarray(inputs["input_ids"])
@@ -399,30 +421,24 @@ class ContinuousEngine:
             pad = (np.asarray(inputs["mask"]).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if "mask" in inputs else None
             self.model.set_penalties(st, penalties_mod.pack(prows), ids2, row0,
                                      bias=penalties_mod.bias_table(prows, self.model.cfg.vocab_size), pad=pad)
+        # 1. the records: a group with any of the three options draws its first token under them (greedy members: temperature
+        # 0), counters reset -- draw 0 comes from the prefill logits; a plain group writes greedy records only where a sampled
+        # request may have had these rows before
+        drawn = sampled or penalized or guided
+        if drawn or getattr(st, "sample_rows", None) is not None:
             self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
-            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-            toks = self.model.sample_logits(st, mask(self.model.penalized_logits(st, logits, row0)), row0)
-        elif guided:                                             # the masked prefill logits, under the group's sampling records
-            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
-            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-            toks = self.model.sample_logits(st, mask(logits), row0)
-        elif any(r.sampling is not None for r in group):
-            # the group's records (greedy members: temperature 0), counters reset: draw 0 comes from the prefill logits
-            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
-            _, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-            toks = self.model.sample_logits(st, logits, row0)
-        elif any(r.logprobs is not None for r in group):         # (greedy, scored: the same prefill, its logits kept)
-            if getattr(st, "sample_rows", None) is not None:
-                self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
+        # 2. the prefill: its logits kept where the first token is drawn or scored (the plain call otherwise: no keyword)
+        if drawn or scored:
             toks, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
         else:
-            if getattr(st, "sample_rows", None) is not None:     # a sampled request had these rows before: greedy records now
-                self.model.set_sampling(st, _pack([_GREEDY] * n, counter=0), row0)
             toks = self.model.prefill_slot(st, row0, inputs, **kw_prefix)
+        # 3. the first token: drawn, or the prefill's own arg-max
+        if drawn:
+            toks = self._first_tokens(logits, row0, penalized, guided)
         first = toks.reshape(-1).tolist()
         if min(first) < 0:
             raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
-        if any(r.logprobs is not None for r in group):
+        if scored:
             # the rows' wants into the table (-1 for the members that did not ask), the first token's record from the prefill logits
             self.model.set_logprobs(st, [-1 if r.logprobs is None else r.logprobs for r in group], row0)
             recs0 = _unpack_records(self.model.logprobs_of(st, logits, toks, row0))
@@ -457,9 +473,8 @@ class ContinuousEngine:
             for row in rows:
                 model.set_row_adapters(st, [head.adapter], row)
         penalized, sampled, scored = head.penalties is not None, head.sampling is not None, head.logprobs is not None
-        if not penalized and getattr(st, "penalty", None) is not None:
-            for row in rows:
-                model.clear_penalties(st, row, 1)
+        if not penalized:
+            self._vacate("penalty", "clear_penalties", [(row, 1) for row in rows])
         if penalized:
             from . import penalties as penalties_mod
             ids2 = np.asarray(inputs["input_ids"]).reshape(1, -1)
@@ -467,9 +482,8 @@ class ContinuousEngine:
             for row in rows:
                 model.set_penalties(st, penalties_mod.pack([head.penalties]), ids2, row, bias=bias)
         guided = head.guide is not None
-        if not guided and getattr(st, "guide", None) is not None:
-            for row in rows:
-                model.clear_guides(st, row, 1)
+        if not guided:
+            self._vacate("guide", "clear_guides", [(row, 1) for row in rows])
         if guided:                                              # the leader's row; fork_rows hands region and start state to the others
             self._set_guides([head.guide], row0)
         if sampled or penalized or guided or getattr(st, "sample_rows", None) is not None:
@@ -485,10 +499,7 @@ class ContinuousEngine:
             self.families = families_without(self.families, rows) + [(tuple(rows), int(st.offset))]
             model.set_families(st, self.families)
         if sampled or penalized or guided:
-            def first_row(r):
-                lg = model.penalized_logits(st, logits, r.row) if penalized else logits
-                return model.guided_logits(st, lg, r.row) if guided else lg
-            toks = torch.cat([model.sample_logits(st, first_row(r), r.row) for r in members]).reshape(-1)
+            toks = torch.cat([self._first_tokens(logits, r.row, penalized, guided) for r in members]).reshape(-1)
         else:
             toks = toks0.reshape(-1)[:1].expand(len(members))    # greedy: the one arg-max serves every row
         first = toks.tolist()
@@ -570,12 +581,7 @@ class ContinuousEngine:
                         if self.rows[x.row] is x:
                             self.rows[x.row] = None
                         self.st.pad_len[x.row:x.row + 1].fill_(self.window)
-                        if getattr(self.st, "logprob_want", None) is not None and x.logprobs is not None:
-                            self.model.set_logprobs(self.st, [-1], x.row)
-                        if getattr(self.st, "penalty", None) is not None and x.penalties is not None:
-                            self.model.clear_penalties(self.st, x.row, 1)
-                        if getattr(self.st, "guide", None) is not None and x.guide is not None:
-                            self.model.clear_guides(self.st, x.row, 1)
+                        self._options_over(x.row, [x], if_made=True)
                     del x.logprob_records[:], x.tokens[:]
                 head.fail(e)
         admit = [r for r in admit if len(r.members) == 1]
@@ -597,12 +603,7 @@ class ContinuousEngine:
                         self.rows[r.row] = None
                     self.st.pad_len[r.row:r.row + 1].fill_(self.window)
                     del r.logprob_records[:]
-                if getattr(self.st, "logprob_want", None) is not None and any(r.logprobs is not None for r in group):
-                    self.model.set_logprobs(self.st, [-1] * n, row0)
-                if getattr(self.st, "penalty", None) is not None and any(r.penalties is not None for r in group):
-                    self.model.clear_penalties(self.st, row0, n)
-                if getattr(self.st, "guide", None) is not None and any(r.guide is not None for r in group):
-                    self.model.clear_guides(self.st, row0, n)
+                self._options_over(row0, group, if_made=True)
                 if n == 1:
                     group[0].fail(e)
                     continue
@@ -625,33 +626,19 @@ class ContinuousEngine:
         if not active:
             return 0
         g = self.model.decode_graph(self.st)
-        # the sampled replay while any active row samples (its greedy rows take the arg-max there too), the greedy one otherwise
-        replay = self.model.sample_step if any(r.sampling is not None for r in active) else self.model.greedy_step
-        # the penalised replay while any active row is penalised (a penalised row is active from its prefill to its release, so
-        # every one of its steps counts the token it is fed; the other rows' logits pass through bit for bit)
-        penalized = any(r.penalties is not None for r in active)
-        if penalized:
-            replay = self.model.penal_step
-        # the guided replay while any active row is guided: the penalised step plus the mask (rows without a guide are not touched)
-        guided = any(r.guide is not None for r in active)
-        if guided:
-            replay = self.model.guide_step
-        scored = any(r.logprobs is not None for r in active)
-        if scored:
-            # ... followed by the log-probability launch while any active row wants records (the others: one early exit each).
-            # Records are indexed by the capture's step counter, which EVERY replay advances, plain and sampled ones too, and
-            # they have as many slots as `history` (made with the first scored replay): a long-lived state starts the counter
-            # afresh when the slots have run out, whether or not the record buffer exists yet.
-            replay = self.model.sample_logprob_step if any(r.sampling is not None for r in active) else self.model.logprob_step
-            if penalized:
-                replay = self.model.penal_logprob_step
-            if guided:
-                replay = self.model.guide_logprob_step
-            if g.get("n_replays", 0) >= g["history"].shape[1]:
-                self.model.restart_history(self.st)
+        # ONE kind of replay for all rows (steps.py): the sampled tail while any active row samples (its greedy rows take the
+        # arg-max there too), the penalised one while any is penalised (such a row is active from its prefill to its release, so
+        # every one of its steps counts the token it is fed; the other rows pass through bit for bit), the guided one while any
+        # is guided, each followed by the log-probability launch while any row wants records (the others: one early exit each)
+        kind = kind_for(*(any(getattr(r, f) is not None for r in active) for f in ("sampling", "penalties", "guide", "logprobs")))
+        # Records are indexed by the capture's step counter, which EVERY replay advances, and have as many slots as `history`: a
+        # long-lived state starts the counter afresh when the slots have run out, whether or not the record buffer exists yet.
+        if kind.logprobs and g.get("n_replays", 0) >= g["history"].shape[1]:
+            self.model.restart_history(self.st)
+        replay = getattr(self.model, kind.method)
         _, tok = replay(g["host_tok"] if g["host_tok"] is not None else g["tok"].view(-1, 1), self.cache)
         rows = tok.reshape(-1).tolist()                          # ONE D2H copy per step (the reference's mx.eval)
-        recs = _unpack_records(g["records"][:, g["n_replays"] - 1]) if scored else None   # (pinned: the step wrote them itself)
+        recs = _unpack_records(g["records"][:, g["n_replays"] - 1]) if kind.logprobs else None   # (pinned: the step wrote them itself)
         self.steps += 1
         poisoned = False
         for r in active:

@@ -28,7 +28,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, steps
 from .parallel import families_without, family_pays, family_table
 from .config import head_dim, is_vision, rope_scaling_factor
 from .weights import Q4Weight, mlx_quantize, q4_repack
@@ -207,6 +207,7 @@ class LayerCache:
         self.state.offset = int(v)
 
 
+@steps.methods(_on_device)                                      # the eight public step methods: steps.py's table
 class Phi3VModel:
     def __init__(self, cfg, weights, device="cuda:0"):
         if not torch.cuda.is_available():
@@ -1273,54 +1274,53 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         g["d_step"].zero_()                                      # the warm-up run counted as a step
         return g
 
-    def _decode_step(self, st, g, sampled=False, logprobs=False, penalized=False, guided=False):
-        """The launches of one decode step over the loop state `g` of a greedy capture: the layers, then the step's tail -- final
-        norm + lm_head + arg-max + bookkeeping, or with sampled=True each row's token drawn under its record (`set_sampling`)
-        where the greedy step has its arg-max.
+    def _decode_step(self, st, g, kind=steps.GREEDY):
+        """The launches of one decode step of a kind (steps.StepKind) over the loop state `g` of a greedy capture: the layers,
+        then the step's tail -- final norm + lm_head + arg-max + bookkeeping, or with kind.sampled each row's token drawn under
+        its record (`set_sampling`) where the greedy step has its arg-max.
         (round 6) the step's two ends have no launch of their own where the library folds them into the first / last projection
         (B = 1 on bf16, e4m3 or 4-bit weights: ops.gemv_step_begin / gemv_step_end; 129 launches per step instead of 131); the
         sampled tail always goes through `_proj` (every weight format, adapters honoured).
-        logprobs=True: ONE more launch behind that tail, whichever it is -- the record of each row's emitted token
+        kind.logprobs: ONE more launch behind that tail, whichever it is -- the record of each row's emitted token
         (p3v_logprobs_step) into the pinned `records` buffer; it reads the logits and the loop state and changes neither.
-        penalized=True (a sampled tail): ONE more launch between lm_head and the tail -- p3v_penalize counts the token this step
+        kind.penalized (a sampled tail): ONE more launch between lm_head and the tail -- p3v_penalize counts the token this step
         was fed into the rows' `seen` table and writes the adjusted rows to the penalty state's second buffer, which the tail
         draws from (a T = 0 row: its arg-max); `logits` stays raw, for the caller and for the log-probability launch.
-        guided=True (a penalised step): ONE more launch between p3v_penalize and the tail -- p3v_guide_mask walks the token this
+        kind.guided (a penalised step): ONE more launch between p3v_penalize and the tail -- p3v_guide_mask walks the token this
         step was fed through each guided row's DFA and bans, in the adjusted rows, what the new state does not allow."""
         cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
         self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
                      step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
         end = (g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
-        if not sampled:
+        if not kind.sampled:
             w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
             if st.B == 1 and self._packed(head) is not None:
                 w_fold = self.w13[head]                         # one row: the 13-bit packed copy of the bf16 matrix
             if (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
                     and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
-                return self._logprobs_tail(st, g) if logprobs else None
+                return self._logprobs_tail(st, g) if kind.logprobs else None
         self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output)
-        if penalized:
+        if kind.penalized:
             pen = st.penalty
             ops.penalize(g["logits"], pen["rows"], pen["seen"], pen["bias"], g["tok"], out=pen["adj"])
-            if guided:
+            if kind.guided:
                 self._guide_mask(pen["adj"], st.guide, slice(0, st.B), g["tok"])
             ops.sample_step_end(pen["adj"], st.sample_rows, *end)
-        elif sampled:
+        elif kind.sampled:
             ops.sample_step_end(g["logits"], st.sample_rows, *end)
         else:
             ops.step_end(g["logits"], *end)
-        if logprobs:
+        if kind.logprobs:
             self._logprobs_tail(st, g)
 
     def _logprobs_tail(self, st, g):
         ops.logprobs_step(g["logits"], g["next_tok"], st.logprob_want, g["d_step"], g["records"])
 
-    def _replay(self, token, cache, which):
-        """One decode step through a captured graph of the state's greedy capture: `which` = "graph" (greedy), "sample_graph" (a
-        second capture over the same loop state, built on first use -- after the token and the cache length are in place, which
-        its warm-up run reads), "logprob_graph" / "sample_logprob_graph" (either step followed by the log-probability launch,
-        built the same way), "penal_graph" / "penal_logprob_graph" (the sampled step on penalised logits) or "guide_graph" /
-        "guide_logprob_graph" (the penalised step with the guide mask in front of its tail).  Returns (logits [B,1,V], next_token [B,1]), views of persistent buffers."""
+    def _replay(self, token, cache, kind):
+        """One decode step of a kind (steps.StepKind) through its captured graph.  The greedy kind's graph is the greedy capture's
+        own; every other kind is a further capture over the same loop state, built on first use (`_build_capture`) -- after the
+        token and the cache length are in place, which its warm-up run reads.  Returns (logits [B,1,V], next_token [B,1]), views
+        of persistent buffers."""
         st = cache[0].state
         if st.offset + 1 > st.T:
             raise ValueError(f"KV cache overflow: {st.offset}+1 > {st.T} (prompt + max_tokens)")
@@ -1329,14 +1329,9 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
             g["tok"].copy_(token.reshape(-1).to(self.device, I32))   # first step / caller-chosen token
         if g.get("synced_offset") != st.offset:
             g["d_past"].fill_(st.offset)
-        if which != "graph" and which not in g:
-            guided = which in ("guide_graph", "guide_logprob_graph")
-            penalized = guided or which in ("penal_graph", "penal_logprob_graph")
-            g[which] = self._build_sample_graph(st, g, sampled=penalized or which in ("sample_graph", "sample_logprob_graph"),
-                                                logprobs=which in ("logprob_graph", "sample_logprob_graph", "penal_logprob_graph",
-                                                                   "guide_logprob_graph"),
-                                                penalized=penalized, **({"guided": True} if guided else {}))
-        g[which].launch()
+        if kind.capture not in g:
+            g[kind.capture] = self._build_capture(st, g, kind)
+        g[kind.capture].launch()
         g["n_replays"] = g.get("n_replays", 0) + 1              # replay r, greedy or sampled, wrote its token to history[:, r - 1] (while it fits)
         st.offset += 1
         g["synced_offset"] = st.offset
@@ -1363,14 +1358,6 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         (reference phi_3_vision_mlx.py:385-386).  Returns (token [B,1] int32 on the device, cache)."""
         logits, cache = self(**inputs, max_tokens=max_tokens)
         return ops.argmax(logits[:, -1, :].contiguous())[:, None], cache
-
-    @_on_device
-    def greedy_step(self, token, cache):
-        """One greedy decode step through the captured graph.  Equivalent to
-        `logits, cache = model(input_ids=token, cache=cache); next = argmax(logits[:, -1])`
-        (reference phi_3_vision_mlx.py:391-392).  Returns (logits [B,1,V], next_token [B,1])
-        -- views of persistent buffers, valid until the next call."""
-        return self._replay(token, cache, "graph")
 
     # ------------------------------------------------------------------ speculative greedy decoding (include/p3v.h, speculate.py)
     def spec_refusal(self, st=None, K=None):
@@ -1530,53 +1517,56 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         last = logits[:, -1, :] if logits.dim() == 3 else logits
         return ops.sample(last, st.sample_rows[row0:row0 + last.shape[0]])[:, None]
 
-    @_on_device
-    def sample_step(self, token, cache):
-        """One SAMPLED decode step through its captured graph: `greedy_step` with each row's token drawn under its record
-        (`set_sampling`) instead of the arg-max.  The sampled graph is a second capture over the greedy graph's loop-state buffers
-        (built on first use): greedy and sampled replays may alternate on one state.  Returns (logits [B,1,V], next_token [B,1])."""
-        if cache[0].state.sample_rows is None:
-            raise RuntimeError("sample_step: no sampling records on this state (model.set_sampling)")
-        return self._replay(token, cache, "sample_graph")
+    # ------------------------------------------------------------------ captures of the step kinds (steps.py has the table)
+    # what a warm-up run of a kind moves beside the loop state, by flag: it is saved before the capture and put back after it
+    _WARMUP_MOVES = (("sampled", lambda st: st.sample_rows),        # the records' draw counters
+                     ("penalized", lambda st: st.penalty["seen"]),  # the count of the fed token
+                     ("guided", lambda st: st.guide["rows"]))       # the walk of the fed token
 
-    def _build_sample_graph(self, st, g, sampled=True, logprobs=False, penalized=False, guided=False):
-        """Capture the sampled step over the loop state of the greedy capture `g`: the same layers, the final norm + lm_head
-        through `_proj` (every weight format, adapters honoured), then p3v_sample_step_end where the greedy step has its arg-max.
-        The warm-up run leaves every piece of loop state -- tokens, counters, history, the records' draw counters -- as it found it.
-        The two log-probability captures are made here as well: sampled=False keeps the greedy step as `_decode_step` runs it
-        (the folded tail included), logprobs=True appends p3v_logprobs_step; their records land in a pinned buffer beside
-        `history`, made with the first of them.  penalized=True: the sampled step with p3v_penalize in front of its tail; the
-        warm-up run's count of the fed token is taken back with the rest.  guided=True: the penalised step with p3v_guide_mask
-        behind p3v_penalize; the warm-up run's walk of the fed token is taken back too."""
+    def _build_capture(self, st, g, kind):
+        """Capture the step of a kind over the loop state of the greedy capture `g` (`_decode_step` has the launches).  The warm-up
+        run leaves every piece of state it moves -- tokens, counters, history, and by the kind's flags the `_WARMUP_MOVES` -- as
+        it found it.  The records of the log-probability kinds land in a pinned buffer beside `history`, made with the first of
+        them (row b's record of replay r: `records[b, r - 1]`).  Each capture owns its GEMM workspaces."""
         torch.cuda.synchronize()
-        if logprobs and "records" not in g:
+        if kind.logprobs and "records" not in g:
             g["records"] = torch.zeros((st.B, g["history"].shape[1], ops.L.LOGPROB_WORDS), dtype=I32).pin_memory()
-        saved = {k: g[k].clone() for k in ("tok", "next_tok", "d_step", "d_past", "history")}
-        saved_rows = st.sample_rows.clone() if sampled else None
-        saved_seen = st.penalty["seen"].clone() if penalized else None
-        saved_guide = st.guide["rows"].clone() if guided else None
-        ws = g["gemm_ws_" + ("guided" if guided else "penalized" if penalized else "sampled" if sampled else "greedy") + ("_logprobs" if logprobs else "")] = {}
-        graph = self._capture(lambda: self._decode_step(st, g, sampled=sampled, logprobs=logprobs, penalized=penalized,
-                                                        **({"guided": True} if guided else {})), ws)
-        for k, v in saved.items():
-            g[k].copy_(v)
-        if sampled:
-            st.sample_rows.copy_(saved_rows)
-        if penalized:
-            st.penalty["seen"].copy_(saved_seen)
-        if guided:
-            st.guide["rows"].copy_(saved_guide)
+        moved = [g[k] for k in ("tok", "next_tok", "d_step", "d_past", "history")]
+        moved += [of(st) for flag, of in self._WARMUP_MOVES if getattr(kind, flag)]
+        saved = [t.clone() for t in moved]
+        ws = g["gemm_ws_" + kind.capture] = {}
+        graph = self._capture(lambda: self._decode_step(st, g, kind), ws)
+        for t, v in zip(moved, saved):
+            t.copy_(v)
         torch.cuda.synchronize()
         return graph
 
-    # ------------------------------------------------------------------ penalties and logit_bias (include/p3v.h: p3v_penalty_row_t)
     @staticmethod
-    def _drop_penalty_captures(st):
+    def _drop_captures(st, flag):
+        """Forget the state's captures of every kind with a flag set: they baked in a pointer that is being replaced."""
         g = st.graphs.get("greedy")
-        for k in ("penal_graph", "penal_logprob_graph", "guide_graph", "guide_logprob_graph"):   # (the guided step is a penalised one)
-            if g is not None:
-                g.pop(k, None)
+        if g is not None:
+            for kind in steps.with_flag(flag):
+                g.pop(kind.capture, None)
 
+    def _greedy_records(self, st):
+        """Greedy sampling records (all rows at temperature 0) where the state has none: the penalised tail is the sampled one."""
+        if st.sample_rows is None:
+            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))
+
+    def _ensure_penalty_state(self, st):
+        """The state's penalty state, made on first use with every row inactive (p3v_penalize copies such a row through) and no
+        bias table; a new one drops the captures that read the old."""
+        pen = st.penalty
+        if pen is None or pen["seen"].shape[0] != st.B:
+            V, dev = self.cfg.vocab_size, self.device
+            pen = st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
+                                              seen=torch.zeros((st.B, V), dtype=I32, device=dev),
+                                              adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
+            self._drop_captures(st, "penalized")
+        return pen
+
+    # ------------------------------------------------------------------ penalties and logit_bias (include/p3v.h: p3v_penalty_row_t)
     @_on_device
     def set_penalties(self, st, records, prompt_ids, row0=0, bias=None, pad=None):
         """Give rows row0 .. row0+n-1 of a state their penalty records (penalties.pack: int32 [n, 4] on the host) and start their
@@ -1588,18 +1578,12 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         pointer in and are dropped.  One H2D copy per operand and one scatter, outside any graph."""
         V, dev = self.cfg.vocab_size, self.device
         n = records.shape[0]
-        pen = st.penalty
-        if pen is None or pen["seen"].shape[0] != st.B:
-            pen = st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
-                                              seen=torch.zeros((st.B, V), dtype=I32, device=dev),
-                                              adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
-            self._drop_penalty_captures(st)
-        if st.sample_rows is None:
-            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))   # (all rows greedy: temperature 0)
+        pen = self._ensure_penalty_state(st)
+        self._greedy_records(st)
         if bias is not None:
             if pen["bias"] is None:
                 pen["bias"] = torch.zeros((st.B, V), dtype=F32, device=dev)
-                self._drop_penalty_captures(st)
+                self._drop_captures(st, "penalized")
             pen["bias"][row0:row0 + n].copy_(torch.as_tensor(np.ascontiguousarray(bias, dtype=np.float32)).view(n, V))
         pen["rows"][row0:row0 + n].copy_(records)
         self.rebuild_penalties(st, prompt_ids, None, row0, pad)
@@ -1641,33 +1625,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         rows = slice(row0, row0 + last.shape[0])
         return ops.penalize(last, pen["rows"][rows], pen["seen"][rows], None if pen["bias"] is None else pen["bias"][rows])
 
-    @_on_device
-    def penal_step(self, token, cache):
-        """One decode step on PENALISED logits through its captured graph (built on first use over the greedy capture's loop
-        state): lm_head, p3v_penalize (which counts the fed token), then the sampled tail on the adjusted rows.  A state with
-        active penalties takes this replay for EVERY step: each step counts the token it is fed.  Returns (raw logits [B,1,V],
-        next_token [B,1])."""
-        st = cache[0].state
-        if st.penalty is None or st.sample_rows is None:
-            raise RuntimeError("penal_step: no penalty state on this state (model.set_penalties)")
-        return self._replay(token, cache, "penal_graph")
-
-    @_on_device
-    def penal_logprob_step(self, token, cache):
-        """`penal_step` followed by the log-probability launch -- on the RAW logits."""
-        st = cache[0].state
-        if st.penalty is None or st.sample_rows is None or st.logprob_want is None:
-            raise RuntimeError("penal_logprob_step: needs a penalty state and a want-table (set_penalties, set_logprobs)")
-        return self._replay(token, cache, "penal_logprob_graph")
-
     # ------------------------------------------------------------------ guided decoding (include/p3v.h: p3v_guide_row_t, guide.py)
-    @staticmethod
-    def _drop_guide_captures(st):
-        g = st.graphs.get("greedy")
-        for k in ("guide_graph", "guide_logprob_graph"):
-            if g is not None:
-                g.pop(k, None)
-
     @_on_device
     def set_guide_vocab(self, table, eos):
         """The vocabulary table of guided decoding (guide.token_bytes: one per processor) as device tensors, made once, and the
@@ -1681,7 +1639,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         if cur is not None:
             for st in list(self._states):
                 if st.guide is not None:
-                    self._drop_guide_captures(st)
+                    self._drop_captures(st, "guided")
         dev = self.device
         self._guide_vocab = dict(table=table, eos=int(eos), n_bytes=table.n_bytes,
                                  tok_off=torch.from_numpy(table.tok_off.view(np.int32).copy()).to(dev),
@@ -1710,15 +1668,9 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
             gd = st.shared["guide"] = dict(rows=torch.zeros((st.B, ops.L.GUIDE_WORDS), dtype=I32, device=dev),
                                            delta=torch.zeros((st.B, 256, 256), dtype=torch.int16, device=dev),
                                            accept=torch.zeros((st.B, 256), dtype=torch.uint8, device=dev))
-            self._drop_guide_captures(st)
-        if st.penalty is None or st.penalty["seen"].shape[0] != st.B:
-            V = self.cfg.vocab_size                             # (every row inactive: p3v_penalize copies the logits through)
-            st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
-                                        seen=torch.zeros((st.B, V), dtype=I32, device=dev),
-                                        adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
-            self._drop_penalty_captures(st)
-        if st.sample_rows is None:
-            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))
+            self._drop_captures(st, "guided")
+        self._ensure_penalty_state(st)
+        self._greedy_records(st)
         recs = []
         for i, dfa in enumerate(guides):
             recs.append(guide_mod.record(dfa, 1 if states is None else states[i]))
@@ -1747,25 +1699,6 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         last = (logits[:, -1, :] if logits.dim() == 3 else logits).clone()
         return self._guide_mask(last, gd, slice(row0, row0 + last.shape[0]), None)
 
-    @_on_device
-    def guide_step(self, token, cache):
-        """One decode step on penalised AND guided logits through its captured graph (built on first use over the greedy
-        capture's loop state): lm_head, p3v_penalize, p3v_guide_mask (which walks the fed token), then the sampled tail on the
-        adjusted rows.  A state with active guides takes this replay for EVERY step.  Returns (raw logits [B,1,V], next_token
-        [B,1])."""
-        st = cache[0].state
-        if st.guide is None or st.penalty is None or st.sample_rows is None:
-            raise RuntimeError("guide_step: no guide state on this state (model.set_guides)")
-        return self._replay(token, cache, "guide_graph")
-
-    @_on_device
-    def guide_logprob_step(self, token, cache):
-        """`guide_step` followed by the log-probability launch -- on the RAW logits."""
-        st = cache[0].state
-        if st.guide is None or st.penalty is None or st.sample_rows is None or st.logprob_want is None:
-            raise RuntimeError("guide_logprob_step: needs a guide state and a want-table (set_guides, set_logprobs)")
-        return self._replay(token, cache, "guide_logprob_graph")
-
     # ------------------------------------------------------------------ token log-probabilities (include/p3v.h: p3v_logprob_t)
     @_on_device
     def set_logprobs(self, st, wants, row0=0):
@@ -1788,23 +1721,6 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
             raise RuntimeError("logprobs_of: no want-table on this state (model.set_logprobs)")
         last = logits[:, -1, :] if logits.dim() == 3 else logits
         return ops.logprobs(last, tokens.reshape(-1).to(I32).contiguous(), st.logprob_want[row0:row0 + last.shape[0]])
-
-    @_on_device
-    def logprob_step(self, token, cache):
-        """`greedy_step` followed by the log-probability launch (a capture of its own over the greedy capture's loop state, built
-        on first use): the same logits and tokens, plus row b's record at `records[b, n_replays - 1]` of the greedy capture.
-        Plain, sampled and log-probability replays may alternate on one state."""
-        if cache[0].state.logprob_want is None:
-            raise RuntimeError("logprob_step: no want-table on this state (model.set_logprobs)")
-        return self._replay(token, cache, "logprob_graph")
-
-    @_on_device
-    def sample_logprob_step(self, token, cache):
-        """`sample_step` followed by the log-probability launch."""
-        st = cache[0].state
-        if st.sample_rows is None or st.logprob_want is None:
-            raise RuntimeError("sample_logprob_step: needs sampling records and a want-table (set_sampling, set_logprobs)")
-        return self._replay(token, cache, "sample_logprob_graph")
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,
