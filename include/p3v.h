@@ -75,6 +75,15 @@ enum {
   P3V_EPI_PATCH = 7,       /* out f32 row (m/P)*(P+1)+1+m%P = acc + pos[1+m%P]   phi.py:199-205 */
   P3V_EPI_F32 = 8          /* out f32 = acc (+ bias if given)                               */
 };
+/* The roundings every projection kernel makes (p3v_gemm, p3v_gemv and the entry points tied to them bit for bit; pinned on exact-sum
+ * inputs by tests/test_proj_kernels_gpu.py).  acc is the fp32 sum over K; bf16() rounds to nearest, ties to even; every other step is
+ * one fp32 operation.
+ *   NONE, BIAS, BIAS_QGELU, BIAS_GELU: one rounding, of the whole fp32 expression (acc + bias, g(acc + bias)).
+ *   RESID_BF16: out = bf16(resid + bf16(acc)) -- TWO roundings: the Linear's output is a bf16 tensor before the residual add.
+ *   SILU_MUL:   g = bf16(acc_gate), u = bf16(acc_up); out = bf16(bf16(g * bf16(sigmoid(g))) * u), sigmoid(g) = 1 / (1 + exp(-g)) in
+ *               fp32 -- every elementwise op of the reference is a bf16 op (FOUR roundings after the two sums).
+ *   BIAS_RESID_F32, PATCH, F32: no rounding; fp32 adds of acc, bias, resid / pos.
+ * K slices (the split-K paths) keep their partial sums in fp32 and add them in slice order before any of the above. */
 typedef struct {
   const uint16_t* A;   /* [M, lda] bf16 */
   const uint16_t* W;   /* [N or 2N, ldw] bf16 */
