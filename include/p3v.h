@@ -156,7 +156,13 @@ int p3v_pack_b13(const uint16_t* W, int rows, int K, int silu_pairs, void* out, 
 int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pairs, int exp_base, uint16_t* out_bf16, void* stream);
 /* p3v_gemv on packed weights: M = 1 only (P3V_ERR_UNSUPPORTED otherwise: the caller keeps the bf16 copy for more rows), N even,
  * K = 3072 or 8192, every epilogue and the fused RMSNorm of p3v_gemv; bit-identical to p3v_gemv on the bf16 matrix.
- * silu_pairs must be what the matrix was packed with and equal (epilogue == P3V_EPI_SILU_MUL). */
+ * silu_pairs must be what the matrix was packed with and equal (epilogue == P3V_EPI_SILU_MUL).
+ * Knob gemv_b13_xscale (default 1): for a matrix with K = 3072 and exp_base - 1 <= 96 the kernel does not add the base back to every weight; it
+ * multiplies the activations it stages by 2^(exp_base - 1) once (a power of two: every product is the same number) and feeds the
+ * codes to the dot product as they are.  That holds for a row of zeros and normal numbers with |x| * 2^(exp_base - 1) finite --
+ * every |x| < 2^32; a row with any other element (larger, Inf, NaN, a bf16 denormal) is served by the exact decode inside the same
+ * launch, as are matrices with a larger base, K = 8192 (measured slower there) and everything at gemv_b13_xscale = 0.  The bits out do
+ * not depend on which form ran. */
 typedef struct {
   const uint16_t* x; const void* W; void* out;
   const uint16_t* resid; const uint16_t* norm_w;

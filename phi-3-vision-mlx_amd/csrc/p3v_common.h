@@ -163,5 +163,6 @@ struct P3vTuning {
   int attn_fo_map;          // fused decode attention + o_proj: 2 / 1 = roles placed by virtual CU (fo_map, round 6), 0 = the (split, head) grid
   int gemv_no_mfma, gemv_no_mfma8, gemv_wpc, gemv8_wgs, gemv_variant, gemv_rows, gemv8_min, gemv_mfma8, gemv_f8_wpc, gemv_q4_wpc, gemv_wpw, gemv_q4_rows_wgs, gemv_q4_rows8;
   int gemv_b13_wpc, gemv_b13_wpc_end;   // 13-bit codes: waves per CU (the bf16 stream keeps gemv_wpc); _end: of the vocabulary head's fold
+  int gemv_b13_xscale;      // 13-bit codes: 1 = the exponent base rides in the staged activations where the matrix allows it, 0 = the exact decode everywhere
 };
 const P3vTuning& p3v_tuning();

@@ -30,13 +30,24 @@ template <int CH> struct B13 {
 
 typedef unsigned short b13_u16x2_t __attribute__((ext_vector_type(2)));
 
-// eight weights back to bf16: lo0 / lo1 = low bytes of weights 0-3 / 4-7, nib = their 8 nibbles, sg0 / sg1 = the sign dword shifted so
-// that the group's four signs are bits 7, 15, 23, 31, cc = ((base - 1) << 7) in both halves.  12-bit code | mantissa + cc is the
+// eight weights as s | 000 | q5 | m7 in bf16 positions: lo0 / lo1 = low bytes of weights 0-3 / 4-7, nib = their 8 nibbles, sg0 / sg1 =
+// the sign dword shifted so that the group's four signs are bits 7, 15, 23, 31.  Read as bf16 this is the weight times 2^-(base - 1),
+// exactly: the code q (1 .. 31) is a normal number's exponent field and code 0 is +-0.  The GEMV whose activations carry 2^(base - 1)
+// (GemvB13<true>) feeds it to v_dot2c as it is.
+// (four scalars, not a u32x4: hipcc 7.2 folds `bit_cast<2 x u16>(v[d])` of a vector's four dwords into element 0, see p3v_dot_bf16.h)
+__device__ __forceinline__ void b13_pre8(uint32_t lo0, uint32_t lo1, uint32_t nib, uint32_t sg0, uint32_t sg1, uint32_t (&pre)[4]) {
+  const uint32_t hi0 = (sg0 & 0x80808080u) | (nib & 0x0f0f0f0fu), hi1 = (sg1 & 0x80808080u) | ((nib >> 4) & 0x0f0f0f0fu);
+  pre[0] = __builtin_amdgcn_perm(hi0, lo0, 0x05010400u);
+  pre[1] = __builtin_amdgcn_perm(hi0, lo0, 0x07030602u);
+  pre[2] = __builtin_amdgcn_perm(hi1, lo1, 0x05010400u);
+  pre[3] = __builtin_amdgcn_perm(hi1, lo1, 0x07030602u);
+}
+
+// eight weights back to bf16: b13_pre8 + the base, cc = ((base - 1) << 7) in both halves.  12-bit code | mantissa + cc is the
 // bf16 magnitude unless the code is 0 (then the magnitude is 0): min(v, 1) * cc adds it only to the others, two weights per instruction.
 __device__ __forceinline__ u32x4_t b13_decode8(uint32_t lo0, uint32_t lo1, uint32_t nib, uint32_t sg0, uint32_t sg1, uint32_t cc) {
-  const uint32_t hi0 = (sg0 & 0x80808080u) | (nib & 0x0f0f0f0fu), hi1 = (sg1 & 0x80808080u) | ((nib >> 4) & 0x0f0f0f0fu);
-  const uint32_t pre[4] = {__builtin_amdgcn_perm(hi0, lo0, 0x05010400u), __builtin_amdgcn_perm(hi0, lo0, 0x07030602u),
-                           __builtin_amdgcn_perm(hi1, lo1, 0x05010400u), __builtin_amdgcn_perm(hi1, lo1, 0x07030602u)};
+  uint32_t pre[4];
+  b13_pre8(lo0, lo1, nib, sg0, sg1, pre);
   const b13_u16x2_t c2 = __builtin_bit_cast(b13_u16x2_t, cc), one = {1, 1}, mag = {0x7fff, 0x7fff};
   u32x4_t w;
 #pragma unroll

@@ -148,7 +148,7 @@ extern "C" int p3v_gemv_timing_read(long long* out, int n) {
 struct GemvBf16 {
   typedef GemvP P;
   static constexpr int WPL = 8, MAX_MT = 4, MIN_WG = 1;
-  static constexpr bool XSUM = false;
+  static constexpr bool XSUM = false, XSCALE = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; };
   static int wpc() { return p3v_tuning().gemv_wpc; }
   static __device__ __forceinline__ void mark(int k) { GMARK(k); }

@@ -8,6 +8,9 @@
 //   load        requests a Stage, in the order that format's stream wants;  dot: folds lane load j of both rows into the two
 //               accumulators from the activations in LDS;  finish: applied to a row's sum after wave_sum (the e4m3 row scale)
 //   XSUM        the 4-bit form needs the sum of every 16 activations: one more pass over LDS between staging and streaming
+//   XSCALE      the scaled 13-bit form (GemvB13<true>, p3v_gemv_b13.hip) wants the staged activations times its matrix's factor: stage_x
+//               (a pair on its way to LDS), x_unfit (does this thread's part of the row take the factor?) and dot_exact, the dot of
+//               the plain second loop that a workgroup with an unfit row runs on the row as it was
 //   wpc         the format's waves-per-CU tuning knob;  mark: timing stamp hook (tools/gemv_timeline.py: bf16 and the 13-bit codes;
 //               0 entry, 1 exit, 2 first dot)
 //   MIN_WG      workgroups per CU the kernels are compiled to fit (__launch_bounds__): 1 = whatever the registers allow; a format
@@ -206,6 +209,10 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
   if (n_st > 0) issue(0, IC0{});
 
   // ---- 3. RMSNorm prologue (waits for the x loads only) -> LDS
+  // (F::XSCALE: what goes to LDS is F::stage_x of the rounded activations; `xkeep` holds them as they were and F::x_unfit says
+  // whether an element of this thread's does not take the format's factor -- see 3b)
+  [[maybe_unused]] u32x4_t xkeep[F::XSCALE ? MT : 1][F::XSCALE ? XC : 1];
+  [[maybe_unused]] uint32_t xacc[2] = {0u, 0xffffffffu};    // (what F::stage_x folds the row into, for F::x_unfit)
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     float r = 1.f;
@@ -235,12 +242,38 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
           for (int j = 0; j < 4; ++j)
             o[j] = rms_pair(xv[m][k][j], r, gv[k][j]);
         }
+        if constexpr (F::XSCALE) {
+          xkeep[m][k] = o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o[j] = F::stage_x(p, o[j], xacc);
+        }
         xs[m * XCH + c] = live(m) ? o : (u32x4_t){0, 0, 0, 0};
       }
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  // ---- 3b. (F::XSCALE) one wave-vote per wave rides on the staging barrier; a workgroup with an unfit element -- uniform, cold --
+  // puts the rows back as they were and takes the exact copy of the pipeline below
+  [[maybe_unused]] bool x_exact = false;
+  if constexpr (F::XSCALE) {
+    __shared__ int s_unfit[4];
+    const bool any = __builtin_amdgcn_ballot_w64(F::x_unfit(p, xacc)) != 0;
+    if (lane == 0) s_unfit[wave] = any;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    x_exact = ((s_unfit[0] | s_unfit[1]) | (s_unfit[2] | s_unfit[3])) != 0;
+    if (x_exact) {
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int k = 0; k < XC; ++k)
+          if (tid + k * 256 < XCH) xs[m * XCH + tid + k * 256] = live(m) ? xkeep[m][k] : (u32x4_t){0, 0, 0, 0};
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+  } else {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  }
   if constexpr (F::XSUM) {
     for (int pc = tid; pc < K / 16; pc += 256) {         // X of every piece, from the (rounded) activations the dots see
       const u32x4_t a = xs[2 * pc], b = xs[2 * pc + 1];
@@ -261,13 +294,20 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
   ArgMaxVI best[MT];                                         // STEP_END: this wave's arg-max candidates (lane 0's copy counts)
 #pragma unroll
   for (int m = 0; m < MT; ++m) best[m] = ArgMaxVI{-INFINITY, 0x7fffffff};
-  auto compute = [&](int gs, auto bufc) {
+  auto compute = [&](int gs, auto bufc, auto exactc) {           // exactc: IC1 = F::dot_exact (F::XSCALE, 3b), IC0 = F::dot
     constexpr int buf = decltype(bufc)::value;
     const int s = gs % NST;
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
 #pragma unroll
-      for (int m = 0; m < MT; ++m) F::dot(wbuf[buf], j, xs + m * XCH, xsum, (s * CH + j) * 64 + lane, a0[m], a1[m]);
+      for (int m = 0; m < MT; ++m) {
+        if constexpr (F::XSCALE) {
+          if constexpr (decltype(exactc)::value) F::dot_exact(p, wbuf[buf], j, xs + m * XCH, xsum, (s * CH + j) * 64 + lane, a0[m], a1[m]);
+          else F::dot(wbuf[buf], j, xs + m * XCH, xsum, (s * CH + j) * 64 + lane, a0[m], a1[m]);
+        } else {
+          F::dot(wbuf[buf], j, xs + m * XCH, xsum, (s * CH + j) * 64 + lane, a0[m], a1[m]);
+        }
+      }
     }
     if (s == NST - 1) {                                   // row pair complete (compile-time true when NST == 1)
       const int u = u_begin + gs / NST;
@@ -303,19 +343,27 @@ __device__ __forceinline__ void gemv_stream_body(const typename F::P& p, int uni
     }
   };
   int gs = 0;
+  if constexpr (F::XSCALE) {                              // 3b: the exact form of the loop below, chosen once.  Cold: one stage at a
+    if (x_exact) {                                        // time through buffer 0 (which holds stage 0 already), so that it costs the
+      for (; gs < n_st; ++gs) {                           // pipelined loop neither registers nor much code
+        if (gs > 0) issue(gs, IC0{});
+        compute(gs, IC0{}, IC1{});
+      }
+    }
+  }
   while (gs + 2 < n_st) {                                 // branch-free body: counted vmcnt survives
     issue(gs + 1, IC1{});
-    compute(gs, IC0{});
+    compute(gs, IC0{}, IC0{});
     issue(gs + 2, IC0{});
-    compute(gs + 1, IC1{});
+    compute(gs + 1, IC1{}, IC0{});
     gs += 2;
   }
   if (gs + 1 < n_st) {
     issue(gs + 1, IC1{});
-    compute(gs, IC0{});
-    compute(gs + 1, IC1{});
+    compute(gs, IC0{}, IC0{});
+    compute(gs + 1, IC1{}, IC0{});
   } else if (gs < n_st) {
-    compute(gs, IC0{});
+    compute(gs, IC0{}, IC0{});
   }
   if (STEP == STEP_BEGIN && bx == 0) gemv_step_begin_tail<MT>(sp, xrow, MT == 1 ? 1 : p.M, XCH, tid);
   if (STEP == STEP_END) gemv_step_end_tail<MT>(sp, best, MT == 1 ? 1 : p.M, bx, tid);

@@ -27,15 +27,21 @@ extern "C" int p3v_gemv_b13_timing_read(long long* out, int n) {
 #else
 #define B13MARK(k)
 #endif
-struct GemvB13 {
+// SCALED: the activations staged in LDS carry the matrix's 2^(base - 1) (stage_x below), so the codes go to v_dot2c as b13_pre8 leaves
+// them -- every product w' * x' is the real number w * x, both factors normal bf16 values, and the sums come out bit for bit.  An x
+// row with an element that does not take the factor (it would overflow, is Inf or NaN, or a bf16 denormal) makes the workgroup restage
+// the row as it was and run the exact decode for that launch (dot_exact: the body's second, plain loop).
+template <int CH, bool WITH_CC> struct B13Stage { uint32_t sg[B13<CH>::NS]; u32x4_t nib[CH / 2]; u32x4_t lo[CH]; uint32_t cc; };   // (cc: uniform, rides along for dot)
+template <int CH> struct B13Stage<CH, false> { uint32_t sg[B13<CH>::NS]; u32x4_t nib[CH / 2]; u32x4_t lo[CH]; };
+template <bool SCALED> struct GemvB13 {
   typedef GemvB13P P;
   static constexpr int WPL = 8, MAX_MT = 1, MIN_WG = 4;
-  static constexpr bool XSUM = false;
-  // 4 workgroups a CU (at most 128 VGPRs): the decode's ~2.6 VALU operations per weight want the fourth wave of a SIMD, and
+  static constexpr bool XSUM = false, XSCALE = SCALED;
+  // 4 workgroups a CU (at most 128 VGPRs): the decode's VALU operations want the fourth wave of a SIMD, and
   // gemv_b13_wpc = 16 puts it there (gate_up: 4096 waves, all resident)
-  template <int CH> struct Stage { uint32_t sg[B13<CH>::NS]; u32x4_t nib[CH / 2]; u32x4_t lo[CH]; uint32_t cc; };   // (cc: uniform, rides along for dot)
+  template <int CH> using Stage = B13Stage<CH, !SCALED>;   // (the scaled form needs no base in the pipeline)
   static int wpc() { return p3v_tuning().gemv_b13_wpc; }
-  static int wpc_end() { return p3v_tuning().gemv_b13_wpc_end; }   // the vocabulary head's fold: 131 VGPRs, 16 waves a CU would not be resident
+  static int wpc_end() { return p3v_tuning().gemv_b13_wpc_end; }   // the vocabulary head's fold: 16 waves a CU would not be resident
   static __device__ __forceinline__ void mark(int k) { B13MARK(k); }
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int, int c0, Stage<CH>& st) {
@@ -59,19 +65,64 @@ struct GemvB13 {
     for (int i = 0; i < CH / 2; ++i) st.nib[i] = __builtin_nontemporal_load(np + i * 64);
 #pragma unroll
     for (int j = 0; j < CH; ++j) st.lo[j] = __builtin_nontemporal_load(lp + j * 64);
-    st.cc = p.cc;
+    if constexpr (!SCALED) st.cc = p.cc;
+  }
+  // the weights of lane load j of one row: as bf16 (EXACT: + the base, cc) or times 2^-(base - 1)
+  template <bool EXACT, int CH>
+  static __device__ __forceinline__ u32x4_t weights_as(const Stage<CH>& st, uint32_t cc, int j, int row) {
+    typedef B13<CH> L;
+    const uint32_t lo0 = st.lo[j][2 * row], lo1 = st.lo[j][2 * row + 1], nib = st.nib[j >> 1][(j & 1) * 2 + row];
+    const uint32_t sg0 = st.sg[L::sign_word(row, j, 0)] << L::sign_shift(row, j, 0), sg1 = st.sg[L::sign_word(row, j, 1)] << L::sign_shift(row, j, 1);
+    if constexpr (EXACT) return b13_decode8(lo0, lo1, nib, sg0, sg1, cc);
+    else {
+      uint32_t pre[4];
+      b13_pre8(lo0, lo1, nib, sg0, sg1, pre);
+      return (u32x4_t){pre[0], pre[1], pre[2], pre[3]};
+    }
   }
   template <int CH>
   static __device__ __forceinline__ u32x4_t weights(const Stage<CH>& st, int j, int row) {
-    typedef B13<CH> L;
-    return b13_decode8(st.lo[j][2 * row], st.lo[j][2 * row + 1], st.nib[j >> 1][(j & 1) * 2 + row],
-                       st.sg[L::sign_word(row, j, 0)] << L::sign_shift(row, j, 0), st.sg[L::sign_word(row, j, 1)] << L::sign_shift(row, j, 1), st.cc);
+    static_assert(!SCALED, "the bf16 weights: the exact form only");
+    return weights_as<true>(st, st.cc, j, row);
   }
   template <int CH>
   static __device__ __forceinline__ void dot(const Stage<CH>& st, int j, const u32x4_t* x, const float*, int c, float& a0, float& a1) {
     const u32x4_t xa = x[c];
-    a0 = dot8(weights(st, j, 0), xa, a0);
-    a1 = dot8(weights(st, j, 1), xa, a1);
+    if constexpr (SCALED) {
+      a0 = dot8(weights_as<false>(st, 0u, j, 0), xa, a0);
+      a1 = dot8(weights_as<false>(st, 0u, j, 1), xa, a1);
+    } else {
+      a0 = dot8(weights(st, j, 0), xa, a0);
+      a1 = dot8(weights(st, j, 1), xa, a1);
+    }
+  }
+  // (XSCALE) the exact decode on the scaled form's stages, for a launch whose x row does not take the factor
+  template <int CH>
+  static __device__ __forceinline__ void dot_exact(const P& p, const Stage<CH>& st, int j, const u32x4_t* x, const float*, int c, float& a0, float& a1) {
+    const u32x4_t xa = x[c];
+    a0 = dot8(weights_as<true>(st, p.cc, j, 0), xa, a0);
+    a1 = dot8(weights_as<true>(st, p.cc, j, 1), xa, a1);
+  }
+  // XSCALE: one staged activation pair (already rounded to bf16) times 2^(base - 1), in integers: cc = (base - 1) << 7 added to the
+  // exponent field of every non-zero element (min(magnitude, 1) * cc, as b13_decode8 adds it to the codes) -- exact for a normal number
+  // that stays finite.  acc[0] / acc[1] collect the largest magnitude and the smallest magnitude - 1 (a zero wraps to 0xffff) of the
+  // row, per 16-bit half; x_unfit then says whether the row must keep the exact decode: an element at or above 2^(128 - (base - 1))
+  // (Inf and NaN with them: they are not worth a form of their own) or a bf16 denormal.  Six VALU operations a pair.
+  static __device__ __forceinline__ uint32_t stage_x(const P& p, uint32_t x2, uint32_t (&acc)[2]) {
+    const b13_u16x2_t one = {1, 1};
+    const uint32_t mag = x2 & 0x7fff7fffu;
+    uint32_t nz, y2, m1;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(nz) : "v"(mag), "v"(one));
+    asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(y2) : "v"(nz), "v"(p.cc), "v"(x2));
+    asm("v_pk_max_u16 %0, %1, %2" : "=v"(acc[0]) : "v"(acc[0]), "v"(mag));
+    asm("v_pk_sub_u16 %0, %1, %2" : "=v"(m1) : "v"(mag), "v"(one));
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(acc[1]) : "v"(acc[1]), "v"(m1));
+    return y2;
+  }
+  static __device__ __forceinline__ bool x_unfit(const P& p, const uint32_t (&acc)[2]) {
+    const uint32_t top = 0x7f80u - (p.cc & 0xffffu);                      // (255 - (base - 1)) << 7: the first exponent that overflows
+    const uint32_t mx = max(acc[0] & 0xffffu, acc[0] >> 16), mn = min(acc[1] & 0xffffu, acc[1] >> 16);
+    return mx >= top || mn < 0x7fu;
   }
   template <int CH> static __device__ __forceinline__ float finish(float v, const Stage<CH>&, int) { return v; }
 };
@@ -163,12 +214,12 @@ __global__ void __launch_bounds__(256) k_b13_unpack(GemvB13P p, u32x4_t* __restr
   const int lane = (int)(t & 63), u = (int)(ci / NST), s = (int)(ci % NST);
   const bool silu = p.epi == P3V_EPI_SILU_MUL;
   const int r[2] = {silu ? u : 2 * u, silu ? u + rows / 2 : 2 * u + 1};
-  GemvB13::Stage<CH> st;
-  GemvB13::load<K, CH>(p, r[0], r[1], s * CH * 64 + lane, st);
+  GemvB13<false>::Stage<CH> st;
+  GemvB13<false>::load<K, CH>(p, r[0], r[1], s * CH * 64 + lane, st);
 #pragma unroll
   for (int row = 0; row < 2; ++row)
 #pragma unroll
-    for (int j = 0; j < CH; ++j) out[(size_t)r[row] * (K / 8) + (s * CH + j) * 64 + lane] = GemvB13::weights(st, j, row);
+    for (int j = 0; j < CH; ++j) out[(size_t)r[row] * (K / 8) + (s * CH + j) * 64 + lane] = GemvB13<false>::weights(st, j, row);
 }
 
 static bool b13_shape_ok(int rows, int K) { return rows > 0 && rows % 2 == 0 && (K == 3072 || K == 8192); }
@@ -202,11 +253,18 @@ extern "C" int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pair
 }
 
 // ---------------------------------------------------------------- entry points: the twins of p3v_gemv_fp8 / p3v_gemv_fp8_step, one row only
-static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p) {
+// The scaled form (GemvB13<true>) serves a matrix whose factor 2^(base - 1) leaves the activations room: base - 1 <= 96, so that every
+// |x| < 2^32 fits (a row that does not falls back inside the kernel) -- at K = 3072 (qkv, gate_up, the vocabulary head).  K = 8192
+// (down) keeps the exact decode: its waves stage 16 KB of x for ONE row pair each, the staging sits in front of the first dot and the
+// loop's VALU work hides behind the stream either way (measured 8.86 -> 9.02 us scaled, profiles/pack13_xscale_step_trace_summary.txt),
+// so that instantiation is not built.  gemv_b13_xscale = 0 keeps the exact decode everywhere.
+#define B13_XSCALE_MAX_SHIFT 96
+static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p, bool& scaled) {
   if (a->M <= 0 || a->N <= 0) return P3V_ERR_ARG;
   if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192)) return P3V_ERR_UNSUPPORTED;
   if (a->exp_base < 1 || a->exp_base > 224 || ((uintptr_t)a->W & 15)) return P3V_ERR_ARG;
   if ((a->silu_pairs != 0) != (a->epilogue == P3V_EPI_SILU_MUL)) return P3V_ERR_ARG;   // the row pairing is part of the packing
+  scaled = p3v_tuning().gemv_b13_xscale != 0 && a->exp_base - 1 <= B13_XSCALE_MAX_SHIFT && a->K == 3072;
   p = {a->x, (const uint32_t*)a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
        a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2, b13_cc(a->exp_base)};
   return P3V_OK;
@@ -215,20 +273,25 @@ static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p) {
 extern "C" int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out) {
   if (!out || N <= 0 || n_cu <= 0) return P3V_ERR_ARG;
   if (N % 2 || (K != 3072 && K != 8192)) return P3V_ERR_UNSUPPORTED;
-  const GemvPlan g = gemv_stream_plan(epilogue == P3V_EPI_SILU_MUL ? N : N / 2, n_cu, GemvB13::wpc(), p3v_tuning().gemv_wpw);
+  const GemvPlan g = gemv_stream_plan(epilogue == P3V_EPI_SILU_MUL ? N : N / 2, n_cu, GemvB13<true>::wpc(), p3v_tuning().gemv_wpw);
   out[0] = g.upw; out[1] = g.waves; out[2] = g.wpw; out[3] = p3v_cdiv(g.waves, g.wpw);
   return P3V_OK;
 }
 
+static int b13_launch_step(const GemvB13P& p, int K, bool scaled, bool begin, const GemvStepP& sp, hipStream_t s) {
+  if (K == 8192) return begin ? launch_gemv_stream<GemvB13<false>, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<false>, 1, 4, 4, STEP_END>(p, s, &sp);
+  if (scaled) return begin ? launch_gemv_stream<GemvB13<true>, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<true>, 1, 1, 6, STEP_END>(p, s, &sp);
+  return begin ? launch_gemv_stream<GemvB13<false>, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<false>, 1, 1, 6, STEP_END>(p, s, &sp);
+}
+
 extern "C" int p3v_gemv_b13_step(const p3v_gemv_b13_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->out) return P3V_ERR_ARG;
-  GemvStepP sp; bool begin;
+  GemvStepP sp; bool begin, scaled;
   if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
   GemvB13P p;
-  if (const int rc = b13_params(a, p)) return rc;
+  if (const int rc = b13_params(a, p, scaled)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv_stream<GemvB13, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13, 1, 1, 6, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv_stream<GemvB13, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13, 1, 4, 4, STEP_END>(p, s, &sp);
+  return b13_launch_step(p, a->K, scaled, begin, sp, s);
 }
 
 extern "C" int p3v_gemv_b13(const p3v_gemv_b13_args_t* a, void* stream) {
@@ -237,8 +300,9 @@ extern "C" int p3v_gemv_b13(const p3v_gemv_b13_args_t* a, void* stream) {
       a->epilogue != P3V_EPI_F32)
     return P3V_ERR_UNSUPPORTED;
   if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
-  GemvB13P p;
-  if (const int rc = b13_params(a, p)) return rc;
+  GemvB13P p; bool scaled;
+  if (const int rc = b13_params(a, p, scaled)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  return a->K == 3072 ? launch_gemv_stream<GemvB13, 1, 1, 6>(p, s) : launch_gemv_stream<GemvB13, 1, 4, 4>(p, s);
+  if (a->K == 8192) return launch_gemv_stream<GemvB13<false>, 1, 4, 4>(p, s);
+  return scaled ? launch_gemv_stream<GemvB13<true>, 1, 1, 6>(p, s) : launch_gemv_stream<GemvB13<false>, 1, 1, 6>(p, s);
 }

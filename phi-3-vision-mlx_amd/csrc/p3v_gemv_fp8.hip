@@ -26,7 +26,7 @@ struct GemvF8P {
 struct GemvF8 {
   typedef GemvF8P P;
   static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
-  static constexpr bool XSUM = false;
+  static constexpr bool XSUM = false, XSCALE = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; float scale[2]; };
   static int wpc() { return p3v_tuning().gemv_f8_wpc; }   // (a stage is half the bytes of the bf16 kernel's: twice the waves keep as many in flight; 8: 1.321, 16: 1.301, 24: 1.333 ms/step)
   static __device__ __forceinline__ void mark(int) {}

@@ -30,7 +30,7 @@ struct GemvQ4P {
 struct GemvQ4 {
   typedef GemvQ4P P;
   static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
-  static constexpr bool XSUM = true;
+  static constexpr bool XSUM = true, XSCALE = false;
   template <int CH> struct Stage { u32x2_t w[2][CH]; uint32_t sb[2][CH]; };
   static int wpc() { return p3v_tuning().gemv_q4_wpc; }
   static __device__ __forceinline__ void mark(int) {}

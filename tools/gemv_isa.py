@@ -46,7 +46,9 @@ def table(path):
         cnt = lambda pat: sum(1 for l in ins if re.match(pat, l))
         vm = [int(m.group(1)) for l in ins for m in [re.match(r"s_waitcnt.*vmcnt\((\d+)\)", l)] if m]
         waves = min(8, 512 // (-(-vgpr // 8) * 8))
-        short = re.sub(r".*<\w+, |>.*", "", names[k]).replace(" ", "")
+        # "1,1,6" of k_gemv3<GemvBf16, 1, 1, 6>; a policy that is a template itself (GemvB13<true>) puts its argument in front: "true 1,1,6"
+        m = re.match(r".*?<\w+(?:<(\w+)>)?, ([^>]*)>", names[k])
+        short = ((m.group(1) + " ") if m.group(1) else "") + m.group(2).replace(" ", "")
         print("%-16s | %5d %5d %4d %13d %5d %4d %4d %4d %4d %4d %6d %6d %4d %4d" % (
             short, vgpr, waves, scr, cnt("scratch_"), cnt("global_load"), cnt("global_load_dwordx4"), cnt("global_load_dwordx3"),
             cnt("global_load_dwordx2"), cnt("v_dot2c"), cnt("v_perm_b32"), cnt("v_pk_min_u16"), cnt("v_pk_mad_u16"),
