@@ -132,7 +132,9 @@ int p3v_gemv(const p3v_gemv_args_t* args /* host */, void* stream);
 
 /* ---- fp8 (OCP e4m3fn) weight-only projections (quantize_model=True; replaces the int4 `nn.quantize` of
  * phi_3_vision_mlx.py:264,296): W is u8 [N or 2N, K] bit patterns, w = fp8 * w_scale[row]; x, accumulation
- * and outputs as in p3v_gemv.  K in {3072, 8192}, M <= 16.  p3v_dequant_fp8 expands rows to bf16 (prefill). */
+ * and outputs as in p3v_gemv.  K in {3072, 8192}, M <= 16, N even.  Every kernel behind it sums x * fp8 in fp32 first (an e4m3 value
+ * is exact in bf16, so each product is) and multiplies the sum by w_scale[row] afterwards, one fp32 rounding; the epilogue's roundings
+ * are p3v_gemm's.  p3v_dequant_fp8 expands rows to bf16 (prefill). */
 typedef struct {
   const uint16_t* x; const uint8_t* W; const float* w_scale; void* out;
   const uint16_t* resid; const uint16_t* norm_w;
@@ -182,8 +184,11 @@ int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out /* host, 4 
  * QuantizedLinear, phi_3_vision_mlx.py:264,291-305, under `quantize_model=True`).
  *   out[M, N] = epilogue((a_scale[m] * w_scale[n]) * sum_k A8[m,k] * W8[n,k])     A8 [M, lda], W8 [N or 2N, ldw]: e4m3 bytes
  * on v_mfma_scale_f32_16x16x128_f8f6f4 (block scales 1.0).  epilogue: P3V_EPI_NONE, P3V_EPI_RESID_BF16 (resid bf16 [M, ldo]),
- * P3V_EPI_SILU_MUL (W8 / w_scale hold the N gate rows then the N up rows; out [M, N]).  K % 128 == 0, N % 256 == 0
- * (128 for SILU_MUL), 16-byte aligned pointers and row strides.
+ * P3V_EPI_SILU_MUL (W8 / w_scale hold the N gate rows then the N up rows; out [M, N]).  K % 128 == 0, N % 128 == 0 (every
+ * epilogue: an N that is no multiple of 256 runs on the 256 x 128 tile, which the launcher also picks where the wide one would
+ * leave most of the chip idle; knob gemm_f8_narrow = 0 / 1 pins the tile where both fit), lda, ldw >= K and % 16 == 0, ldo % 8 == 0,
+ * 16-byte aligned pointers.  The sum over k is exact products added in fp32; it is multiplied ONCE by the fp32 product
+ * a_scale[m] * w_scale[n], then the epilogue's roundings are p3v_gemm's (pinned on exact-sum inputs by tests/test_qproj_kernels_gpu.py).
  * p3v_quant_fp8_rows makes A8 / a_scale from bf16 rows: one scale s per row = max|h| / 448, codes e4m3(h * (1 / s)),
  * h = x or, with norm_w,
  * h = bf16(x * rsqrt(mean x^2 + eps) * norm_w) (nn.RMSNorm, phi.py:478-479), so the norm costs no extra pass. */
@@ -431,6 +436,13 @@ int p3v_topk(const uint16_t* x, int32_t* idx_out, int rows, int n, int k, int64_
  *   the reference's QuantizedLinear (phi_3_vision_mlx.py:296).  norm_w: up to 8 rows the input RMSNorm may ride along (the rows are
  *   normalised to the bf16 values p3v_rmsnorm writes while the first weights are in flight); 9 .. 16 rows: must be NULL
  *   (P3V_ERR_UNSUPPORTED otherwise -- the caller runs p3v_rmsnorm first).
+ *   What a weight is: M = 1 adds scale * (D - 128 X) + bias * X per 16 weights in fp32 (D = sum x (128 + q), X = sum x): scale * q + bias
+ *   with its full bf16 scale and bias.  2 <= M <= 16 multiplies fp16(x) by w = fp16(scale * q + bias) -- ONE rounding to 11 bits, scale
+ *   and bias converted to fp16 first -- with exact products and fp32 sums.  That path therefore holds what fp16 holds and no more:
+ *   an activation with |x| > 65504 becomes Inf; activations, scales and biases below 2^-14 are fp16 subnormals (steps of 2^-24), exact
+ *   while their 8 bits stay at or above 2^-24 -- down to 2^-17 -- and rounded below that (zero under 2^-25), where the M = 1 path
+ *   keeps them as bf16.  Checkpoints quantised from bf16 weights sit far inside (scales around 2^-7); tests/test_qproj_kernels_gpu.py
+ *   runs both paths on scales in [2^-17, 2^-14) and activations in [2^-14, 2^15].
  * p3v_dequant_q4: -> bf16 [rows, K] (prefill / batched decode run the bf16 kernels on a dequantised scratch). */
 typedef struct {
   const uint16_t* x; const uint32_t* W; const uint32_t* sb; void* out;

@@ -292,6 +292,12 @@ class Probe:
         """The family as printed: under the GEMV norm fold the second family is not SPIKES but a sparse integer W (_inputs_norm)."""
         return "grid-sparse" if self.case.norm and self.case.entry == "gemv" and not self.grid else self.family
 
+    @property
+    def scale_after(self):
+        """Norm fold: the kernel scales the dot product of bf16(x w) by r afterwards (k_gemv_mfma, k_gemv_mfma8), where the others
+        normalise every element to bf16(bf16(x r) w) first."""
+        return self.case.kernel.startswith("k_gemv_mfma")
+
     # ---- inputs
     def _inputs(self, gen):
         c = self.case
@@ -345,7 +351,7 @@ class Probe:
         M, K, Nw = c.M, c.K, c.w_rows
         self.s = s = math.floor(math.log2(1.3 / (2.2 * 0.8 * math.sqrt(K))))      # |normalised x| ~ 1, |j| std 2.0 (spikes: see below), weights 0.79 rms
         cm = to_bf16(0.5 + 3.0 * torch.rand((M, 1), generator=gen)).to(F64)
-        if c.kernel.startswith("k_gemv_mfma"):                       # there acc = (c r) t with c r = (1 + eps / c^2)^-1/2: a small c keeps it
+        if self.scale_after:                                         # there acc = (c r) t with c r = (1 + eps / c^2)^-1/2: a small c keeps it
             cm = cm * 2.0 ** -7                                      # percents away from 1, so that t's many rounding ties are none of acc
         sign = torch.randint(0, 2, (M, K), generator=gen).to(F64) * 2 - 1
         self.A = to_bf16(sign * cm)
@@ -414,7 +420,7 @@ class Probe:
         cm = x64[:, :1].abs()
         r = torch.rsqrt((x64 * x64).mean(-1, keepdim=True) + EPS)
         t = (x64.sign() * self.norm_w.to(F64)) @ self.W.to(F64).T                  # integer 2^(s - 1): exact
-        if c.kernel.startswith("k_gemv_mfma"):
+        if self.scale_after:
             v = cm * r
             return v * (1 - s * 2.0 ** -16) * t, v * (1 + s * 2.0 ** -16) * t, torch.ones(c.M, dtype=torch.bool)
         v_lo, v_hi = bracket(cm * r, cm * r * (s * 2.0 ** -16))
@@ -427,7 +433,7 @@ class Probe:
         kept = None
         if c.norm and c.entry == "gemv":
             a_lo, a_hi, kept = self._norm_acc(s)
-            if c.kernel.startswith("k_gemv_mfma"):
+            if self.scale_after:
                 mid, E = (a_lo + a_hi) / 2, (a_hi - a_lo).abs() / 2
             else:
                 mid, E = None, None
@@ -614,7 +620,7 @@ class Probe:
     def _restate_norm(self, A):
         nw = self.norm_w.float()
         r = torch.rsqrt((A * A).sum(-1, keepdim=True) * (1.0 / self.case.K) + EPS)
-        if self.case.kernel.startswith("k_gemv_mfma"):
+        if self.scale_after:
             return (A * nw).to(BF16).float(), r
         return ((A * r).to(BF16).float() * nw).to(BF16).float(), None
 

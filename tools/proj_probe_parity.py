@@ -1,7 +1,8 @@
-"""Projection parity table: the lines tests/test_proj_kernels_gpu.py prints per case and family -- `id [family]: kernel: result` -- as
+"""Projection parity table: the lines tests/test_proj_kernels_gpu.py and tests/test_qproj_kernels_gpu.py print per case and family -- `id [family]: kernel: result` -- as
 columns.  The test is the only thing that runs the kernels; this reads its output.
 
-    python -m pytest -m gpu -s -q tests/test_proj_kernels_gpu.py | python tools/proj_probe_parity.py > profiles/proj_probe_parity.txt"""
+    python -m pytest -m gpu -s -q tests/test_proj_kernels_gpu.py | python tools/proj_probe_parity.py > profiles/proj_probe_parity.txt
+    python -m pytest -m gpu -s -q tests/test_qproj_kernels_gpu.py | python tools/proj_probe_parity.py > profiles/qproj_probe_parity.txt"""
 import re
 import sys
 
