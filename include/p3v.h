@@ -257,7 +257,15 @@ int p3v_gemm_qkv(const p3v_gemm_args_t* gemm /* host */, const p3v_qkv_split_t* 
  * appended to the cache).  V^T columns beyond the valid keys must hold finite values.
  * out [B, L, nh*hd] bf16.
  * Query i sees key t iff (!causal || t <= past+i) && t >= pad_len[b]; a query
- * that is itself padding outputs 0.  hd in {64, 96}. */
+ * that is itself padding outputs 0.  hd in {64, 96}.
+ * What the prompt path (L > P3V_DECODE_MAX_L) rounds: the scores q . k accumulate in fp32 and are not rounded; with
+ * q_prescaled, P = 2^(s - r) is taken against a per-query exponent reference r -- the row maximum of the query's first
+ * visible 64-key tile, raised to the running row maximum at the latest when a score exceeds it by more than 8 (so r <= max s <= r + 8
+ * at the end of every tile, P <= 2^8) -- and ROUNDED TO bf16 before P x V; the row sum is taken over the same rounded P
+ * and, like P x V, accumulated in fp32; the output P x V / sum P is rounded to bf16 ONCE.  Nothing is read outside
+ * [pad_len[b], past + L) for its value: finite K rows / V^T columns in the dead positions of a walked tile do not reach
+ * the output, and no buffer but `out` is written (tests/test_attn_prefill_probe_gpu.py holds the pre-scaled kernels to
+ * this against plain fp64). */
 typedef struct {
   const uint16_t* q;
   const uint16_t* k_past; const uint16_t* v_past;
