@@ -699,9 +699,27 @@ int p3v_penalize(const uint16_t* logits, int64_t row_stride, const p3v_penalty_r
  *      vocabulary table is read; a token whose offsets do not lie in [0, n_bytes] in order counts as one without bytes.
  * No atomics, plain vector stores, no allocation; every pointer is device memory, so the call is capturable.  One workgroup per
  * row: the state is stored by one thread behind the barrier that follows every thread's read of it.  guide.reference_mask
- * (NumPy) gives every output bit and every state. */
+ * (NumPy) gives every output bit and every state.
+ *
+ * THE WIDE FORM (a guide of more than 255 states: a JSON schema's, guide.compile_json).  A row is WIDE when flags &
+ * P3V_GUIDE_WIDE; the record's `reserved` then carries the class count C, 1 <= C <= 256 (a narrow row's `reserved` is not read).
+ * The row keeps the same region, read differently:
+ *   cls    uint8  [256]          in the accept region: the class of every byte, 0 .. C-1;
+ *   table  uint16 [S + 1][pitch] from the start of the delta region: row s is state s (row 0, the dead state, is never walked
+ *                                from); column 0 is the state's accept flag, column 1 + c its successor on a byte of class c;
+ *   pitch  = (C + 1) | 1 (the columns padded to an odd count) where (S + 1) * ((C + 1) | 1) <= P3V_GUIDE_WIDE_MAX_ENTRIES, else
+ *            C + 1: a function of S and C alone, so the record needs no further field.
+ * The bound is (S + 1) * (C + 1) <= P3V_GUIDE_WIDE_MAX_ENTRIES, the region the row already has.
+ *   walk(s, bytes): s = table[s][1 + cls[b]] for each byte b in order, stopping at 0; a byte whose cls[b] >= C leads to 0, and an
+ *   entry above S counts as 0 -- in column 0 as well: the state accepts iff its column-0 entry lies in 1..S.
+ * The rule is points 0 to 4 above with this walk and this accept flag; point 4 reads: a wide record with S < 1, C outside
+ * 1..256, (S + 1) * (C + 1) over the bound, or a state outside {-1, 1..S} is treated as DONE and is not written.  Whatever a
+ * record holds, nothing outside the row's region and the vocabulary table is read.  Rows of both forms, inactive rows and DONE
+ * rows share one launch; a row changes form by a new record and region, without a new capture. */
 #define P3V_GUIDE_MAX_STATES 255
 #define P3V_GUIDE_ACTIVE 1
+#define P3V_GUIDE_WIDE 256                   /* bit 8 of flags (bits 1..7 are not read) */
+#define P3V_GUIDE_WIDE_MAX_ENTRIES 65536     /* uint16 entries of one row's delta region */
 #define P3V_GUIDE_DONE (-1)
 typedef struct { int32_t flags, n_states, state, reserved; } p3v_guide_row_t;   /* 16 bytes */
 /* eos: the EOS id (a launch argument; outside [0, n) there is no EOS position).  fed may be NULL (the first token, drawn from the

@@ -128,6 +128,7 @@ class GuideRow(C.Structure):
 
 GUIDE_WORDS = C.sizeof(GuideRow) // 4            # 4
 GUIDE_MAX_STATES, GUIDE_ACTIVE, GUIDE_DONE = 255, 1, -1     # P3V_GUIDE_MAX_STATES, P3V_GUIDE_ACTIVE, P3V_GUIDE_DONE
+GUIDE_WIDE, GUIDE_WIDE_MAX_ENTRIES = 256, 65536             # P3V_GUIDE_WIDE, P3V_GUIDE_WIDE_MAX_ENTRIES
 
 
 class KvCopyJob(C.Structure):

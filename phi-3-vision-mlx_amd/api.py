@@ -591,7 +591,7 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
               speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
               frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None, share_prefix=False,
-              guided_regex=None, guided_choice=None):
+              guided_regex=None, guided_choice=None, guided_json=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -628,7 +628,12 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     state does not allow, and allows EOS exactly in accepting states; the sampler then draws as usual and `logprobs` stay those
     of the raw logits.  With n / best_of every completion walks its own state.  max_tokens can still cut the output before
     the pattern completes.  None -- the default -- launches, allocates and captures nothing that was not there before; under
-    speculate a guide raises."""
+    speculate a guide raises.
+    guided_json (a JSON schema: a dict or its JSON text, one for every prompt, or a list of one schema / None per prompt): the
+    output is the JSON text of an instance of the schema, in declared key order with at most one space after ':' and ','
+    (guide.json_regex lists the keywords it translates and the ones it refuses by name).  It is a third kind of guide and
+    excludes the other two for the same prompt; a schema may need more than 255 states and then travels in the wide,
+    class-compressed form of the same record and kernel (include/p3v.h: P3V_GUIDE_WIDE), bounded by 65,536 table entries."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
     n, fam = parallel_mod.check(n, best_of)
@@ -654,7 +659,7 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
                              getattr(getattr(model, "cfg", None), "vocab_size", None))
     pen = None if penalties_mod.off(pen) else pen
     penalties_mod.refuse_speculation(pen, speculate)
-    guides = guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice)
+    guides = guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice, guided_json)
     guide_mod.refuse_speculation(guides, speculate)
     guide_state = None
     if guides is not None:                                      # compiled and checked against the vocabulary before anything runs
@@ -766,7 +771,7 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
              prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
              presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None,
-             share_prefix=False, guided_regex=None, guided_choice=None):
+             share_prefix=False, guided_regex=None, guided_choice=None, guided_json=None):
     """reference phi_3_vision_mlx.py:1324-1374, plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
     strings, see `_generate`), plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
@@ -774,7 +779,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
     log-probabilities (`logprobs=N`, `logprob_info`, see `_generate`) and the penalties on tokens already seen
     (`repetition_penalty`, `presence_penalty`, `frequency_penalty`) and per-token biases (`logit_bias`), see `_generate`, and
     `share_prefix` (the n rows of a family read their prompt's K/V once per decode step, see `_generate`), and guided decoding
-    (`guided_regex`, `guided_choice`: the output full-matches a regular expression or is one of a list, see `_generate`)."""
+    (`guided_regex`, `guided_choice`, `guided_json`: the output full-matches a regular expression, is one of a list, or is the
+    JSON text of an instance of a JSON schema, see `_generate`)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
     n, fam = parallel_mod.check(n, best_of)                      # before a model is loaded or run
@@ -786,8 +792,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
     logprobs_mod.refuse_speculation(lp_wants, speculate)
     penalties_mod.refuse_speculation(penalties_mod.rows(B, repetition_penalty,
                                                         presence_penalty, frequency_penalty, logit_bias), speculate)
-    guide_mod.refuse_speculation(guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice),
-                                 speculate)                     # (a bad pattern raises here, before a model is loaded)
+    guide_mod.refuse_speculation(guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice,
+                                                      guided_json), speculate)   # (a bad pattern raises here, before a model is loaded)
     if preload is None:
         preload = load(blind_model=blind_model, quantize_model=quantize_model, quantize_cache=quantize_cache, use_adapter=use_adapter)
     return _generate(*preload, *_apply_chat_template(prompt, images, verbose, apply_chat_template), max_tokens=max_tokens,
@@ -798,7 +804,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
                      **({} if (n, best_of, family_info) == (1, None, None) else dict(n=n, best_of=best_of, family_info=family_info)),
                      **({"share_prefix": True} if share_prefix else {}),
                      **({} if guided_regex is None and guided_choice is None else
-                        dict(guided_regex=guided_regex, guided_choice=guided_choice)))
+                        dict(guided_regex=guided_regex, guided_choice=guided_choice)),
+                     **({} if guided_json is None else dict(guided_json=guided_json)))
 
 
 # ----------------------------------------------------------------------------- score

@@ -219,8 +219,8 @@ class ContinuousEngine:
         rule of include/p3v.h (p3v_penalty_row_t) before its token is drawn, from its first token on, whoever shares the
         batch; rows that did not ask pass through bit for bit.  While no active request asks, nothing of it runs.
         Guided decoding: `submit(guide_args(inputs, regex=pattern), ...)` or `guide_args(inputs, choice=[...])` puts the request's
-        guide beside the inputs in the same way; it is compiled and checked against the vocabulary HERE, so a bad pattern fails
-        the handle at once.  The request's row then has its penalised logits masked by the rule of include/p3v.h
+        guide beside the inputs in the same way (`guide_args(inputs, schema={...})`: a JSON schema); it is compiled and checked
+        against the vocabulary HERE, so a bad pattern or schema fails the handle at once.  The request's row then has its penalised logits masked by the rule of include/p3v.h
         (p3v_guide_row_t) before its token is drawn, from its first token on; a refilled row starts from its own start state.
         While no active request asks, nothing of it runs.
         n completions: `submit(n_args(inputs, n, best_of=None), ...)` puts the count beside the inputs in the same way, so the
@@ -701,13 +701,15 @@ def penalty_args(inputs, repetition_penalty=1.0, presence_penalty=0.0, frequency
         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)))
 
 
-def guide_args(inputs, regex=None, choice=None):
-    """... the request's guide: a regular expression or a choice list (one of them; guide.py compiles and checks it at submit)."""
-    if regex is not None and choice is not None:
-        raise ValueError("guided_regex and guided_choice exclude each other: give one per prompt")
-    if regex is None and choice is None:
+def guide_args(inputs, regex=None, choice=None, schema=None):
+    """... the request's guide: a regular expression, a choice list or a JSON schema (a dict or its JSON text) -- one of them;
+    guide.py compiles and checks it at submit."""
+    from .guide import exclusive
+    exclusive(regex, choice, schema)
+    if regex is None and choice is None and schema is None:
         return inputs
-    return carry(inputs, GUIDE_ARGS, RequestOptions(guide={"regex": regex} if regex is not None else {"choice": list(choice)}))
+    guide = {"regex": regex} if regex is not None else {"choice": list(choice)} if choice is not None else {"schema": schema}
+    return carry(inputs, GUIDE_ARGS, RequestOptions(guide=guide))
 
 
 def logprob_args(inputs, logprobs):
@@ -757,7 +759,7 @@ def _generate_text(engine, processor, prompts, images, max_tokens, timeout, samp
     records -- token_ids / token_logprobs / ranks / top_logprobs over the tokens of the returned text -- or None).
     logprobs: None, N in 0..8, or one such value per prompt.  penalties: None, one {"repetition_penalty", "presence_penalty",
     "frequency_penalty", "logit_bias"} dict for every prompt, or one dict / None per prompt.  guide: None, one {"regex": pattern} /
-    {"choice": [strings]} dict for every prompt, or one dict / None per prompt."""
+    {"choice": [strings]} / {"schema": JSON schema} dict for every prompt, or one dict / None per prompt."""
     from . import api
     prompts = [prompts] if isinstance(prompts, str) else list(prompts)
     opts = options_per_prompt(len(prompts), sampling, adapter, logprobs, penalties, cache_prompt, n, best_of,

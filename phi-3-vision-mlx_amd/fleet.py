@@ -90,7 +90,7 @@ class EngineFleet:
         """Prefix-cache arguments (`engine.cache_args`) travel inside `inputs` to whichever rank takes the request (one store per
         engine; no cache-affinity routing: the least-loaded rank wins as before).  So does `logprobs` (`engine.logprob_args`);
         the records come back with the tokens.  Penalties and logit_bias (`engine.penalty_args`) ride there too; a bad value is
-        refused here, on rank 0.  A guide (`engine.guide_args`: a regular expression or a choice list) rides there as the plain
+        refused here, on rank 0.  A guide (`engine.guide_args`: a regular expression, a choice list or a JSON schema) rides there as the plain
         dict it is and is compiled by the rank that serves it; a pattern that does not compile is refused here.  A family of n completions (`engine.n_args`) goes to ONE rank as one request: its engine
         prefills once and forks; the returned completions come back in one message and fill the head's `completions`."""
         try:                                                     # a bad value never leaves rank 0 (the vocabulary bound: the rank's engine)

@@ -4,8 +4,10 @@ vocabulary's byte table, the liveness check of a DFA against a vocabulary, and a
 The rule itself is written out in include/p3v.h above `p3v_guide_row_t`; the kernel in csrc/p3v_guide.hip implements it and
 `reference_mask` here reproduces every output bit and every state.
 
-A guide is a DFA over BYTES: states 1..S (S <= 255), state 0 dead, state 1 the start, `delta` uint16 [S + 1, 256], `accept`
-uint8 [S + 1].  It constrains the UTF-8 bytes of the whole output (full-match semantics): the concatenated byte strings of the
+A guide is a DFA over BYTES: states 1..S, state 0 dead, state 1 the start, `delta` uint16 [S + 1, 256], `accept` uint8 [S + 1].
+A regular expression or a choice list holds S <= 255 states and travels to the device in the NARROW form (one table row of 256
+entries per state); a JSON schema (`json_regex`, `compile_json`) may need more and then travels in the WIDE form, its table
+compressed to the byte classes the guide distinguishes, bounded by (S + 1) * (C + 1) <= 65,536 entries (`region`, `record`).  It constrains the UTF-8 bytes of the whole output (full-match semantics): the concatenated byte strings of the
 generated token ids up to EOS.  EOS is allowed exactly in accepting states; `max_tokens` can still cut the output before the
 pattern completes.
 
@@ -23,8 +25,10 @@ from collections import OrderedDict
 import numpy as np
 
 MAX_STATES = 255                      # P3V_GUIDE_MAX_STATES
+WIDE_MAX_ENTRIES = 65536              # P3V_GUIDE_WIDE_MAX_ENTRIES: (S + 1) * (C + 1) of a wide guide
 DONE = -1                             # p3v_guide_row_t.state after EOS
 ACTIVE = 1                            # P3V_GUIDE_ACTIVE (bit 0 of flags)
+WIDE = 256                            # P3V_GUIDE_WIDE (bit 8 of flags): the record's `reserved` is then the class count C
 RECORD_WORDS = 4                      # sizeof(p3v_guide_row_t) / 4: {flags, n_states, state, reserved}
 NEG_INF = 0xFF80                      # bf16 -inf
 _SUBSET_CAP = 20000                   # subset construction gives up beyond this many DFA states
@@ -45,6 +49,19 @@ class Dfa:
         self.accept = np.ascontiguousarray(accept, dtype=np.uint8)
         self.n_states = int(self.delta.shape[0]) - 1
         self.pattern = pattern
+        self._classes = None
+
+    def classes(self):
+        """The byte classes of the table -- its distinct columns: (cls uint8 [256], the class 0 .. C-1 of every byte; a
+        representative byte of every class int64 [C])."""
+        if self._classes is None:
+            _, first, inv = np.unique(self.delta.T, axis=0, return_index=True, return_inverse=True)
+            self._classes = (inv.reshape(-1).astype(np.uint8), first.astype(np.int64))
+        return self._classes
+
+    @property
+    def n_classes(self):
+        return len(self.classes()[1])
 
     def walk(self, data, state=1):
         for b in bytes(data):
@@ -265,7 +282,8 @@ _MULTIBYTE = [("cat", [_r(0xC2, 0xDF), _CONT]),
 
 # ----------------------------------------------------------------------------- Thompson construction: AST -> NFA over bytes
 class _Nfa:
-    def __init__(self):
+    def __init__(self, what="guided_regex"):
+        self.what = what                                        # the option an error names
         self.eps = []                                           # state -> [states]
         self.edges = []                                         # state -> [(frozenset of bytes, state)]
 
@@ -273,7 +291,7 @@ class _Nfa:
         self.eps.append([])
         self.edges.append([])
         if len(self.eps) > 200000:
-            raise ValueError("guided_regex: the pattern expands to more than 200000 NFA states")
+            raise ValueError(f"{self.what}: the pattern expands to more than 200000 NFA states")
         return len(self.eps) - 1
 
     def build(self, node):
@@ -340,22 +358,38 @@ class _Nfa:
 
 
 # ----------------------------------------------------------------------------- subset construction, minimisation, pruning
-def _subset(nfa, start, final):
-    """-> (delta int32 [N, 256] complete over N subsets, subset 0 = the start; accept bool [N])."""
+def _byte_classes(nfa):
+    """The partition of 0..255 by the pattern's byte sets: (class of every byte int64 [256], the classes of every byte set)."""
+    sets = list({bs for edges in nfa.edges for bs, _ in edges})
+    if not sets:                                                # (the empty pattern: one class, no edge)
+        return np.zeros(256, dtype=np.int64), {}
+    member = np.zeros((len(sets), 256), dtype=bool)
+    for i, bs in enumerate(sets):
+        member[i, list(bs)] = True
+    _, inv = np.unique(member.T, axis=0, return_inverse=True)
+    inv = inv.reshape(-1).astype(np.int64)
+    return inv, {bs: np.unique(inv[member[i]]).tolist() for i, bs in enumerate(sets)}
+
+
+def _subset(nfa, start, final, wide=False):
+    """-> (delta int64 [N, K] complete over N subsets and the K byte classes of the pattern, subset 0 = the start; accept bool
+    [N]; the class of every byte int64 [256]).  Two bytes that no byte set of the pattern tells apart share a column."""
+    byte_cls, classes_of = _byte_classes(nfa)
+    K = int(byte_cls.max()) + 1
     s0 = nfa.closure([start])
     index, order, rows = {s0: 0}, [s0], []
     k = 0
     while k < len(order):
         cur = order[k]
         k += 1
-        by_byte = {}
+        by_cls = {}
         for s in cur:
             for bs, t in nfa.edges[s]:
-                for b in bs:
-                    by_byte.setdefault(b, set()).add(t)
-        row = np.full(256, -1, dtype=np.int64)
+                for c in classes_of[bs]:
+                    by_cls.setdefault(c, set()).add(t)
+        row = np.full(K, -1, dtype=np.int64)
         memo = {}
-        for b, ts in by_byte.items():
+        for c, ts in by_cls.items():
             key = frozenset(ts)
             if key not in memo:
                 nxt = nfa.closure(key)
@@ -363,16 +397,17 @@ def _subset(nfa, start, final):
                     index[nxt] = len(order)
                     order.append(nxt)
                     if len(order) > _SUBSET_CAP:
-                        raise ValueError(f"guided_regex: more than {_SUBSET_CAP} states in the subset construction "
-                                         f"(a guide holds at most {MAX_STATES})")
+                        holds = f"{WIDE_MAX_ENTRIES} table entries, (states + 1) * (byte classes + 1)" if wide else MAX_STATES
+                        raise ValueError(f"{nfa.what}: more than {_SUBSET_CAP} states in the subset construction "
+                                         f"(a guide holds at most {holds})")
                 memo[key] = index[nxt]
-            row[b] = memo[key]
+            row[c] = memo[key]
         rows.append(row)
     delta = np.stack(rows)
     dead = len(order)                                           # one explicit dead state completes the table
-    delta = np.concatenate([np.where(delta < 0, dead, delta), np.full((1, 256), dead, dtype=np.int64)])
+    delta = np.concatenate([np.where(delta < 0, dead, delta), np.full((1, K), dead, dtype=np.int64)])
     accept = np.array([final in s for s in order] + [False])
-    return delta, accept
+    return delta, accept, byte_cls
 
 
 def _minimise(delta, accept):
@@ -389,7 +424,7 @@ def _minimise(delta, accept):
         cls, n_cls = new, n_new
 
 
-def _finish(delta, accept, pattern):
+def _finish(delta, accept, byte_cls, pattern, wide=False, what="guided_regex"):
     cls, n = _minimise(delta, accept)
     rep = np.zeros(n, dtype=np.int64)
     rep[cls[::-1]] = np.arange(len(cls))[::-1]                  # one member per class
@@ -403,32 +438,38 @@ def _finish(delta, accept, pattern):
         live = grown
     start = int(cls[0])
     if not live[start]:
-        raise ValueError(f"guided_regex: {pattern!r} matches nothing")
+        raise ValueError(f"{what}: {pattern!r} matches nothing")
+    mdelta = mdelta[:, byte_cls]                                # back to one column per byte
     # renumber: 0 dead, 1 the start, the rest in breadth-first order from the start
     number, queue = {start: 1}, [start]
     for s in queue:
-        for t in mdelta[s]:
-            t = int(t)
+        for t in mdelta[s].tolist():
             if live[t] and t not in number:
                 number[t] = len(number) + 1
                 queue.append(t)
     S = len(number)
-    if S > MAX_STATES:
+    if not wide and S > MAX_STATES:
         raise ValueError(f"guided_regex: {pattern!r} needs {S} states after minimisation; a guide holds at most {MAX_STATES}")
+    num = np.zeros(n, dtype=np.int64)
+    for s, k in number.items():
+        num[s] = k
     out = np.zeros((S + 1, 256), dtype=np.uint16)
     acc = np.zeros(S + 1, dtype=np.uint8)
-    for s, k in number.items():
-        row = mdelta[s]
-        out[k] = [number[int(t)] if live[t] else 0 for t in row]
-        acc[k] = 1 if maccept[s] else 0
-    return Dfa(out, acc, pattern)
+    out[1:] = num[mdelta[queue]]
+    acc[1:] = maccept[queue]
+    dfa = Dfa(out, acc, pattern)
+    if wide and S > MAX_STATES and (S + 1) * (dfa.n_classes + 1) > WIDE_MAX_ENTRIES:
+        C = dfa.n_classes
+        raise ValueError(f"{what}: the guide needs {S} states and {C} byte classes after minimisation, ({S} + 1) * ({C} + 1) = "
+                         f"{(S + 1) * (C + 1)} table entries; a guide holds at most {WIDE_MAX_ENTRIES}")
+    return dfa
 
 
-def _compile(pattern):
+def _compile(pattern, wide=False, what="guided_regex"):
     ast = _Parser(pattern).parse()
-    nfa = _Nfa()
+    nfa = _Nfa(what)
     start, final = nfa.build(ast)
-    return _finish(*_subset(nfa, start, final), pattern)
+    return _finish(*_subset(nfa, start, final, wide), pattern, wide, what)
 
 
 # ----------------------------------------------------------------------------- the host LRU cache of compiled guides
@@ -441,15 +482,258 @@ def compile_regex(pattern):
     or the state count beyond 255.  Compiled guides are kept in a small LRU cache keyed by the pattern."""
     if not isinstance(pattern, str):
         raise ValueError(f"guided_regex must be a string, got {type(pattern).__name__}")
-    hit = _cache.get(pattern)
+    return _cached(pattern, lambda: _compile(pattern))
+
+
+def _cached(key, make):
+    hit = _cache.get(key)
     if hit is not None:
-        _cache.move_to_end(pattern)
+        _cache.move_to_end(key)
         return hit
-    dfa = _compile(pattern)
-    _cache[pattern] = dfa
+    dfa = make()
+    _cache[key] = dfa
     while len(_cache) > CACHE_SIZE:
         _cache.popitem(last=False)
     return dfa
+
+
+def compile_wide(pattern, what="guided_regex"):
+    """`pattern` compiled under the WIDE bound: any number of states S whose class-compressed table fits, (S + 1) * (C + 1) <=
+    65,536 entries with C the byte classes (the distinct columns) of the minimised table; up to 255 states always fit (the
+    narrow form).  ValueError reports S, C and the bound otherwise.  Not cached: `compile_json` caches by schema."""
+    if not isinstance(pattern, str):
+        raise ValueError(f"a guide pattern must be a string, got {type(pattern).__name__}")
+    return _compile(pattern, wide=True, what=what)
+
+
+# ----------------------------------------------------------------------------- JSON schema -> pattern
+_J_ANNOTATIONS = ("title", "description", "default", "examples", "$schema", "$id", "$defs", "definitions")
+_J_REFUSED = {
+    "pattern": "a string's own regular expression is not translated", "format": "formats are not translated",
+    "minimum": "numeric bounds are not regular in a useful size", "maximum": "numeric bounds are not regular in a useful size",
+    "exclusiveMinimum": "numeric bounds are not regular in a useful size",
+    "exclusiveMaximum": "numeric bounds are not regular in a useful size", "multipleOf": "divisibility is not translated",
+    "allOf": "an intersection of schemas is not translated", "not": "a complement is not translated",
+    "if": "conditionals are not translated", "then": "conditionals are not translated", "else": "conditionals are not translated",
+    "prefixItems": "tuple arrays are not translated (one `items` schema for every element)"}
+_J_BY_TYPE = {"object": ("properties", "required", "additionalProperties"), "array": ("items", "minItems", "maxItems"),
+              "string": ("minLength", "maxLength"), "integer": (), "number": (), "boolean": (), "null": ()}
+_J_CHAR = r'(?:[^"\\\x00-\x1f]|\\(?:["\\/bfnrt]|u[0-9a-fA-F]{4}))'
+_J_INTEGER = r"-?(?:0|[1-9][0-9]{0,17})"
+_J_NUMBER = _J_INTEGER + r"(?:\.[0-9]{1,17})?(?:[eE][+-]?[0-9]{1,3})?"
+_J_COLON, _J_COMMA = ": ?", ", ?"
+
+
+def _j_fail(path, msg):
+    raise ValueError(f"guided_json: {msg} (at {path or '#'})")
+
+
+def _j_count(schema, key, path, default):
+    if key not in schema:
+        return default
+    v = schema[key]
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        _j_fail(path, f"{key} must be a non-negative integer, got {v!r}")
+    return v
+
+
+def _j_literal(v, path, key):
+    import json
+    if isinstance(v, float) and (v != v or v in (float("inf"), float("-inf"))):
+        _j_fail(path, f"{key} holds {v!r}, which JSON cannot spell")
+    if v is not None and not isinstance(v, (str, int, float, bool)):
+        _j_fail(path, f"{key} takes scalars only (string, number, boolean, null), got {type(v).__name__}")
+    return escape(json.dumps(v, ensure_ascii=False))
+
+
+def _j_is(v, t):
+    if t == "string":
+        return isinstance(v, str)
+    if t == "boolean":
+        return isinstance(v, bool)
+    if t == "null":
+        return v is None
+    if t == "integer":
+        return isinstance(v, int) and not isinstance(v, bool)
+    if t == "number":
+        return isinstance(v, (int, float)) and not isinstance(v, bool)
+    return False                                                # (enum / const hold scalars only)
+
+
+def _j_alt(branches):
+    seen = list(dict.fromkeys(branches))
+    return seen[0] if len(seen) == 1 else "(?:" + "|".join(seen) + ")"
+
+
+def _j_types(schema, path):
+    t = schema.get("type")
+    types = [t] if isinstance(t, str) else t
+    if not isinstance(types, list) or not types or any(not isinstance(x, str) or x not in _J_BY_TYPE for x in types):
+        _j_fail(path, f"type must be one of {sorted(_J_BY_TYPE)} or a non-empty list of them, got {t!r}")
+    return types
+
+
+def _j_node(schema, root, path, stack):
+    if not isinstance(schema, dict):
+        _j_fail(path, f"a schema must be an object, got {schema!r} (the schemas true and false are not translated)")
+    for k in schema:
+        if k in _J_REFUSED:
+            _j_fail(path, f"the keyword {k!r} is not supported: {_J_REFUSED[k]}")
+    keys = [k for k in schema if k not in _J_ANNOTATIONS]
+    heads = [k for k in ("$ref", "anyOf", "oneOf", "enum", "const") if k in schema]
+    if len(heads) > 1:
+        _j_fail(path, f"{heads[0]!r} beside {heads[1]!r} is not translated: give one of them")
+    head = heads[0] if heads else None
+    if head in ("$ref", "anyOf", "oneOf"):                      # these stand alone (beside annotations)
+        extra = [k for k in keys if k != head]
+        if extra:
+            _j_fail(path, f"the keyword {extra[0]!r} beside {head!r} is not translated (an intersection of schemas)")
+    if head == "$ref":
+        ref = schema["$ref"]
+        m = _re.fullmatch(r"#/(\$defs|definitions)/([^/]+)", ref) if isinstance(ref, str) else None
+        if m is None:
+            _j_fail(path, f"$ref {ref!r} is not supported: only '#/$defs/NAME' and '#/definitions/NAME'")
+        name = m.group(2).replace("~1", "/").replace("~0", "~")
+        target = root.get(m.group(1)) if isinstance(root, dict) else None
+        if not isinstance(target, dict) or name not in target:
+            _j_fail(path, f"$ref {ref!r} points at nothing")
+        if ref in stack:
+            _j_fail(path, f"$ref {ref!r} is recursive ({' -> '.join(stack + (ref,))}): a recursive schema is not regular")
+        return _j_node(target[name], root, ref, stack + (ref,))
+    if head in ("anyOf", "oneOf"):
+        subs = schema[head]
+        if not isinstance(subs, list) or not subs:
+            _j_fail(path, f"{head} must be a non-empty list of schemas")
+        return _j_alt([_j_node(sub, root, f"{path}/{head}/{i}", stack) for i, sub in enumerate(subs)])
+    if head in ("enum", "const"):
+        extra = [k for k in keys if k not in (head, "type")]
+        if extra:
+            _j_fail(path, f"the keyword {extra[0]!r} beside {head!r} is not translated")
+        values = [schema["const"]] if head == "const" else schema["enum"]
+        if not isinstance(values, list) or not values:
+            _j_fail(path, "enum must be a non-empty list of scalars")
+        lits = [(v, _j_literal(v, path, head)) for v in values]
+        if "type" in schema:                                    # both hold: the values of the enum that have the type
+            types = _j_types(schema, path)
+            lits = [(v, lit) for v, lit in lits if any(_j_is(v, t) for t in types)]
+            if not lits:
+                _j_fail(path, f"no value of {head} has the type {schema['type']!r}: the schema matches nothing")
+        return _j_alt([lit for _, lit in lits])
+    if "type" not in schema:
+        _j_fail(path, "a schema needs one of type, enum, const, anyOf, oneOf or $ref (free-form JSON is not regular)")
+    types = _j_types(schema, path)
+    known = {"type"} | {k for t in types for k in _J_BY_TYPE[t]}
+    for k in keys:
+        if k not in known:
+            where = [t for t, ks in _J_BY_TYPE.items() if k in ks]
+            _j_fail(path, f"the keyword {k!r} does not apply to type {schema['type']!r}" if where else f"unknown keyword {k!r}")
+    return _j_alt([_J_OF_TYPE[t](schema, root, path, stack) for t in types])
+
+
+def _j_object(schema, root, path, stack):
+    import json
+    if schema.get("additionalProperties", False) is not False:
+        _j_fail(path, "additionalProperties other than false is not supported: an object holds its declared properties only")
+    props = schema.get("properties")
+    if not isinstance(props, dict):
+        _j_fail(path, "an object needs properties (a free-form object is not regular)")
+    required = schema.get("required", [])
+    if not isinstance(required, list) or any(not isinstance(r, str) for r in required):
+        _j_fail(path, "required must be a list of property names")
+    for r in required:
+        if r not in props:
+            _j_fail(path, f"required names {r!r}, which is not among the properties: the schema matches nothing")
+    members = [(escape(json.dumps(k, ensure_ascii=False)) + _J_COLON + _j_node(v, root, f"{path}/properties/{k}", stack), k in required)
+               for k, v in props.items()]
+    # declared order; the branches differ in WHICH property comes first (no required one may lie before it), the properties
+    # behind it follow with their commas, the optional ones in (?: )?
+    branches = []
+    for i, (first, _) in enumerate(members):
+        rest = "".join(_J_COMMA + m if req else "(?:" + _J_COMMA + m + ")?" for m, req in members[i + 1:])
+        branches.append(first + rest)
+        if members[i][1]:
+            break
+    else:
+        branches.append("")                                     # no required property: {} matches
+    body = branches[0] if len(branches) == 1 else "(?:" + "|".join(branches) + ")"
+    return r"\{" + body + r"\}"
+
+
+def _j_array(schema, root, path, stack):
+    if "items" not in schema:
+        _j_fail(path, "an array needs items (a free-form array is not regular)")
+    lo, hi = _j_count(schema, "minItems", path, 0), _j_count(schema, "maxItems", path, None)
+    if hi is not None and hi < lo:
+        _j_fail(path, f"minItems {lo} > maxItems {hi}: the schema matches nothing")
+    if hi == 0:
+        return r"\[\]"
+    item = _j_node(schema["items"], root, f"{path}/items", stack)
+    more = "(?:" + _J_COMMA + item + ")" + ("{%d,}" % max(lo - 1, 0) if hi is None else "{%d,%d}" % (max(lo - 1, 0), hi - 1))
+    return r"\[" + (item + more if lo >= 1 else "(?:" + item + more + ")?") + r"\]"
+
+
+def _j_string(schema, root, path, stack):
+    lo, hi = _j_count(schema, "minLength", path, 0), _j_count(schema, "maxLength", path, None)
+    if hi is not None and hi < lo:
+        _j_fail(path, f"minLength {lo} > maxLength {hi}: the schema matches nothing")
+    rep = ("*" if lo == 0 else "{%d,}" % lo) if hi is None else "{%d,%d}" % (lo, hi)
+    return '"' + _J_CHAR + rep + '"'
+
+
+_J_OF_TYPE = {"object": _j_object, "array": _j_array, "string": _j_string, "integer": lambda *a: _J_INTEGER,
+              "number": lambda *a: _J_NUMBER, "boolean": lambda *a: "(?:true|false)", "null": lambda *a: "null"}
+
+
+def _j_schema(schema):
+    """A dict, or a JSON text of one -> (the dict, its cache key: the JSON text in DECLARED key order)."""
+    import json
+    if isinstance(schema, (str, bytes)):
+        try:
+            schema = json.loads(schema)
+        except ValueError as e:
+            raise ValueError(f"guided_json: the schema is not valid JSON: {e}") from None
+    if not isinstance(schema, dict):
+        raise ValueError(f"guided_json must be a JSON schema (an object or its JSON text), got {type(schema).__name__}")
+    try:
+        return schema, json.dumps(schema, separators=(",", ":"), allow_nan=False)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"guided_json: the schema is not JSON: {e}") from None
+
+
+def json_regex(schema):
+    """A JSON schema (a dict or its JSON text) as a pattern of this module's regex subset: the JSON texts of the instances that
+    satisfy it.  Every keyword is translated, ignored as an annotation, or refused with a ValueError that names it:
+      type       object, array, string, integer, number, boolean, null, or a list of them (an alternation);
+      object     `properties` in DECLARED order, `required` (the others are optional and keep their place in that order);
+                 `additionalProperties` absent or false; true or a schema is refused, as is an object without `properties`;
+      array      `items` (one schema), `minItems`, `maxItems`; `prefixItems` and an array without `items` are refused;
+      string     any code point except `"`, `\\` and those below 0x20, and the escapes \\" \\\\ \\/ \\b \\f \\n \\r \\t \\uXXXX;
+                 `minLength` / `maxLength`; `pattern` and `format` are refused;
+      integer    -?(0|[1-9][0-9]{0,17});  number: that plus an optional fraction of 1..17 digits and an exponent of 1..3 digits;
+                 minimum, maximum, exclusiveMinimum, exclusiveMaximum and multipleOf are refused;
+      enum/const scalars only, each as json.dumps(v, ensure_ascii=False); beside `type`, the values that have the type;
+      anyOf/oneOf  an alternation; allOf, not, if / then / else are refused;
+      $ref       to #/$defs/NAME or #/definitions/NAME, inlined; a cycle raises and names the reference;
+      ignored    title, description, default, examples, $schema, $id, $defs, definitions.
+    Whitespace: ONE optional space after ':' and after ',' and nowhere else, so json.dumps(x) and json.dumps(x, separators=
+    (",", ":")) of a valid instance both match -- in declared key order.
+    Departures from the JSON Schema specification: the key order is fixed (declared order) and no key may repeat; other keys are
+    never allowed (`additionalProperties` defaults to false, not true); `oneOf` is `anyOf` (an instance that satisfies two
+    branches matches); `minLength` / `maxLength` count one per character or escape, so a surrogate pair written as two \\uXXXX
+    escapes counts two; integers hold at most 18 digits, fractions 17, exponents 3, and `1.0` or `1e2` is not an integer;
+    a keyword of another type (`minLength` beside type integer), `enum` / `const` beside anything but `type`, and anyOf / oneOf /
+    $ref beside other keywords are refused instead of being combined; the schemas `true`, `false` and `{}` are refused."""
+    schema, _ = _j_schema(schema)
+    return _j_node(schema, schema, "", ())
+
+
+def compile_json(schema):
+    """The guide of a JSON schema (a dict or its JSON text): `json_regex` through the same compiler under the wide bound
+    (`compile_wide`).  ValueError names a refused keyword, or the state count, class count and bound of a guide that does not
+    fit.  Compiled guides share the LRU cache of the patterns, keyed by the schema's JSON text -- in declared key order, NOT
+    sort_keys: the order of `properties` is part of the meaning here."""
+    schema, key = _j_schema(schema)
+    return _cached(("json", key), lambda: compile_wide(_j_node(schema, schema, "", ()), what="guided_json"))
 
 
 def escape(text):
@@ -467,21 +751,35 @@ def compile_choice(choices):
     return compile_regex("|".join("(?:" + escape(c) + ")" for c in choices))
 
 
-def compile_guide(regex=None, choice=None):
-    """One request's guide: None when it asks for none; both at once raise."""
-    if regex is not None and choice is not None:
-        raise ValueError("guided_regex and guided_choice exclude each other: give one per prompt")
+def exclusive(regex=None, choice=None, schema=None):
+    """At most one kind of guide per prompt: two at once raise, naming them."""
+    given = [name for name, v in (("guided_regex", regex), ("guided_choice", choice), ("guided_json", schema)) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f"{', '.join(given[:-1])} and {given[-1]} exclude each other: give one per prompt")
+
+
+def compile_guide(regex=None, choice=None, schema=None):
+    """One request's guide: None when it asks for none; two kinds at once raise."""
+    exclusive(regex, choice, schema)
     if regex is not None:
         return compile_regex(regex)
     if choice is not None:
         return compile_choice(choice)
+    if schema is not None:
+        return compile_json(schema)
     return None
 
 
-def per_prompt(B, regex=None, choice=None):
+def per_prompt(B, regex=None, choice=None, schema=None):
     """The public arguments -- each one value for every prompt, or a list of one value / None per prompt -- as B compiled
     guides / None, or None when no prompt has one.  (A choice list is a list of strings: a per-prompt list of choices is a
-    list of lists / None.)"""
+    list of lists / None.  A schema is a dict or its JSON text: a list is one schema / None per prompt.)"""
+    if isinstance(schema, (list, tuple)):
+        if len(schema) != B:
+            raise ValueError(f"guided_json: {len(schema)} values for {B} prompts")
+        sc = list(schema)
+    else:
+        sc = [schema] * B
     if isinstance(regex, (list, tuple)):
         if len(regex) != B:
             raise ValueError(f"guided_regex: {len(regex)} values for {B} prompts")
@@ -494,7 +792,7 @@ def per_prompt(B, regex=None, choice=None):
         ch = list(choice)
     else:
         ch = [choice] * B
-    out = [compile_guide(r, c) for r, c in zip(rx, ch)]
+    out = [compile_guide(r, c, s) for r, c, s in zip(rx, ch, sc)]
     return None if all(g is None for g in out) else out
 
 
@@ -650,35 +948,91 @@ def checked(dfa, table, eos):
 
 
 # ----------------------------------------------------------------------------- records and the rule in NumPy
-def record(dfa, state=1):
-    """One row's p3v_guide_row_t words: an inactive row for None."""
-    return [0, 0, 0, 0] if dfa is None else [ACTIVE, dfa.n_states, int(state), 0]
+def is_wide(dfa, wide=None):
+    """Does this guide travel in the wide form?  Above 255 states it must; `wide=True` forces a smaller one into it."""
+    return dfa.n_states > MAX_STATES if wide is None else bool(wide) or dfa.n_states > MAX_STATES
 
 
-def region(dfa):
-    """A guide as one row's table region: (delta uint16 [256, 256], accept uint8 [256]), zero beyond its states."""
+def wide_pitch(n_states, n_classes):
+    """The row pitch of a wide table (include/p3v.h): C + 1 columns, padded to an odd count where rows 0..S still fit."""
+    odd = (n_classes + 1) | 1
+    return odd if (n_states + 1) * odd <= WIDE_MAX_ENTRIES else n_classes + 1
+
+
+def record(dfa, state=1, wide=None):
+    """One row's p3v_guide_row_t words: an inactive row for None; the narrow form up to 255 states, the wide form (the flag,
+    and the class count in `reserved`) above -- or where `wide` forces it."""
+    if dfa is None:
+        return [0, 0, 0, 0]
+    if is_wide(dfa, wide):
+        return [ACTIVE | WIDE, dfa.n_states, int(state), dfa.n_classes]
+    return [ACTIVE, dfa.n_states, int(state), 0]
+
+
+def region(dfa, wide=None):
+    """A guide as one row's table region, (delta uint16 [256, 256], accept uint8 [256]), zero beyond what it fills.  Narrow (up
+    to 255 states): the dense table and the accept flags.  Wide (above, or forced): `accept` holds the class of every byte and
+    `delta`, read flat, the table [S + 1, pitch] -- column 0 the accept flag, column 1 + c the successor on class c."""
     d = np.zeros((256, 256), dtype=np.uint16)
     a = np.zeros(256, dtype=np.uint8)
-    d[:dfa.n_states + 1] = dfa.delta
-    a[:dfa.n_states + 1] = dfa.accept
+    S = dfa.n_states
+    if not is_wide(dfa, wide):
+        d[:S + 1] = dfa.delta
+        a[:S + 1] = dfa.accept
+        return d, a
+    cls, rep = dfa.classes()
+    C = len(rep)
+    if (S + 1) * (C + 1) > WIDE_MAX_ENTRIES:
+        raise ValueError(f"a guide of {S} states and {C} byte classes needs ({S} + 1) * ({C} + 1) = {(S + 1) * (C + 1)} table "
+                         f"entries; a guide holds at most {WIDE_MAX_ENTRIES}")
+    pitch = wide_pitch(S, C)
+    table = d.reshape(-1)[:(S + 1) * pitch].reshape(S + 1, pitch)
+    table[:, 0] = dfa.accept
+    table[:, 1:C + 1] = dfa.delta[:, rep]
+    a[:] = cls
     return d, a
+
+
+def region_rows(dfa, wide=None):
+    """How many of the 256 rows of `region(dfa)[0]` the guide fills (the rest is zero and never read)."""
+    S = dfa.n_states
+    return -(-(S + 1) * wide_pitch(S, dfa.n_classes) // 256) if is_wide(dfa, wide) else S + 1
+
+
+def _dense(n_states, n_classes, region_delta, region_cls):
+    """A wide row's region read back as the rule's walk sees it: (delta int64 [S + 1, 256], accept uint8 [S + 1])."""
+    pitch = wide_pitch(n_states, n_classes)
+    table = np.asarray(region_delta, dtype=np.uint16).reshape(-1)[:(n_states + 1) * pitch].reshape(n_states + 1, pitch).astype(np.int64)
+    table[table > n_states] = 0                                                 # an entry above S counts as 0, in every column
+    cls = np.asarray(region_cls, dtype=np.uint8).reshape(256).astype(np.int64)
+    delta = np.where(cls[None, :] < n_classes, table[:, 1 + np.minimum(cls, n_classes - 1)], 0)   # a class outside 0..C-1: dead
+    return delta, (table[:, 0] != 0).astype(np.uint8)
 
 
 def reference_mask(logits_bf16, rec, delta, accept, table, fed, eos):
     """The rule of include/p3v.h (p3v_guide_mask) on ONE row.  logits_bf16: uint16 [n] (bf16 bits); rec: the row's four record
     words {flags, n_states, state, reserved}; delta uint16 [256, 256] and accept uint8 [256]: the row's region; table: a
     VocabTable over at least n ids; fed: the token the step was fed, or None (the kernel's fed == NULL); eos: the EOS id.
+    A record with the WIDE flag reads the same region as the wide form (cls in `accept`, the class-compressed table in `delta`,
+    C in the record's fourth word); the rule is the same from there on.
     Returns (masked bits uint16 [n], the record's state afterwards)."""
     bits = np.array(logits_bf16, dtype=np.uint16)
     n = bits.shape[0]
     flags, n_states, state = int(rec[0]), int(rec[1]), int(rec[2])
     if not flags & ACTIVE:                                                      # 0.
         return bits, state
-    delta = np.asarray(delta, dtype=np.uint16).reshape(256, 256)
-    accept = np.asarray(accept, dtype=np.uint8).reshape(256)
     lens, mat = table.padded()
     lens, mat = lens[:n], mat[:n]
-    good = 1 <= n_states <= MAX_STATES and (state == DONE or 1 <= state <= n_states)
+    good = n_states >= 1 and (state == DONE or 1 <= state <= n_states)
+    if flags & WIDE:
+        n_classes = int(rec[3])
+        good = good and 1 <= n_classes <= 256 and (n_states + 1) * (n_classes + 1) <= WIDE_MAX_ENTRIES
+        if good:
+            delta, accept = _dense(n_states, n_classes, delta, accept)
+    else:
+        good = good and n_states <= MAX_STATES
+        delta = np.asarray(delta, dtype=np.uint16).reshape(256, 256)
+        accept = np.asarray(accept, dtype=np.uint8).reshape(256)
     if good and state != DONE and fed is not None:                              # 1. (a record out of range is not written)
         f = int(fed)
         if f == int(eos):
@@ -700,11 +1054,12 @@ def reference_mask(logits_bf16, rec, delta, accept, table, fed, eos):
 
 
 # ---- a request's guide as one JSON-able dict (engine.guide_args, the fleet, the server)
-FIELDS = ("regex", "choice")
+FIELDS = ("regex", "choice", "schema")
 
 
 def request_guide(d):
-    """One request's {"regex": str} or {"choice": [str, ...]} -> its compiled guide, or None when it asks for none."""
+    """One request's {"regex": str}, {"choice": [str, ...]} or {"schema": a JSON schema (a dict or its JSON text)} -> its compiled
+    guide, or None when it asks for none."""
     if d is None:
         return None
     if not isinstance(d, dict):
@@ -715,4 +1070,4 @@ def request_guide(d):
     regex, choice = d.get("regex"), d.get("choice")
     if regex is not None and not isinstance(regex, str):
         raise ValueError(f"guided_regex must be a string, got {type(regex).__name__}")
-    return compile_guide(regex, choice)
+    return compile_guide(regex, choice, d.get("schema"))

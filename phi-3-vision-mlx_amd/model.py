@@ -1676,9 +1676,10 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
             recs.append(guide_mod.record(dfa, 1 if states is None else states[i]))
             if dfa is None:
                 continue
-            S1 = dfa.n_states + 1
-            gd["delta"][row0 + i, :S1].copy_(torch.from_numpy(dfa.delta.view(np.int16)))
-            gd["accept"][row0 + i, :S1].copy_(torch.from_numpy(dfa.accept))
+            delta, accept = guide_mod.region(dfa)               # (narrow up to 255 states, wide above: include/p3v.h)
+            filled = guide_mod.region_rows(dfa)                 # (only the part of the 128 KB the guide fills is copied)
+            gd["delta"][row0 + i, :filled].copy_(torch.from_numpy(delta[:filled].view(np.int16)))
+            gd["accept"][row0 + i].copy_(torch.from_numpy(accept))
         if n:
             gd["rows"][row0:row0 + n].copy_(torch.tensor(recs, dtype=I32))
 

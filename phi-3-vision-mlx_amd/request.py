@@ -25,7 +25,7 @@ class RequestOptions:
     adapter: object = None          # None (the base model) or the name of an adapter of the model's bank
     logprobs: object = None         # None (off) or N in 0..8
     penalties: object = None        # None (off) or {"repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"}
-    guide: object = None            # None (off) or {"regex": pattern} / {"choice": [strings]}; checked: the compiled guide.Dfa
+    guide: object = None            # None (off) or {"regex": pattern} / {"choice": [strings]} / {"schema": JSON schema}; checked: the compiled guide.Dfa
     n: object = 1                   # completions returned ...
     best_of: object = None          # ... of this many generated (None: n)
     image_digests: object = None    # prefix cache: one prefix.image_digest per source image
@@ -151,7 +151,7 @@ def options_per_prompt(n_prompts, sampling=None, adapter=None, logprobs=None, pe
                        guide=None):
     """The arguments of a text-level call -> one record per prompt.  sampling: None or one settings dict per prompt; adapter: None,
     a name, or one name / None per prompt; logprobs: None, N, or one value per prompt; penalties: None, one dict for every prompt,
-    or one dict / None per prompt; n / best_of: a family, of one prompt only; guide: None, one {"regex"} / {"choice"} dict for every
+    or one dict / None per prompt; n / best_of: a family, of one prompt only; guide: None, one {"regex"} / {"choice"} / {"schema"} dict for every
     prompt, or one dict / None per prompt.  ValueError for a list of the wrong length."""
     from .logprobs import OFF, wants
     from .parallel import check, refusal

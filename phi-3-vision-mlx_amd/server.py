@@ -33,7 +33,13 @@
      sentencepiece vocabulary counts as a space); "max_tokens" can still cut it short.  The guide is a byte-level DFA walked on
      the device (include/p3v.h: p3v_guide_row_t).  A bad type, an unsupported construct or more than 255 states -> 400 with the
      reason; so does an explicit "speculate" > 0 next to it, and the batch-sharded path.  Honoured on the one-request, the
-     merged and the --continuous path; merged requests keep their own.)
+     merged and the --continuous path; merged requests keep their own.
+     "guided_json": a JSON schema (an object, or its JSON text) is the third kind and excludes the other two: the generated text
+     is the JSON text of an instance, keys in declared order, at most one space after ':' and ',' (guide.json_regex names the
+     keywords it translates and refuses).  The OpenAI form "response_format": {"type": "json_schema", "json_schema": {"schema":
+     {...}}} means the same; {"type": "text"} is no guide; {"type": "json_object"} -> 400: free-form JSON is not a regular
+     language, and the guide is a finite automaton of at most 65,536 table entries -- send a schema.  A refused keyword, or a
+     schema whose automaton exceeds that bound -> 400 with the keyword, or with the state and class counts.)
     (extension: "n": 1 .. 16 completions of ONE prompt (a string), and "best_of": n .. 16 -- the prompt is prefilled once, its
      K/V forked into the other rows (include/p3v.h: p3v_kv_fork_t), and "responses" has n entries; "best_of" generates that many
      and returns the n with the largest cumulative raw-logit log-probability, best first.  A sampled request's "seeds" has
@@ -251,22 +257,52 @@ def parse_penalties(request, n_prompts, vocab=None):
     return [d] * n_prompts
 
 
+def _response_format_schema(fmt):
+    """The OpenAI "response_format" field -> a JSON schema, or None for {"type": "text"}."""
+    if not isinstance(fmt, dict) or not isinstance(fmt.get("type"), str):
+        raise ValueError('response_format must be an object with a "type": "text" or "json_schema"')
+    kind = fmt["type"]
+    if kind == "text":
+        return None
+    if kind == "json_object":
+        raise ValueError('response_format {"type": "json_object"} is not supported: free-form JSON is not a regular language, and '
+                         'a guide is a finite automaton of at most 65536 table entries; send {"type": "json_schema", '
+                         '"json_schema": {"schema": {...}}} or "guided_json"')
+    if kind != "json_schema":
+        raise ValueError(f'response_format type {kind!r} is not supported: "text" or "json_schema"')
+    inner = fmt.get("json_schema")
+    if not isinstance(inner, dict) or not isinstance(inner.get("schema"), (dict, str)):
+        raise ValueError('response_format {"type": "json_schema"} needs "json_schema": {"schema": {...}}')
+    return inner["schema"]
+
+
 def parse_guide(request, n_prompts):
-    """The "guided_regex" (a string) and "guided_choice" (a non-empty list of strings) fields of a request body -> None (both
-    absent or null) or one {"regex": pattern} / {"choice": [...]} dict per prompt (the same for each).  ValueError (-> 400) with
-    the reason on a wrong type, both at once, an unsupported construct or more than 255 states: the guide is compiled here (the
-    compiled form is cached by pattern, so the backend's own compilation is a look-up)."""
+    """The "guided_regex" (a string), "guided_choice" (a non-empty list of strings) and "guided_json" (a JSON schema: an object
+    or its JSON text; also as the OpenAI "response_format" of type "json_schema") fields of a request body -> None (all absent or
+    null) or one {"regex": pattern} / {"choice": [...]} / {"schema": ...} dict per prompt (the same for each).  ValueError (->
+    400) with the reason on a wrong type, two at once, an unsupported construct or keyword, more than 255 states of a pattern or
+    more than 65,536 table entries of a schema: the guide is compiled here (the compiled form is cached, so the backend's own
+    compilation is a look-up)."""
     from . import guide as guide_mod
-    regex, choice = request.get("guided_regex"), request.get("guided_choice")
-    if regex is None and choice is None:
+    regex, choice, schema = request.get("guided_regex"), request.get("guided_choice"), request.get("guided_json")
+    if request.get("response_format") is not None:
+        fmt = _response_format_schema(request["response_format"])
+        if fmt is not None and schema is not None:
+            raise ValueError("guided_json and response_format exclude each other: send one")
+        schema = fmt if schema is None else schema
+    if regex is None and choice is None and schema is None:
         return None
     if regex is not None and choice is not None:
         raise ValueError("guided_regex and guided_choice exclude each other: send one")
+    if schema is not None and (regex is not None or choice is not None):
+        raise ValueError(f"{'guided_regex' if regex is not None else 'guided_choice'} and guided_json exclude each other: send one")
     if regex is not None and not isinstance(regex, str):
         raise ValueError(f"guided_regex must be a string, got {type(regex).__name__}")
     if choice is not None and (not isinstance(choice, list) or not choice or not all(isinstance(c, str) for c in choice)):
         raise ValueError("guided_choice must be a non-empty list of strings")
-    d = {"regex": regex} if regex is not None else {"choice": list(choice)}
+    if schema is not None and not isinstance(schema, (dict, str)):
+        raise ValueError(f"guided_json must be a JSON schema (an object or its JSON text), got {type(schema).__name__}")
+    d = {"regex": regex} if regex is not None else {"choice": list(choice)} if choice is not None else {"schema": schema}
     guide_mod.request_guide(d)
     return [d] * n_prompts
 
@@ -687,16 +723,16 @@ def generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculat
     not None: one prompt) takes scalars -- its sampling record's fields, the penalty fields it gave, its N, its adapter --, n and
     best_of.  A speculating request (one greedy prompt) takes `speculate` and its adapter.  Any other request takes one value per
     row (a single prompt: its adapter as a name), a row that asked for no penalty the defaults.  guide: the rows' {"regex"} /
-    {"choice"} dicts (None for a row without one) -> `guided_regex` / `guided_choice`, one value per row."""
+    {"choice"} / {"schema"} dicts (None for a row without one) -> `guided_regex` / `guided_choice` / `guided_json`, one value per row."""
     fam = n is not None
     if speculate and not fam:
         sampling = logprobs = penalties = guide = None
     kw = {}
     if guide is not None and any(d is not None for d in guide):
-        for f in ("regex", "choice"):
+        for f, name in (("regex", "guided_regex"), ("choice", "guided_choice"), ("schema", "guided_json")):
             vals = [None if d is None else d.get(f) for d in guide]
             if any(v is not None for v in vals):
-                kw["guided_" + f] = vals[0] if fam else vals
+                kw[name] = vals[0] if fam else vals
     if sampling is not None:
         kw.update({f: sampling[0][f] if fam else [r[f] for r in sampling] for f in SAMPLING_FIELDS})
     if penalties is not None and fam:
