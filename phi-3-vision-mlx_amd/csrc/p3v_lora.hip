@@ -98,13 +98,14 @@ extern "C" int p3v_lora_up(const uint16_t* y, const float* t, const float* lora_
 struct lora_entry_t { const float* a; const float* b; int32_t rank; float scale; };   // == p3v_lora_entry_t
 static_assert(sizeof(lora_entry_t) == 24, "p3v_lora_entry_t layout");
 
+// e keeps the entry's own rank -- the row stride of lora_a [K, rank] --, r is the number of columns in use, min(rank, r_max)
 __device__ __forceinline__ bool lora_row_entry(const lora_entry_t* __restrict__ table, const int32_t* __restrict__ row_adapter,
-                                               int m, int n_slots, int r_max, lora_entry_t& e) {
+                                               int m, int n_slots, int r_max, lora_entry_t& e, int& r) {
   const int slot = row_adapter[m];
   if (slot < 0 || slot >= n_slots) return false;
   e = table[slot];
-  e.rank = min(e.rank, r_max);
-  return e.rank > 0 && e.a && e.b;
+  r = min(e.rank, r_max);
+  return r > 0 && e.a && e.b;
 }
 
 template <bool NORM>
@@ -117,7 +118,8 @@ __global__ void __launch_bounds__(256) k_lora_down_rows(const bf16_t* __restrict
   const int m = blockIdx.x / slices, s = blockIdx.x - m * slices;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   lora_entry_t e;
-  if (!lora_row_entry(table, row_adapter, m, n_slots, r_max, e)) return;     // (uniform over the workgroup)
+  int r;
+  if (!lora_row_entry(table, row_adapter, m, n_slots, r_max, e, r)) return;  // (uniform over the workgroup)
   const bf16_t* xr = x + (size_t)m * K;
   const int k = s * P3V_LORA_SLICE_K + tid;
   float xv = k < K ? bf16_to_f32(xr[k]) : 0.f;
@@ -143,8 +145,8 @@ __global__ void __launch_bounds__(256) k_lora_down_rows(const bf16_t* __restrict
   }
   const float* ar = e.a + (size_t)(k < K ? k : 0) * e.rank;
   float* tr = t + ((size_t)m * slices + s) * r_max;
-  for (int rc = 0; rc < e.rank; rc += 8) {
-    const int nr = min(8, e.rank - rc);
+  for (int rc = 0; rc < r; rc += 8) {
+    const int nr = min(8, r - rc);
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = j < nr ? xv * ar[rc + j] : 0.f;
@@ -189,8 +191,9 @@ __global__ void __launch_bounds__(256) k_lora_up_rows(const bf16_t* __restrict__
   __shared__ float ts[64];
   const int m = blockIdx.x / nblk, n = (blockIdx.x - m * nblk) * 256 + threadIdx.x;
   lora_entry_t e;
-  const bool on = lora_row_entry(table, row_adapter, m, n_slots, r_max, e);
-  const int r = on ? e.rank : 0;
+  int rr = 0;
+  const bool on = lora_row_entry(table, row_adapter, m, n_slots, r_max, e, rr);
+  const int r = on ? rr : 0;
   if ((int)threadIdx.x < r) {                                   // the row's K slices, added in slice order
     const float* tr = t + (size_t)m * slices * r_max + threadIdx.x;
     float v = 0.f;

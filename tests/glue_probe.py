@@ -154,10 +154,10 @@ class RmsProbe:
     """Gaussian rows (std 3) and HOT-CHUNK rows: background std 0.05, one 8-wide chunk 8.0 (low half) / 16.0 (high half), so the
     chunk carries almost the whole sum of squares and a swapped pair shows.  Weights 1 + 0.1 N(0, 1), every 7th negated."""
 
-    def __init__(self, case):
+    def __init__(self, case, seed=0):
         self.case = case
         H, R = case.hidden, case.rows
-        gen = _gen("rms", H, R)
+        gen = _gen("rms", H, R) if seed == 0 else _gen("rms", H, R, seed)        # (seed > 0: other draws, for tests/quant_probe.py)
         hot = hot_positions(H // 8)
         hot = hot[:{1: 0, 6: 3, 33: 33}[R]]
         x = torch.randn((R, H), generator=gen) * 3.0

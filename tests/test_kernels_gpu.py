@@ -1015,8 +1015,9 @@ def _dequant(u8, sc, axis):
 def test_kv_quantize_and_q8_decode(ops, orc, past, L, n_split, fused):
     """int8 KV: (a) quantiser = round(x/s)+128 with s = amax/127 per token, (b) the q8 decode attention equals the
     bf16 oracle attention over the DEQUANTISED cache, (c) the appended rows are stored quantised.
-    n_split 3 -> multi-tile single-wave kernel, 4 (= tiles) -> single-tile 4-wave kernel, 2 (= one split per 128 keys) ->
-    k_attn_decode128_q8 (raw bytes by LDS-DMA, fp16 conversion at fragment read); (62, 5) / (126, 5) cross a tile boundary;
+    n_split 4 (= tiles) -> single-tile 4-wave kernel; 2 (= one split per 128 keys) and, at these 256 keys, 3 (3 x 128 >= 256 > 3 x 64, the
+    third split empty) -> k_attn_decode128_q8 (raw bytes by LDS-DMA, fp16 conversion at fragment read); the multi-tile single-wave
+    kernel's append is run by tests/test_quant_kernels_gpu.py; (62, 5) / (126, 5) cross a tile boundary;
     fused: the split partials are merged inside the attention launch (ready flags), twice in a row (the flags re-arm)."""
     from phi_3_vision_mlx_amd.config import make_config, rope_scaling_factor
     cfg = make_config()
