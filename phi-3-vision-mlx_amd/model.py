@@ -243,28 +243,25 @@ class Phi3VModel:
         # quantize_model=True (fp8): prompt-sized projections run W8A8 on the fp8 MFMA unless fp8_activations=False
         # (then: dequantise to a bf16 scratch + bf16 MFMA, weight-only accuracy at bf16 prefill speed)
         self.fp8_act = bool(getattr(cfg, "fp8_activations", True)) and os.environ.get("P3V_FP8_PREFILL", "mfma") != "dequant"
-        if getattr(cfg, "quantized_fp8", False):
-            self._quantize_decoder_fp8()
-        if getattr(cfg, "quantized_int4", False):
-            self._quantize_decoder_q4()
-        if self.w4 and not hasattr(self, "_deq"):
-            n_max = max(v[0].shape[0] * v[0].shape[1] * 8 for v in self.w4.values())
-            self._deq = torch.empty(n_max, dtype=BF16, device=self.device)  # one dequantised matrix (prefill GEMM scratch)
+        if getattr(cfg, "quantized_fp8", False):     # e4m3 bytes + per-row scale: 7.4 GB -> 3.7 GB streamed per token
+            self._quantize_decoder(self.w8, ops.quantize_fp8_rows)
+        if getattr(cfg, "quantized_int4", False):    # 4-bit group-64 (the reference's nn.quantize(model, 64, 4)) by the MLX algorithm, on the device: -> 2.1 GB
+            self._quantize_decoder(self.w4, lambda v: tuple(t.to(self.device) for t in q4_repack(*mlx_quantize(v))))
+        if self.w8 or self.w4:                       # one dequantised matrix (prefill GEMM scratch): the largest there is
+            n_max = max(math.prod(ops.weight_shape(v)) for v in (*self.w8.values(), *self.w4.values()))
+            self._deq = torch.empty(n_max, dtype=BF16, device=self.device)
         self.w13 = {}                                # weight key -> ops.PackedB13: what the one-row decode projections stream
         if os.environ.get("P3V_PACK13", "1") != "0":
             self._pack_decoder_b13()
         if self.vision:
             self._prep_vision()
 
-    # ------------------------------------------------------------------ fp8 weights (quantize_model=True)
-    def _quantize_decoder_fp8(self):
-        """Decoder projections + lm_head -> e4m3 bytes + per-row scale (7.4 GB -> 3.7 GB streamed per token).
-        Embedding, norms, the ViT and the projector stay bf16 (prefill-only / tiny)."""
-        names = [k for k in self.w if k == "lm_head.weight" or (k.startswith("model.layers.") and k.endswith("_proj.weight"))]
-        for k in names:
-            self.w8[k] = ops.quantize_fp8_rows(self.w.pop(k))
-        n_max = max(v[0].shape[0] * v[0].shape[1] for v in self.w8.values())
-        self._deq = torch.empty(n_max, dtype=BF16, device=self.device)      # one dequantised matrix (prefill GEMM scratch)
+    # ------------------------------------------------------------------ fp8 / 4-bit weights (quantize_model=True, quantized_int4)
+    def _quantize_decoder(self, dst, quantise):
+        """Decoder projections + lm_head leave `w` for `dst` (w8 or w4) as `quantise` makes them; the rest stays bf16 (prefill-only / tiny).
+        A key lives in exactly ONE of w, w8 and w4: `_handle` and the fused o_proj's format rule (`_fused_oproj_kw`) rely on it."""
+        for k in [k for k in self.w if k == "lm_head.weight" or (k.startswith("model.layers.") and k.endswith("_proj.weight"))]:
+            dst[k] = quantise(self.w.pop(k))
 
     # ------------------------------------------------------------------ 13-bit packed bf16 weights (B = 1 decode)
     @_on_device
@@ -316,7 +313,7 @@ class Phi3VModel:
     @_on_device
     def _set_adapters(self, adapters):
         for k, (a, b, _) in adapters.items():
-            shape = self._weight_shape(k)
+            shape = ops.weight_shape(self._weight(k))
             if tuple(a.shape[:1]) != (shape[1],) or tuple(b.shape[1:]) != (shape[0],):
                 raise ValueError(f"LoRA shapes {tuple(a.shape)} x {tuple(b.shape)} do not fit {k} {tuple(shape)}")
         self.adapters = {k: (a.to(self.device, F32).contiguous(), b.to(self.device, F32).contiguous(), float(s))
@@ -327,13 +324,36 @@ class Phi3VModel:
         self._lora_tmp, self._lora_flat = {}, None
         self._prefill_graphs.clear()
 
-    def _weight_shape(self, k):
-        """(out, in) of a projection in whichever format the model holds it."""
-        if k in self.w:
-            return tuple(self.w[k].shape)
-        if k in self.w8:
-            return tuple(self.w8[k][0].shape)
-        return (self.w4[k][0].shape[0], self.w4[k][0].shape[1] * 8)
+    def _handle(self, key, rows=0):
+        """(weight handle, its format as ops.py names it) a launch of `rows` rows streams for `key`, or (None, None): for one row the packed
+        copy while `_packed` still returns it, else the entry of `w`, `w8` or `w4` (the dict names the format).  Every eager projection pays for this call."""
+        if rows == 1 and (pk := self.w13.get(key)) is not None and (pk.current(self.w.get(key)) or self._packed(key)):
+            return pk, "b13"                         # (a stale copy: `_packed` drops it, bumps `epoch` and answers None)
+        if self.w8 and (w := self.w8.get(key)) is not None:      # (a quantised model holds every decoder matrix in w8 or w4,
+            return w, "fp8"                                       #  a bf16 model leaves both empty: one lookup either way)
+        if self.w4 and (w := self.w4.get(key)) is not None:
+            return w, "q4"
+        return (w, "bf16") if (w := self.w.get(key)) is not None else (None, None)
+
+    def _weight(self, key, rows=0):
+        return self._handle(key, rows)[0]            # the handle alone
+
+    def _fold_weight(self, key, B):
+        """The handle a decode step of B rows streams where `key`'s projection carries the step's head or tail (ops.gemv_step_begin /
+        gemv_step_end), or None where it runs through `_proj`: an adapter or the bank on it, or P3V_STEP_FOLD=0.  (The bank never holds
+        lm_head -- set_adapter_bank refuses it -- so one test serves both ends; `_proj_frozen` then drops a stale packed copy, same step.)"""
+        if key in self.adapters or key in self._bank or os.environ.get("P3V_STEP_FOLD", "1") == "0":
+            return None
+        return self._weight(key, B)
+
+    def _fused_oproj_kw(self, o_key, x, rearm):
+        """The o_proj keywords of a fused attention + o_proj launch.  The weight format names the launch: bf16 and 4-bit weights go
+        with the bf16 cache (ops.attention_decode), e4m3 weights with the int8 cache (ops.attention_decode_q8; `_plan_fused_oproj`)."""
+        w, fmt = self._handle(o_key)
+        kw = dict(o_proj_x=x, o_rearm=rearm)
+        if fmt == "fp8":
+            return dict(kw, o_proj_w8=w[0], o_proj_scale=w[1])
+        return dict(kw, o_proj_w=w[0], o_proj_sb=w[1]) if fmt == "q4" else dict(kw, o_proj_w=w)
 
     # ------------------------------------------------------------------ adapter bank: N resident adapters, one per row
     def set_adapter_bank(self, bank):
@@ -353,9 +373,9 @@ class Phi3VModel:
             if not isinstance(name, str) or not name:
                 raise ValueError(f"adapter names are non-empty strings, got {name!r}")
             for k, (a, b, _) in ad.items():
-                if not (k.startswith("model.layers.") and k.endswith("_proj.weight")) or not (k in self.w or k in self.w8 or k in self.w4):
+                if not (k.startswith("model.layers.") and k.endswith("_proj.weight")) or self._weight(k) is None:
                     raise ValueError(f"adapter {name!r}: {k} is not a decoder projection of this model")
-                shape = self._weight_shape(k)
+                shape = ops.weight_shape(self._weight(k))
                 if a.dim() != 2 or b.dim() != 2 or a.shape[0] != shape[1] or b.shape[1] != shape[0] or a.shape[1] != b.shape[0]:
                     raise ValueError(f"adapter {name!r}: LoRA shapes {tuple(a.shape)} x {tuple(b.shape)} do not fit {k} {tuple(shape)}")
                 if not 1 <= a.shape[1] <= ops.L.LORA_MAX_RANK:
@@ -430,7 +450,7 @@ class Phi3VModel:
 
     def _proj_bank(self, x, key, table, r_max, epilogue, resid, norm_w, out, h):
         M, K = x.shape
-        N, S = self._weight_shape(key)[0], ops.lora_slices(K)
+        N, S = ops.weight_shape(self._weight(key))[0], ops.lora_slices(K)
         y, t = self._lora_scratch(M, [("y", (M, N), BF16), ("t", (M, S, r_max), F32)])
         rows = self._rows_cur
         if rows is None or rows.numel() != M:
@@ -439,13 +459,6 @@ class Phi3VModel:
         self._proj_frozen(x, key, EPI_NONE, None, norm_w, y, h)
         ops.lora_down_rows(x, table, rows, r_max, norm_w=norm_w, norm_eps=self.cfg.rms_norm_eps, out=t)
         return ops.lora_up_rows(y, t, table, rows, K, r_max, epilogue, resid=resid, out=out)
-
-    def _quantize_decoder_q4(self):
-        """Decoder projections + lm_head -> 4-bit group-64 (the reference's nn.quantize(model, 64, 4)): 7.4 GB -> 2.1 GB
-        streamed per token.  Quantised on the device with the MLX algorithm (weights.mlx_quantize)."""
-        names = [k for k in self.w if k == "lm_head.weight" or (k.startswith("model.layers.") and k.endswith("_proj.weight"))]
-        for k in names:
-            self.w4[k] = tuple(t.to(self.device) for t in q4_repack(*mlx_quantize(self.w.pop(k))))
 
     def _proj(self, x, key, epilogue=EPI_NONE, resid=None, norm_w=None, out=None, h=None):
         """One projection of the decoder (+ its LoRA adapter, if one is attached)."""
@@ -468,36 +481,35 @@ class Phi3VModel:
         """Weight-streaming kernel for skinny x, MFMA GEMM otherwise; bf16 or fp8 weights."""
         eps = self.cfg.rms_norm_eps
         M, K = x.shape
-        q, q4 = self.w8.get(key), self.w4.get(key)
-        pk = self._packed(key) if M == 1 else None
-        if pk is not None and pk.silu_pairs == (epilogue == EPI_SILU_MUL):      # (an adapted gate_up runs with a plain epilogue: bf16)
-            return ops.gemv_b13(x, pk, epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
+        w, fmt = self._handle(key, M)
+        if fmt == "b13":
+            if w.silu_pairs == (epilogue == EPI_SILU_MUL):
+                return ops.gemv_b13(x, w, epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
+            w, fmt = self.w[key], "bf16"                          # (an adapted gate_up runs with a plain epilogue: bf16)
         skinny = M <= 8 or (M <= ops.GEMV_MAX_M and K % 512 == 0)
-        if skinny and M > 8 and q is None and q4 is None and K % 64 == 0 and self.w[key].shape[0] % 64 == 0:
+        if fmt == "q4":
+            if M == 1 and K in (3072, 8192):
+                return ops.gemv_q4(x, w[0], w[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
+            if (2 <= M <= 16 and K in (3072, 8192) and os.environ.get("P3V_Q4_ROWS", "1") != "0"
+                    and (w[0].shape[0] // (2 if epilogue == EPI_SILU_MUL else 1)) % 16 == 0):
+                # 2 .. 16 rows straight on the 4-bit weights (round 6: k_gemv8_q4 / k_gemm_rows_q4; the reference runs QuantizedLinear at
+                # every batch size, phi_3_vision_mlx.py:296) instead of dequantising the whole matrix into the bf16 scratch per call
+                if norm_w is not None and (M > 8 or os.environ.get("P3V_Q4_ROWS8_NORM", "1") == "0"):
+                    x, norm_w = ops.rmsnorm(x, norm_w, eps, out=h), None       # 9 .. 16 rows: one p3v_rmsnorm launch in front
+                return ops.gemv_q4(x, w[0], w[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
+            w = ops.dequant_q4(w[0], w[1], out=self._deq[:w[0].numel() * 8].view(w[0].shape[0], w[0].shape[1] * 8))
+        elif fmt == "fp8":
+            if skinny and K in (3072, 8192):
+                return ops.gemv_fp8(x, w[0], w[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
+            if not skinny and self.fp8_act and ops.gemm_fp8_ok(M, w[0].shape[0], K, epilogue):
+                # prompt-sized input: W8A8 on the fp8 matrix cores, activations quantised per token row (fused with the norm)
+                a8, sa = ops.quant_fp8_rows(x, norm_w, eps)
+                return ops.gemm_fp8(a8, sa, w[0], w[1], epilogue, resid=resid, out=out)
+            w = ops.dequant_fp8(w[0], w[1], out=self._deq[:w[0].numel()].view(w[0].shape))
+        elif skinny and M > 8 and K % 64 == 0 and w.shape[0] % 64 == 0:
             # 9 .. 16 rows on bf16 weights: the 64-row tiles of the weight-streaming GEMM (p3v_gemm_skinny.hip) beat the 16-row MFMA
             # GEMV by a quarter of the step (B = 16 at 512 keys: 3.9 -> 3.1 ms); up to 8 rows k_gemv_mfma8 stays ahead
             skinny = False
-        if q4 is not None and M == 1 and K in (3072, 8192):
-            return ops.gemv_q4(x, q4[0], q4[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
-        if (q4 is not None and 2 <= M <= 16 and K in (3072, 8192) and os.environ.get("P3V_Q4_ROWS", "1") != "0"
-                and (q4[0].shape[0] // (2 if epilogue == EPI_SILU_MUL else 1)) % 16 == 0):
-            # 2 .. 16 rows straight on the 4-bit weights (round 6: k_gemv8_q4 / k_gemm_rows_q4; the reference runs QuantizedLinear at
-            # every batch size, phi_3_vision_mlx.py:296) instead of dequantising the whole matrix into the bf16 scratch per call
-            if norm_w is not None and (M > 8 or os.environ.get("P3V_Q4_ROWS8_NORM", "1") == "0"):
-                x, norm_w = ops.rmsnorm(x, norm_w, eps, out=h), None       # 9 .. 16 rows: one p3v_rmsnorm launch in front
-            return ops.gemv_q4(x, q4[0], q4[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
-        if q is not None and skinny and K in (3072, 8192):
-            return ops.gemv_fp8(x, q[0], q[1], epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
-        if q is not None and not skinny and self.fp8_act and ops.gemm_fp8_ok(M, q[0].shape[0], K, epilogue):
-            # prompt-sized input: W8A8 on the fp8 matrix cores, activations quantised per token row (fused with the norm)
-            a8, sa = ops.quant_fp8_rows(x, norm_w, eps)
-            return ops.gemm_fp8(a8, sa, q[0], q[1], epilogue, resid=resid, out=out)
-        if q4 is not None:
-            w = ops.dequant_q4(q4[0], q4[1], out=self._deq[:q4[0].numel() * 8].view(q4[0].shape[0], q4[0].shape[1] * 8))
-        elif q is not None:
-            w = ops.dequant_fp8(q[0], q[1], out=self._deq[:q[0].numel()].view(q[0].shape))
-        else:
-            w = self.w[key]
         if skinny:
             return ops.gemv(x, w, epilogue, resid=resid, norm_w=norm_w, norm_eps=eps, out=out)
         if norm_w is not None:
@@ -1023,7 +1035,7 @@ class Phi3VModel:
         ok = (os.environ.get("P3V_ATTN_FUSE_OPROJ", "1") != "0" and os.environ.get("P3V_PROFILING") != "1"
               and B == 1 and L == 1
               and cfg.num_hidden_layers % 2 == 0 and not self.serving
-              and not self.adapters and not self._bank_has("self_attn.o_proj.weight") and (o_key in self.w8) == bool(quantized) and not (quantized and o_key in self.w4)
+              and not self.adapters and not self._bank_has("self_attn.o_proj.weight") and (self._handle(o_key)[1] == "fp8") == bool(quantized)
               # (without the in-launch merge -- long contexts: the MERGE launch carries the o_proj, k_attn_combine_o, round 6)
               and can(B, L, cfg.num_attention_heads, self.hd, bufs["n_split"], T, cfg.hidden_size, bool(bufs.get("attn_merge", False))))
         if not ok and bufs.get("attn_merge", False) and B == 1 and L == 1 and not quantized:
@@ -1148,12 +1160,9 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                                              q_scale=scale * ops.Q_PRESCALE)
             if i == 0 and step_begin is not None:               # replayed greedy step: the embedding gather + rotation-row staging
                 sb = step_begin                                 # ride in this projection's prologue when the library takes the shape
-                w_fold = w.get(k_w) if k_w in w else (self.w8.get(k_w) or self.w4.get(k_w))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
-                if B == 1 and self._packed(k_w) is not None:
-                    w_fold = self.w13[k_w]                      # one row: the 13-bit packed copy of the bf16 matrix
-                if not (w_fold is not None and k_w not in self.adapters and k_w not in self._bank and os.environ.get("P3V_STEP_FOLD", "1") != "0"
-                        and ops.gemv_step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"], sb["sin_o"],
-                                                w_fold, w[p + "input_layernorm.weight"], eps, qkv)):
+                w_fold = self._fold_weight(k_w, B)
+                if not (w_fold is not None and ops.gemv_step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"],
+                                                                   sb["sin_o"], w_fold, w[p + "input_layernorm.weight"], eps, qkv)):
                     ops.step_begin(sb["tok"], sb["table"], x, st.cos, st.sin, d_past, sb["cos_o"], sb["sin_o"])
                     self._proj(x, k_w, norm_w=w[p + "input_layernorm.weight"], out=qkv, h=h)
             elif not fused_qkv:
@@ -1161,15 +1170,12 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                     self._proj(h, p + "self_attn.qkv_proj.weight", out=qkv)
                 else:
                     self._proj(x, p + "self_attn.qkv_proj.weight", norm_w=w[p + "input_layernorm.weight"], out=qkv, h=h)
-            o_i = o
+            o_i, kw_o = o, {}
             if fuse_o:                                          # (B = L = 1 plans only) + o_proj + residual in the attention's launch,
                 o_i, o_other = (bufs["o_f"], bufs["o_f2"]) if i % 2 == 0 else (bufs["o_f2"], bufs["o_f"])   # x += bf16(W_o . o)
+                kw_o = self._fused_oproj_kw(p + "self_attn.o_proj.weight", x, o_other)
             if st.quantized:
                 if decode:
-                    kw_o = {}
-                    if fuse_o:                                  # (o_proj on e4m3 weights)
-                        w8o = self.w8[p + "self_attn.o_proj.weight"]
-                        kw_o = dict(o_proj_w8=w8o[0], o_proj_scale=w8o[1], o_proj_x=x, o_rearm=o_other)
                     ops.attention_decode_q8(qkv, rc, rs, rb, st.k8[i], st.v8[i], st.ks[i], st.vs[i], o_i, B, L, nh, nkv,
                                             hd, scale, past, st.Tp, ws, n_split, pad_len=st.pad_len, d_past=d_past,
                                             merge_in_launch=attn_merge, **kw_o)
@@ -1192,11 +1198,6 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                                             past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split, st.family,
                                             family_host=st.family_host, pad_len=st.pad_len, d_past=d_past)
             elif decode:
-                kw_o = {}
-                if fuse_o:                                      # (o_proj on bf16 or 4-bit weights)
-                    q4o = self.w4.get(p + "self_attn.o_proj.weight")
-                    kw_o = dict(o_proj_w=q4o[0], o_proj_sb=q4o[1]) if q4o is not None else dict(o_proj_w=w[p + "self_attn.o_proj.weight"])
-                    kw_o.update(o_proj_x=x, o_rearm=o_other)
                 # (captured step: `past` is read from d_past; the host value passed along is a LOWER BOUND of it -- the kernel fetches
                 #  tiles below it at once and lets the others wait for the length, so tiles beyond the live keys cost nothing)
                 ops.attention_decode(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, L, nh, nkv, hd, scale,
@@ -1293,11 +1294,8 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                      step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
         end = (g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
         if not kind.sampled:
-            w_fold = w.get(head) if head in w else (self.w8.get(head) or self.w4.get(head))   # bf16, (e4m3, row scales) or (4-bit, scale | bias)
-            if st.B == 1 and self._packed(head) is not None:
-                w_fold = self.w13[head]                         # one row: the 13-bit packed copy of the bf16 matrix
-            if (w_fold is not None and head not in self.adapters and os.environ.get("P3V_STEP_FOLD", "1") != "0"
-                    and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"])):
+            w_fold = self._fold_weight(head, st.B)
+            if w_fold is not None and ops.gemv_step_end(g["x"], w_fold, w["model.norm.weight"], cfg.rms_norm_eps, g["logits"], *end, g["amax_ws"]):
                 return self._logprobs_tail(st, g) if kind.logprobs else None
         self._proj(g["x"], head, norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])   # (h: the norm's output)
         if kind.penalized:
@@ -1817,7 +1815,8 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         # tensors on a live model; in-place weight updates are seen by the graph as they are by every launch)
         nl = cfg.num_hidden_layers - 1
         def wptr(k):
-            return self.w[k].data_ptr() if k in self.w else self.w4[k][0].data_ptr()
+            w, fmt = self._handle(k)
+            return (w if fmt == "bf16" else w[0]).data_ptr()
         key = (S, max_tokens, rope_scaling_factor(cfg), float(cfg.rope_theta), cfg.original_max_position_embeddings,
                self.w["model.embed_tokens.weight"].data_ptr(), wptr("lm_head.weight"),
                wptr("model.layers.0.self_attn.qkv_proj.weight"), wptr(f"model.layers.{nl}.mlp.down_proj.weight"))

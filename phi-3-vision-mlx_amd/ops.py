@@ -4,6 +4,7 @@ torch is used for device memory and the current stream only; every function
 here launches a hand-written gfx950 kernel from ``csrc/`` and nothing else.
 Each op names the MLX call site of the reference it replaces.
 """
+import collections
 import contextlib
 import ctypes as C
 import weakref
@@ -160,15 +161,79 @@ def gemm_resid_norm(a, w, resid, norm_w, eps, normed, out=None):
 GEMV_MAX_M = 16
 
 
+class PackedB13:
+    """A bf16 matrix [rows, K] as exact 13-bit codes (include/p3v.h: p3v_pack_b13): `data` u8 [rows, K * 13 / 8] in the container layout
+    of the streaming GEMV, `base` the matrix's exponent base, `silu_pairs` the row pairing it was packed for (gate / up rows of
+    EPI_SILU_MUL, or neighbouring rows for every other epilogue); `src` / `version` a weak reference to the tensor it was made from and
+    that tensor's in-place modification count then (`current` says whether the copy still stands for a given tensor)."""
+    __slots__ = ("data", "base", "rows", "K", "silu_pairs", "src", "version")
+
+    def __init__(self, data, base, rows, K, silu_pairs, src=None):
+        self.data, self.base, self.rows, self.K, self.silu_pairs = data, int(base), int(rows), int(K), bool(silu_pairs)
+        self.src, self.version = (weakref.ref(src) if src is not None else None), (src._version if src is not None else 0)
+
+    def current(self, w):
+        return w is not None and self.src is not None and w is self.src() and w._version == self.version
+
+
+# One record per weight format, for the GEMV wrappers: `shape` handle -> (rows, K); `tensors` handle -> what the struct points at, in
+# field order; `checks` (index into tensors, _chk name, dtype) for a handle nobody has looked at yet; `struct` the argument struct;
+# `entry` the plain symbol (entry + "_step" carries a decode step's head or tail); `tail` handle -> the fields behind `epilogue`.
+_WeightFormat = collections.namedtuple("_WeightFormat", "name shape tensors checks struct entry tail", defaults=(lambda w: (),))
+_BF16 = _WeightFormat("bf16", lambda w: tuple(w.shape), lambda w: (w,), ((0, "w", BF16),), L.GemvArgs, "p3v_gemv")
+_FP8 = _WeightFormat("fp8", lambda w: tuple(w[0].shape), lambda w: w, ((0, "w8", torch.uint8), (1, "w_scale", F32)), L.GemvF8Args, "p3v_gemv_fp8")
+# (a pair is 4-bit BECAUSE its first tensor is int32: `_weight_format` has read that dtype, gemv_q4 checks it under its own name)
+_Q4 = _WeightFormat("q4", lambda w: (w[0].shape[0], w[0].shape[1] * 8), lambda w: w, ((1, "sb", I32),), L.GemvQ4Args, "p3v_gemv_q4")
+_B13 = _WeightFormat("b13", lambda w: (w.rows, w.K), lambda w: (w.data,), (), L.GemvB13Args, "p3v_gemv_b13",
+                     lambda w: (w.base, int(w.silu_pairs)))
+
+
+def _weight_format(w):
+    """The format of a weight HANDLE: the one value that stands for a decoder matrix wherever one is streamed -- what
+    `gemv_step_begin` / `gemv_step_end` take as `w`, what Phi3VModel's `w` / `w8` / `w4` / `w13` dicts hold and its `_weight` returns:
+        bf16 tensor [N, K]                                          "bf16"   gemv      p3v_gemv[_step]
+        (u8 e4m3 [N, K], f32 row scales [N])                        "fp8"    gemv_fp8  p3v_gemv_fp8[_step]
+        (i32 nibbles [N, K / 8], i32 scale | bias words [N, K / 64])  "q4"     gemv_q4   p3v_gemv_q4[_step]
+        PackedB13 (exact 13-bit codes of a bf16 matrix)             "b13"    gemv_b13  p3v_gemv_b13[_step]
+    This is the only place that tells the formats apart by what a value looks like: `weight_shape` and `_gemv_launch` work
+    from its record (Phi3VModel knows the name from the dict it keeps the handle in: `_handle`)."""
+    t = type(w)
+    if t is tuple:
+        return _Q4 if w[0].dtype is I32 else _FP8
+    return _B13 if t is PackedB13 else _BF16
+
+
+def weight_shape(w):
+    """(rows, K) of a weight handle (`_weight_format`): the matrix it stands for, whatever its storage (4-bit: K = 8 x columns)."""
+    return _weight_format(w).shape(w)
+
+
+def _gemv_launch(what, f, w, x, M, epilogue, resid, norm_w, norm_eps, out, step=None):
+    """The one GEMV launch: handle `w` of format `f`, `x` [M, K] (None: the step's prologue gathers it), optional fused RMSNorm /
+    epilogue, and with `step` (a GemvStep) the entry that carries the decode step's head or tail.  Allocates `out` for a plain
+    call that gave none.  Returns (the library's code, out)."""
+    rows, K = f.shape(w)
+    tensors = f.tensors(w)
+    for i, name, dtype in f.checks:
+        _chk(tensors[i], dtype, name)
+    if x is not None:
+        if f is _B13 and x.shape[1] != K:
+            raise ValueError(f"{what}: x has {x.shape[1]} columns, the packed matrix {K}")
+        K = x.shape[1]
+    N = rows // 2 if epilogue == EPI_SILU_MUL else rows
+    if out is None and step is None:
+        out = torch.empty((M, N), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
+    args = f.struct(_p(x), *map(_p, tensors), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, K, epilogue, *f.tail(w))
+    if step is None:
+        return getattr(L.lib(), f.entry)(C.byref(args), _stream()), out
+    return getattr(L.lib(), f.entry + "_step")(C.byref(args), C.byref(step), _stream()), out
+
+
 def gemv(x, w, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, out=None):
     """Skinny nn.Linear for decode (M<=16) with optional fused RMSNorm / epilogue."""
-    _chk(x, BF16, "x"), _chk(w, BF16, "w")
-    M, K = x.shape
-    N = w.shape[0] // 2 if epilogue == EPI_SILU_MUL else w.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
-    args = L.GemvArgs(_p(x), _p(w), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, K, epilogue)
-    L.check(L.lib().p3v_gemv(C.byref(args), _stream()), "gemv")
+    _chk(x, BF16, "x")
+    rc, out = _gemv_launch("gemv", _BF16, w, x, x.shape[0], epilogue, resid, norm_w, norm_eps, out)
+    L.check(rc, "gemv")
     return out
 
 
@@ -282,13 +347,9 @@ def gemv_q4(x, w4, sb, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0,
     """`gemv` on 4-bit group-64 weights (device layout of weights.q4_repack): x [M,K] bf16, w4 [N,K/8] i32, sb [N,K/64] i32.
     M = 1: the streaming GEMV (fused RMSNorm allowed); 2 <= M <= 8: k_gemv8_q4 (fused RMSNorm allowed); 9 <= M <= 16: k_gemm_rows_q4
     (no fused norm)."""
-    _chk(x, BF16, "x"), _chk(w4, I32, "w4"), _chk(sb, I32, "sb")
-    M, K = x.shape
-    N = w4.shape[0] // 2 if epilogue == EPI_SILU_MUL else w4.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
-    args = L.GemvQ4Args(_p(x), _p(w4), _p(sb), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, K, epilogue)
-    L.check(L.lib().p3v_gemv_q4(C.byref(args), _stream()), "gemv_q4")
+    _chk(x, BF16, "x"), _chk(w4, I32, "w4")
+    rc, out = _gemv_launch("gemv_q4", _Q4, (w4, sb), x, x.shape[0], epilogue, resid, norm_w, norm_eps, out)
+    L.check(rc, "gemv_q4")
     return out
 
 
@@ -312,29 +373,10 @@ def quantize_fp8_rows(w):
 
 def gemv_fp8(x, w8, w_scale, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, out=None):
     """`gemv` on fp8 weights (half the streamed bytes)."""
-    _chk(x, BF16, "x"), _chk(w8, torch.uint8, "w8"), _chk(w_scale, F32, "w_scale")
-    M, K = x.shape
-    N = w8.shape[0] // 2 if epilogue == EPI_SILU_MUL else w8.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
-    args = L.GemvF8Args(_p(x), _p(w8), _p(w_scale), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, K, epilogue)
-    L.check(L.lib().p3v_gemv_fp8(C.byref(args), _stream()), "gemv_fp8")
+    _chk(x, BF16, "x")
+    rc, out = _gemv_launch("gemv_fp8", _FP8, (w8, w_scale), x, x.shape[0], epilogue, resid, norm_w, norm_eps, out)
+    L.check(rc, "gemv_fp8")
     return out
-
-
-class PackedB13:
-    """A bf16 matrix [rows, K] as exact 13-bit codes (include/p3v.h: p3v_pack_b13): `data` u8 [rows, K * 13 / 8] in the container layout
-    of the streaming GEMV, `base` the matrix's exponent base, `silu_pairs` the row pairing it was packed for (gate / up rows of
-    EPI_SILU_MUL, or neighbouring rows for every other epilogue); `src` / `version` a weak reference to the tensor it was made from and
-    that tensor's in-place modification count then (`current` says whether the copy still stands for a given tensor)."""
-    __slots__ = ("data", "base", "rows", "K", "silu_pairs", "src", "version")
-
-    def __init__(self, data, base, rows, K, silu_pairs, src=None):
-        self.data, self.base, self.rows, self.K, self.silu_pairs = data, int(base), int(rows), int(K), bool(silu_pairs)
-        self.src, self.version = (weakref.ref(src) if src is not None else None), (src._version if src is not None else 0)
-
-    def current(self, w):
-        return w is not None and self.src is not None and w is self.src() and w._version == self.version
 
 
 def pack_b13(w, silu_pairs=False):
@@ -358,21 +400,11 @@ def unpack_b13(pk, out=None):
     return out
 
 
-def _b13_args(x, pk, out, resid, norm_w, norm_eps, M, epilogue):
-    N = pk.rows // 2 if epilogue == EPI_SILU_MUL else pk.rows
-    return L.GemvB13Args(_p(x), _p(pk.data), _p(out), _p(resid), _p(norm_w), float(norm_eps), M, N, pk.K, epilogue, pk.base, int(pk.silu_pairs))
-
-
 def gemv_b13(x, pk, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, out=None):
     """`gemv` on 13-bit packed bf16 weights: one row of x, 13/16 of the streamed bytes, the same bits out."""
     _chk(x, BF16, "x")
-    M, K = x.shape
-    if K != pk.K:
-        raise ValueError(f"gemv_b13: x has {K} columns, the packed matrix {pk.K}")
-    if out is None:
-        out = torch.empty((M, pk.rows // 2 if epilogue == EPI_SILU_MUL else pk.rows), dtype=F32 if epilogue == EPI_F32 else BF16, device=x.device)
-    args = _b13_args(x, pk, out, resid, norm_w, norm_eps, M, epilogue)
-    L.check(L.lib().p3v_gemv_b13(C.byref(args), _stream()), "gemv_b13")
+    rc, out = _gemv_launch("gemv_b13", _B13, pk, x, x.shape[0], epilogue, resid, norm_w, norm_eps, out)
+    L.check(rc, "gemv_b13")
     return out
 
 
@@ -758,25 +790,10 @@ def gemv_step_begin(tok, table, x_out, cos_t, sin_t, d_past, cos_out, sin_out, w
     B, tab_t, half = tok.numel(), cos_t.shape[-2], cos_t.shape[-1]
     st = L.GemvStep(_p(tok), _p(table), table.shape[0], _p(x_out), _p(cos_t), _p(sin_t), _p(cos_out), _p(sin_out), tab_t, half,
                     None, None, None, None, None, None, 0, _p(d_past))
-    if isinstance(w, PackedB13):                                # 13-bit packed bf16 weights: p3v_gemv_b13_step
-        if table.shape[1] != w.K or x_out.shape[-1] != w.K:
-            raise ValueError(f"gemv_step_begin: table / x_out rows of {table.shape[1]} / {x_out.shape[-1]} columns, the packed matrix {w.K}")
-        args = _b13_args(None, w, out, None, norm_w, norm_eps, B, EPI_NONE)
-        rc = L.lib().p3v_gemv_b13_step(C.byref(args), C.byref(st), _stream())
-    elif isinstance(w, tuple) and w[0].dtype == I32:            # (4-bit weights, scale | bias words): p3v_gemv_q4_step
-        w4, sb = w
-        _chk(sb, I32, "sb")
-        args = L.GemvQ4Args(None, _p(w4), _p(sb), _p(out), None, _p(norm_w), float(norm_eps), B, w4.shape[0], w4.shape[1] * 8, EPI_NONE)
-        rc = L.lib().p3v_gemv_q4_step(C.byref(args), C.byref(st), _stream())
-    elif isinstance(w, tuple):                                  # (e4m3 weights, fp32 row scales): p3v_gemv_fp8_step
-        w8, ws = w
-        _chk(w8, torch.uint8, "w8"), _chk(ws, F32, "w_scale")
-        args = L.GemvF8Args(None, _p(w8), _p(ws), _p(out), None, _p(norm_w), float(norm_eps), B, w8.shape[0], w8.shape[1], EPI_NONE)
-        rc = L.lib().p3v_gemv_fp8_step(C.byref(args), C.byref(st), _stream())
-    else:
-        _chk(w, BF16, "w")
-        args = L.GemvArgs(None, _p(w), _p(out), None, _p(norm_w), float(norm_eps), B, w.shape[0], w.shape[1], EPI_NONE)
-        rc = L.lib().p3v_gemv_step(C.byref(args), C.byref(st), _stream())
+    f = _weight_format(w)
+    if f is _B13 and (table.shape[1] != w.K or x_out.shape[-1] != w.K):
+        raise ValueError(f"gemv_step_begin: table / x_out rows of {table.shape[1]} / {x_out.shape[-1]} columns, the packed matrix {w.K}")
+    rc, _ = _gemv_launch("gemv_step_begin", f, w, None, B, EPI_NONE, None, norm_w, norm_eps, out, step=st)
     if rc == L.ERR_UNSUPPORTED:
         return False
     L.check(rc, "gemv_step(begin)")
@@ -789,28 +806,9 @@ def gemv_step_end(x, w, norm_w, norm_eps, out, next_tok, tok, history, d_step, d
     _chk(x, BF16, "x"), _chk(out, BF16, "out")
     if amax_ws.numel() * amax_ws.element_size() < L.GEMV_STEP_WS_BYTES:
         raise ValueError("gemv_step_end: amax_ws smaller than P3V_GEMV_STEP_WS_BYTES")
-    M, K = x.shape
     st = L.GemvStep(None, None, 0, None, None, None, None, None, 0, 0,
                     _p(next_tok), _p(tok), _p(history), _p(d_step), _p(ticket), _p(amax_ws), history.shape[1], _p(d_past))
-    if isinstance(w, PackedB13):                                # 13-bit packed bf16 weights
-        if K != w.K:
-            raise ValueError(f"gemv_step_end: x has {K} columns, the packed matrix {w.K}")
-        args = _b13_args(x, w, out, None, norm_w, norm_eps, M, EPI_NONE)
-        rc = L.lib().p3v_gemv_b13_step(C.byref(args), C.byref(st), _stream())
-    elif isinstance(w, tuple) and w[0].dtype == I32:            # (4-bit weights, scale | bias words)
-        w4, sb = w
-        _chk(sb, I32, "sb")
-        args = L.GemvQ4Args(_p(x), _p(w4), _p(sb), _p(out), None, _p(norm_w), float(norm_eps), M, w4.shape[0], K, EPI_NONE)
-        rc = L.lib().p3v_gemv_q4_step(C.byref(args), C.byref(st), _stream())
-    elif isinstance(w, tuple):                                  # (e4m3 weights, fp32 row scales)
-        w8, ws = w
-        _chk(w8, torch.uint8, "w8"), _chk(ws, F32, "w_scale")
-        args = L.GemvF8Args(_p(x), _p(w8), _p(ws), _p(out), None, _p(norm_w), float(norm_eps), M, w8.shape[0], K, EPI_NONE)
-        rc = L.lib().p3v_gemv_fp8_step(C.byref(args), C.byref(st), _stream())
-    else:
-        _chk(w, BF16, "w")
-        args = L.GemvArgs(_p(x), _p(w), _p(out), None, _p(norm_w), float(norm_eps), M, w.shape[0], K, EPI_NONE)
-        rc = L.lib().p3v_gemv_step(C.byref(args), C.byref(st), _stream())
+    rc, _ = _gemv_launch("gemv_step_end", _weight_format(w), w, x, x.shape[0], EPI_NONE, None, norm_w, norm_eps, out, step=st)
     if rc == L.ERR_UNSUPPORTED:
         return False
     L.check(rc, "gemv_step(end)")
