@@ -415,6 +415,46 @@ typedef struct {
 int p3v_attention_decode_q8(const p3v_attn_decode_q8_args_t* args /* host */, void* stream);
 int p3v_attention_decode_q8_can_fuse_oproj(int B, int L, int n_heads, int hd, int n_split, int cache_t, int o_n, int merge_in_launch);
 
+/* ---- the decode attention's route: what p3v_attention_decode / p3v_attention_decode_q8 launch for a call, and what the two
+ * can_fuse functions answer -- all four ask this one function (host-only, no launch).  A negative knob means the library's current
+ * setting (p3v_set_tuning); a negative `capacity` / `cu_count` asks the current device, as the entry points do, and only where
+ * the answer depends on it: with both given the function touches no device and runs without a GPU (tests/test_attn_route_cpu.py). */
+typedef enum { P3V_ATTN_O_NONE = 0, P3V_ATTN_O_BF16 = 1, P3V_ATTN_O_F8 = 2, P3V_ATTN_O_Q4 = 3 } p3v_attn_oproj_t;
+typedef enum {
+  P3V_ATTN_K_DECODE = 0,        /* bf16 cache: one 64-key tile per workgroup */
+  P3V_ATTN_K_DECODE128,         /*   one 128-key tile per workgroup */
+  P3V_ATTN_K_DECODE128_O,       /*   ... + the bf16 o_proj + residual */
+  P3V_ATTN_K_DECODE128_O4,      /*   ... + the 4-bit o_proj + residual */
+  P3V_ATTN_K_DECODE_STREAM,     /*   single-wave workgroups walking several tiles */
+  P3V_ATTN_K_DECODE_Q8,         /* int8 cache: single-wave workgroups (never merges in the launch) */
+  P3V_ATTN_K_DECODE_Q8S,        /*   one 64-key tile per 4-wave workgroup */
+  P3V_ATTN_K_DECODE128_Q8,      /*   one 128-key tile per workgroup */
+  P3V_ATTN_K_DECODE128_Q8_O,    /*   ... + the e4m3 o_proj + residual */
+  P3V_ATTN_K_COUNT
+} p3v_attn_kernel_t;
+typedef enum { P3V_ATTN_MERGE_IN_LAUNCH = 0, P3V_ATTN_MERGE_COMBINE2 = 1, P3V_ATTN_MERGE_COMBINE_O = 2 } p3v_attn_merge_t;
+typedef struct {
+  int kv_int8;                  /* 0: the bf16 cache (p3v_attention_decode), 1: the int8 cache (p3v_attention_decode_q8) */
+  int B, L, n_heads, hd, n_split, cache_t, merge_in_launch;
+  int o_proj;                   /* p3v_attn_oproj_t: the format of the o_proj the call carries */
+  int o_n;
+  int q8_old, attn_fo_map, attn_fo_map_q8;   /* the tuning knobs the route depends on */
+  int64_t capacity;             /* workgroups of the fused attention + o_proj launch that are resident at once */
+  int cu_count;                 /* compute units (the merge launch that carries the o_proj: one workgroup per CU) */
+} p3v_attn_route_query_t;
+typedef struct {
+  int status;                   /* P3V_OK, or P3V_ERR_UNSUPPORTED: an o_proj that no launch of this call can carry */
+  int kernel;                   /* p3v_attn_kernel_t */
+  int grid[3], block;
+  int merge;                    /* p3v_attn_merge_t */
+  int merge_grid, merge_block;  /* of the merge launch (0 with P3V_ATTN_MERGE_IN_LAUNCH) */
+  int fuse_form;                /* 0: no o_proj in this call, 1: in the attention launch, 2: in the merge launch (the can_fuse answer) */
+  int fo_remap;                 /* fuse_form 1: the 1-D grid's placement (p3v_attention_decode_fused_role's `map`), 0 = the (split, head) grid */
+  const char* kernel_name;      /* as a profiler prints them: "k_attn_decode128_q8<true>", "k_attn_combine_o<1>", "" for no merge launch */
+  const char* merge_name;
+} p3v_attn_route_t;
+int p3v_attention_decode_route(const p3v_attn_route_query_t* query /* host */, p3v_attn_route_t* route /* host */);
+
 /* ---- CLIP patch unfold: pixel_values [N,3,S,S] f32 -> patches [N*P, kpad] bf16, (c,ky,kx) order, zero padded */
 int p3v_im2col_patches(const float* pix, uint16_t* patches, int n_img, int img, int patch, int kpad, void* stream);
 /* ---- CLS rows: x[n, 0, :] = class_emb + pos[0]  (phi.py:202-205); x [N, P+1, D] f32 */

@@ -94,6 +94,23 @@ class AttnDecQ8Args(C.Structure):
                 ("o_proj_w8", vp), ("o_proj_scale", vp), ("o_proj_x", vp), ("o_rearm", vp), ("o_n", i32)]   # optional fused o_proj (e4m3)
 
 
+ATTN_O_NONE, ATTN_O_BF16, ATTN_O_F8, ATTN_O_Q4 = range(4)                       # p3v_attn_oproj_t
+ATTN_MERGE_IN_LAUNCH, ATTN_MERGE_COMBINE2, ATTN_MERGE_COMBINE_O = range(3)     # p3v_attn_merge_t
+
+
+class AttnRouteQuery(C.Structure):
+    """p3v_attn_route_query_t (include/p3v.h): a negative knob, capacity or cu_count = the library's / the device's own."""
+    _fields_ = [("kv_int8", i32), ("B", i32), ("L", i32), ("n_heads", i32), ("hd", i32), ("n_split", i32), ("cache_t", i32),
+                ("merge_in_launch", i32), ("o_proj", i32), ("o_n", i32), ("q8_old", i32), ("attn_fo_map", i32), ("attn_fo_map_q8", i32),
+                ("capacity", i64), ("cu_count", i32)]
+
+
+class AttnRoute(C.Structure):
+    """p3v_attn_route_t (include/p3v.h)."""
+    _fields_ = [("status", i32), ("kernel", i32), ("grid", i32 * 3), ("block", i32), ("merge", i32), ("merge_grid", i32),
+                ("merge_block", i32), ("fuse_form", i32), ("fo_remap", i32), ("kernel_name", C.c_char_p), ("merge_name", C.c_char_p)]
+
+
 class SampleRow(C.Structure):
     """p3v_sample_row_t: one row's sampling settings + its draw counter (include/p3v.h)."""
     _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
@@ -204,6 +221,7 @@ SIGNATURES = {
     "p3v_kv_quantize_mlx4": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p3v_attention_decode_q8": (i32, [C.POINTER(AttnDecQ8Args), vp]),
     "p3v_attention_decode_q8_can_fuse_oproj": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "p3v_attention_decode_route": (i32, [C.POINTER(AttnRouteQuery), C.POINTER(AttnRoute)]),   # added after round 6, no version change
     "p3v_stage_rope": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p3v_attention_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
     "p3v_im2col_patches": (i32, [vp, vp, i32, i32, i32, i32, vp]),

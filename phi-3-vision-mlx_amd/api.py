@@ -460,7 +460,7 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             # the row is poisoned).  Once per call: plan without it (as a server-owned model does), rewind to the last good token,
             # go on.  Anything else -- or a second failure -- is raised.
             g = st.graphs.get("greedy")
-            if degraded or g is None or not g["bufs"].get("fuse_o", False):
+            if degraded or g is None or not g["bufs"]["plan"].fuse_o:
                 st.mark_dirty() if hasattr(st, "mark_dirty") else None    # (a captured-prefill entry on these buffers is dropped)
                 raise
             degraded = True

@@ -2600,21 +2600,12 @@ __global__ void __launch_bounds__(512) k_attn_combine_o(const float* __restrict_
   fo_project<KIND, 2>(FoP{o_w, o_sb, o_x, out, nh}, u, lds, u + n_uw < n_units ? u + n_uw : -1);
 }
 
-// B = L = 1, 32 x 96: one workgroup per head + one per two row-pair quartets, all resident at once (one per CU, 8 CUs of head-room)
-static bool combine_o_ok(int B, int L, int n_heads, int hd, int n_split, int o_n) {
-  if (B != 1 || L != 1 || hd != 96 || n_heads * hd != 3072 || o_n <= 0 || o_n % 8) return false;
-  if (n_split < 1 || n_split > 128 || combine_threads(n_split) > 512) return false;
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return false;
-  return n_heads + (o_n / 8 + 1) / 2 <= pr.multiProcessorCount - 8;
-}
+// (grid: one workgroup per head + one per two row-pair quartets, decode_route's merge_grid)
 template <int KIND>
 static int launch_combine_o(const float* ws, void* out, void* o_rearm, const void* o_w, const void* o_sb, void* o_x, int n_heads, int n_split,
-                            int o_n, hipStream_t s) {
-  const int n_units = o_n / 8, grid_o = n_heads + (n_units + 1) / 2;
-  hipLaunchKernelGGL(k_attn_combine_o<KIND>, dim3(grid_o), dim3(combine_threads(n_split)), 0, s, ws, (bf16_t*)out, (bf16_t*)o_rearm, o_w, o_sb,
-                     (bf16_t*)o_x, n_heads, n_split, n_units);
+                            int o_n, int grid, int block, hipStream_t s) {
+  hipLaunchKernelGGL(k_attn_combine_o<KIND>, dim3(grid), dim3(block), 0, s, ws, (bf16_t*)out, (bf16_t*)o_rearm, o_w, o_sb, (bf16_t*)o_x, n_heads,
+                     n_split, o_n / 8);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }
@@ -2646,34 +2637,109 @@ extern "C" int p3v_debug_read(unsigned long long* out) {
 }
 #endif
 
-// The fused form needs: one row, one new token, a 3072-wide attention output (k_gemv3<1, 1, 6>'s shape), the 128-key plan with the
-// in-launch merge, enough non-merging workgroups for the o_n / 8 row-pair quartets, and EVERY workgroup of the launch resident at
-// once (3 per CU) -- the polling workgroups then cannot keep a producer from being scheduled.
+// =====================================================================================
+// The decode attention's route (host): which kernel a call runs, who merges the split partials and whether the layer's o_proj rides
+// along -- stated ONCE, for p3v_attention_decode, p3v_attention_decode_q8, the two can_fuse queries and p3v_attention_decode_route.
+static long resident_capacity(bool q8);                        // (behind the kernels it asks the runtime about, at the end of this file)
+static int device_cus();
+
+static int decode_route(const p3v_attn_route_query_t& q, p3v_attn_route_t* r) {
+  static const char* const names[P3V_ATTN_K_COUNT] = {"k_attn_decode", "k_attn_decode128", "k_attn_decode128_o", "k_attn_decode128_o4",
+      "k_attn_decode_stream<64>", "k_attn_decode_q8", "k_attn_decode_q8s", "k_attn_decode128_q8<false>", "k_attn_decode128_q8<true>"};
+  static const char* const combine_o_names[4] = {"", "k_attn_combine_o<1>", "k_attn_combine_o<2>", "k_attn_combine_o<3>"};
+  static_assert(FO_BF16 == P3V_ATTN_O_BF16 && FO_F8 == P3V_ATTN_O_F8 && FO_Q4 == P3V_ATTN_O_Q4, "k_attn_combine_o<KIND> is named by the public format");
+  const bool q8 = q.kv_int8 != 0;
+  if (q.o_proj < P3V_ATTN_O_NONE || q.o_proj > P3V_ATTN_O_Q4 || (q.o_proj && q8 != (q.o_proj == P3V_ATTN_O_F8))) return P3V_ERR_ARG;
+  const bool q8_old = q8 && (q.q8_old < 0 ? p3v_tuning().q8_old : q.q8_old) != 0;   // A/B knob: the single-wave int8 kernel everywhere
+  // the tile classes of a (n_split, cache_t) plan
+  const bool one_tile64 = q.n_split * 64 >= q.cache_t;                                             // one 64-key tile per workgroup
+  const bool one_tile128 = q.cache_t % 128 == 0 && q.n_split * 128 >= q.cache_t && !one_tile64;    // one 128-key tile per workgroup
+  // int8 cache, one tile per workgroup and at most 16 of them (contexts up to 1k): the 4-wave kernel, which with `merge_in_launch` also
+  // merges the splits inside the launch.  Beyond that the single-wave kernel + merge launch is as fast or faster
+  // (measured at 42 tiles, config 5 decode: 1.543 ms/step against 1.560 with the 4-wave kernel + fused merge: its
+  // bytes go through registers and a ds_write pass into the fp16 images, where the bf16 kernel uses LDS-DMA).
+  const bool q8_single_tile = one_tile64 && q.n_split <= 16;
+  int kernel = !q8 ? (one_tile64 ? P3V_ATTN_K_DECODE : one_tile128 ? P3V_ATTN_K_DECODE128 : P3V_ATTN_K_DECODE_STREAM)
+                   : q8_old ? P3V_ATTN_K_DECODE_Q8 : one_tile128 ? P3V_ATTN_K_DECODE128_Q8 : q8_single_tile ? P3V_ATTN_K_DECODE_Q8S : P3V_ATTN_K_DECODE_Q8;
+  int merge = q.merge_in_launch && kernel != P3V_ATTN_K_DECODE_Q8 ? P3V_ATTN_MERGE_IN_LAUNCH : P3V_ATTN_MERGE_COMBINE2;
+  int fuse_form = 0, fo_remap = 0;
+  // The o_proj needs: one row, one new token, a 3072-wide attention output (k_gemv3<1, 1, 6>'s shape) ...
+  if (q.o_proj && q.B == 1 && q.L == 1 && q.hd == 96 && q.n_heads * q.hd == 3072 && q.o_n > 0 && q.o_n % 8 == 0) {
+    if (!q.merge_in_launch) {
+      // ... and, where the partials are merged by a launch of their own, that launch takes it (k_attn_combine_o, answer 2): one workgroup
+      // per head + one per two row-pair quartets, all resident at once (one per CU, 8 CUs of head-room)
+      if (q.n_split >= 1 && q.n_split <= 128 && combine_threads(q.n_split) <= 512 &&
+          q.n_heads + (q.o_n / 8 + 1) / 2 <= (q.cu_count < 0 ? device_cus() : q.cu_count) - 8)
+        fuse_form = 2, merge = P3V_ATTN_MERGE_COMBINE_O;
+    } else if (one_tile128 && q.n_split >= 2 && (long)(q.n_split - 1) * q.n_heads * 8 >= q.o_n && !q8_old &&
+               (long)q.B * q.n_heads * q.n_split <= (q.capacity < 0 ? resident_capacity(q8) : q.capacity)) {
+      // ... or (answer 1) the 128-key plan with the in-launch merge, enough non-merging workgroups for the o_n / 8 row-pair quartets, and
+      // EVERY workgroup of the launch resident at once -- the polling workgroups then cannot keep a producer from being scheduled
+      fuse_form = 1;
+      kernel = q8 ? P3V_ATTN_K_DECODE128_Q8_O : q.o_proj == P3V_ATTN_O_Q4 ? P3V_ATTN_K_DECODE128_O4 : P3V_ATTN_K_DECODE128_O;
+      // the virtual-CU placement (fo_map; 1: second units on the second-to-last workgroups, 2: on the last ones).  Off by default on the
+      // int8 twin: with 24 KB tiles and 9.4 MB of e4m3 W_o the (split, head) grid measured 0.3 - 0.8 % FASTER on config 5 -- 1.197 vs
+      // 1.203 ms per step, profiles/r06_attn_oproj_placement.txt
+      const int map = q8 ? (q.attn_fo_map_q8 < 0 ? p3v_tuning().attn_fo_map_q8 : q.attn_fo_map_q8)
+                         : (q.attn_fo_map < 0 ? p3v_tuning().attn_fo_map : q.attn_fo_map);
+      if (map && fo_map_ok(q.n_split, q.n_heads, q.o_n)) fo_remap = map;
+    }
+  }
+  const bool wave1 = kernel == P3V_ATTN_K_DECODE_STREAM || kernel == P3V_ATTN_K_DECODE_Q8;
+  *r = {q.o_proj && !fuse_form ? P3V_ERR_UNSUPPORTED : P3V_OK, kernel,
+        {fo_remap ? q.n_split * q.n_heads : q.n_split, fo_remap ? 1 : q.n_heads, fo_remap ? 1 : q.B}, wave1 ? 64 : 256, merge,
+        merge == P3V_ATTN_MERGE_COMBINE2 ? q.B * q.n_heads * q.L : merge == P3V_ATTN_MERGE_COMBINE_O ? q.n_heads + (q.o_n / 8 + 1) / 2 : 0,
+        merge == P3V_ATTN_MERGE_IN_LAUNCH ? 0 : combine_threads(q.n_split), fuse_form, fo_remap, names[kernel],
+        merge == P3V_ATTN_MERGE_COMBINE2 ? "k_attn_combine2" : merge == P3V_ATTN_MERGE_COMBINE_O ? combine_o_names[q.o_proj] : ""};
+  return P3V_OK;
+}
+
+// the shape both entry points route, with the library's knobs and this device's capacities
+static p3v_attn_route_query_t decode_query(bool q8, int B, int L, int n_heads, int hd, int n_split, int cache_t, int merge_in_launch, int o_proj,
+                                           int o_n) {
+  return {q8, B, L, n_heads, hd, n_split, cache_t, merge_in_launch, o_proj, o_n, -1, -1, -1, -1, -1};
+}
+static int can_fuse_oproj(bool q8, int B, int L, int n_heads, int hd, int n_split, int cache_t, int o_n, int merge_in_launch) {
+  p3v_attn_route_t r;
+  const int rc = decode_route(decode_query(q8, B, L, n_heads, hd, n_split, cache_t, merge_in_launch, q8 ? P3V_ATTN_O_F8 : P3V_ATTN_O_BF16, o_n), &r);
+  return rc == P3V_OK && r.status == P3V_OK ? r.fuse_form : 0;
+}
 extern "C" int p3v_attention_decode_can_fuse_oproj(int B, int L, int n_heads, int hd, int n_split, int cache_t, int o_n, int merge_in_launch) {
-  if (B != 1 || L != 1 || hd != 96 || n_heads * hd != 3072 || o_n <= 0 || o_n % 8) return 0;
-  if (!merge_in_launch)      // the partials are merged by a launch of their own: that launch takes the o_proj (k_attn_combine_o) -- answer 2
-    return combine_o_ok(B, L, n_heads, hd, n_split, o_n) ? 2 : 0;
-  if (!(n_split * 128 >= cache_t && cache_t % 128 == 0 && n_split * 64 < cache_t) || n_split < 2) return 0;
-  if ((long)(n_split - 1) * n_heads * 8 < o_n) return 0;
-  // every workgroup of the launch must be resident at once (the projecting ones wait for the merging ones): ask the runtime how
-  // many of THIS kernel fit a CU rather than assume the 3 that its 52 KB of LDS and ~100 VGPRs give today
-  // (cached PER DEVICE: ADVICE r04 -- a process-wide value was whatever the first device that asked had)
-  static long capacity_of[P3V_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= P3V_MAX_DEVICES) return 0;
-  if (!capacity_of[dev]) {
-    int per_cu = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-    int per_cu4 = 0;                                           // (the bf16 and the 4-bit form of the launch: the smaller of the two)
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_attn_decode128_o, 256, 0) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_attn_decode128_o4, 256, 0) != hipSuccess) return 0;
-    per_cu = min(per_cu, per_cu4);
-    if (per_cu < 1) return 0;
-    capacity_of[dev] = (long)per_cu * (pr.multiProcessorCount - 8);   // 8 CUs of head-room: a grid of exactly the queried capacity
-  }                                                                   // did not co-reside in tools/scratch/persistent_chain.hip
-  const long capacity = capacity_of[dev];
-  return (long)B * n_heads * n_split <= capacity;
+  return can_fuse_oproj(false, B, L, n_heads, hd, n_split, cache_t, o_n, merge_in_launch);
+}
+extern "C" int p3v_attention_decode_q8_can_fuse_oproj(int B, int L, int n_heads, int hd, int n_split, int cache_t, int o_n, int merge_in_launch) {
+  return can_fuse_oproj(true, B, L, n_heads, hd, n_split, cache_t, o_n, merge_in_launch);
+}
+extern "C" int p3v_attention_decode_route(const p3v_attn_route_query_t* query, p3v_attn_route_t* route) {
+  return query && route ? decode_route(*query, route) : P3V_ERR_ARG;
+}
+
+// What both entry points check before they ask for a route, and in this order ...
+static int decode_shape_check(int B, int L, int n_heads, int n_kv, int hd, int n_split, int cache_t, const void* ws, const void* out) {
+  if (hd != 96) return P3V_ERR_UNSUPPORTED;
+  if (B <= 0 || L <= 0 || L > P3V_DECODE_MAX_L || n_heads % n_kv) return P3V_ERR_ARG;
+  if (n_split < 1 || n_split > 128 || cache_t % 64) return P3V_ERR_ARG;
+  if (((uintptr_t)ws | (uintptr_t)out) & 15) return P3V_ERR_ARG;           // 16-byte write-through stores of the partial records / merged rows
+  return P3V_OK;
+}
+// ... and after it, when the route carries an o_proj: 16-byte rows of W_o, x and the buffer to re-arm; `sb` is the 4-bit format's
+// scale | bias words (absent on bf16 weights) or the e4m3 format's row scales (required)
+static int o_proj_ptrs_check(int o_proj, const void* w, const void* sb, const void* x, const void* rearm) {
+  if ((o_proj == P3V_ATTN_O_F8 && !sb) || !x || !rearm || ((uintptr_t)w | (uintptr_t)x | (uintptr_t)rearm) & 15) return P3V_ERR_ARG;
+  if (o_proj != P3V_ATTN_O_F8 && sb && ((uintptr_t)sb & 3)) return P3V_ERR_ARG;
+  return P3V_OK;
+}
+// The launch that merges the partials, as the route names it: none, k_attn_combine2, or k_attn_combine_o with the o_proj + residual
+static int launch_merge(const p3v_attn_route_t& r, int o_proj, const float* ws, void* out, void* o_rearm, const void* o_w, const void* o_sb,
+                        void* o_x, int L, int n_heads, int hd, int n_split, int o_n, hipStream_t s) {
+  if (r.merge == P3V_ATTN_MERGE_IN_LAUNCH) return P3V_OK;      // the last workgroup of every (b, head) merged in-kernel
+  if (r.merge == P3V_ATTN_MERGE_COMBINE_O)
+    return (o_proj == P3V_ATTN_O_Q4   ? launch_combine_o<FO_Q4>
+            : o_proj == P3V_ATTN_O_F8 ? launch_combine_o<FO_F8>
+                                      : launch_combine_o<FO_BF16>)(ws, out, o_rearm, o_w, o_sb, o_x, n_heads, n_split, o_n, r.merge_grid, r.merge_block, s);
+  hipLaunchKernelGGL(k_attn_combine2, dim3(r.merge_grid), dim3(r.merge_block), 0, s, ws, (bf16_t*)out, L, n_heads, hd, n_split);
+  P3V_CHECK_LAUNCH();
+  return P3V_OK;
 }
 
 extern "C" int p3v_attention_decode_fused_role(int wg, int n_heads, int n_split, int o_n, int map, int* out4) {
@@ -2686,48 +2752,30 @@ extern "C" int p3v_attention_decode_fused_role(int wg, int n_heads, int n_split,
 
 extern "C" int p3v_attention_decode(const p3v_attn_decode_args_t* a, void* stream) {
   if (!a || !a->qkv || !a->cos_t || !a->sin_t || !a->k_cache || !a->v_cache || !a->out || !a->ws) return P3V_ERR_ARG;
-  if (a->hd != 96) return P3V_ERR_UNSUPPORTED;
-  if (a->B <= 0 || a->L <= 0 || a->L > P3V_DECODE_MAX_L || a->n_heads % a->n_kv) return P3V_ERR_ARG;
-  if (a->n_split < 1 || a->n_split > 128 || a->cache_t % 64) return P3V_ERR_ARG;
-  if (((uintptr_t)a->ws | (uintptr_t)a->out) & 15) return P3V_ERR_ARG;      // 16-byte write-through stores of the partial records / merged rows
+  if (int rc = decode_shape_check(a->B, a->L, a->n_heads, a->n_kv, a->hd, a->n_split, a->cache_t, a->ws, a->out)) return rc;
+  const int o_proj = !a->o_proj_w ? P3V_ATTN_O_NONE : a->o_proj_sb ? P3V_ATTN_O_Q4 : P3V_ATTN_O_BF16;
+  p3v_attn_route_t r;
+  if (int rc = decode_route(decode_query(false, a->B, a->L, a->n_heads, a->hd, a->n_split, a->cache_t, a->merge_in_launch, o_proj, a->o_n), &r)) return rc;
+  if (r.status != P3V_OK) return r.status;
+  if (o_proj)
+    if (int rc = o_proj_ptrs_check(o_proj, a->o_proj_w, a->o_proj_sb, a->o_proj_x, a->o_rearm)) return rc;
   const int grp = a->n_heads / a->n_kv;
   const int chunk = ((a->cache_t + a->n_split - 1) / a->n_split + 63) & ~63;
-  AttnDecP p = {a->qkv, a->cos_t, a->sin_t, a->k_cache, a->v_cache, a->pad_len, a->d_past, a->ws,
-                a->B, a->L, a->n_heads, a->n_kv, a->past, a->cache_t, a->rope_bstride, a->n_split, a->scale,
-                chunk, grp, (65536 + grp - 1) / grp, a->merge_in_launch, (bf16_t*)a->out,
-                a->o_proj_w, a->o_proj_sb, (bf16_t*)a->o_proj_x, (bf16_t*)a->o_rearm, a->o_n, 0};
+  const AttnDecP p = {a->qkv, a->cos_t, a->sin_t, a->k_cache, a->v_cache, a->pad_len, a->d_past, a->ws,
+                      a->B, a->L, a->n_heads, a->n_kv, a->past, a->cache_t, a->rope_bstride, a->n_split, a->scale,
+                      chunk, grp, (65536 + grp - 1) / grp, a->merge_in_launch, (bf16_t*)a->out,
+                      a->o_proj_w, a->o_proj_sb, (bf16_t*)a->o_proj_x, (bf16_t*)a->o_rearm, a->o_n, r.fo_remap};
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(a->n_split, a->n_heads, a->B);
-  const int fuse_form = a->o_proj_w ? p3v_attention_decode_can_fuse_oproj(a->B, a->L, a->n_heads, a->hd, a->n_split, a->cache_t, a->o_n, a->merge_in_launch) : 0;
-  if (a->o_proj_w && !fuse_form) return P3V_ERR_UNSUPPORTED;
-  if (a->o_proj_w && (!a->o_proj_x || !a->o_rearm || ((uintptr_t)a->o_proj_w | (uintptr_t)a->o_proj_x | (uintptr_t)a->o_rearm) & 15)) return P3V_ERR_ARG;
-  if (a->o_proj_w && a->o_proj_sb && ((uintptr_t)a->o_proj_sb & 3)) return P3V_ERR_ARG;
-  if (fuse_form == 1) {                                        // attention + o_proj + residual in one launch
-    if (p3v_tuning().attn_fo_map && fo_map_ok(a->n_split, a->n_heads, a->o_n)) {
-      p.fo_remap = p3v_tuning().attn_fo_map;                    // 1: second units on the second-to-last workgroups, 2: on the last ones
-      grid = dim3(a->n_split * a->n_heads, 1, 1);
-    }
-    if (a->o_proj_sb) {                                        // 4-bit group-64 o_proj weights
-      if ((uintptr_t)a->o_proj_sb & 3) return P3V_ERR_ARG;
-      hipLaunchKernelGGL(k_attn_decode128_o4, grid, dim3(256), 0, s, p);
-    } else {
-      hipLaunchKernelGGL(k_attn_decode128_o, grid, dim3(256), 0, s, p);
-    }
-    P3V_CHECK_LAUNCH();
-    return P3V_OK;
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  switch (r.kernel) {
+    case P3V_ATTN_K_DECODE: hipLaunchKernelGGL(k_attn_decode, grid, block, 0, s, p); break;
+    case P3V_ATTN_K_DECODE128: hipLaunchKernelGGL(k_attn_decode128, grid, block, 0, s, p); break;
+    case P3V_ATTN_K_DECODE128_O: hipLaunchKernelGGL(k_attn_decode128_o, grid, block, 0, s, p); break;    // attention + o_proj + residual in one launch
+    case P3V_ATTN_K_DECODE128_O4: hipLaunchKernelGGL(k_attn_decode128_o4, grid, block, 0, s, p); break;  // ... on 4-bit group-64 o_proj weights
+    default: hipLaunchKernelGGL(k_attn_decode_stream<64>, grid, block, 0, s, p);
   }
-  if (a->n_split * 64 >= a->cache_t) hipLaunchKernelGGL(k_attn_decode, grid, dim3(256), 0, s, p);
-  else if (a->n_split * 128 >= a->cache_t && a->cache_t % 128 == 0) hipLaunchKernelGGL(k_attn_decode128, grid, dim3(256), 0, s, p);   // 128-key tiles
-  else hipLaunchKernelGGL(k_attn_decode_stream<64>, grid, dim3(64), 0, s, p);
   P3V_CHECK_LAUNCH();
-  if (a->merge_in_launch) return P3V_OK;                       // the last workgroup of every (b, head) merged in-kernel
-  if (fuse_form == 2)                                          // the merge launch carries the o_proj + residual
-    return a->o_proj_sb ? launch_combine_o<FO_Q4>(a->ws, a->out, a->o_rearm, a->o_proj_w, a->o_proj_sb, a->o_proj_x, a->n_heads, a->n_split, a->o_n, s)
-                        : launch_combine_o<FO_BF16>(a->ws, a->out, a->o_rearm, a->o_proj_w, nullptr, a->o_proj_x, a->n_heads, a->n_split, a->o_n, s);
-  hipLaunchKernelGGL(k_attn_combine2, dim3(a->B * a->n_heads * a->L), dim3(combine_threads(a->n_split)), 0, s, a->ws, a->out, a->L, a->n_heads,
-                     a->hd, a->n_split);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
+  return launch_merge(r, o_proj, a->ws, a->out, a->o_rearm, a->o_proj_w, a->o_proj_sb, a->o_proj_x, a->L, a->n_heads, a->hd, a->n_split, a->o_n, s);
 }
 
 // =====================================================================================
@@ -3660,95 +3708,62 @@ __global__ void __launch_bounds__(256) k_attn_decode128_q8(AttnDecQ8P p) {
   }
 }
 
-extern "C" int p3v_attention_decode_q8_can_fuse_oproj(int B, int L, int n_heads, int hd, int n_split, int cache_t, int o_n, int merge_in_launch) {
-  if (!merge_in_launch) return combine_o_ok(B, L, n_heads, hd, n_split, o_n) ? 2 : 0;      // the merge launch carries the e4m3 o_proj (k_attn_combine_o)
-  if (B != 1 || L != 1 || hd != 96 || n_heads * hd != 3072 || o_n <= 0 || o_n % 8) return 0;
-  if (!(n_split * 128 >= cache_t && cache_t % 128 == 0 && n_split * 64 < cache_t) || n_split < 2) return 0;
-  if ((long)(n_split - 1) * n_heads * 8 < o_n || p3v_tuning().q8_old) return 0;
-  static long capacity_of[P3V_MAX_DEVICES] = {0};              // every workgroup resident at once: see p3v_attention_decode_can_fuse_oproj
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= P3V_MAX_DEVICES) return 0;
-  if (!capacity_of[dev]) {
-    int per_cu = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_attn_decode128_q8<true>, 256, 0) != hipSuccess || per_cu < 1) return 0;
-    capacity_of[dev] = (long)per_cu * (pr.multiProcessorCount - 8);
-  }
-  const long capacity = capacity_of[dev];
-  return (long)B * n_heads * n_split <= capacity;
-}
-
 extern "C" int p3v_attention_decode_q8(const p3v_attn_decode_q8_args_t* a, void* stream) {
   if (!a || !a->qkv || !a->cos_t || !a->sin_t || !a->k8 || !a->v8t || !a->k_scale || !a->v_scale || !a->out || !a->ws)
     return P3V_ERR_ARG;
-  if (a->hd != 96) return P3V_ERR_UNSUPPORTED;
-  if (a->B <= 0 || a->L <= 0 || a->L > P3V_DECODE_MAX_L || a->n_heads % a->n_kv) return P3V_ERR_ARG;
-  if (a->n_split < 1 || a->n_split > 128 || a->cache_t % 64) return P3V_ERR_ARG;
-  if (((uintptr_t)a->ws | (uintptr_t)a->out) & 15) return P3V_ERR_ARG;      // (16-byte write-through stores, as p3v_attention_decode)
+  if (int rc = decode_shape_check(a->B, a->L, a->n_heads, a->n_kv, a->hd, a->n_split, a->cache_t, a->ws, a->out)) return rc;
+  const int o_proj = a->o_proj_w8 ? P3V_ATTN_O_F8 : P3V_ATTN_O_NONE;
+  p3v_attn_route_t r;
+  if (int rc = decode_route(decode_query(true, a->B, a->L, a->n_heads, a->hd, a->n_split, a->cache_t, a->merge_in_launch, o_proj, a->o_n), &r)) return rc;
+  if (r.status != P3V_OK) return r.status;                       // (the in-launch o_proj exists for the 128-key plan only)
+  if (o_proj)
+    if (int rc = o_proj_ptrs_check(o_proj, a->o_proj_w8, a->o_proj_scale, a->o_proj_x, a->o_rearm)) return rc;
   const int grp = a->n_heads / a->n_kv;
   AttnDecQ8P p = {a->qkv, a->cos_t, a->sin_t, a->k8, a->v8t, a->k_scale, a->v_scale, a->pad_len, a->d_past, a->ws,
                   a->B, a->L, a->n_heads, a->n_kv, a->past, a->cache_t, a->rope_bstride, a->n_split, a->scale,
-                  grp, (65536 + grp - 1) / grp, 0, (bf16_t*)a->out, nullptr, nullptr, nullptr, nullptr, 0};
+                  grp, (65536 + grp - 1) / grp, r.merge == P3V_ATTN_MERGE_IN_LAUNCH ? a->merge_in_launch : 0, (bf16_t*)a->out,
+                  nullptr, nullptr, nullptr, nullptr, 0, r.fo_remap};
+  if (r.fuse_form == 1) {                                        // attention + o_proj (e4m3) + residual in one launch
+    p.o_w = a->o_proj_w8; p.o_scale = a->o_proj_scale; p.o_x = (bf16_t*)a->o_proj_x; p.o_rearm = (bf16_t*)a->o_rearm; p.o_n = a->o_n;
+  }
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(a->n_split, a->n_heads, a->B);
-  const bool old_only = p3v_tuning().q8_old != 0;   // A/B knob
-  // the o_proj rides either in the one-tile attention launch (in-launch merge) or in the merge launch (k_attn_combine_o, round 6)
-  const bool merge_o = a->o_proj_w8 && !a->merge_in_launch;
-  if (merge_o) {
-    if (!combine_o_ok(a->B, a->L, a->n_heads, a->hd, a->n_split, a->o_n)) return P3V_ERR_UNSUPPORTED;
-    if (!a->o_proj_scale || !a->o_proj_x || !a->o_rearm || ((uintptr_t)a->o_proj_w8 | (uintptr_t)a->o_proj_x | (uintptr_t)a->o_rearm) & 15)
-      return P3V_ERR_ARG;
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  switch (r.kernel) {
+    case P3V_ATTN_K_DECODE128_Q8_O: hipLaunchKernelGGL(k_attn_decode128_q8<true>, grid, block, 0, s, p); break;
+    case P3V_ATTN_K_DECODE128_Q8: hipLaunchKernelGGL(k_attn_decode128_q8<false>, grid, block, 0, s, p); break;
+    case P3V_ATTN_K_DECODE_Q8S: hipLaunchKernelGGL(k_attn_decode_q8s, grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL(k_attn_decode_q8, grid, block, 0, s, p);
   }
-  auto merge = [&]() -> int {                                    // the launch that merges the partials
-    if (merge_o)
-      return launch_combine_o<FO_F8>(a->ws, a->out, a->o_rearm, a->o_proj_w8, a->o_proj_scale, a->o_proj_x, a->n_heads, a->n_split, a->o_n, s);
-    hipLaunchKernelGGL(k_attn_combine2, dim3(a->B * a->n_heads * a->L), dim3(combine_threads(a->n_split)), 0, s, a->ws, a->out, a->L, a->n_heads,
-                       a->hd, a->n_split);
-    P3V_CHECK_LAUNCH();
-    return P3V_OK;
-  };
-  if (a->o_proj_w8 && a->merge_in_launch &&
-      !(!old_only && a->cache_t % 128 == 0 && a->n_split * 128 >= a->cache_t && a->n_split * 64 < a->cache_t))
-    return P3V_ERR_UNSUPPORTED;                                 // (the in-launch form exists for the 128-key plan only)
-  // one tile per workgroup and at most 16 of them (contexts up to 1k): the 4-wave kernel, which with `merge_in_launch` also
-  // merges the splits inside the launch.  Beyond that the single-wave kernel + merge launch is as fast or faster
-  // (measured at 42 tiles, config 5 decode: 1.543 ms/step against 1.560 with the 4-wave kernel + fused merge: its
-  // bytes go through registers and a ds_write pass into the fp16 images, where the bf16 kernel uses LDS-DMA).
-  if (!old_only && a->cache_t % 128 == 0 && a->n_split * 128 >= a->cache_t && a->n_split * 64 < a->cache_t) {   // 128-key tiles
-    p.merge = a->merge_in_launch;
-    if (a->o_proj_w8 && a->merge_in_launch) {                  // attention + o_proj (e4m3) + residual in one launch
-      if (!p3v_attention_decode_q8_can_fuse_oproj(a->B, a->L, a->n_heads, a->hd, a->n_split, a->cache_t, a->o_n, a->merge_in_launch))
-        return P3V_ERR_UNSUPPORTED;
-      if (!a->o_proj_scale || !a->o_proj_x || !a->o_rearm || ((uintptr_t)a->o_proj_w8 | (uintptr_t)a->o_proj_x | (uintptr_t)a->o_rearm) & 15)
-        return P3V_ERR_ARG;
-      p.o_w = a->o_proj_w8; p.o_scale = a->o_proj_scale; p.o_x = (bf16_t*)a->o_proj_x; p.o_rearm = (bf16_t*)a->o_rearm; p.o_n = a->o_n;
-      // (the virtual-CU placement of k_attn_decode128_o, off by default here: with 24 KB tiles and 9.4 MB of e4m3 W_o the (split, head)
-      //  grid measured 0.3 - 0.8 % FASTER on config 5 -- 1.197 vs 1.203 ms per step, profiles/r06_attn_oproj_placement.txt)
-      if (p3v_tuning().attn_fo_map_q8 && fo_map_ok(a->n_split, a->n_heads, a->o_n)) {
-        p.fo_remap = p3v_tuning().attn_fo_map_q8;
-        hipLaunchKernelGGL(k_attn_decode128_q8<true>, dim3(a->n_split * a->n_heads, 1, 1), dim3(256), 0, s, p);
-        P3V_CHECK_LAUNCH();
-        return P3V_OK;
-      }
-      hipLaunchKernelGGL(k_attn_decode128_q8<true>, grid, dim3(256), 0, s, p);
-      P3V_CHECK_LAUNCH();
-      return P3V_OK;
-    }
-    hipLaunchKernelGGL(k_attn_decode128_q8<false>, grid, dim3(256), 0, s, p);
-    P3V_CHECK_LAUNCH();
-    if (a->merge_in_launch) return P3V_OK;
-    return merge();
-  }
-  const bool single_tile = !old_only && a->n_split * 64 >= a->cache_t && a->n_split <= 16;
-  if (single_tile && a->merge_in_launch) {
-    p.merge = a->merge_in_launch;
-    hipLaunchKernelGGL(k_attn_decode_q8s, grid, dim3(256), 0, s, p);
-    P3V_CHECK_LAUNCH();
-    return P3V_OK;
-  }
-  if (single_tile) hipLaunchKernelGGL(k_attn_decode_q8s, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_attn_decode_q8, grid, dim3(64), 0, s, p);
   P3V_CHECK_LAUNCH();
-  return merge();
+  return launch_merge(r, o_proj, a->ws, a->out, a->o_rearm, a->o_proj_w8, a->o_proj_scale, a->o_proj_x, a->L, a->n_heads, a->hd, a->n_split, a->o_n, s);
+}
+
+// Every workgroup of a fused attention + o_proj launch must be resident at once (the projecting ones wait for the merging ones): ask
+// the runtime how many of THIS kernel fit a CU rather than assume the 3 that its 52 KB of LDS and ~100 VGPRs give today (bf16 cache:
+// the bf16 and the 4-bit form of the launch, the smaller of the two).  Cached PER DEVICE (ADVICE r04 -- a process-wide value was
+// whatever the first device that asked had).  0: could not ask.
+static long resident_capacity(bool q8) {
+  static long capacity_of[2][P3V_MAX_DEVICES] = {{0}};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= P3V_MAX_DEVICES) return 0;
+  if (!capacity_of[q8][dev]) {
+    int per_cu = 0, per_cu4 = 0;
+    const int cus = device_cus();
+    if (!cus) return 0;
+    if (q8) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_attn_decode128_q8<true>, 256, 0) != hipSuccess) return 0;
+    } else {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_attn_decode128_o, 256, 0) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_attn_decode128_o4, 256, 0) != hipSuccess) return 0;
+      per_cu = min(per_cu, per_cu4);
+    }
+    if (per_cu < 1) return 0;
+    capacity_of[q8][dev] = (long)per_cu * (cus - 8);            // 8 CUs of head-room: a grid of exactly the queried capacity
+  }                                                             // did not co-reside in tools/scratch/persistent_chain.hip
+  return capacity_of[q8][dev];
+}
+static int device_cus() {
+  int dev = 0;
+  hipDeviceProp_t pr;
+  return hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 0;
 }

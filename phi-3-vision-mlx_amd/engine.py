@@ -179,7 +179,7 @@ class ContinuousEngine:
     def _new_state(self):
         self.st = self.model.new_slot_state(self.slots, self.window)
         self.model.serving = True                               # (the owner is a server: model.py)
-        self.st.serving = True                                  # long-lived: the split-KV merge must not lean on dispatch order (model._split_plan)
+        self.st.serving = True                                  # long-lived: the split-KV merge must not lean on dispatch order (model._plan)
         self.cache = [type("L", (), {"state": self.st})()]      # greedy_step reads cache[0].state
         self.families = []
         if self.share_prefix:                                   # the table BEFORE the step is captured: the capture then follows it
@@ -348,7 +348,8 @@ class ContinuousEngine:
         """The in-launch split-KV merge expects an all-sentinel workspace (ops.attention_ws); after a poisoned step a late
         partial may have landed on top of the restored sentinels -- refill before the next replay."""
         g = self.st.graphs.get("greedy")
-        ws = g and g["bufs"].get("ws")
+        plan = g and g["bufs"].get("plan")
+        ws = plan and plan.ws
         if ws is not None:
             _sync(self.model.device)
             ws.view(torch.int32).fill_(-1)

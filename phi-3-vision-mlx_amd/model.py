@@ -23,6 +23,7 @@ tolerance the parity tests state.
 """
 import math
 import copy
+import dataclasses
 import os
 
 import numpy as np
@@ -52,6 +53,33 @@ def _on_device(fn):
 
 V_PREFIX = "model.vision_embed_tokens.img_processor.vision_model."
 E_PREFIX = "model.vision_embed_tokens."
+
+
+@dataclasses.dataclass(slots=True)
+class AttnPlan:
+    """The decode attention's plan of one pass over a state (Phi3VModel._plan makes it; nothing writes it afterwards): `bufs["plan"]` of
+    an eager pass, `g["bufs"]["plan"]` of a capture."""
+    n_split: int = 0            # key splits per (row, head); 0: a prompt-sized pass (no split plan, no workspace)
+    ws: object = None           # the split partials' workspace, all-ones between launches (ops.attention_ws)
+    attn_merge: bool = False    # the partials are merged inside the attention launch (`merge_in_launch`), not by a launch of their own
+    fuse_o: bool = False        # the layer's o_proj + residual ride in the attention launch, or in the merge launch without attn_merge
+    family: bool = False        # ops.attention_decode_family: the state's families read their prompt K/V once
+    past_lb: int = -1           # captured step: the host's lower bound of the device-side cache length (-1: none)
+    rope_cos: object = None     # captured step: the step's staged rotation rows [B, L, hd / 2]
+    rope_sin: object = None
+    o_f: object = None          # fuse_o: the attention output's two buffers, used by alternate layers, all-ones = "not written yet"
+    o_f2: object = None
+
+
+def _attn_knobs():
+    """The environment's say in a plan, read once per plan (at plan time: tests set them per test) -> (128-key tiles allowed, forced
+    n_split or None, P3V_ATTN_FUSED_MERGE's mode: "0" never / "1" by rule / "2" wherever the kernels can, fused o_proj allowed,
+    profiling).  P3V_PROFILING=1: no launch of the step may wait for another workgroup of its own grid (whole-graph rocprofv3 --pmc
+    passes serialise / mask what they profile) -- separate merge launch, separate o_proj launch."""
+    env = os.environ.get
+    forced = env("P3V_ATTN_NSPLIT")
+    return (env("P3V_ATTN_TILE128", "1") != "0", int(forced) if forced else None, env("P3V_ATTN_FUSED_MERGE", "1"),
+            env("P3V_ATTN_FUSE_OPROJ", "1") != "0", env("P3V_PROFILING") == "1")
 
 
 class CacheState:
@@ -109,7 +137,7 @@ class CacheState:
         self.epoch = None                                       # model.epoch the graphs were captured under
         self.shared = {"dirty": False}                          # shared by the per-request views of a captured-prefill entry (copy.copy)
         self.slots = False                                      # a slot state of the continuous-batching engine (model.new_slot_state)
-        self.serving = False                                    # owned by a long-lived server (engine.py): see model._split_plan
+        self.serving = False                                    # owned by a long-lived server (engine.py): see _plan
         self.fresh_rows = False                                 # a rows_view whose columns left of its offset hold nothing its rows may see
         self.row_adapter = None                                 # adapter bank: int32 [B] slot per row, made on first use (model._state_rows)
         self.sample_rows = None                                 # sampling records int32 [B, 6] (model.set_sampling)
@@ -348,7 +376,7 @@ class Phi3VModel:
 
     def _fused_oproj_kw(self, o_key, x, rearm):
         """The o_proj keywords of a fused attention + o_proj launch.  The weight format names the launch: bf16 and 4-bit weights go
-        with the bf16 cache (ops.attention_decode), e4m3 weights with the int8 cache (ops.attention_decode_q8; `_plan_fused_oproj`)."""
+        with the bf16 cache (ops.attention_decode), e4m3 weights with the int8 cache (ops.attention_decode_q8; `_plan`)."""
         w, fmt = self._handle(o_key)
         kw = dict(o_proj_x=x, o_rearm=rearm)
         if fmt == "fp8":
@@ -980,91 +1008,46 @@ class Phi3VModel:
         and rebuilt if the cache was rewound below the lower bound it was captured with."""
         self._sync_epoch(st)
         g = st.graphs.get("greedy")
-        if g is None or st.offset < g["bufs"]["past_lb"]:
+        if g is None or st.offset < g["bufs"]["plan"].past_lb:
             g = st.graphs["greedy"] = self._build_decode_graph(st)
             g["host_tok"] = None
         return g
 
     # ------------------------------------------------------------------ decoder stack
+    FAMILY_CHUNK = 256          # keys per split of the family plan (tools/share_step_time.py sets it on its model to time the alternatives)
+
     def _plan(self, st, B, L, fuse_o, captured=False, family=True):
-        """The buffers and the attention plan of a pass over B x L rows of a state.  fuse_o: also plan the fused attention + o_proj
-        launch (_plan_fused_oproj; it sets bufs["fuse_o"]).  captured:
-        the plan is for a captured step, which reads the cache length from the device -- it carries the step's staging rows for the
-        rotation tables and `past_lb`, the host's lower bound of that length: the cache only grows under a captured step (the
-        capture is rebuilt if it is ever found below the bound); a slot state's column moves both ways (engine.py), so it gets none."""
+        """The buffers of a pass over B x L rows of a state and, as `bufs["plan"]`, its attention plan (AttnPlan), chosen top to
+        bottom: family or split plan, n_split, workspace, merge form, o_proj form.  fuse_o: the caller can take the layer's o_proj +
+        residual inside the attention's launches.  captured: the plan is for a captured step, which reads the cache length from the
+        device -- it carries the step's staging rows for the rotation tables and `past_lb`, the host's lower bound of that length: the
+        cache only grows under a captured step (the capture is rebuilt if it is ever found below the bound); a slot state's column
+        moves both ways (engine.py), so it gets none.
+        The split plan comes from the cache CAPACITY, eager or captured: same kernel, same split boundaries -> eager and replayed
+        steps agree bit for bit.  Which kernel the library runs for (n_split, capacity), and which o_proj form it takes, is its
+        route's to say (ops.attention_decode_route; tests/test_attn_probe_cpu.py ties the two)."""
+        cfg, T = self.cfg, st.Tp
+        nh, hd = cfg.num_attention_heads, self.hd
         bufs = self._alloc_bufs(B, L)
-        # split plan from the cache CAPACITY, eager or captured: same kernel, same split boundaries -> eager and replayed steps
-        # agree bit for bit
+        plan = bufs["plan"]
         if family and L == 1 and st.family is not None and B == st.B and not st.quantized and not st.mlx4:
-            self._family_plan(bufs, B, st.Tp)                   # a state with a family table: ops.attention_decode_family, no fused o_proj
-            fuse_o = False
-        else:
-            self._split_plan(bufs, B, L, st.Tp, st.quantized, serving=st.serving or self.serving)
-        if captured:
-            bufs["past_lb"] = -1 if st.slots else int(st.offset)
-            bufs["rope_cos"] = torch.empty((B, L, self.hd // 2), dtype=F32, device=self.device)
-            bufs["rope_sin"] = torch.empty_like(bufs["rope_cos"])
-        if fuse_o:
-            self._plan_fused_oproj(bufs, B, L, st.Tp, st.quantized)
-        return bufs
-
-    def _alloc_bufs(self, B, L):
-        cfg = self.cfg
-        nh, nkv, hd, H, I = cfg.num_attention_heads, cfg.num_key_value_heads, self.hd, cfg.hidden_size, cfg.intermediate_size
-        M, dev = B * L, self.device
-        bufs = dict(
-            q=torch.empty((B, nh, L, hd), dtype=BF16, device=dev), o=torch.empty((M, nh * hd), dtype=BF16, device=dev),
-            qkv=torch.empty((M, (nh + 2 * nkv) * hd), dtype=BF16, device=dev), a=torch.empty((M, I), dtype=BF16, device=dev),
-            h=torch.empty((M, H), dtype=BF16, device=dev), n_split=0, ws=None)
-        return bufs
-
-    def _plan_fused_oproj(self, bufs, B, L, T, quantized=False):
-        """B = L = 1 decode: attention + o_proj + residual as ONE launch per layer where the library takes the shape -- on bf16 or
-        MLX 4-bit weights and a bf16 cache (k_attn_decode128_o / _o4), or on e4m3 weights and the int8 cache (config 5:
-        k_attn_decode128_q8<true>); p3v_attention.hip.  Long contexts (round 6), whose partials are merged by a launch of their own:
-        that launch carries the o_proj (k_attn_combine_o).  The attention output then lives in two buffers that alternate layers use, both all-ones (= "not written
-        yet") between launches; P3V_ATTN_FUSE_OPROJ=0 switches it off."""
-        cfg = self.cfg
-        can = ops.attention_decode_q8_can_fuse_oproj if quantized else ops.attention_decode_can_fuse_oproj
-        o_key = "model.layers.0.self_attn.o_proj.weight"
-        # The launch of layer i re-arms the OTHER buffer, so the two alternate cleanly only over an EVEN number of layers (an odd
-        # stack would hand layer 0 of the next step the buffer the last layer just filled: stale words read as "written").
-        # It also needs the GPU to itself (every workgroup resident at once): not for a server-owned model.
-        # P3V_PROFILING=1: no launch of the step may wait for another workgroup of its own grid (whole-graph rocprofv3 --pmc passes
-        # serialise / mask what they profile): separate o_proj launch here, separate merge launch in _split_plan
-        ok = (os.environ.get("P3V_ATTN_FUSE_OPROJ", "1") != "0" and os.environ.get("P3V_PROFILING") != "1"
-              and B == 1 and L == 1
-              and cfg.num_hidden_layers % 2 == 0 and not self.serving
-              and not self.adapters and not self._bank_has("self_attn.o_proj.weight") and (self._handle(o_key)[1] == "fp8") == bool(quantized)
-              # (without the in-launch merge -- long contexts: the MERGE launch carries the o_proj, k_attn_combine_o, round 6)
-              and can(B, L, cfg.num_attention_heads, self.hd, bufs["n_split"], T, cfg.hidden_size, bool(bufs.get("attn_merge", False))))
-        if not ok and bufs.get("attn_merge", False) and B == 1 and L == 1 and not quantized:
-            # Short contexts (64-key one-tile plans: the in-launch form above is for 128-key tiles): attention that only writes its partials
-            # + the merge launch carrying the o_proj beats attention with the in-launch merge + an o_proj launch (1.587 -> 1.570 ms per
-            # step at 128 keys, 1.662 -> 1.652 at 1000; with the int8 cache it loses: 1.165 -> 1.179 at 128 keys, so not there)
-            bufs["attn_merge"] = False
-            self._plan_fused_oproj(bufs, B, L, T, quantized)
-            if not bufs["fuse_o"]:
-                bufs["attn_merge"] = True
-            return
-        bufs["fuse_o"] = bool(ok)
-        if ok:
-            for k in ("o_f", "o_f2"):                            # all-ones = "not written yet"
-                bufs[k] = torch.full((1, cfg.num_attention_heads * self.hd), -1, dtype=torch.int16, device=self.device).view(BF16)
-
-    def _split_plan(self, bufs, B, L, T, quantized=False, serving=False):
-        """Split-KV plan for the decode-shaped attention (L <= 16): enough blocks to fill 256 CUs.
-        serving: the plan is for a slot state of the continuous-batching engine (a long-lived server) -- the in-launch merge is
-        then used only when EVERY workgroup of the launch is resident at once (no assumption about dispatch order at all)."""
-        nh, hd = self.cfg.num_attention_heads, self.hd
-        if L <= ops.L.DECODE_MAX_L:
-            # 64-key tiles.  Up to ~4096 workgroups: ONE tile per 4-wave workgroup (the kernel then lasts a single
-            # tile's dependency chain); beyond that ~768 single-wave workgroups (one resident round, each with its
-            # next 24 KB tile in flight) walking several tiles
+            # A state with a family table (ops.attention_decode_family, no fused o_proj).  A family's whole splits below share_end are
+            # read once, by its leader, and the up-to-one-chunk remainder by every member, so the chunk is small and fixed: 256 keys
+            # (four tiles of the one-wave kernel per split), as many splits as the workspace and the merge launch take (128; longer
+            # caches get longer chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 keys, shared step,
+            # n = 4 / n = 8 (profiles/share_prefix_step_time.txt): 64 keys 2.4306 / 2.8538 ms, 128 keys 2.2363 / 2.4925 ms, 256 keys
+            # 2.1288 / 2.4102 ms -- fewer, longer single-wave workgroups and half the partials to merge outweigh the longer remainder.
+            plan.family, fuse_o = True, False
+            plan.n_split = max(1, min(128, -(-T // int(self.FAMILY_CHUNK))))
+            plan.ws = ops.attention_ws(B, 1, nh, hd, plan.n_split, self.device)
+        elif L <= ops.L.DECODE_MAX_L:
+            # Split-KV plan of the decode-shaped attention: enough blocks to fill 256 CUs.  64-key tiles; up to ~4096 workgroups ONE
+            # tile per 4-wave workgroup (the kernel then lasts a single tile's dependency chain); beyond that ~768 single-wave
+            # workgroups (one resident round, each with its next 24 KB tile in flight) walking several tiles
+            tile128_ok, forced_split, merge_mode, fuse_o_ok, profiling = _attn_knobs()   # (the family plan has none)
             tiles = -(-T // 64)
-            tiles128 = T // 128 if T % 128 == 0 else 0           # T is the cache CAPACITY when the plan is for a captured graph
-            if tiles128 and tiles > 16 and tiles128 <= 48 and B * nh * tiles128 <= 2048 \
-                    and os.environ.get("P3V_ATTN_TILE128", "1") != "0":
+            tiles128 = T // 128 if T % 128 == 0 else 0
+            if tiles128 and tiles > 16 and tiles128 <= 48 and B * nh * tiles128 <= 2048 and tile128_ok:
                 # one 128-key tile per workgroup: every workgroup of the launch resident at once (3 per CU), half the
                 # partials to merge (k_attn_decode128).  Short caches keep 64-key tiles (more workgroups than CUs matters more)
                 n_split = tiles128
@@ -1073,44 +1056,57 @@ class Phi3VModel:
             else:
                 # (int8 KV: a tile is half the bytes and the single-wave kernel's 27.5 KB of LDS lets 5 workgroups share a CU,
                 #  so ~1280 workgroups keep as many bytes in flight: 3.68 -> 3.40 ms/step at 32k)
-                n_split = max(1, min(128, tiles, -(-(1280 if quantized else 768) // max(1, B * nh))))
-            if os.environ.get("P3V_ATTN_NSPLIT"):
-                n_split = int(os.environ["P3V_ATTN_NSPLIT"])
-            bufs["n_split"] = n_split
-            bufs["ws"] = ops.attention_ws(B, L, nh, hd, n_split, self.device)
+                n_split = max(1, min(128, tiles, -(-(1280 if st.quantized else 768) // max(1, B * nh))))
+            plan.n_split = n_split = n_split if forced_split is None else forced_split
+            plan.ws = ops.attention_ws(B, L, nh, hd, n_split, self.device)
             # in-launch split-KV merge (`merge_in_launch`): with the one-tile-per-workgroup plans, and with the
             # multi-tile streaming kernel when a head has at most 4 splits (B = 8: 3 splits -- the merge launch costs 4.9 us a
             # layer, the in-launch merge 0.5; with 24 splits at B = 1 / 32k the one merging workgroup per head is the slower
             # way: +1.6 % per step, +4.5 % at 8k)
-            mode = os.environ.get("P3V_ATTN_FUSED_MERGE", "1")
-            fused = (n_split in (tiles, tiles128) or n_split <= 4 or mode == "2") and n_split <= 48 and mode != "0"
+            merge = (n_split in (tiles, tiles128) or n_split <= 4 or merge_mode == "2") and n_split <= 48 and merge_mode != "0"
             # The merging workgroup of a (row, head) waits -- bounded, NaN-poisoned on expiry -- for partials of workgroups that
             # the hardware dispatches before it (linear order; observed, not documented).  When the whole grid is resident at once
-            # (128-key tiles: 3 workgroups per CU, 64-key: 5) nothing depends on that order.  A server takes the separate merge
-            # launch wherever the grid is larger (B = 8: +4.9 us per layer); one-shot generate() keeps the faster in-launch form,
-            # whose failure mode is loud (api._rows raises).  P3V_ATTN_FUSED_MERGE=2 forces it everywhere.
-            if serving and fused and mode != "2":
+            # (128-key tiles: 3 workgroups per CU, 64-key: 5) nothing depends on that order.  A plan for a long-lived server (a slot
+            # state of the continuous-batching engine, a server-owned model) takes the separate merge launch wherever the grid is
+            # larger (B = 8: +4.9 us per layer); one-shot generate() keeps the faster in-launch form, whose failure mode is loud
+            # (api._rows raises).  P3V_ATTN_FUSED_MERGE=2 forces it everywhere.
+            if (st.serving or self.serving) and merge and merge_mode != "2":
                 per_cu = 3 if n_split == tiles128 else 5
-                fused = B * nh * n_split <= per_cu * ops.device_props(torch.device(self.device).index or 0)["cu_count"]
-            if os.environ.get("P3V_PROFILING") == "1":           # (see _plan_fused_oproj)
-                fused = False
-            bufs["attn_merge"] = bool(fused)
+                merge = B * nh * n_split <= per_cu * ops.device_props(torch.device(self.device).index or 0)["cu_count"]
+            plan.attn_merge = bool(merge and not profiling)
+        if captured:
+            plan.past_lb = -1 if st.slots else int(st.offset)
+            plan.rope_cos = torch.empty((B, L, hd // 2), dtype=F32, device=self.device)
+            plan.rope_sin = torch.empty_like(plan.rope_cos)
+        # B = L = 1: attention + o_proj + residual as ONE launch per layer where the library takes the shape -- on bf16 or MLX 4-bit
+        # weights and a bf16 cache (k_attn_decode128_o / _o4), or on e4m3 weights and the int8 cache (config 5:
+        # k_attn_decode128_q8<true>); without the in-launch merge (long contexts, round 6) the MERGE launch carries the o_proj
+        # (k_attn_combine_o).  The launch of layer i re-arms the OTHER output buffer, so the two alternate cleanly only over an EVEN
+        # number of layers (an odd stack would hand layer 0 of the next step the buffer the last layer just filled: stale words read
+        # as "written").  It also needs the GPU to itself (every workgroup resident at once): not for a server-owned model.
+        o_key = "model.layers.0.self_attn.o_proj.weight"
+        if (fuse_o and B == 1 and L == 1 and fuse_o_ok and not profiling and cfg.num_hidden_layers % 2 == 0 and not self.serving   # (L = 1: the knobs were read)
+                and not self.adapters and not self._bank_has("self_attn.o_proj.weight") and (self._handle(o_key)[1] == "fp8") == bool(st.quantized)):
+            can = ops.attention_decode_q8_can_fuse_oproj if st.quantized else ops.attention_decode_can_fuse_oproj
+            # The merge forms to offer the library, the plan's own first.  Short contexts on the bf16 cache (64-key one-tile plans: the
+            # in-launch o_proj is for 128-key tiles): attention that only writes its partials + the merge launch carrying the o_proj
+            # beats attention with the in-launch merge + an o_proj launch (1.587 -> 1.570 ms per step at 128 keys, 1.662 -> 1.652 at
+            # 1000; with the int8 cache it loses: 1.165 -> 1.179 at 128 keys, so not there)
+            for merge in (plan.attn_merge, False) if plan.attn_merge and not st.quantized else (plan.attn_merge,):
+                if can(B, L, nh, hd, plan.n_split, T, cfg.hidden_size, merge):
+                    plan.attn_merge, plan.fuse_o = merge, True
+                    plan.o_f, plan.o_f2 = (torch.full((1, nh * hd), -1, dtype=torch.int16, device=self.device).view(BF16) for _ in range(2))
+                    break
+        return bufs
 
-    FAMILY_CHUNK = 256
-
-    def _family_plan(self, bufs, B, T):
-        """Split plan of the shared-prefix decode attention.  A family's whole splits below share_end are read once, by its
-        leader, and the up-to-one-chunk remainder by every member, so the chunk is small and fixed: 256 keys (four tiles of the
-        one-wave kernel per split), as many splits as the workspace and the merge launch take (128; longer caches get longer
-chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 keys, shared step, n = 4 / n = 8
-        (profiles/share_prefix_step_time.txt): 64 keys 2.4306 / 2.8538 ms, 128 keys 2.2363 / 2.4925 ms, 256 keys 2.1288 /
-        2.4102 ms -- fewer, longer single-wave workgroups and half the partials to merge outweigh the longer remainder.
-        FAMILY_CHUNK is the target (tools/share_step_time.py sets it on its model to time the alternatives)."""
-        nh, hd = self.cfg.num_attention_heads, self.hd
-        keys = int(self.FAMILY_CHUNK)
-        n_split = max(1, min(128, -(-T // keys)))
-        bufs["n_split"], bufs["attn_merge"], bufs["family"] = n_split, False, True
-        bufs["ws"] = ops.attention_ws(B, 1, nh, hd, n_split, self.device)
+    def _alloc_bufs(self, B, L):
+        cfg = self.cfg
+        nh, nkv, hd, H, I = cfg.num_attention_heads, cfg.num_key_value_heads, self.hd, cfg.hidden_size, cfg.intermediate_size
+        M, dev = B * L, self.device
+        return dict(
+            q=torch.empty((B, nh, L, hd), dtype=BF16, device=dev), o=torch.empty((M, nh * hd), dtype=BF16, device=dev),
+            qkv=torch.empty((M, (nh + 2 * nkv) * hd), dtype=BF16, device=dev), a=torch.empty((M, I), dtype=BF16, device=dev),
+            h=torch.empty((M, H), dtype=BF16, device=dev), plan=AttnPlan())
 
     def _layers(self, x, st, B, L, past, n_beam, bufs=None, d_past=None, last_only=False, step_begin=None):
         """Phi3DecoderLayer stack (phi.py:473-485).  `d_past` (device int32) makes every
@@ -1126,10 +1122,10 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         decode = L <= ops.L.DECODE_MAX_L                        # decode-shaped rows: one fused attention launch (+ merge) per layer
         if bufs is None:
             bufs = self._plan(st, B, L, fuse_o=decode and n_beam == 1, family=n_beam == 1)
-        q, o, qkv, a, h, n_split, ws = (bufs[k] for k in ("q", "o", "qkv", "a", "h", "n_split", "ws"))
-        fuse_o, attn_merge = bufs.get("fuse_o", False), bufs.get("attn_merge", False)
+        q, o, qkv, a, h, plan = (bufs[k] for k in ("q", "o", "qkv", "a", "h", "plan"))
+        n_split, ws, fuse_o, attn_merge = plan.n_split, plan.ws, plan.fuse_o, plan.attn_merge
         if decode and d_past is not None:                       # graph replay: rotation rows staged once per step by the caller
-            rc, rs, rb = bufs["rope_cos"], bufs["rope_sin"], L
+            rc, rs, rb = plan.rope_cos, plan.rope_sin, L
         elif decode:                                            # eager: views into the prompt tables at `past`
             rc, rs, rb = st.cos[:, past:], st.sin[:, past:], st.T
         if self._bank:                                          # adapter bank: one table entry per row of x (token rows share their request's)
@@ -1172,7 +1168,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                     self._proj(x, p + "self_attn.qkv_proj.weight", norm_w=w[p + "input_layernorm.weight"], out=qkv, h=h)
             o_i, kw_o = o, {}
             if fuse_o:                                          # (B = L = 1 plans only) + o_proj + residual in the attention's launch,
-                o_i, o_other = (bufs["o_f"], bufs["o_f2"]) if i % 2 == 0 else (bufs["o_f2"], bufs["o_f"])   # x += bf16(W_o . o)
+                o_i, o_other = (plan.o_f, plan.o_f2) if i % 2 == 0 else (plan.o_f2, plan.o_f)   # x += bf16(W_o . o)
                 kw_o = self._fused_oproj_kw(p + "self_attn.o_proj.weight", x, o_other)
             if st.quantized:
                 if decode:
@@ -1193,15 +1189,15 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                 ops.attention(q, o, B, L, nh, nkv, hd, scale, True, k_new=k_new, v_new=v_new, new_t=Lp, past=past,
                               k_past=st.k[i], v_past=st.v[i], past_t=st.Tp, past_div=n_beam, pad_len=st.pad_len,
                               pad_div=n_beam, ws=ws, n_split=n_split)
-            elif decode and bufs.get("family"):                 # a state with a family table: its prompts' K/V read once per family
+            elif decode and plan.family:                        # a state with a family table: its prompts' K/V read once per family
                 ops.attention_decode_family(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, nh, nkv, hd, scale,
-                                            past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split, st.family,
+                                            past if d_past is None else plan.past_lb, st.Tp, ws, n_split, st.family,
                                             family_host=st.family_host, pad_len=st.pad_len, d_past=d_past)
             elif decode:
                 # (captured step: `past` is read from d_past; the host value passed along is a LOWER BOUND of it -- the kernel fetches
                 #  tiles below it at once and lets the others wait for the length, so tiles beyond the live keys cost nothing)
                 ops.attention_decode(qkv, rc, rs, rb, st.k[i], st.v[i], o_i, B, L, nh, nkv, hd, scale,
-                                     past if d_past is None else bufs.get("past_lb", -1), st.Tp, ws, n_split,
+                                     past if d_past is None else plan.past_lb, st.Tp, ws, n_split,
                                      pad_len=st.pad_len, d_past=d_past, merge_in_launch=attn_merge, **kw_o)
             else:
                 # queries leave the RoPE kernel multiplied by scale * log2(e) (before their one rounding to bf16, as
@@ -1291,7 +1287,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         step was fed through each guided row's DFA and bans, in the adjusted rows, what the new state does not allow."""
         cfg, w, bufs, head = self.cfg, self.w, g["bufs"], "lm_head.weight"
         self._layers(g["x"], st, st.B, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
-                     step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["rope_cos"], sin_o=bufs["rope_sin"]))
+                     step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["plan"].rope_cos, sin_o=bufs["plan"].rope_sin))
         end = (g["next_tok"], g["tok"], g["history"], g["d_step"], g["d_past"], g["ticket"])
         if not kind.sampled:
             w_fold = self._fold_weight(head, st.B)
@@ -1394,10 +1390,9 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
                  logits=torch.empty((Lq, cfg.vocab_size), dtype=BF16, device=dev), n_replays=0)
         g["state"] = ops.spec_state(g, n_max, n_min)
         bufs = g["bufs"] = self._plan(st, 1, Lq, fuse_o=False, captured=True)
-        bufs["fuse_o"] = False                                   # (the fused attention + o_proj launch is B = L = 1 only)
 
         def step():
-            ops.spec_begin(g["tok"], w["model.embed_tokens.weight"], g["x"], st.cos, st.sin, g["d_past"], bufs["rope_cos"], bufs["rope_sin"])
+            ops.spec_begin(g["tok"], w["model.embed_tokens.weight"], g["x"], st.cos, st.sin, g["d_past"], bufs["plan"].rope_cos, bufs["plan"].rope_sin)
             self._layers(g["x"], st, 1, Lq, 0, 1, bufs=bufs, d_past=g["d_past"])
             self._proj(g["x"], "lm_head.weight", norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])
             ops.spec_end(g["logits"], g["state"])
@@ -1431,7 +1426,7 @@ chunks: 320 keys at 32k).  Always the separate merge launch.  Timed at 2,531 key
         self._sync_epoch(st)
         key = ("spec", K, n_max, n_min)
         g = st.graphs.get(key)
-        if g is not None and st.offset < g["bufs"]["past_lb"]:  # rewound below the captured lower bound (as _greedy_capture)
+        if g is not None and st.offset < g["bufs"]["plan"].past_lb:  # rewound below the captured lower bound (as _greedy_capture)
             g = None
         if g is None:
             g = st.graphs[key] = self._build_spec_graph(st, K, n_max, n_min)

@@ -525,6 +525,18 @@ def attention_decode_q8_can_fuse_oproj(B, Lq, nh, hd, n_split, cache_t, o_n, mer
     return bool(L.lib().p3v_attention_decode_q8_can_fuse_oproj(B, Lq, nh, hd, n_split, cache_t, o_n, int(bool(merge_in_launch))))
 
 
+def attention_decode_route(kv_int8, B, Lq, nh, hd, n_split, cache_t, merge_in_launch, o_proj=L.ATTN_O_NONE, o_n=0, q8_old=-1,
+                           attn_fo_map=-1, attn_fo_map_q8=-1, capacity=-1, cu_count=-1):
+    """What `attention_decode` (kv_int8: `attention_decode_q8`) launches for this call -> L.AttnRoute: kernel, grid, block, merge form,
+    fused-o_proj form (the can_fuse answer) and status (include/p3v.h: p3v_attention_decode_route).  A negative knob is the library's
+    setting; with `capacity` and `cu_count` given no device is asked."""
+    q = L.AttnRouteQuery(int(bool(kv_int8)), B, Lq, nh, hd, n_split, cache_t, int(bool(merge_in_launch)), o_proj, o_n, q8_old, attn_fo_map,
+                         attn_fo_map_q8, capacity, cu_count)
+    r = L.AttnRoute()
+    L.check(L.lib().p3v_attention_decode_route(C.byref(q), C.byref(r)), "attention_decode_route")
+    return r
+
+
 def attention_decode(qkv, cos_new, sin_new, rope_bstride, k_cache, v_cache, out, B, Lq, nh, nkv, hd, scale, past, cache_t, ws,
                      n_split, pad_len=None, d_past=None, merge_in_launch=False, o_proj_w=None, o_proj_x=None, o_rearm=None,
                      o_proj_sb=None):

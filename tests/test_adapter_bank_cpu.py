@@ -113,8 +113,9 @@ class SlotStub:
     def decode_graph(self, st):
         g = st.graphs.get("greedy")
         if g is None:
+            from phi_3_vision_mlx_amd.model import AttnPlan
             g = st.graphs["greedy"] = {"tok": torch.zeros(len(st.pad_len), dtype=torch.int32), "host_tok": None,
-                                       "bufs": {"ws": torch.full((8,), -1, dtype=torch.int32).view(torch.float32)}}
+                                       "bufs": {"plan": AttnPlan(ws=torch.full((8,), -1, dtype=torch.int32).view(torch.float32))}}
         return g
 
     def set_row_adapters(self, st, adapters, row0=0):

@@ -85,22 +85,22 @@ PLANS = {("bf16", 33280, 24): (1, False, "k_attn_decode_stream"), ("bf16", 8256,
 
 
 def test_case_table_is_the_models_split_plan(monkeypatch):
-    """Every (capacity, n_split) of the case table is what model._split_plan yields for the full 32-head model at that capacity
+    """Every (capacity, n_split) of the case table is what the split plan of model._plan yields for the full 32-head model at that capacity
     and batch, with the merge form named in the table, and reaches the kernel named there (the launcher's rule on (cap, n_split))."""
     from types import SimpleNamespace
 
-    from phi_3_vision_mlx_amd.model import Phi3VModel
+    from phi_3_vision_mlx_amd.model import AttnPlan, Phi3VModel
     for name in ("P3V_ATTN_TILE128", "P3V_ATTN_NSPLIT", "P3V_ATTN_FUSED_MERGE", "P3V_PROFILING"):
         monkeypatch.delenv(name, raising=False)
-    model = SimpleNamespace(cfg=SimpleNamespace(num_attention_heads=ap.FULL_NH), hd=ap.HD, device="cpu")
+    model = SimpleNamespace(cfg=SimpleNamespace(num_attention_heads=ap.FULL_NH), hd=ap.HD, device="cpu", serving=False, _alloc_bufs=lambda B, L: {"plan": AttnPlan()})
     assert {(c.kind, c.cap, c.n_split) for c in ap.CASES} == set(PLANS)
     for c in ap.CASES:
         plan_B, plan_fused, kernel = PLANS[c.kind, c.cap, c.n_split]
         assert (c.plan_B, c.plan_fused) == (plan_B, plan_fused) and c.kernel.split()[0] == kernel, c.id
     for (kind, cap, n_split), (plan_B, plan_fused, _) in PLANS.items():
-        bufs = {}
-        Phi3VModel._split_plan(model, bufs, plan_B, 1, cap, quantized=kind == "q8")
-        assert (bufs["n_split"], bufs["attn_merge"]) == (n_split, plan_fused), (kind, cap, bufs["n_split"], bufs["attn_merge"])
+        st = SimpleNamespace(Tp=cap, quantized=kind == "q8", serving=False, family=None)
+        plan = Phi3VModel._plan(model, st, plan_B, 1, fuse_o=False)["plan"]
+        assert (plan.n_split, plan.attn_merge) == (n_split, plan_fused), (kind, cap, plan.n_split, plan.attn_merge)
     # both merge forms wherever the launcher has both
     for key in (("bf16", 33280), ("bf16", 8256), ("bf16", 640), ("bf16", 6144), ("q8", 2688), ("q8", 1024)):
         assert {c.fused for c in ap.CASES if (c.kind, c.cap) == key} == {False, True}, key

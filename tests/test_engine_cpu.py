@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from phi_3_vision_mlx_amd.engine import ContinuousEngine, RegimeRouter
+from phi_3_vision_mlx_amd.model import AttnPlan
 
 EOS = 32007
 
@@ -40,7 +41,7 @@ class SlotStub:
         g = st.graphs.get("greedy")
         if g is None:
             g = st.graphs["greedy"] = {"tok": torch.zeros(len(st.pad_len), dtype=torch.int32), "host_tok": None,
-                                       "bufs": {"ws": torch.full((8,), -1, dtype=torch.int32).view(torch.float32)}}
+                                       "bufs": {"plan": AttnPlan(ws=torch.full((8,), -1, dtype=torch.int32).view(torch.float32))}}
         return g
 
     def _tok(self, st):
@@ -159,11 +160,11 @@ def test_negative_token_fails_that_row_only_and_rearms_the_workspace():
     e = ContinuousEngine(m, None, slots=2, window=4096)
     a, b = e.submit(req(20, 1), 30), e.submit(req(20, 2), 30)
     e.step()
-    e.st.graphs["greedy"]["bufs"]["ws"].view(torch.int32)[3] = 12345    # a stale partial a late split left behind
+    e.st.graphs["greedy"]["bufs"]["plan"].ws.view(torch.int32)[3] = 12345    # a stale partial a late split left behind
     m.poison_row = a.row
     e.step()
     assert a.done.is_set() and a.error is not None and -1 not in a.tokens
-    assert (e.st.graphs["greedy"]["bufs"]["ws"].view(torch.int32) == -1).all()
+    assert (e.st.graphs["greedy"]["bufs"]["plan"].ws.view(torch.int32) == -1).all()
     e.run_until_idle()
     assert b.error is None and b.tokens == solo(req(20, 2), 30)
 

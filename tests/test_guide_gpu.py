@@ -533,7 +533,7 @@ def test_replan_after_a_failed_step_rebuilds_the_states(monkeypatch, capsys):
         assert int(st.guide["rows"][0, 2]) == guide.replay_state(dfa, table, fed, EOS) == len(fed) + 1
         out = b"".join(table.bytes_of(t) for t in fed + seen[-1]).decode()
         assert re.fullmatch("[a-z ]{11}", out), out
-        return seen, st.graphs["greedy"]["bufs"].get("fuse_o", False)
+        return seen, st.graphs["greedy"]["bufs"]["plan"].fuse_o
 
     good, fused = run(None)
     assert fused and len(good) == 10

@@ -1179,6 +1179,35 @@ def test_q8_merge_launch_with_fused_fp8_oproj_is_bit_identical_to_three_launches
     assert not torch.isnan(x1.float()).any() and (x1.float() - x0.float()).abs().max().item() > 0.01
 
 
+def test_decode_route_on_this_device_is_what_the_can_fuse_functions_answer(ops):
+    """p3v_attention_decode_route asked with 'this device' (capacity and CU count negative): its fused form is what the two can_fuse
+    functions answer, on the fused cases of tests/golden/attn_decode_routes.json and up to the largest n_split either takes; and
+    the answers are the recorded device's wherever this one has its CU count."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attn_decode_routes.json")) as f:
+        rows = json.load(f)
+    device, cases = next(v for k, v in rows if k == "device"), [v for k, v in rows if k == "case" and v["o_proj"] and not v["knobs"]]
+    assert len(cases) == 36
+    fmt = {"bf16": ops.L.ATTN_O_BF16, "q4": ops.L.ATTN_O_Q4, "e4m3": ops.L.ATTN_O_F8}
+    shapes = {(c["kind"], c["o_proj"], c["B"], c["heads"], c["n_split"], c["cache_t"], m) for c in cases for m in (0, 1)}
+    shapes |= {(kind, o, 1, 32, n, 128 * n, 1) for kind, o in (("bf16", "bf16"), ("q8", "e4m3")) for n in range(13, 49)}
+    same_device = ops.device_props(0)["cu_count"] == device["cu_count"]
+    recorded = {(c["kind"], c["o_proj"], c["B"], c["heads"], c["n_split"], c["cache_t"], c["merge_in_launch"]): c for c in cases}
+    forms = set()
+    for key in sorted(shapes):
+        kind, o, B, nh, n_split, T, merge = key
+        can = ops.L.lib().p3v_attention_decode_q8_can_fuse_oproj if kind == "q8" else ops.L.lib().p3v_attention_decode_can_fuse_oproj
+        r = ops.attention_decode_route(kind == "q8", B, 1, nh, 96, n_split, T, merge, o_proj=fmt[o], o_n=3072)
+        assert r.fuse_form == can(B, 1, nh, 96, n_split, T, 3072, merge), key
+        assert (r.status == 0) == (r.fuse_form > 0), key
+        forms.add(r.fuse_form)
+        if same_device and key in recorded:
+            c = recorded[key]
+            assert r.status == c["status"] and (not c["launches"] or r.kernel_name.decode() == c["launches"][0][0]), key
+    assert forms == {0, 1, 2}
+
+
 def test_attention_beam_view(ops, orc):
     """n_beam: keys [0,past) come from cache row b//n_beam, new keys from a scratch (phi.py:523-527)."""
     Bc, nb, L, past, nh, hd = 2, 3, 4, 50, 2, 96

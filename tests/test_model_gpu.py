@@ -142,7 +142,7 @@ def test_generate_loop_survives_a_timed_out_fused_launch(monkeypatch, capsys):
         token = ops_mod.argmax(logits[:, -1].contiguous())[:, None]
         keep = Keep()
         out = api.greedy_loop(model, token, cache, 12, keep, lambda rows: False)
-        return keep.rows, out.reshape(-1).tolist(), cache[0].state.offset, cache[0].state.graphs["greedy"]["bufs"].get("fuse_o", False)
+        return keep.rows, out.reshape(-1).tolist(), cache[0].state.offset, cache[0].state.graphs["greedy"]["bufs"]["plan"].fuse_o
 
     from phi_3_vision_mlx_amd import ops as ops_mod
     model.serving = False
@@ -352,7 +352,7 @@ def test_split_merge_launch_is_a_tested_fallback_of_the_in_launch_merge(text, mo
         for _ in range(n - 1):
             lg, t = model.greedy_step(t, cache)
             toks.append(t.cpu().clone()), lgs.append(lg[:, -1].float().cpu().clone())
-        assert cache[0].state.graphs["greedy"]["bufs"]["attn_merge"] == (mode == "1")
+        assert cache[0].state.graphs["greedy"]["bufs"]["plan"].attn_merge == (mode == "1")
         runs[mode] = (torch.cat(toks, 1), torch.stack(lgs))
     assert torch.equal(runs["1"][0], runs["0"][0])
     assert_logits(runs["1"][1].flatten(0, 1), runs["0"][1].flatten(0, 1), "merge in launch vs merge launch", rel_atol=1e-2)
@@ -1377,7 +1377,7 @@ def test_fused_oproj_decode_needs_an_even_stack_and_an_exclusive_gpu(layers, ser
     for _ in range(8):                                       # graph replays (the second step onwards would read the stale buffer)
         lg, t = model.greedy_step(t, cache)
         got.append((lg.clone(), t.clone()))
-    fused = cache[0].state.graphs["greedy"]["bufs"]["fuse_o"]
+    fused = cache[0].state.graphs["greedy"]["bufs"]["plan"].fuse_o
     assert fused == (layers % 2 == 0 and not serving)
     monkeypatch.setenv("P3V_ATTN_FUSE_OPROJ", "0")
     _, cache2 = model(input_ids=ids, max_tokens=12)

@@ -520,7 +520,7 @@ def test_replan_after_a_failed_step_rebuilds_the_tables(monkeypatch, capsys):
         fed = token.reshape(-1).cpu().tolist() + [r[0] for r in seen[:-1]]
         table = _u32_of(st.penalty["seen"]).reshape(-1)
         assert np.array_equal(table, penalties.seen_table(ids[0], fed, table.size))
-        return seen, st.graphs["greedy"]["bufs"].get("fuse_o", False)
+        return seen, st.graphs["greedy"]["bufs"]["plan"].fuse_o
 
     good, fused = run(None)
     assert fused and len(good) == 10

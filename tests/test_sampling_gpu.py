@@ -231,7 +231,7 @@ def test_sampled_loop_survives_a_timed_out_fused_launch(monkeypatch, capsys):
         token = ops.sample(logits[:, -1, :], sampling.pack(rows, 0).cuda())[:, None]
         seen = []
         out = api.greedy_loop(model, token, cache, 12, lambda r: seen.append(list(r)), lambda r: False, sampling=rows)
-        return seen, out.reshape(-1).tolist(), cache[0].state.offset, cache[0].state.graphs["greedy"]["bufs"].get("fuse_o", False)
+        return seen, out.reshape(-1).tolist(), cache[0].state.offset, cache[0].state.graphs["greedy"]["bufs"]["plan"].fuse_o
 
     model.serving = False
     good, last, off, fused = run(None)

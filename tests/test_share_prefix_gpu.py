@@ -32,9 +32,9 @@ def _bits(t):
 def _dead_end(model, st):
     """Columns [0, dead_end) of a follower are not read: the whole family-plan splits below share_end."""
     from phi_3_vision_mlx_amd import ops
-    plan = {}
-    model._family_plan(plan, st.B, st.Tp)
-    chunk = ops.attention_family_chunk(st.Tp, plan["n_split"])
+    plan = model._plan(st, st.B, 1, fuse_o=False)["plan"]
+    assert plan.family
+    chunk = ops.attention_family_chunk(st.Tp, plan.n_split)
     (rows, share_end), = st.families
     return share_end // chunk * chunk, chunk
 
@@ -81,7 +81,7 @@ def test_a_family_equals_the_cleared_table_bit_for_bit(temperature):
     b = _memo(("cleared", temperature), share=True, table="cleared", temperature=temperature)
     st = a["st"]
     assert st.family is not None and len(st.families) == 1 and b["st"].family is not None and b["st"].families == []
-    assert st.graphs["greedy"]["bufs"].get("family") and b["st"].graphs["greedy"]["bufs"].get("family")
+    assert st.graphs["greedy"]["bufs"]["plan"].family and b["st"].graphs["greedy"]["bufs"]["plan"].family
     dead_end, chunk = _dead_end(model, st)
     assert dead_end >= 2048 and dead_end >= 8 * chunk, (dead_end, chunk)   # the comparison is about many shared splits
     assert a["toks"] == b["toks"]
@@ -104,7 +104,7 @@ def test_share_prefix_against_the_unshared_plan():
     the unshared run's tokens.  At most a quarter of the steps may be too close to call: the unshared run alone decides which."""
     g, model, proc, _ = _serve()
     ref = _memo(("unshared", 0.0), share=False, temperature=0.0)
-    assert ref["st"].family is None and not ref["st"].graphs["greedy"]["bufs"].get("family")
+    assert ref["st"].family is None and not ref["st"].graphs["greedy"]["bufs"]["plan"].family
     got = _run(share=True, temperature=0.0, force=ref["toks"][:-1])
     unclear = 0
     for step, (x, y) in enumerate(zip(got["lgs"], ref["lgs"])):
@@ -397,7 +397,7 @@ def test_defaults_launch_what_the_parent_launched(monkeypatch):
     out_f, n_f, st_f = go(share_prefix=False)
     out_s, n_s, st_s = go(share_prefix=True)
     assert n_d == n_f and out_d == out_f and "p3v_attention_decode_family" not in n_d and n_d["p3v_kv_fork"] == 1
-    assert st_d.family is None and st_d.family_host is None and st_d.families == [] and not st_d.graphs["greedy"]["bufs"].get("family")
+    assert st_d.family is None and st_d.family_host is None and st_d.families == [] and not st_d.graphs["greedy"]["bufs"]["plan"].family
     assert st_s.family is not None and n_s["p3v_attention_decode_family"] == n_d["p3v_attention_decode"] - n_s.get("p3v_attention_decode", 0)
     assert {k: v for k, v in n_s.items() if not k.startswith("p3v_attention_decode")} == \
         {k: v for k, v in n_d.items() if not k.startswith("p3v_attention_decode")}

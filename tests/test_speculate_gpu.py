@@ -354,7 +354,7 @@ def test_captured_step_equals_eager_step_bit_for_bit_and_rebuild_after_rewind():
     # rewind below the captured lower bound: the capture is rebuilt (as greedy_step rebuilds), and the run goes on correctly
     S = len(ids)
     g_old = st.graphs["spec"]
-    assert g_old["bufs"]["past_lb"] == S
+    assert g_old["bufs"]["plan"].past_lb == S
     token, cache = _prefill(model, inputs, len(fix), K)
     st = cache[0].state
     tok = token
@@ -362,12 +362,12 @@ def test_captured_step_equals_eager_step_bit_for_bit_and_rebuild_after_rewind():
         _, tok = model.greedy_step(tok, cache)
     torch.cuda.synchronize()
     g1 = model.spec_start(cache, ids + fix[:6], tok, K)
-    assert g1["bufs"]["past_lb"] == S + 6
+    assert g1["bufs"]["plan"].past_lb == S + 6
     model.spec_step(cache, K)
     model.spec_sync(cache)
     st.offset = S + 2
     g2 = model.spec_start(cache, ids + fix[:2], torch.tensor([[fix[2]]], dtype=I32), K)
-    assert g2 is not g1 and g2["bufs"]["past_lb"] == S + 2
+    assert g2 is not g1 and g2["bufs"]["plan"].past_lb == S + 2
     out = fix[:3]
     while len(out) < n_cmp:
         model.spec_step(cache, K)

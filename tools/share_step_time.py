@@ -3,8 +3,8 @@ this file).
 
 Full-size synthetic model, bf16 weights and cache.  For each prompt length (512, 2,531 and 32,768 keys) one text prompt is prefilled
 once and its B = 1 state forked (model.fork_state) into B = n states, n = 2, 4, 8, 16 where memory allows (the cleared arm is left out where a third state does not fit):
-    unshared  fork_state(n)              the B = n sampled step as without the feature: p3v_attention_decode under model._split_plan
-    cleared   fork_state(n, share=True), then set_families(st, []): the family launch under model._family_plan with a table of
+    unshared  fork_state(n)              the B = n sampled step as without the feature: p3v_attention_decode under the split plan of model._plan
+    cleared   fork_state(n, share=True), then set_families(st, []): the family launch under the family plan of model._plan with a table of
               single rows -- every row reads its own copy: what the PLAN costs or gains without any sharing
     shared    fork_state(n, share=True)  the same launch, the family registered: whole splits below share_end read once
 The three captured sampled steps (temperature 0.8, seeds s + j) are replayed in turn, `--replays` replays per timing between two
@@ -77,9 +77,9 @@ def main():
             return None
         finally:
             model.FAMILY_CHUNK = default
-        bufs = st.graphs["greedy"]["bufs"]
-        plan = f"{bufs['n_split']} splits of {ops.attention_family_chunk(st.Tp, bufs['n_split'])} keys, " + \
-               ("family launch + merge launch" if bufs.get("family") else "merge in launch" if bufs.get("attn_merge") else "merge launch")
+        p = st.graphs["greedy"]["bufs"]["plan"]
+        plan = f"{p.n_split} splits of {ops.attention_family_chunk(st.Tp, p.n_split)} keys, " + \
+               ("family launch + merge launch" if p.family else "merge in launch" if p.attn_merge else "merge launch")
 
         def replay():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -121,8 +121,7 @@ def main():
                 arms["cleared"] = third
             del third
             st = arms["shared"][1]
-            bufs = st.graphs["greedy"]["bufs"]
-            chunk = ops.attention_family_chunk(st.Tp, bufs["n_split"])
+            chunk = ops.attention_family_chunk(st.Tp, st.graphs["greedy"]["bufs"]["plan"].n_split)
             saved = (n - 1) * (keys // chunk) * chunk * TOKEN_BYTES
             print(f"  n = {n:2d}: byte model: shared reads {saved / 1e9:6.2f} GB less than cleared = {saved / HBM * 1e3:7.4f} ms at 7.2 TB/s")
             r = report(keys, n, arms)
@@ -131,7 +130,7 @@ def main():
                   f"{'shared WINS by more than the spread' if gain > spread else 'shared LOSES by more than the spread' if -gain > spread else 'inside the spread'};"
                   + (f" cleared - shared = {(r['cleared'][0] - r['shared'][0]) * 1e3:+9.1f} us = {100 * (r['cleared'][0] - r['shared'][0]) / (saved / HBM * 1e3 + 1e-12):4.0f} % of the byte model"
                      if "cleared" in r else " cleared: not measured (memory)"))
-            del arms, st, bufs
+            del arms, st
             torch.cuda.empty_cache()
             if a.chunks and keys == 2531 and n in (4, 8):
                 alt = {f"shared, chunk {c}": arm(st1, logits, n, "shared", chunk=int(c)) for c in a.chunks.split(",")}
