@@ -882,6 +882,51 @@ int p3v_spec_end(const uint16_t* logits, const p3v_spec_state_t* state /* host *
 int p3v_ngram_propose(const int32_t* ctx, int n, int K, int n_max, int n_min, int vocab, int32_t* draft, int32_t* n_draft,
                       void* stream);
 
+/* ---- embeddings: final RMSNorm + pooling + L2 normalisation, fp32 out (added after round 6, no version change).
+ * x [B, L, hidden] bf16 is the last layer's output BEFORE model.norm, w [hidden] bf16, start [B] int32 in device memory the
+ * count of left-pad columns of each row (0 <= start[b] < L; read in P3V_POOL_MEAN only, values outside are clamped), out
+ * [B, hidden] fp32.  The rule:
+ *   y_t   = the bf16 row p3v_rmsnorm writes for x[b, t]: the same per-lane sum of squares, the same two roundings.
+ *   LAST  : p = f32(y_{L-1}).  Row L - 1 is the only row read.
+ *   MEAN  : p_j = (sum over t in [start_b, L) of f32(y_{t,j})) / (L - start_b): fp32 sums, ONE fp32 division.  The order of
+ *           the sum is fixed by (start_b, L): sixteen partial sums over t = start_b + v (mod 16), added in the order of v.
+ *   normalize = 1: e = p / sqrtf(sum_j p_j^2) (fp32 sum, IEEE square root and division).  A zero row stays zero, a NaN
+ *           reaches every element of its row.
+ * No floating-point atomics: row b's output bits depend on x[b], w and start[b] alone -- not on B, the neighbours or a
+ * second launch.  hidden: every size p3v_rmsnorm takes (a multiple of 8), and multiples of 4 (8-byte loads; the rule is
+ * the same with the row's last half chunk zero-extended).  ws: p3v_embed_pool_ws_bytes(B, L, hidden, mode) bytes of device
+ * scratch (one fp32 per normalised row).  Three launches at most, nothing allocated, nothing synchronised.
+ * Measured (profiles/embed_time.txt): a prefill that ends here costs 0.995 - 0.999x (LAST) / 1.007 - 1.015x (MEAN) the plain prefill.
+ * P3V_ERR_ARG, nothing launched: a null x / w / out / ws, a null start in MEAN, B outside 1..65535, L < 1, hidden % 4,
+ * pointers not 16-byte aligned (8 for hidden % 8 == 4), an unknown mode, normalize outside {0, 1}, a short workspace. */
+#define P3V_POOL_LAST 0
+#define P3V_POOL_MEAN 1
+int64_t p3v_embed_pool_ws_bytes(int B, int L, int hidden, int mode);
+int p3v_embed_pool(const uint16_t* x, const uint16_t* w, const int32_t* start, float* out, int B, int L, int hidden, float eps,
+                   int mode, int normalize, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- retrieval: scores of Q queries against N stored vectors and the k best per query (added after round 6, no version
+ * change).  index [N, D] bf16 contiguous (N >= 0: the live rows of a possibly larger allocation), queries [Q, D] bf16,
+ * idx [Q, k] int32, score [Q, k] fp32.  1 <= Q <= 16, 1 <= k <= P3V_SIM_TOPK_MAX, D % 8 == 0, 8 <= D <= 8192.  The rule:
+ *   s(i, q) = sum_j f32(index[i, j]) * f32(queries[q, j]): exact products, an fp32 sum whose order is the kernel's own but
+ *   FIXED per row -- 32-wide blocks of D in ascending order, each one v_mfma_f32_16x16x32_bf16 into the same accumulator
+ *   (a last partial block is zero-extended).  s(i, q) has the same bits whatever N, Q, k or the split over workgroups.
+ *   Output row q = the first k of a stable sort of the rows by (-s, i): ties go to the lower index, -0 == +0 (reported as
+ *   +0), a NaN score sorts last (reported as a quiet NaN).  Where N < k the tail is idx -1 / score -inf.
+ * Every index byte is read once per launch whatever Q is; the [Q, N] score matrix is never written.  Two launches: one
+ * workgroup per rows_per_wg rows keeps its k candidates per query, one workgroup per query merges them out of ws
+ * (p3v_sim_topk_ws_bytes(N, Q, k, D) bytes of device scratch, 8-byte aligned; may be NULL when that is 0).
+ * p3v_sim_topk_plan states the split: workgroup g scores rows [g * rows_per_wg, min(N, (g + 1) * rows_per_wg)), n_wg of
+ * them (0 for N = 0), each wave row_tile rows at a time.  It reads no device property: the same answer everywhere.
+ * Measured at D = 3072 (profiles/embed_time.txt): N = 2^20, Q = 1: 1.09 ms at k = 1 (5.9 TB/s), 1.17 ms at k = 32; Q = 16:
+ * 1.40 / 1.52 / 1.76 ms at k = 1 / 10 / 32 -- the candidate lists, not the stream, are what Q and k cost.
+ * P3V_ERR_ARG, nothing launched: a shape outside the limits, null or misaligned (16 bytes) pointers, a short workspace. */
+#define P3V_SIM_TOPK_MAX 32
+int p3v_sim_topk_plan(int N, int Q, int k, int D, int* rows_per_wg /* host */, int* n_wg /* host */, int* row_tile /* host */);
+int64_t p3v_sim_topk_ws_bytes(int N, int Q, int k, int D);
+int p3v_sim_topk(const uint16_t* index, const uint16_t* queries, int32_t* idx, float* score, int N, int Q, int k, int D,
+                 void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- hipGraph helpers: capture a sequence of the launches above and replay it */
 int p3v_graph_begin(void* stream);
 int p3v_graph_end(void* stream, void** graph_exec_out /* host */);

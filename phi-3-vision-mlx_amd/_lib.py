@@ -181,6 +181,8 @@ SPEC_CTL_N, SPEC_CTL_NDRAFT, SPEC_CTL_FORCED, SPEC_CTL_REPLAY, SPEC_CTL_NLIMIT, 
 KV_COPY_MAX_JOBS = 4                             # P3V_KV_COPY_MAX_JOBS
 LORA_SLICE_K, LORA_MAX_RANK = 256, 64            # P3V_LORA_SLICE_K; largest rank of p3v_lora_* (include/p3v.h)
 SAMPLE_MAX_N, SAMPLE_MAX_ROWS = 32768, 1024      # p3v_sample / p3v_sample_step_end: larger -> P3V_ERR_UNSUPPORTED
+POOL_LAST, POOL_MEAN = 0, 1                       # P3V_POOL_LAST / P3V_POOL_MEAN
+SIM_TOPK_MAX, SIM_TOPK_MAX_Q = 32, 16             # P3V_SIM_TOPK_MAX; queries of one p3v_sim_topk launch
 # name -> (restype, argtypes); must list every symbol include/p3v.h declares
 SIGNATURES = {
     "p3v_version": (i32, []),
@@ -255,6 +257,11 @@ SIGNATURES = {
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "p3v_kv_copy": (i32, [C.POINTER(KvCopyJob), i32, i32, i32, i32, i32, vp]),
     "p3v_kv_fork": (i32, [C.POINTER(KvFork), i32, i32, i32, i32, vp]),                   # added after round 6, no version change
+    "p3v_embed_pool": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, i64, vp]),   # added after round 6, no version change
+    "p3v_embed_pool_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "p3v_sim_topk": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),               # added after round 6, no version change
+    "p3v_sim_topk_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "p3v_sim_topk_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "p3v_graph_begin": (i32, [vp]),
     "p3v_graph_end": (i32, [vp, C.POINTER(vp)]),
     "p3v_graph_launch": (i32, [vp, vp]),

@@ -38,6 +38,7 @@ from .steps import kind_for
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
 from .weights import load_adapter, load_safetensors_dir, resolve_adapter, synth_weights
+from .retrieval import VDB  # noqa: F401
 
 PATH_ADAPTERS = "adapters"
 PATH_ORIGINAL_PHI3_VISION = "models/phi3_v"
@@ -857,6 +858,57 @@ def score(prompt, images=None, preload=None, top=0, apply_chat_template=True):
     model, processor = preload
     prompt, images = _apply_chat_template(prompt, images, False, apply_chat_template)
     out = _score(model, processor, prompt, images, top)
+    return out if isinstance(prompt, list) else out[0]
+
+
+# ----------------------------------------------------------------------------- embed
+POOLINGS = ("last", "mean")
+
+
+def check_pooling(pooling):
+    if pooling not in POOLINGS:
+        raise ValueError(f"pooling must be 'last' or 'mean', got {pooling!r}")
+    return pooling
+
+
+def _embed_inputs(model, dict_input, pooling, normalize, kw_adapter=None):
+    kw = {k: v for k, v in dict_input.items() if k in ("input_ids", "pixel_values", "image_sizes", "positions", "pids", "mask")}
+    return model.embed(**kw, pooling=pooling, normalize=normalize, **(kw_adapter or {}))
+
+
+def prompt_token_counts(dict_input):
+    """Live tokens of every row of a processor result (the left padding of a batch does not count)."""
+    ids = np.asarray(dict_input["input_ids"])
+    ids = ids[None] if ids.ndim == 1 else ids
+    if dict_input.get("mask") is None:
+        return [int(ids.shape[1])] * ids.shape[0]
+    return [int(n) for n in (np.asarray(dict_input["mask"]).reshape(ids.shape) != 0).sum(1)]
+
+
+def embed(prompt, images=None, preload=None, pooling="last", normalize=True, adapter=None, apply_chat_template=True, info=None):
+    """The prompt as a vector (retrieval, reranking, deduplication, classification heads): the final-normed hidden state of the
+    last token (pooling="last", what embedding fine-tunes of this architecture pool) or its mean over the prompt's tokens
+    ("mean"), L2-normalised unless normalize=False (include/p3v.h: p3v_embed_pool).  One prefill without lm_head; a list of prompts
+    runs as one left-padded batch.  adapter: as in generate.  info (a dict) receives "prompt_tokens", one count per prompt.
+    Returns np.float32 [H] for one prompt, [n, H] for a list."""
+    check_pooling(pooling)
+    if images is not None and isinstance(prompt, list):
+        raise ValueError("Images cannot be provided when prompt is a list")
+    if preload is None:
+        preload = load()
+    model, processor = preload
+    kw_adapter = {}
+    if adapter is not None:
+        from .engine import _check_adapter, adapter_list
+        names = adapter_list(adapter, len(prompt) if isinstance(prompt, list) else 1)
+        for a in names:
+            _check_adapter(a, list(getattr(model, "adapter_names", None) or []))
+        kw_adapter = {"row_adapters": names}
+    prompt, images = _apply_chat_template(prompt, images, False, apply_chat_template)
+    dict_input = processor(prompt, images)
+    if info is not None:
+        info["prompt_tokens"] = prompt_token_counts(dict_input)
+    out = _embed_inputs(model, dict_input, pooling, bool(normalize), kw_adapter).cpu().numpy()
     return out if isinstance(prompt, list) else out[0]
 
 

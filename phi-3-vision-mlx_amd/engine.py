@@ -147,6 +147,27 @@ def make_family(head, n, m):
     return head
 
 
+class EmbedJob:
+    """Handle of `ContinuousEngine.embed`: wait on `.done`, then read `.result` (np.float32 [B, H]) or `.error`; `cancel()` drops
+    a job the engine has not started."""
+    __slots__ = ("inputs", "pooling", "normalize", "adapter", "result", "error", "done", "cancelled")
+
+    def __init__(self, inputs, pooling, normalize, adapter):
+        self.inputs, self.pooling, self.normalize, self.adapter = inputs, pooling, bool(normalize), adapter
+        self.result, self.error, self.cancelled = None, None, False
+        self.done = threading.Event()
+
+    def cancel(self):
+        self.cancelled = True
+
+    def fail(self, error):
+        self.error = error
+        self.done.set()
+
+
+EMBED_INPUT_KEYS = ("input_ids", "pixel_values", "image_sizes", "positions", "pids", "mask")
+
+
 def generate(self, prompts, images=None, max_tokens=512, timeout=600.0, sampling=None, adapter=None, cache_prompt=None, info=None,
              logprobs=None, penalties=None, n=None, best_of=None, guide=None):
     """Text in, text out (what the HTTP backend calls): the `generate` of ContinuousEngine, RegimeRouter and fleet.EngineFleet."""
@@ -169,6 +190,7 @@ class ContinuousEngine:
         self.long_rope = window > ROPE_WINDOW
         self.rows = [None] * slots                               # row -> active Request
         self.waiting = collections.deque()
+        self.embed_jobs = collections.deque()                    # EmbedJob handles, served between two steps (`embed`)
         self.lock = threading.Lock()
         self.steps = 0                                           # decode steps replayed (observability / tests)
         self.joined_mid_flight = 0                               # requests admitted while other rows were generating
@@ -259,7 +281,44 @@ class ContinuousEngine:
                 self.waiting.append(r)
         return r
 
+    def embed(self, inputs, pooling="last", normalize=True, adapter=None):
+        """inputs: a `processor(text[, images])` result, B >= 1 (a left-padded batch carries its mask).  Returns an EmbedJob.  The
+        stepping thread serves it between two decode steps, before it admits new requests, through `model.embed` on the job's
+        own transient state: the slot state and its captures are untouched, the rows in flight do not see it.  adapter: None, a
+        name, or one name / None per row.  A prompt above the engine's window, an unknown pooling or adapter: ValueError, here."""
+        from .api import check_pooling
+        check_pooling(pooling)
+        ids = np.asarray(inputs["input_ids"])
+        B, S = (1, ids.shape[-1]) if ids.ndim == 1 else ids.shape
+        if S < 1 or S > self.window:
+            raise ValueError(f"embed: a prompt of {S} tokens is outside this engine's window of {self.window}")
+        names = adapter_list(adapter, B)
+        for a in names:
+            _check_adapter(a, self.adapter_names())
+        if self.dead is not None:
+            raise RuntimeError(f"engine is down: {self.dead!r}")
+        job = EmbedJob(inputs, pooling, normalize, None if adapter is None else names)
+        with self.lock:
+            self.embed_jobs.append(job)
+        return job
+
     # ---- engine side (ONE thread)
+    def _serve_embeds(self):
+        while self.embed_jobs:
+            with self.lock:
+                job = self.embed_jobs.popleft()
+            if job.cancelled:
+                job.done.set()
+                continue
+            try:
+                kw = {k: v for k, v in job.inputs.items() if k in EMBED_INPUT_KEYS}
+                if job.adapter is not None:
+                    kw["row_adapters"] = job.adapter
+                job.result = self.model.embed(**kw, pooling=job.pooling, normalize=job.normalize).cpu().numpy()
+            except Exception as e:                              # noqa: BLE001 -- reported to the job, the engine lives on
+                job.error = e
+            job.done.set()
+
     def _active(self):
         return [r for r in self.rows if r is not None]
 
@@ -314,6 +373,9 @@ class ContinuousEngine:
     def _fail_all(self, error):
         with self.lock:
             waiting, self.waiting = list(self.waiting), collections.deque()
+        if self.dead is not None:                                # (nobody will serve them any more)
+            while self.embed_jobs:
+                self.embed_jobs.popleft().fail(error)
         for r in self._active() + [x for h in waiting for x in h.members]:   # (a waiting head: its whole family)
             r.error = error
             if r.row is not None and self.rows[r.row] is r:
@@ -619,6 +681,7 @@ class ContinuousEngine:
         """Admit what fits, then one decode step for every active row.  Returns the number of active rows."""
         if self.dead is not None:
             return 0
+        self._serve_embeds()
         self._admit()
         for r in self._active():
             if r.cancelled:
@@ -679,7 +742,7 @@ class ContinuousEngine:
         """Engine thread body: step while there is work, nap when idle."""
         _set_device(self.model.device)
         while not stop_event.is_set():
-            if not self.safe_step() and not self.waiting:
+            if not self.safe_step() and not self.waiting and not self.embed_jobs:
                 stop_event.wait(idle_sleep)
 
     generate = generate

@@ -1783,6 +1783,39 @@ class Phi3VModel:
         logits = self._proj(x, "lm_head.weight", norm_w=w["model.norm.weight"])
         return logits.view(B, -1, cfg.vocab_size), cache
 
+    @_on_device
+    def embed(self, input_ids, pixel_values=None, image_sizes=None, positions=None, pids=None, mask=None, pooling="last",
+              normalize=True, row_adapters=None):
+        """The prompt as a vector: a prefill that ends in p3v_embed_pool (include/p3v.h) instead of lm_head -> fp32 [B, H] on the
+        device.  pooling="last": the final-normed hidden state of the last position (the final layer builds one row per prompt,
+        as generate's prefill does); "mean": its mean over the live positions, the left-pad counts taken from `mask`.
+        normalize: divided by its L2 norm.  The KV state is the call's own (max_tokens = 0) and is dropped on return; the captured
+        short-prompt prefill is bypassed, as full_logits bypasses it.  `row_adapters` as in __call__."""
+        cfg, w = self.cfg, self.w
+        if pooling not in ops.POOLING:
+            raise ValueError(f"pooling must be 'last' or 'mean', got {pooling!r}")
+        if torch.is_tensor(input_ids):
+            ids = input_ids.to(self.device, I32)
+        else:
+            ids = torch.as_tensor(np.asarray(input_ids).astype(np.int32)).to(self.device)
+        if ids.dim() == 1:
+            ids = ids[None]
+        ids = ids.contiguous()
+        B, L = ids.shape
+        st = self._new_state(B, L, 0, pids, mask)
+        if row_adapters is not None:
+            self.set_row_adapters(st, row_adapters)
+        x = ops.embed_gather(ids.view(-1), w["model.embed_tokens.weight"])
+        if pixel_values is not None and self.vision:
+            self.vision_embed(x, pixel_values, image_sizes, positions, L)
+        last = pooling == "last"
+        x = self._layers(x, st, B, L, 0, 1, last_only=last)
+        start = None
+        if not last and mask is not None:
+            pad = (np.asarray(mask.cpu() if torch.is_tensor(mask) else mask).reshape(B, L) == 0).sum(1)
+            start = torch.as_tensor(pad.astype(np.int32)).to(self.device)
+        return ops.embed_pool(x.view(B, -1, cfg.hidden_size), w["model.norm.weight"], cfg.rms_norm_eps, start, pooling, normalize)
+
     # ------------------------------------------------------------------ captured prefill of short text prompts
     PREFILL_GRAPH_MAX_S = 512
     PREFILL_GRAPH_ENTRIES = 4

@@ -795,6 +795,66 @@ def topk(x2d, k):
     return out
 
 
+POOLING = {"last": L.POOL_LAST, "mean": L.POOL_MEAN}
+
+
+def embed_pool(x, w, eps, start=None, pooling="last", normalize=True, out=None):
+    """Final RMSNorm + pooling + L2 normalisation (include/p3v.h: p3v_embed_pool): x bf16 [B, L, H] before model.norm, w bf16 [H],
+    start int32 [B] left-pad counts (None: no padding) -> fp32 [B, H].  "last" reads row L - 1 only."""
+    if pooling not in POOLING:
+        raise ValueError(f"pooling must be 'last' or 'mean', got {pooling!r}")
+    _chk(x, BF16, "x"), _chk(w, BF16, "w")
+    if x.dim() != 3 or w.shape != (x.shape[-1],):
+        raise ValueError(f"embed_pool: x must be [B, L, H] and w [H], got {tuple(x.shape)} and {tuple(w.shape)}")
+    B, Lq, H = x.shape
+    if start is None:
+        start = torch.zeros((B,), dtype=I32, device=x.device)
+    _chk(start, I32, "start")
+    if start.shape != (B,):
+        raise ValueError(f"embed_pool: start must be [{B}], got {tuple(start.shape)}")
+    out = torch.empty((B, H), dtype=F32, device=x.device) if out is None else _chk(out, F32, "out")
+    if out.shape != (B, H):
+        raise ValueError(f"embed_pool: out must be [{B}, {H}], got {tuple(out.shape)}")
+    mode = POOLING[pooling]
+    nbytes = L.lib().p3v_embed_pool_ws_bytes(B, Lq, H, mode)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=F32, device=x.device)
+    L.check(L.lib().p3v_embed_pool(_p(x), _p(w), _p(start), _p(out), B, Lq, H, float(eps), mode, int(bool(normalize)), _p(ws),
+                                   nbytes, _stream()), "embed_pool")
+    return out
+
+
+def sim_topk_plan(N, Q, k, D):
+    """(rows per workgroup, workgroups, rows of one wave's pass) of a `sim_topk` launch.  Host arithmetic only."""
+    a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().p3v_sim_topk_plan(int(N), int(Q), int(k), int(D), C.byref(a), C.byref(b), C.byref(c)), "sim_topk_plan")
+    return a.value, b.value, c.value
+
+
+def sim_topk(index, queries, k, n=None, out=None):
+    """The k best rows of index[:n] (bf16 [>= n, D]) for each of <= 16 bf16 queries [Q, D], by (-score, row): (idx int32 [Q, k],
+    score fp32 [Q, k]); fp32 scores, the score matrix never written (include/p3v.h: p3v_sim_topk).  out: an (idx, score) pair."""
+    _chk(index, BF16, "index"), _chk(queries, BF16, "queries")
+    if index.dim() != 2 or queries.dim() != 2 or index.shape[1] != queries.shape[1]:
+        raise ValueError(f"sim_topk: index [N, D] and queries [Q, D], got {tuple(index.shape)} and {tuple(queries.shape)}")
+    N = index.shape[0] if n is None else int(n)
+    Q, D = queries.shape
+    if not 0 <= N <= index.shape[0]:
+        raise ValueError(f"sim_topk: n = {N} outside the index's {index.shape[0]} rows")
+    if not 1 <= k <= L.SIM_TOPK_MAX:
+        raise ValueError(f"sim_topk: k = {k} outside 1..{L.SIM_TOPK_MAX} (P3V_SIM_TOPK_MAX)")
+    if not 1 <= Q <= L.SIM_TOPK_MAX_Q:
+        raise ValueError(f"sim_topk: {Q} queries, one launch takes 1..{L.SIM_TOPK_MAX_Q}")
+    idx, score = out if out is not None else (torch.empty((Q, k), dtype=I32, device=queries.device),
+                                              torch.empty((Q, k), dtype=F32, device=queries.device))
+    _chk(idx, I32, "idx"), _chk(score, F32, "score")
+    if idx.shape != (Q, k) or score.shape != (Q, k):
+        raise ValueError(f"sim_topk: idx and score must be [{Q}, {k}]")
+    nbytes = L.lib().p3v_sim_topk_ws_bytes(N, Q, k, D)
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=queries.device)
+    L.check(L.lib().p3v_sim_topk(_p(index), _p(queries), _p(idx), _p(score), N, Q, k, D, _p(ws), nbytes, _stream()), "sim_topk")
+    return idx, score
+
+
 def gemv_step_begin(tok, table, x_out, cos_t, sin_t, d_past, cos_out, sin_out, w, norm_w, norm_eps, out):
     """The step's FIRST projection with `step_begin` in its prologue (include/p3v.h: p3v_gemv_step): out = W . RMSNorm(table[tok]),
     x_out = table[tok], rotation rows of *d_past staged.  False (nothing launched) where the library keeps the separate launch."""

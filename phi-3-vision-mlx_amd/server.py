@@ -52,6 +52,14 @@
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
      allow-listed directory / host list.  Images are always fetched AND decoded in the HTTP handler thread, with a timeout,
      a byte cap and a pixel cap -- never on the engine thread -- and errors never echo the path.)
+    POST /v1/embeddings    {"input": str | [str, ...], "images": as above (with ONE input only), "pooling": "last" | "mean",
+                            "normalize": bool, "adapter": as above, "encoding_format": "float" | "base64" (little-endian fp32)}
+      -> 200 {"object": "list", "model": ..., "data": [{"object": "embedding", "index": i, "embedding": [...] | "..."}],
+              "usage": {"prompt_tokens": n, "total_tokens": n}}
+    (extension: the prompt as a vector, api.embed: one prefill that ends in p3v_embed_pool instead of lm_head; a list is one
+     left-padded batch.  Runs on the engine thread in order with generation; under --continuous between two decode steps, on
+     a state of its own.  A bad field -> 400 with the reason; behind a fleet, a regime router or a process group -> 400 naming
+     that limit; a backend started without an embed function keeps answering 404.)
 
 with one difference in the plumbing: requests do not call the model from the HTTP thread.  They go into a queue that a
 single engine thread drains (the model object holds one in-flight sequence group).  By default every
@@ -115,6 +123,57 @@ class _Job:
 
 
 SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "seed")
+
+
+class _EmbedJob:
+    """One /v1/embeddings request on the queue: served by the worker thread, in order with generation."""
+
+    def __init__(self, prompts, images, pooling, normalize, adapter):
+        self.prompts, self.images, self.pooling, self.normalize, self.adapter = prompts, images, pooling, normalize, adapter
+        self.done = threading.Event()
+        self.result = None
+        self.error = None
+
+
+EMBED_NOT_BUILT = ("embeddings are not available on a fleet, a regime router (--long-window) or the batch-sharded path of a process "
+                   "group: run one engine (--continuous without --long-window and WORLD_SIZE 1, or the queue server)")
+
+
+def parse_embeddings(request):
+    """The fields of a POST /v1/embeddings body, checked: (inputs, image specs or None, pooling, normalize, encoding)."""
+    from .api import check_pooling
+    inputs = request.get("input")
+    inputs = [inputs] if isinstance(inputs, str) else inputs
+    if not isinstance(inputs, list) or not inputs or not all(isinstance(p, str) for p in inputs):
+        raise ValueError("input must be a string or a non-empty list of strings")
+    images = request.get("images")
+    if images is not None:
+        images = [images] if isinstance(images, str) else list(images)
+        if len(images) != len(inputs):
+            raise ValueError("images must list one entry (or null) per input")
+        if len(inputs) > 1 and any(i is not None for i in images):
+            raise ValueError("Images cannot be provided when input is a list")
+    pooling = check_pooling(request.get("pooling", "last"))
+    normalize = request.get("normalize", True)
+    if not isinstance(normalize, bool):
+        raise ValueError("normalize must be true or false")
+    encoding = request.get("encoding_format", "float")
+    if encoding not in ("float", "base64"):
+        raise ValueError(f"encoding_format must be 'float' or 'base64', got {encoding!r}")
+    return inputs, images, pooling, normalize, encoding
+
+
+def format_embeddings(vectors, n_tokens, encoding):
+    """-> the response body: the OpenAI embeddings list ("base64": little-endian fp32)."""
+    import base64
+    import numpy as np
+    rows = np.asarray(vectors, dtype="<f4")
+    rows = rows[None] if rows.ndim == 1 else rows
+    data = [{"object": "embedding", "index": i,
+             "embedding": base64.b64encode(r.tobytes()).decode("ascii") if encoding == "base64" else [float(x) for x in r]}
+            for i, r in enumerate(rows)]
+    n = int(sum(n_tokens))
+    return {"object": "list", "model": MODEL_NAME, "data": data, "usage": {"prompt_tokens": n, "total_tokens": n}}
 
 
 def parse_sampling(request, n_prompts):
@@ -427,7 +486,12 @@ class EngineQueue:
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
                  length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=(), speculate=False,
-                 speculate_default=0, decode_fn=None, vocab_size=None, share_refusal=None):
+                 speculate_default=0, decode_fn=None, vocab_size=None, share_refusal=None, embed_fn=None, embed_refusal=None):
+        # embed_fn(prompts, images, pooling, normalize, adapter) -> (vectors [n, H], prompt tokens per prompt): /v1/embeddings, run
+        # by the worker thread in order with generation; None: the path does not exist (404).  embed_refusal: why it cannot be
+        # served here (-> 400), or None
+        self.embed_fn, self.embed_refusal = embed_fn, embed_refusal
+        self.embed = self._embed if embed_fn is not None else None
         self.share_refusal = share_refusal                      # --share-prefix: why a family cannot share its prefix here (-> 400), or None
         self.vocab_size = vocab_size                            # bound of a request's logit_bias keys (None: checked by generate_fn)
         self.decode_fn = decode_fn                              # token id -> text piece (the "tokens" of a logprobs response)
@@ -450,6 +514,15 @@ class EngineQueue:
                penalties=None, n=None, best_of=None, guide=None):
         job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images,
                    in_use(sampling, adapter, logprobs, penalties, n, best_of, guide=guide), speculate, info)
+        self.jobs.put(job)
+        if not job.done.wait(self.timeout_s):
+            raise TimeoutError(f"no result within {self.timeout_s} s")
+        if job.error is not None:
+            raise job.error
+        return job.result
+
+    def _embed(self, prompts, images=None, pooling="last", normalize=True, adapter=None):
+        job = _EmbedJob(prompts, images, pooling, normalize, adapter)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -485,6 +558,9 @@ class EngineQueue:
             if job is None:
                 self.jobs.put(None)
                 break
+            if isinstance(job, _EmbedJob):      # keeps its place behind this group
+                held.append(job)
+                continue
             if not alone(job) and job.max_tokens == first.max_tokens and n + len(job.prompts) <= self.max_batch \
                     and self._regime(job.prompts, job.max_tokens) == regime and ("sampling" in job.opts) == ("sampling" in first.opts):
                 group.append(job)
@@ -503,6 +579,13 @@ class EngineQueue:
             first = self.jobs.get()
             if first is None:
                 break
+            if isinstance(first, _EmbedJob):
+                try:
+                    first.result = self.embed_fn(first.prompts, first.images, first.pooling, first.normalize, first.adapter)
+                except Exception as e:          # noqa: BLE001 -- reported to the waiting request
+                    first.error = e
+                first.done.set()
+                continue
             group = self._collect(first)
             flat = [p for j in group for p in j.prompts]
             try:
@@ -594,7 +677,34 @@ def make_handler(engine, image_policy=None):
                 return
             self._send(200, {"model": MODEL_NAME, "adapters": known_adapters(engine)})
 
+        def _embeddings(self):
+            try:
+                request = json.loads(self.rfile.read(int(self.headers.get("Content-Length", 0))).decode("utf-8"))
+                refusal = getattr(engine, "embed_refusal", None)
+                if refusal:
+                    raise ValueError(refusal)
+                inputs, images, pooling, normalize, encoding = parse_embeddings(request)
+                if images is not None:
+                    images = [decode_image(i, image_policy) for i in images]          # fetched + decoded in THIS thread
+                    images = None if all(i is None for i in images) else images
+                adapter = parse_adapter(request, len(inputs), known_adapters(engine))
+            except (ValueError, TypeError, AttributeError, OSError) as e:
+                self._send(400, {"error": str(e)})
+                return
+            try:
+                vectors, n_tokens = engine.embed(inputs, images, pooling, normalize, adapter)
+            except ValueError as e:             # (a prompt beyond the engine's window, ...)
+                self._send(400, {"error": str(e)})
+                return
+            except Exception as e:              # noqa: BLE001
+                self._send(500, {"error": f"{type(e).__name__}: {e}"})
+                return
+            self._send(200, format_embeddings(vectors, n_tokens, encoding))
+
         def do_POST(self):
+            if self.path == "/v1/embeddings" and (getattr(engine, "embed", None) is not None or getattr(engine, "embed_refusal", None)):
+                self._embeddings()
+                return
             if self.path != "/v1/completions":
                 self.send_error(404, "Not Found")
                 return
@@ -662,10 +772,12 @@ def make_handler(engine, image_policy=None):
     return CompletionHandler
 
 
-def serve(generate_fn, port=8000, host="127.0.0.1", max_batch=64, image_policy=None, **engine_kwargs):
+def serve(generate_fn, port=8000, host="127.0.0.1", max_batch=64, image_policy=None, embed_fn=None, **engine_kwargs):
     """-> (httpd, engine); call httpd.serve_forever() (or run it in a thread) and engine.close() at the end.
-    Binds the loopback interface unless told otherwise (`host=""` = all interfaces, as the reference's server.py:31)."""
-    engine = EngineQueue(generate_fn, max_batch=max_batch, **engine_kwargs)
+    Binds the loopback interface unless told otherwise (`host=""` = all interfaces, as the reference's server.py:31).
+    embed_fn(prompts, images, pooling, normalize, adapter) -> (vectors, prompt tokens per prompt) serves POST /v1/embeddings on
+    the queue's worker thread; without it that path is a 404."""
+    engine = EngineQueue(generate_fn, max_batch=max_batch, embed_fn=embed_fn, **engine_kwargs)
     httpd = ThreadingHTTPServer((host, port), make_handler(engine, image_policy))
     return httpd, engine
 
@@ -707,6 +819,30 @@ class ContinuousBackend:
         if "n" in kw and not isinstance(prompts, str) and len(prompts) == 1:
             prompts = prompts[0]                                 # a family: one prompt (a string for the engine), n texts back
         return self.engine.generate(prompts, images, max(1, min(int(max_tokens), self.max_tokens_cap)), self.timeout_s, **kw)
+
+    @property
+    def embed_refusal(self):
+        """Why /v1/embeddings cannot be served here (a router or a fleet in front: -> 400), or None."""
+        in_front = hasattr(self.engine, "engines") or hasattr(self.engine, "engine")      # RegimeRouter / fleet.EngineFleet
+        return EMBED_NOT_BUILT if in_front and not hasattr(self.engine, "embed") else None
+
+    @property
+    def embed(self):
+        """None where the engine has no `embed` (-> 404, or 400 with `embed_refusal`)."""
+        return self._embed if hasattr(self.engine, "embed") else None
+
+    def _embed(self, prompts, images=None, pooling="last", normalize=True, adapter=None):
+        from .api import _apply_chat_template, prompt_token_counts
+        single = len(prompts) == 1
+        text, imgs = _apply_chat_template(prompts[0] if single else list(prompts), images[0] if single and images is not None else None, False)
+        inputs = self.engine.processor(text, imgs)
+        job = self.engine.embed(inputs, pooling, normalize, None if adapter is None else (adapter[0] if single else list(adapter)))
+        if not job.done.wait(self.timeout_s):
+            job.cancel()
+            raise TimeoutError(f"no result within {self.timeout_s} s")
+        if job.error is not None:
+            raise job.error
+        return job.result, prompt_token_counts(inputs)
 
     def close(self):
         self.stop.set()
@@ -757,7 +893,7 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
     prefix_cache_gb (with continuous): byte budget of the prompt prefix store of EACH engine (0 = off).
     share_prefix: the rows of an "n" > 1 request read their prompt's K/V once per decode step (engine.ContinuousEngine /
     api.generate: share_prefix); every rank of a fleet builds its engine from the same flag.  No request field, same responses."""
-    from .api import _apply_chat_template, generate, load, load_adapters
+    from .api import _apply_chat_template, embed, generate, load, load_adapters
     preload = load(blind_model=blind_model, synthetic=synthetic or None)
     if adapters:
         load_adapters(preload, adapters)
@@ -820,7 +956,16 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
     def length_fn(prompt):
         return len(processor.tokenizer(_apply_chat_template(prompt, None, False)[0]).input_ids)
 
-    httpd, engine = serve(generate_fn, port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
+    def embed_fn(prompts, images=None, pooling="last", normalize=True, adapter=None):
+        info, single = {}, len(prompts) == 1
+        out = embed(prompts[0] if single else prompts, images[0] if single and images is not None else None, preload=preload,
+                    pooling=pooling, normalize=normalize, adapter=None if adapter is None else (adapter[0] if single else adapter), info=info)
+        return out, info["prompt_tokens"]
+
+    import torch.distributed as dist
+    grouped = dist.is_available() and dist.is_initialized()          # a process group: batches go down the batch-sharded path
+    httpd, engine = serve(generate_fn, embed_fn=embed_fn, **({"embed_refusal": EMBED_NOT_BUILT} if grouped else {}),
+                          port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
                           image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True,
                           speculate_default=speculate, decode_fn=lambda i: processor.tokenizer.decode([int(i)]),
                           vocab_size=getattr(getattr(preload[0], "cfg", None), "vocab_size", None),

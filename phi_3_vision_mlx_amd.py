@@ -15,8 +15,8 @@ if __spec__ is not None:
 
 from phi_3_vision_mlx_amd import api as _api  # noqa: E402
 from phi_3_vision_mlx_amd.api import (  # noqa: E402,F401
-    ID_ASS, ID_EOS, LogitStopper, Streamer, TokenStopper, benchmark, choose,
-    constrain, load,
+    ID_ASS, ID_EOS, VDB, LogitStopper, Streamer, TokenStopper, benchmark, choose,
+    constrain, embed, load,
 )
 
 
