@@ -99,9 +99,9 @@ typedef struct {
   int64_t ws_bytes;    /* its size; see p3v_gemm_ws_bytes */
 } p3v_gemm_args_t;
 /* Operands are addressed with 32-bit byte offsets: M * lda * 2 and rows(W) * ldw * 2 must stay below 4 GiB
- * (P3V_ERR_UNSUPPORTED otherwise).  Shapes with 17 <= M <= 1024 and fewer than 256 output tiles (short prompts) run split
- * over K through fp32 partials in `ws`: p3v_gemm_ws_bytes(M, N, K, epilogue) is the size that path needs (0 = the shape
- * does not use a workspace).  The library never allocates, frees or synchronises: with ws == null or too small the same
+ * (P3V_ERR_UNSUPPORTED otherwise).  Which kernels a call takes is p3v_gemm_route's answer (below).  Short prompts run split
+ * over K through fp32 partials in `ws`: p3v_gemm_ws_bytes(M, N, K, epilogue) is the size that path needs, the route's ws_bytes
+ * (0 = the shape does not use a workspace).  The library never allocates, frees or synchronises: with ws == null or too small the same
  * shape runs on the one-pass kernel (slower for short prompts, same results up to fp32 summation order).  The workspace
  * is only live between the two launches of one call, so calls on ONE stream may share it; concurrent streams need their
  * own.  Graph-capturable. */
@@ -110,7 +110,7 @@ int64_t p3v_gemm_ws_bytes(int M, int N, int K, int epilogue);
 /* Round 6: 9 .. 32 rows of A on bf16 weights with K = 3072 or 8192 (a 9 .. 32-sequence decode batch; the reference's batched benchmark
  * runs 15, phi_3_vision_mlx.py:1226-1243) take a register-streaming kernel inside p3v_gemm / p3v_gemm_resid_norm (weights HBM ->
  * registers in whole lines, A resident as MFMA fragments): this query says how -- 0 = not that kernel's shape, 1 = one pass,
- * S > 1 = S K slices through the `ws` partials + the reduction launch.  Host-only. */
+ * S > 1 = S K slices through the `ws` partials + the reduction launch (the rows kernel's line of the route's split rule).  Host-only. */
 int p3v_gemm_rows_slices(int M, int N, int K, int epilogue);
 
 /* ---- skinny projection for decode: y[M,N] = x[M,K] * W[N,K]^T, M <= 16, weight-streaming
@@ -226,19 +226,17 @@ int p3v_rope_kv_append(const uint16_t* qkv, const float* cos_t, const float* sin
 /* ---- a residual projection whose consumer is an RMSNorm, as one launch sequence (round 5; phi.py:478-484: `r + o_proj(...)` followed
  *      by `post_attention_layernorm`, `r + down_proj(...)` followed by the next layer's `input_layernorm`):
  *      p3v_gemm_resid_norm(g, w, eps, normed) == p3v_gemm(g) with P3V_EPI_RESID_BF16 + p3v_rmsnorm(g->out, w, normed, M, N, eps), bit
- *      for bit, where the projection runs as K slices (9 .. 256 rows and N small enough that the split pays: the fp32 partials are
- *      summed, the residual added, the row normalised by the SAME launch).  P3V_ERR_UNSUPPORTED -- nothing launched, the caller runs the
- *      two calls -- for every other shape, without a workspace of p3v_gemm_ws_bytes(), or N > 3072.  normed: bf16 [M, N] contiguous. */
+ *      for bit, where the route (p3v_gemm_route, entry P3V_GEMM_ENTRY_RESID_NORM) runs the projection as K slices: the fp32 partials are
+ *      summed, the residual added, the row normalised by the SAME launch.  P3V_ERR_UNSUPPORTED -- nothing launched, the caller runs the
+ *      two calls -- wherever the route says so (no split, no workspace of p3v_gemm_ws_bytes(), N > 3072).  normed: bf16 [M, N] contiguous. */
 int p3v_gemm_resid_norm(const p3v_gemm_args_t* gemm /* host */, const uint16_t* norm_w, float eps, uint16_t* normed, void* stream);
 
 /* ---- the qkv projection with the split, the rotation and the KV append in its EPILOGUE (round 5):
  *      p3v_gemm_qkv(g, s) == p3v_gemm(g) into a scratch [M, N] + p3v_rope_kv_append(scratch, ...) with s's arguments, bit for bit, in the
  *      GEMM's launches alone (phi.py:437-452 / 140-147: `qkv_proj` + `split` + `_rotate_half` + KVCache append; CLIP: q/k/v projections
  *      + head split).  g: A [B*L, K], W [(nh + 2 nkv) * hd, K] (q rows, k rows, v rows), epilogue P3V_EPI_NONE or P3V_EPI_BIAS; out /
- *      resid / ws unused.  P3V_ERR_UNSUPPORTED (nothing launched) unless hd % 32 == 0, (hd / 2) % 16 == 0, an 8-aligned append
- *      offset and dst_t (round 6: batch rows of any length L -- CLIP's 577-token crops), and either M >= 1024 with whole 128-column tiles per region (the 256 x 256 /
- *      128 x 128-tile kernels) or 9 <= M <= 256 without bias, whole 64-column Q / K tiles and 128-row V tiles (the 128 x 64-tile
- *      weight-streaming kernel) -- callers then run the two calls. */
+ *      resid / ws unused.  P3V_ERR_UNSUPPORTED (nothing launched) wherever the route (p3v_gemm_route, entry P3V_GEMM_ENTRY_QKV)
+ *      says so -- callers then run the two calls. */
 typedef struct {
   const float* cos_t; const float* sin_t;          /* as p3v_rope_kv_append; both null: plain head split */
   uint16_t* q_out; uint16_t* k_dst; uint16_t* v_dst;
@@ -247,6 +245,51 @@ typedef struct {
   float q_scale;
 } p3v_qkv_split_t;
 int p3v_gemm_qkv(const p3v_gemm_args_t* gemm /* host */, const p3v_qkv_split_t* split /* host */, void* stream);
+
+/* ---- the bf16 prefill GEMM's route: what p3v_gemm / p3v_gemm_resid_norm / p3v_gemm_qkv launch for a call.  The shape must pass the
+ * entry points' own checks (K % 64, N % 8, lda and ldw >= K and multiples of 8; qkv: N == (n_heads + 2 n_kv) * hd) or the answer
+ * is P3V_ERR_ARG; pointers are not its business.  The three entry points ask this one function and launch what it says; p3v_gemm_ws_bytes and
+ * p3v_gemm_rows_slices are projections of it (host-only, no launch).  The `gemm_*` knobs are read from the library's current settings
+ * (p3v_set_tuning works without a device).  cu_count <= 0 asks the current device, as the entry points do, and only where a
+ * 256 x 256-tile launch is part of the route: with cu_count given the function touches no device (tests/test_gemm_route_cpu.py). */
+typedef enum { P3V_GEMM_ENTRY_GEMM = 0, P3V_GEMM_ENTRY_RESID_NORM = 1, P3V_GEMM_ENTRY_QKV = 2 } p3v_gemm_entry_t;
+typedef enum {
+  P3V_GEMM_K_ROWS = 0,          /* k_gemm_rows: 9 .. 32 rows, weights straight to registers (tile_m = 16 or 32 rows held) */
+  P3V_GEMM_K_SKINNY,            /* k_gemm_skinny: tile_m (64 or 128) x 64 tiles, weight-streaming */
+  P3V_GEMM_K_SKINNY_QKV,        /*   ... with the qkv epilogue */
+  P3V_GEMM_K_128,               /* k_gemm: 128 x 128 tiles (S > 1: fp32 K-slice partials) */
+  P3V_GEMM_K_128_QKV,
+  P3V_GEMM_K_256,               /* k_gemm256: 256 x 256 tiles */
+  P3V_GEMM_K_256_QKV,
+  P3V_GEMM_K_REDUCE,            /* k_splitk_reduce: adds the S partials, applies the epilogue */
+  P3V_GEMM_K_REDUCE_NORM,       /* k_splitk_reduce_norm: ... and the RMSNorm of p3v_gemm_resid_norm */
+  P3V_GEMM_K_COUNT
+} p3v_gemm_kernel_t;
+typedef struct {
+  int entry;                    /* p3v_gemm_entry_t */
+  int M, N, K, lda, ldw;
+  int epilogue, has_bias;
+  int64_t ws_bytes;             /* the workspace offered (0: none) */
+  int n_heads, n_kv, hd;        /* P3V_GEMM_ENTRY_QKV */
+  int dst_off, dst_t;           /*   the append offset (past if dst_off_is_past, else 0) and the cache's row length */
+  int cu_count;
+} p3v_gemm_route_query_t;
+typedef struct {
+  int kernel;                   /* p3v_gemm_kernel_t */
+  int grid[3], block;
+  int row0, rows;               /* the rows of A the launch covers (a reduction: the rows of the partials it finishes) */
+  int tile_m;                   /* rows of A per workgroup */
+  char name[48];                /* as a profiler prints it: "k_gemm_skinny<5, true, 64, 128>" (filled by p3v_gemm_route only) */
+} p3v_gemm_launch_t;
+typedef struct {
+  int status;                   /* P3V_OK, or P3V_ERR_UNSUPPORTED (then no launch); P3V_ERR_HIP: no device answered for cu_count */
+  int n_launches;
+  p3v_gemm_launch_t launch[3];  /* in order */
+  int S;                        /* K slices the launches run (1: one pass) */
+  int64_t ws_bytes;             /* the workspace the shape's split needs, whatever was offered (0: no split): p3v_gemm_ws_bytes */
+  int ws_short;                 /* 1: ws_bytes > 0 and the workspace offered is smaller: the call runs without that split */
+} p3v_gemm_route_t;
+int p3v_gemm_route(const p3v_gemm_route_query_t* query /* host */, p3v_gemm_route_t* route /* host */);
 
 /* ---- attention, phi.py:454-457 (decoder, causal + left-pad, Mask4D phi.py:550-563)
  * and phi.py:148 (CLIP, no mask).  q [B, nh, L, hd]; keys/values come from two

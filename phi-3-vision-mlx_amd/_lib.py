@@ -111,6 +111,28 @@ class AttnRoute(C.Structure):
                 ("merge_block", i32), ("fuse_form", i32), ("fo_remap", i32), ("kernel_name", C.c_char_p), ("merge_name", C.c_char_p)]
 
 
+GEMM_ENTRY_GEMM, GEMM_ENTRY_RESID_NORM, GEMM_ENTRY_QKV = range(3)                # p3v_gemm_entry_t
+(GEMM_K_ROWS, GEMM_K_SKINNY, GEMM_K_SKINNY_QKV, GEMM_K_128, GEMM_K_128_QKV, GEMM_K_256, GEMM_K_256_QKV, GEMM_K_REDUCE,
+ GEMM_K_REDUCE_NORM) = range(9)                                                    # p3v_gemm_kernel_t
+
+
+class GemmRouteQuery(C.Structure):
+    """p3v_gemm_route_query_t (include/p3v.h): cu_count <= 0 = the device's own."""
+    _fields_ = [("entry", i32), ("M", i32), ("N", i32), ("K", i32), ("lda", i32), ("ldw", i32), ("epilogue", i32), ("has_bias", i32),
+                ("ws_bytes", i64), ("n_heads", i32), ("n_kv", i32), ("hd", i32), ("dst_off", i32), ("dst_t", i32), ("cu_count", i32)]
+
+
+class GemmLaunch(C.Structure):
+    """p3v_gemm_launch_t (include/p3v.h)."""
+    _fields_ = [("kernel", i32), ("grid", i32 * 3), ("block", i32), ("row0", i32), ("rows", i32), ("tile_m", i32), ("name", C.c_char * 48)]
+
+
+class GemmRoute(C.Structure):
+    """p3v_gemm_route_t (include/p3v.h)."""
+    _fields_ = [("status", i32), ("n_launches", i32), ("launch", GemmLaunch * 3), ("S", i32),
+                ("ws_bytes", i64), ("ws_short", i32)]
+
+
 class SampleRow(C.Structure):
     """p3v_sample_row_t: one row's sampling settings + its draw counter (include/p3v.h)."""
     _fields_ = [("temperature", f32), ("top_k", i32), ("top_p", f32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
@@ -196,6 +218,7 @@ SIGNATURES = {
     "p3v_gemm": (i32, [C.POINTER(GemmArgs), vp]),
     "p3v_gemm_ws_bytes": (i64, [i32, i32, i32, i32]),
     "p3v_gemm_rows_slices": (i32, [i32, i32, i32, i32]),
+    "p3v_gemm_route": (i32, [C.POINTER(GemmRouteQuery), C.POINTER(GemmRoute)]),               # added after round 6, no version change
     "p3v_gemv": (i32, [C.POINTER(GemvArgs), vp]),
     "p3v_gemv_step": (i32, [C.POINTER(GemvArgs), C.POINTER(GemvStep), vp]),
     "p3v_gemv_fp8_step": (i32, [C.POINTER(GemvF8Args), C.POINTER(GemvStep), vp]),

@@ -19,13 +19,11 @@
 //             staging (rounds 1-4 went through a wave-private LDS tile).
 //
 // Roofline: MFMA-bound for M >= ~512 (2*M*N*K flops vs (M+N)*K*2 bytes).
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-
-#include "p3v_gemm_qkv.h"
-
-#define P3V_EPI_QKV 100                // internal: qkv projection with split + RoPE + KV append in the epilogue (p3v_gemm_qkv.h)
+#include "p3v_gemm_route.h"
 
 #define BM 128
 #define BN 128
@@ -302,43 +300,35 @@ __global__ void __launch_bounds__(256, 2) k_gemm(GemmP p) {
   }
 }
 
-template <int EPI, int ORD>
-static int launch_gemm_v(const GemmP& p, hipStream_t s) {
+template <int EPI, int ORD = 0>
+static int launch_gemm(const GemmP& p, const p3v_gemm_launch_t& l, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)k_gemm<EPI, ORD>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS) != hipSuccess)
       return P3V_ERR_HIP;
     attr_set = true;
   }
-  const int n_tile = EPI == P3V_EPI_SILU_MUL ? BN / 2 : BN;
-  dim3 grid(p3v_cdiv(p.N, n_tile), p3v_cdiv(p.M, BM), p.kslice ? p.K / p.kslice : 1);
-  hipLaunchKernelGGL((k_gemm<EPI, ORD>), grid, dim3(256), GEMM_LDS, s, p);
+  hipLaunchKernelGGL((k_gemm<EPI, ORD>), dim3(l.grid[0], l.grid[1], l.grid[2]), dim3(256), GEMM_LDS, s, p);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }
-
-template <int EPI>
-static int launch_gemm(const GemmP& p, hipStream_t s) { return launch_gemm_v<EPI, 0>(p, s); }
-
-int p3v_gemm256_try(const p3v_gemm_args_t* a, hipStream_t s);   // p3v_gemm256.hip: 256x256 tiles, P3V_ERR_UNSUPPORTED if the shape does not fit
-static int gemm128(const p3v_gemm_args_t* a, hipStream_t s);
 
 // How many leading rows go to the 256x256 kernel (a multiple of 256, or M for all of them); the rest runs on the
 // 128x128 kernel in a second launch on the same stream.  The machine holds 256 big workgroups or 512 small ones
 // per round; a round of big tiles costs 1, a round of small ones 0.675 (half the output area at 0.97 vs 1.31
 // PFLOP/s), a last round that leaves every CU at most one small workgroup 0.42 -- pick the cheapest whole-round
 // packing, e.g. 2531 x 16384 (gate_up): 8 x 64 = 512 big tiles = 2 rounds + 4 x 128 small = 1 round.
-static int gemm_big_rows(const p3v_gemm_args_t* a) {
-  const int n_big = a->epilogue == P3V_EPI_SILU_MUL ? 128 : 256, n_small = n_big / 2;
-  if (a->M < 1024 || a->N % n_big || a->epilogue == P3V_EPI_PATCH) return 0;
-  if (const int force = p3v_tuning().gemm_big_rows; force >= 0) return min(force / 256 * 256, a->M);   // tests: pin the split
-  const int mt = p3v_cdiv(a->M, 256), nt_big = a->N / n_big, nt_small = p3v_cdiv(a->N, n_small);
+static int gemm_big_rows(int M, int N, int K, int epilogue) {
+  const int n_big = epilogue == P3V_EPI_SILU_MUL ? 128 : 256, n_small = n_big / 2;
+  if (M < 1024 || N % n_big || epilogue == P3V_EPI_PATCH) return 0;
+  if (const int force = p3v_tuning().gemm_big_rows; force >= 0) return min(force / 256 * 256, M);   // tests: pin the split
+  const int mt = p3v_cdiv(M, 256), nt_big = N / n_big, nt_small = p3v_cdiv(N, n_small);
   // a short K loop leaves the big tile's 128-KiB prologue and four-pass epilogue exposed (one workgroup per CU)
-  const float big_round = a->K >= 2048 ? 1.0f : 1.0f + 0.25f * (2048 - a->K) / 1024.f;
+  const float big_round = K >= 2048 ? 1.0f : 1.0f + 0.25f * (2048 - K) / 1024.f;
   float best = 1e30f;
   int best_rows = 0;
   for (int ms = 0; ms <= mt; ++ms) {
-    const int rows_big = min(ms * 256, a->M), rows_small = a->M - rows_big;
+    const int rows_big = min(ms * 256, M), rows_small = M - rows_big;
     const long big = (long)ms * nt_big, small = (long)p3v_cdiv(rows_small, 128) * nt_small;
     float c = (float)((big + 255) / 256) * big_round;
     if (small) {
@@ -449,57 +439,177 @@ __global__ void __launch_bounds__(384) k_splitk_reduce_norm(const float* __restr
   }
 }
 
-// number of K slices for a shape (1 = not a split-K shape)
-static int splitk_slices(int M, int N, int K, int epilogue) {
+// ================================================================================================ the route
+// Every choice a call of p3v_gemm / p3v_gemm_resid_norm / p3v_gemm_qkv makes -- kernels, grids, K slices, workspace -- is made here,
+// once (include/p3v.h: p3v_gemm_route); the entry points below launch what it says.  DESIGN.md section 3.2 has the rules as a table.
+
+// Operands are addressed with 32-bit byte offsets (buffer loads): `rows` rows of `ld` bf16 elements must stay below 4 GiB.
+static inline bool gemm_over_32bit(size_t rows, int ld) { return rows * (size_t)ld * 2 >= (1ull << 32); }
+
+// K slices of a shape on `kernel` (P3V_GEMM_K_ROWS / _SKINNY / _128): 0 = not one of that kernel's shapes (the 128 x 128 kernel takes
+// every shape: 1), 1 = one pass, S > 1 = S slices of fp32 partials + the reduction launch.
+static int gemm_slices(int kernel, int M, int N, int K, int epilogue) {
   const P3vTuning& t = p3v_tuning();
   const bool silu = epilogue == P3V_EPI_SILU_MUL;
-  if (t.gemm_no_splitk || M <= 16 || M > t.gemm_splitk_max_m /* beyond, every projection has >= 256 tiles anyway */ ||
-      N % 128 || K % 512)
-    return 1;
-  if (epilogue != P3V_EPI_NONE && epilogue != P3V_EPI_RESID_BF16 && !silu) return 1;
-  const int w_rows = silu ? 2 * N : N;                        // SiLU: [gate; up] taken as 2N plain output columns
+  const bool splittable = epilogue == P3V_EPI_NONE || epilogue == P3V_EPI_RESID_BF16 || silu;
+  const int w_rows = silu ? 2 * N : N;                          // SiLU: [gate; up] taken as 2N plain output columns
+  if (kernel == P3V_GEMM_K_ROWS) {                              // 9 .. 32 rows, K = 3072 or 8192 (p3v_gemm_rows.hip)
+    if (!t.gemm_rows || M <= 8 || M > 32 || N % (silu ? 8 : 16) || !splittable) return 0;
+    const int n_sets = N / (silu ? 8 : 16);
+    if (K == 3072) return n_sets >= 512 ? 1 : 4;               // qkv / gate_up in one pass; o_proj: 4 slices of 768
+    return K == 8192 ? 4 : 0;                                   // down: 4 slices of 2048
+  }
+  if (kernel == P3V_GEMM_K_SKINNY) {                            // 9 .. gemm_skinny_max_m rows (p3v_gemm_skinny.hip)
+    if (t.gemm_no_skinny || M <= 8 || M > t.gemm_skinny_max_m || K % 64 || N % (silu ? 32 : 64) || !splittable) return 0;
+    // one workgroup per CU: the largest S <= 8 whose tiles * S still fit one round of the chip (slices of >= 6 K-tiles)
+    const int tiles = p3v_cdiv(M, 128) * (w_rows / 64);
+    if (t.gemm_skinny_s > 0) return K % (t.gemm_skinny_s * 64) ? 1 : t.gemm_skinny_s;
+    int best = 1;
+    for (int S = 2; S <= 8; ++S)
+      if (K % (S * 64) == 0 && K / S >= 6 * 64 && tiles * S <= t.gemm_splitk_wgs) best = S;
+    return best;
+  }
+  // the 128 x 128 kernel: 17 .. gemm_splitk_max_m rows (beyond, every projection has >= 256 tiles anyway)
+  if (t.gemm_no_splitk || M <= 16 || M > t.gemm_splitk_max_m || N % 128 || K % 512 || !splittable) return 1;
   const int tiles = p3v_cdiv(M, BM) * (w_rows / BN);
   int S = 1;
   while (S < t.gemm_splitk_max_s && tiles * S < t.gemm_splitk_wgs && (K / (2 * S)) % BK == 0 && K / (2 * S) >= 2 * BK) S *= 2;
   return S;
 }
 
-int p3v_gemm_skinny_slices(int M, int N, int K, int epilogue);   // p3v_gemm_skinny.hip: 0 = not one of its shapes
-int p3v_gemm_skinny_try(const p3v_gemm_args_t* a, hipStream_t s);
-
-extern "C" int64_t p3v_gemm_ws_bytes(int M, int N, int K, int epilogue) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const int sk = p3v_gemm_skinny_slices(M, N, K, epilogue);
-  const int S = sk ? sk : splitk_slices(M, N, K, epilogue);
-  if (S == 1) return 0;
-  return (int64_t)S * M * (epilogue == P3V_EPI_SILU_MUL ? 2 * N : N) * 4;
+static void route_add(p3v_gemm_route_t& r, int kernel, int gx, int gy, int gz, int block, int row0, int rows, int tile_m) {
+  r.launch[r.n_launches++] = {kernel, {gx, gy, gz}, block, row0, rows, tile_m, ""};
 }
 
-// ---- out = resid + bf16(A W^T) and normed = RMSNorm(out) (include/p3v.h): only where the projection runs as K slices anyway
-int p3v_gemm_skinny_partials(const p3v_gemm_args_t* a, int* S_out, hipStream_t s);   // p3v_gemm_skinny.hip
-extern "C" int p3v_gemm_resid_norm(const p3v_gemm_args_t* a, const uint16_t* norm_w, float eps, uint16_t* normed, void* stream) {
-  if (!a || !a->A || !a->W || !a->out || !a->resid || !norm_w || !normed) return P3V_ERR_ARG;
-  if (a->epilogue != P3V_EPI_RESID_BF16 || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->K % BK || a->N % 8 || a->ldo % 8 || a->ldo < a->N) return P3V_ERR_ARG;
-  if (a->lda < a->K || a->ldw < a->K || a->lda % 8 || a->ldw % 8) return P3V_ERR_ARG;
-  if (((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->out | (uintptr_t)a->resid | (uintptr_t)norm_w | (uintptr_t)normed | (uintptr_t)a->ws) & 15)
-    return P3V_ERR_ARG;
-  if (a->N > 6 * 64 * 8 || a->bias || (size_t)a->N * a->ldw * 2 >= (1ull << 32)) return P3V_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  int S = 0;
-  const int rc = p3v_gemm_skinny_partials(a, &S, s);           // P3V_ERR_UNSUPPORTED (nothing launched) unless the shape splits
-  if (rc != P3V_OK) return rc;
-  hipLaunchKernelGGL(k_splitk_reduce_norm, dim3(a->M), dim3(384), 0, s, (const float*)a->ws, (bf16_t*)a->out, (const bf16_t*)a->resid,
-                     (const u32x4_t*)norm_w, (u32x4_t*)normed, a->M, a->N, a->ldo, S, 1.0f / (float)a->N, eps);
-  P3V_CHECK_LAUNCH();
+// `rows` rows from row0 on the 256 x 256 tiles: one workgroup per tile, or the persistent loop's one per CU (a multiple of 8: XCDs)
+static int route_add_256(const p3v_gemm_route_query_t& q, p3v_gemm_route_t& r, int kernel, int n_tile, int row0, int rows) {
+  static int dev_cu = 0;                                          // the device is asked once, and only without a count in the query
+  if (q.cu_count <= 0 && !dev_cu) {
+    int dev = 0;
+    hipDeviceProp_t pr;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
+    dev_cu = pr.multiProcessorCount;
+  }
+  const int cu = q.cu_count > 0 ? q.cu_count : dev_cu, tiles = p3v_cdiv(q.N, n_tile) * p3v_cdiv(rows, 256);
+  route_add(r, kernel, p3v_tuning().gemm_persistent ? min(tiles, cu / 8 * 8) : tiles, 1, 1, 512, row0, rows, 256);
   return P3V_OK;
 }
 
+static void gemm_route(const p3v_gemm_route_query_t& q, p3v_gemm_route_t& r) {
+  const P3vTuning& t = p3v_tuning();
+  const int M = q.M, N = q.N, K = q.K, epi = q.epilogue;
+  const bool silu = epi == P3V_EPI_SILU_MUL, qkv = q.entry == P3V_GEMM_ENTRY_QKV, norm = q.entry == P3V_GEMM_ENTRY_RESID_NORM;
+  const int w_rows = silu ? 2 * N : N;
+  r.status = P3V_ERR_UNSUPPORTED, r.n_launches = 0, r.S = 1;
+  // ---- the split rule: the register-streaming kernel's, else the weight-streaming tiles', else the 128 x 128 kernel's.  A bias keeps
+  // a call off the first two; the qkv epilogue needs whole sums.
+  const int RS = q.has_bias || qkv ? 0 : gemm_slices(P3V_GEMM_K_ROWS, M, N, K, epi);
+  const int SS = q.has_bias || qkv ? 0 : gemm_slices(P3V_GEMM_K_SKINNY, M, N, K, epi);
+  const int S3 = qkv ? 1 : gemm_slices(P3V_GEMM_K_128, M, N, K, epi);
+  const int S_plan = RS ? RS : SS ? SS : S3;
+  const auto need = [&](int S) { return (int64_t)S * M * w_rows * 4; };      // fp32 partials [S, M, W rows]
+  const auto fits = [&](int S) { return S > 1 && q.ws_bytes >= need(S); };   // the workspace-fit test
+  r.ws_bytes = S_plan > 1 ? need(S_plan) : 0;
+  r.ws_short = S_plan > 1 && !fits(S_plan);
+
+  const auto rows_launch = [&](int S) {                         // workgroups along N: all CUs of one pass, a quarter per K slice
+    const int n_sets = N / (silu ? 8 : 16), per = p3v_cdiv(n_sets, p3v_cdiv(256, S));
+    route_add(r, P3V_GEMM_K_ROWS, p3v_cdiv(n_sets, per), S, 1, (K == 3072 && S > 1 ? 3 : 4) * 64, 0, M, M <= 16 ? 16 : 32);
+  };
+  const auto skinny_launch = [&](int S) {                       // <= 64 rows: 64-row tiles
+    const int tm = M <= 64 && !t.gemm_skinny_tm128 ? 64 : 128;
+    route_add(r, P3V_GEMM_K_SKINNY, N / (silu ? 32 : 64), p3v_cdiv(M, tm), S, 512, 0, M, tm);
+  };
+  const auto done = [&](int S, int reduce) {
+    if (reduce == P3V_GEMM_K_REDUCE) route_add(r, reduce, p3v_cdiv((long)M * (N / 8), 256), 1, 1, 256, 0, M, 0);
+    else if (reduce == P3V_GEMM_K_REDUCE_NORM) route_add(r, reduce, M, 1, 1, 384, 0, M, 1);
+    r.S = S, r.status = P3V_OK;
+  };
+
+  if (qkv) {
+    // what the fused epilogue needs: rotation pairs in blocks of 16 inside a head, an 8-aligned append offset and cache row
+    if (q.hd % 32 || (q.hd / 2) % 16 || q.dst_off % 8 || q.dst_t % 8 || t.gemm_no_qkv_fuse) return;
+    if (gemm_over_32bit(M, q.lda) || gemm_over_32bit(N, q.ldw)) return;
+    const int nq = q.n_heads * q.hd, nk = q.n_kv * q.hd;
+    if (M < 1024) {                                             // the weight-streaming tiles: whole Q / K tiles of 32 pairs, V tiles of 128 dims
+      if (t.gemm_no_skinny || M <= 8 || M > t.gemm_skinny_max_m || q.has_bias || nq % 64 || nk % 128) return;
+      route_add(r, P3V_GEMM_K_SKINNY_QKV, ((nq + nk) / 64) * p3v_cdiv(M, 128) + (nk / 128) * p3v_cdiv(M, 64), 1, 1, 512, 0, M, 128);
+      return done(1, -1);
+    }
+    if (nq % BN || nk % BN || t.gemm_128) return;               // whole 128-column tiles per region
+    const int rows_big = nq % 256 || nk % 256 ? 0 : gemm_big_rows(M, N, K, P3V_EPI_NONE);   // (priced as the plain bf16 epilogue)
+    if (rows_big > 0 && (r.status = route_add_256(q, r, P3V_GEMM_K_256_QKV, 256, 0, rows_big)) != P3V_OK) return;
+    if (rows_big < M) route_add(r, P3V_GEMM_K_128_QKV, p3v_cdiv(N, BN), p3v_cdiv(M - rows_big, BM), 1, 256, rows_big, M - rows_big, BM);
+    return done(1, -1);
+  }
+  if (norm) {                                                   // only where the projection runs as K slices anyway
+    if (N > 6 * 64 * 8 || q.has_bias || gemm_over_32bit(N, q.ldw)) return;
+    if (fits(RS)) return rows_launch(RS), done(RS, P3V_GEMM_K_REDUCE_NORM);
+    if (RS != 1 && fits(SS)) return skinny_launch(SS), done(SS, P3V_GEMM_K_REDUCE_NORM);
+    return;
+  }
+  if (gemm_over_32bit(M, q.lda) || gemm_over_32bit(w_rows, q.ldw)) return;
+  if (RS == 1) return rows_launch(1), done(1, -1);
+  if (fits(RS) && !silu) return rows_launch(RS), done(RS, P3V_GEMM_K_REDUCE);
+  // (a SiLU shape whose rows rule says 4 slices has no rows kernel for them: it runs in one pass below -- DESIGN.md section 3.2)
+  if (!fits(RS) && fits(SS)) return skinny_launch(SS), done(SS, P3V_GEMM_K_REDUCE);
+  if (SS) return skinny_launch(1), done(1, -1);
+  if (fits(S3)) {                                               // [gate; up] as 2N plain fp32 columns
+    route_add(r, P3V_GEMM_K_128, p3v_cdiv(w_rows, BN), p3v_cdiv(M, BM), S3, 256, 0, M, BM);
+    return done(S3, P3V_GEMM_K_REDUCE);
+  }
+  // whole rounds of big and small tiles (the 256 x 256 kernel's A offsets: 256 rows below 2 GiB)
+  const int rows_big = t.gemm_128 || (size_t)256 * q.lda * 2 >= ((size_t)1 << 31) ? 0 : gemm_big_rows(M, N, K, epi);
+  if (rows_big > 0 && (r.status = route_add_256(q, r, P3V_GEMM_K_256, silu ? 128 : 256, 0, rows_big)) != P3V_OK) return;
+  if (rows_big < M) route_add(r, P3V_GEMM_K_128, p3v_cdiv(N, silu ? BN / 2 : BN), p3v_cdiv(M - rows_big, BM), 1, 256, rows_big, M - rows_big, BM);
+  done(1, -1);
+}
+
+extern "C" int p3v_gemm_route(const p3v_gemm_route_query_t* q, p3v_gemm_route_t* r) {
+  if (!q || !r || q->entry < 0 || q->entry > P3V_GEMM_ENTRY_QKV || q->M < 0 || q->N <= 0 || q->K <= 0 || q->ws_bytes < 0) return P3V_ERR_ARG;
+  if (q->K % BK || q->N % 8 || q->lda < q->K || q->ldw < q->K || q->lda % 8 || q->ldw % 8) return P3V_ERR_ARG;   // as the entry points
+  if (q->entry == P3V_GEMM_ENTRY_QKV && (q->n_heads <= 0 || q->n_kv <= 0 || q->hd <= 0 || q->N != (q->n_heads + 2 * q->n_kv) * q->hd)) return P3V_ERR_ARG;
+  memset(r, 0, sizeof *r);
+  if (q->M == 0) { r->S = 1; return P3V_OK; }
+  gemm_route(*q, *r);
+  if (r->status != P3V_OK) r->n_launches = 0;
+  const int e = q->entry == P3V_GEMM_ENTRY_QKV ? P3V_EPI_QKV : q->epilogue;
+  for (int i = 0; i < r->n_launches; ++i) {
+    p3v_gemm_launch_t& l = r->launch[i];
+    const char* part = r->S > 1 ? "true" : "false";
+    switch (l.kernel) {
+      case P3V_GEMM_K_ROWS:
+        snprintf(l.name, sizeof l.name, "k_gemm_rows<%s, %d, %d, %d, %s>", e == P3V_EPI_SILU_MUL ? "true" : "false", l.block / 64,
+                 r->S == 1 ? 3 : l.block == 192 ? 1 : 2, l.tile_m / 16, part);
+        break;
+      case P3V_GEMM_K_SKINNY: case P3V_GEMM_K_SKINNY_QKV:
+        snprintf(l.name, sizeof l.name, "k_gemm_skinny<%d, %s, 64, %d>", e == P3V_EPI_SILU_MUL || e == P3V_EPI_RESID_BF16 || e == P3V_EPI_QKV ? e : 0, part, l.tile_m);
+        break;
+      case P3V_GEMM_K_128: case P3V_GEMM_K_128_QKV: snprintf(l.name, sizeof l.name, "k_gemm<%d, 0>", r->S > 1 ? P3V_EPI_F32 : e); break;
+      case P3V_GEMM_K_256: case P3V_GEMM_K_256_QKV: snprintf(l.name, sizeof l.name, "k_gemm256<%d, 80, 2>", e); break;
+      case P3V_GEMM_K_REDUCE: snprintf(l.name, sizeof l.name, "k_splitk_reduce<%d>", e == P3V_EPI_SILU_MUL || e == P3V_EPI_RESID_BF16 ? e : 0); break;
+      default: snprintf(l.name, sizeof l.name, "k_splitk_reduce_norm");
+    }
+  }
+  return P3V_OK;
+}
+
+// the two queries are projections: the route's ws_bytes for a call without a bias (no launch of it matters: any CU count), and the
+// rows kernel's line of the split rule
+extern "C" int64_t p3v_gemm_ws_bytes(int M, int N, int K, int epilogue) {
+  p3v_gemm_route_t r;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return gemm_route({P3V_GEMM_ENTRY_GEMM, M, N, K, K, K, epilogue, 0, 0, 0, 0, 0, 0, 0, 8}, r), r.ws_bytes;
+}
+extern "C" int p3v_gemm_rows_slices(int M, int N, int K, int epilogue) { return gemm_slices(P3V_GEMM_K_ROWS, M, N, K, epilogue); }
+
+// ================================================================================================ the launchers
 // the second launch of a split: adds the S fp32 partials [S, M, W rows] in slice order and applies the epilogue
-int p3v_splitk_reduce(const float* part, const p3v_gemm_args_t* a, int S, hipStream_t s) {
+static int splitk_reduce(const p3v_gemm_args_t* a, const p3v_gemm_launch_t& l, int S, hipStream_t s) {
   const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
   const int w_rows = silu ? 2 * a->N : a->N;
-  const long items = (long)a->M * (a->N / 8);
-  const dim3 grid((unsigned)p3v_cdiv(items, 256));
+  const float* part = (const float*)a->ws;
+  const dim3 grid(l.grid[0]);                                   // a thread per 8 columns of a row
   if (silu) hipLaunchKernelGGL(k_splitk_reduce<P3V_EPI_SILU_MUL>, grid, dim3(256), 0, s, part, a->out, a->resid, a->M, a->N, w_rows, a->ldo, S);
   else if (a->epilogue == P3V_EPI_RESID_BF16)
     hipLaunchKernelGGL(k_splitk_reduce<P3V_EPI_RESID_BF16>, grid, dim3(256), 0, s, part, a->out, a->resid, a->M, a->N, w_rows, a->ldo, S);
@@ -508,19 +618,85 @@ int p3v_splitk_reduce(const float* part, const p3v_gemm_args_t* a, int S, hipStr
   return P3V_OK;
 }
 
-// returns P3V_ERR_UNSUPPORTED when the shape is not one for split-K (or the caller gave no workspace for it)
-static int gemm_splitk(const p3v_gemm_args_t* a, hipStream_t s) {
-  const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-  const int S = splitk_slices(a->M, a->N, a->K, a->epilogue);
-  if (S == 1) return P3V_ERR_UNSUPPORTED;
-  const int w_rows = silu ? 2 * a->N : a->N;
-  if (!a->ws || a->ws_bytes < (int64_t)S * a->M * w_rows * 4) return P3V_ERR_UNSUPPORTED;
-  if ((uintptr_t)a->ws & 15) return P3V_ERR_ARG;
-  float* part = (float*)a->ws;
-  GemmP p = {a->A, a->W, part, nullptr, nullptr, nullptr, a->M, w_rows, a->K, a->lda, a->ldw, w_rows, 0, a->K / S, {}};
-  const int rc = launch_gemm<P3V_EPI_F32>(p, s);
-  if (rc != P3V_OK) return rc;
-  return p3v_splitk_reduce(part, a, S, s);
+static int gemm128(const p3v_gemm_args_t* a, const p3v_gemm_launch_t& l, int S, hipStream_t s) {
+  if (S > 1) {                                                  // K slices: fp32 partials, [gate; up] as 2N plain columns
+    const int w_rows = a->epilogue == P3V_EPI_SILU_MUL ? 2 * a->N : a->N;
+    const GemmP p = {a->A, a->W, a->ws, nullptr, nullptr, nullptr, a->M, w_rows, a->K, a->lda, a->ldw, w_rows, 0, a->K / S, {}};
+    return launch_gemm<P3V_EPI_F32>(p, l, s);
+  }
+  const GemmP p = {a->A, a->W, a->out, a->bias, a->resid, a->pos,
+                   a->M, a->N, a->K, a->lda, a->ldw, a->ldo, a->patches_per_img, 0, {}};
+  switch (a->epilogue) {
+    case P3V_EPI_NONE: return launch_gemm<P3V_EPI_NONE>(p, l, s);
+    case P3V_EPI_BIAS: return launch_gemm<P3V_EPI_BIAS>(p, l, s);
+    case P3V_EPI_BIAS_QGELU: return launch_gemm<P3V_EPI_BIAS_QGELU>(p, l, s);
+    case P3V_EPI_BIAS_GELU: return launch_gemm<P3V_EPI_BIAS_GELU>(p, l, s);
+    case P3V_EPI_BIAS_RESID_F32: return launch_gemm<P3V_EPI_BIAS_RESID_F32>(p, l, s);
+    case P3V_EPI_RESID_BF16: return launch_gemm<P3V_EPI_RESID_BF16>(p, l, s);
+    case P3V_EPI_SILU_MUL: return launch_gemm<P3V_EPI_SILU_MUL>(p, l, s);
+    case P3V_EPI_PATCH: return launch_gemm<P3V_EPI_PATCH>(p, l, s);
+    case P3V_EPI_F32: return launch_gemm<P3V_EPI_F32>(p, l, s);
+    default: return P3V_ERR_ARG;
+  }
+}
+
+// launches a route: `a` is the whole call; a launch that covers part of the rows gets its own view of A, out and resid
+struct NormP { const uint16_t* w; uint16_t* normed; float eps; };   // p3v_gemm_resid_norm's own arguments
+static int gemm_run(const p3v_gemm_args_t* a, const p3v_gemm_route_t& r, QkvP* q, const NormP* nm, hipStream_t s) {
+  for (int i = 0; i < r.n_launches; ++i) {
+    const p3v_gemm_launch_t& l = r.launch[i];
+    p3v_gemm_args_t v = *a;
+    if (l.rows != a->M) {
+      const bool f32_out = a->epilogue == P3V_EPI_BIAS_RESID_F32 || a->epilogue == P3V_EPI_F32;
+      const size_t out_row = (size_t)a->ldo * (f32_out ? 4 : 2);
+      v.M = l.rows;
+      v.A = a->A + (size_t)l.row0 * a->lda;
+      if (a->out) v.out = (char*)a->out + l.row0 * out_row;
+      if (a->resid) v.resid = (const char*)a->resid + l.row0 * out_row;
+    }
+    int rc = P3V_ERR_ARG;
+    switch (l.kernel) {
+      case P3V_GEMM_K_ROWS: rc = p3v_gemm_rows_launch(a, l, r.S, s); break;
+      case P3V_GEMM_K_SKINNY: rc = p3v_gemm_skinny_launch(a, l, r.S, s); break;
+      case P3V_GEMM_K_SKINNY_QKV: rc = p3v_gemm_skinny_qkv(a, *q, l, s); break;
+      case P3V_GEMM_K_128: rc = gemm128(&v, l, r.S, s); break;
+      case P3V_GEMM_K_256: rc = p3v_gemm256_launch(&v, l, s); break;
+      case P3V_GEMM_K_256_QKV: rc = p3v_gemm256_qkv(&v, *q, l, s); break;
+      case P3V_GEMM_K_128_QKV: {
+        q->m_base = l.row0;
+        const GemmP p = {v.A, a->W, nullptr, a->bias, nullptr, nullptr, v.M, a->N, a->K, a->lda, a->ldw, 0, 0, 0, *q};
+        rc = launch_gemm<P3V_EPI_QKV>(p, l, s);
+        break;
+      }
+      case P3V_GEMM_K_REDUCE: rc = splitk_reduce(a, l, r.S, s); break;
+      case P3V_GEMM_K_REDUCE_NORM:
+        hipLaunchKernelGGL(k_splitk_reduce_norm, dim3(l.grid[0]), dim3(l.block), 0, s, (const float*)a->ws, (bf16_t*)a->out, (const bf16_t*)a->resid,
+                           (const u32x4_t*)nm->w, (u32x4_t*)nm->normed, a->M, a->N, a->ldo, r.S, 1.0f / (float)a->N, nm->eps);
+        P3V_CHECK_LAUNCH();
+        rc = P3V_OK;
+        break;
+    }
+    if (rc != P3V_OK) return rc;
+  }
+  return P3V_OK;
+}
+
+static p3v_gemm_route_query_t gemm_query(int entry, const p3v_gemm_args_t* a) {
+  return {entry, a->M, a->N, a->K, a->lda, a->ldw, a->epilogue, a->bias != nullptr, a->ws ? a->ws_bytes : 0, 0, 0, 0, 0, 0, 0};
+}
+
+// ---- out = resid + bf16(A W^T) and normed = RMSNorm(out) (include/p3v.h): only where the route runs the projection as K slices
+extern "C" int p3v_gemm_resid_norm(const p3v_gemm_args_t* a, const uint16_t* norm_w, float eps, uint16_t* normed, void* stream) {
+  if (!a || !a->A || !a->W || !a->out || !a->resid || !norm_w || !normed) return P3V_ERR_ARG;
+  if (a->epilogue != P3V_EPI_RESID_BF16 || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->K % BK || a->N % 8 || a->ldo % 8 || a->ldo < a->N) return P3V_ERR_ARG;
+  if (a->lda < a->K || a->ldw < a->K || a->lda % 8 || a->ldw % 8) return P3V_ERR_ARG;
+  if (((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->out | (uintptr_t)a->resid | (uintptr_t)norm_w | (uintptr_t)normed | (uintptr_t)a->ws) & 15)
+    return P3V_ERR_ARG;
+  p3v_gemm_route_t r;
+  gemm_route(gemm_query(P3V_GEMM_ENTRY_RESID_NORM, a), r);
+  if (r.status != P3V_OK) return r.status;
+  const NormP nm = {norm_w, normed, eps};
+  return gemm_run(a, r, nullptr, &nm, (hipStream_t)stream);
 }
 
 extern "C" int p3v_gemm(const p3v_gemm_args_t* a, void* stream) {
@@ -533,96 +709,33 @@ extern "C" int p3v_gemm(const p3v_gemm_args_t* a, void* stream) {
   if (a->epilogue == P3V_EPI_PATCH && (!a->pos || a->patches_per_img <= 0)) return P3V_ERR_ARG;
   if (a->epilogue < 0 || a->epilogue > P3V_EPI_F32) return P3V_ERR_ARG;
   if (a->M == 0) return P3V_OK;
-  {                                                            // operands are addressed with 32-bit byte offsets (buffer loads)
-    const size_t w_rows = (size_t)a->N * (a->epilogue == P3V_EPI_SILU_MUL ? 2 : 1);
-    if ((size_t)a->M * a->lda * 2 >= (1ull << 32) || w_rows * a->ldw * 2 >= (1ull << 32)) return P3V_ERR_UNSUPPORTED;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (!a->bias) {                                              // 17 .. 256 rows: the weight-streaming kernel (p3v_gemm_skinny.hip)
-    const int rc = p3v_gemm_skinny_try(a, s);
-    if (rc != P3V_ERR_UNSUPPORTED) return rc;
-  }
-  {
-    const int rc = gemm_splitk(a, s);
-    if (rc != P3V_ERR_UNSUPPORTED) return rc;
-  }
-  const bool big_tiles = !p3v_tuning().gemm_128;
-  const int rows_big = big_tiles ? gemm_big_rows(a) : 0;
-  if (rows_big > 0) {
-    p3v_gemm_args_t top = *a;
-    top.M = rows_big;
-    const int rc = p3v_gemm256_try(&top, s);
-    if (rc == P3V_OK && rows_big < a->M) {
-      const bool f32_out = a->epilogue == P3V_EPI_BIAS_RESID_F32 || a->epilogue == P3V_EPI_F32;
-      const size_t out_row = (size_t)a->ldo * (f32_out ? 4 : 2);
-      p3v_gemm_args_t rest = *a;
-      rest.M = a->M - rows_big;
-      rest.A = a->A + (size_t)rows_big * a->lda;
-      rest.out = (char*)a->out + rows_big * out_row;
-      if (a->resid) rest.resid = (const char*)a->resid + rows_big * out_row;
-      return gemm128(&rest, s);
-    }
-    if (rc != P3V_ERR_UNSUPPORTED) return rc;
-  }
-  return gemm128(a, s);
+  p3v_gemm_route_t r;
+  gemm_route(gemm_query(P3V_GEMM_ENTRY_GEMM, a), r);
+  if (r.status != P3V_OK) return r.status;
+  if (r.S > 1 && ((uintptr_t)a->ws & 15)) return P3V_ERR_ARG;
+  return gemm_run(a, r, nullptr, nullptr, (hipStream_t)stream);
 }
 
-static int gemm128(const p3v_gemm_args_t* a, hipStream_t s) {
-  const GemmP p = {a->A, a->W, a->out, a->bias, a->resid, a->pos,
-                   a->M, a->N, a->K, a->lda, a->ldw, a->ldo, a->patches_per_img, 0, {}};
-  switch (a->epilogue) {
-    case P3V_EPI_NONE: return launch_gemm<P3V_EPI_NONE>(p, s);
-    case P3V_EPI_BIAS: return launch_gemm<P3V_EPI_BIAS>(p, s);
-    case P3V_EPI_BIAS_QGELU: return launch_gemm<P3V_EPI_BIAS_QGELU>(p, s);
-    case P3V_EPI_BIAS_GELU: return launch_gemm<P3V_EPI_BIAS_GELU>(p, s);
-    case P3V_EPI_BIAS_RESID_F32: return launch_gemm<P3V_EPI_BIAS_RESID_F32>(p, s);
-    case P3V_EPI_RESID_BF16: return launch_gemm<P3V_EPI_RESID_BF16>(p, s);
-    case P3V_EPI_SILU_MUL: return launch_gemm<P3V_EPI_SILU_MUL>(p, s);
-    case P3V_EPI_PATCH: return launch_gemm<P3V_EPI_PATCH>(p, s);
-    case P3V_EPI_F32: return launch_gemm<P3V_EPI_F32>(p, s);
-    default: return P3V_ERR_ARG;
-  }
-}
-
-// ---- the qkv projection with the head split, the rotation and the KV append in its epilogue (p3v_gemm_qkv.h)
-int p3v_gemm256_qkv(const p3v_gemm_args_t* a, const QkvP& q, hipStream_t s);   // p3v_gemm256.hip
-int p3v_gemm_skinny_qkv(const p3v_gemm_args_t* a, const QkvP& q, hipStream_t s);   // p3v_gemm_skinny.hip
-
+// ---- the qkv projection with the head split, the rotation and the KV append in its epilogue (p3v_gemm_qkv.h).  Where the route
+// reports P3V_ERR_UNSUPPORTED the caller runs p3v_gemm + p3v_rope_kv_append.
 extern "C" int p3v_gemm_qkv(const p3v_gemm_args_t* a, const p3v_qkv_split_t* sp, void* stream) {
   if (!a || !sp || !a->A || !a->W || !sp->q_out || !sp->k_dst || !sp->v_dst || (!sp->cos_t) != (!sp->sin_t)) return P3V_ERR_ARG;
   if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_BIAS) return P3V_ERR_ARG;
   if (a->epilogue == P3V_EPI_BIAS && !a->bias) return P3V_ERR_ARG;
-  const int nh = sp->n_heads, nkv = sp->n_kv, hd = sp->hd, half = hd / 2;
+  const int nh = sp->n_heads, nkv = sp->n_kv, hd = sp->hd;
   if (sp->B <= 0 || sp->L <= 0 || nh <= 0 || nkv <= 0 || hd <= 0 || sp->tab_div <= 0 || !(sp->q_scale > 0.f)) return P3V_ERR_ARG;
   if (a->M != sp->B * sp->L || a->N != (nh + 2 * nkv) * hd || a->K % BK || a->lda < a->K || a->ldw < a->K || a->lda % 8 || a->ldw % 8) return P3V_ERR_ARG;
   if (((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->bias | (uintptr_t)sp->q_out | (uintptr_t)sp->k_dst | (uintptr_t)sp->v_dst |
        (uintptr_t)sp->cos_t | (uintptr_t)sp->sin_t) & 15)
     return P3V_ERR_ARG;
-  // what the fused epilogue needs (anything else: P3V_ERR_UNSUPPORTED, the caller runs p3v_gemm + p3v_rope_kv_append):
-  // prompt-sized M; rotation pairs in blocks of 16 inside a head; whole 128-column tiles per region; an 8-aligned append offset
   const int dpos0 = sp->dst_off_is_past ? sp->past : 0;
   // (round 6: batch rows of any length -- the V^T runs are then stored at whatever offset they fall on, qkv_epilogue_vt)
-  if (hd % 32 || half % 16 || dpos0 % 8 || sp->dst_t % 8 || p3v_tuning().gemm_no_qkv_fuse) return P3V_ERR_UNSUPPORTED;
-  if ((size_t)a->M * a->lda * 2 >= (1ull << 32) || (size_t)a->N * a->ldw * 2 >= (1ull << 32)) return P3V_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
+  p3v_gemm_route_query_t rq = gemm_query(P3V_GEMM_ENTRY_QKV, a);
+  rq.n_heads = nh, rq.n_kv = nkv, rq.hd = hd, rq.dst_off = dpos0, rq.dst_t = sp->dst_t;
+  p3v_gemm_route_t r;
+  gemm_route(rq, r);
+  if (r.status != P3V_OK) return r.status;
   QkvP q = {sp->cos_t, sp->sin_t, sp->q_out, sp->k_dst, sp->v_dst, sp->L, nh, nkv, hd, sp->past, dpos0, sp->dst_t, sp->tab_t, sp->tab_div, 0,
             sp->q_scale};
-  if (a->M < 1024) return p3v_gemm_skinny_qkv(a, q, s);       // 17 .. 256 rows: the weight-streaming kernel (or "unsupported")
-  if ((nh * hd) % BN || (nkv * hd) % BN || p3v_tuning().gemm_128) return P3V_ERR_UNSUPPORTED;
-  p3v_gemm_args_t plain = *a;
-  plain.epilogue = P3V_EPI_NONE;                                // (the row packing below prices the plain bf16 epilogue)
-  int rows_big = (nh * hd) % 256 || (nkv * hd) % 256 ? 0 : gemm_big_rows(&plain);
-  if (rows_big > 0) {
-    p3v_gemm_args_t top = *a;
-    top.M = rows_big;
-    const int rc = p3v_gemm256_qkv(&top, q, s);
-    if (rc == P3V_ERR_UNSUPPORTED) rows_big = 0;
-    else if (rc != P3V_OK) return rc;
-  }
-  if (rows_big < a->M) {
-    q.m_base = rows_big;
-    const GemmP p = {a->A + (size_t)rows_big * a->lda, a->W, nullptr, a->bias, nullptr, nullptr, a->M - rows_big, a->N, a->K, a->lda, a->ldw, 0, 0, 0, q};
-    return launch_gemm<P3V_EPI_QKV>(p, s);
-  }
-  return P3V_OK;
+  return gemm_run(a, r, &q, nullptr, (hipStream_t)stream);
 }

@@ -270,57 +270,38 @@ __global__ void __launch_bounds__(512, 1) k_gemm256(Gemm256P p) {
   }                                                             // next tile of this workgroup
 }
 
-template <int EPI, int SCHED, int ORDER>
-static int launch_gemm256_v(const Gemm256P& p, hipStream_t s) {
+template <int EPI, int SCHED = 0x50, int ORDER = 2>
+static int launch_gemm256(const Gemm256P& p, const p3v_gemm_launch_t& l, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)k_gemm256<EPI, SCHED, ORDER>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM256_LDS) != hipSuccess)
       return P3V_ERR_HIP;
     attr_set = true;
   }
-  const int n_tile = EPI == P3V_EPI_SILU_MUL ? TN / 2 : TN;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
-    n_cu = pr.multiProcessorCount / 8 * 8;                        // persistent grid: one workgroup per CU, a multiple of 8 (XCDs)
-  }
-  const int tiles = p3v_cdiv(p.N, n_tile) * p3v_cdiv(p.M, TM);
-  const int persist = p3v_tuning().gemm_persistent;                // 0: one workgroup per tile (round 2), else the persistent loop
-  dim3 grid(persist ? min(tiles, n_cu) : tiles);
-  hipLaunchKernelGGL((k_gemm256<EPI, SCHED, ORDER>), grid, dim3(512), GEMM256_LDS, s, p);
+  // the route's grid: one workgroup per tile, or the persistent loop's one per CU (a multiple of 8: XCDs)
+  hipLaunchKernelGGL((k_gemm256<EPI, SCHED, ORDER>), dim3(l.grid[0]), dim3(512), GEMM256_LDS, s, p);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }
 
-template <int EPI>
-static int launch_gemm256(const Gemm256P& p, hipStream_t s) { return launch_gemm256_v<EPI, 0x50, 2>(p, s); }
-
 // the qkv projection with split + RoPE + KV append in the epilogue (p3v_gemm_qkv, p3v_gemm.hip): rows of `a` on big tiles
-int p3v_gemm256_qkv(const p3v_gemm_args_t* a, const QkvP& q, hipStream_t s) {
-  if (a->N % TN || a->K % TK || (q.nh * q.hd) % TN || (q.nkv * q.hd) % TN) return P3V_ERR_UNSUPPORTED;
-  if ((size_t)a->N * a->ldw * 2 >= ((size_t)1 << 32) || (size_t)a->M * a->lda * 2 >= ((size_t)1 << 32)) return P3V_ERR_UNSUPPORTED;
+int p3v_gemm256_qkv(const p3v_gemm_args_t* a, const QkvP& q, const p3v_gemm_launch_t& l, hipStream_t s) {
   const Gemm256P p = {a->A, a->W, nullptr, a->bias, nullptr, a->M, a->N, a->K, a->lda, a->ldw, 0, q};
-  return launch_gemm256<P3V_EPI_QKV>(p, s);
+  return launch_gemm256<P3V_EPI_QKV>(p, l, s);
 }
 
-// called by p3v_gemm (which decides how many rows get the big tile); returns P3V_ERR_UNSUPPORTED to fall back
-int p3v_gemm256_try(const p3v_gemm_args_t* a, hipStream_t s) {
-  const int n_tile = a->epilogue == P3V_EPI_SILU_MUL ? TN / 2 : TN;
-  if (a->N % n_tile || a->K % TK || a->epilogue == P3V_EPI_PATCH) return P3V_ERR_UNSUPPORTED;
-  const size_t w_rows = (size_t)a->N * (a->epilogue == P3V_EPI_SILU_MUL ? 2 : 1);
-  if (w_rows * a->ldw * 2 >= ((size_t)1 << 32) || (size_t)256 * a->lda * 2 >= ((size_t)1 << 31)) return P3V_ERR_UNSUPPORTED;  // 32-bit buffer offsets
+// the rows the route gave the big tiles (any epilogue but P3V_EPI_PATCH, which the route keeps on the 128 x 128 kernel)
+int p3v_gemm256_launch(const p3v_gemm_args_t* a, const p3v_gemm_launch_t& l, hipStream_t s) {
   const Gemm256P p = {a->A, a->W, a->out, a->bias, a->resid, a->M, a->N, a->K, a->lda, a->ldw, a->ldo, {}};
   switch (a->epilogue) {
-    case P3V_EPI_NONE: return launch_gemm256<P3V_EPI_NONE>(p, s);
-    case P3V_EPI_BIAS: return launch_gemm256<P3V_EPI_BIAS>(p, s);
-    case P3V_EPI_BIAS_QGELU: return launch_gemm256<P3V_EPI_BIAS_QGELU>(p, s);
-    case P3V_EPI_BIAS_GELU: return launch_gemm256<P3V_EPI_BIAS_GELU>(p, s);
-    case P3V_EPI_BIAS_RESID_F32: return launch_gemm256<P3V_EPI_BIAS_RESID_F32>(p, s);
-    case P3V_EPI_RESID_BF16: return launch_gemm256<P3V_EPI_RESID_BF16>(p, s);
-    case P3V_EPI_SILU_MUL: return launch_gemm256<P3V_EPI_SILU_MUL>(p, s);
-    case P3V_EPI_F32: return launch_gemm256<P3V_EPI_F32>(p, s);
-    default: return P3V_ERR_UNSUPPORTED;
+    case P3V_EPI_NONE: return launch_gemm256<P3V_EPI_NONE>(p, l, s);
+    case P3V_EPI_BIAS: return launch_gemm256<P3V_EPI_BIAS>(p, l, s);
+    case P3V_EPI_BIAS_QGELU: return launch_gemm256<P3V_EPI_BIAS_QGELU>(p, l, s);
+    case P3V_EPI_BIAS_GELU: return launch_gemm256<P3V_EPI_BIAS_GELU>(p, l, s);
+    case P3V_EPI_BIAS_RESID_F32: return launch_gemm256<P3V_EPI_BIAS_RESID_F32>(p, l, s);
+    case P3V_EPI_RESID_BF16: return launch_gemm256<P3V_EPI_RESID_BF16>(p, l, s);
+    case P3V_EPI_SILU_MUL: return launch_gemm256<P3V_EPI_SILU_MUL>(p, l, s);
+    case P3V_EPI_F32: return launch_gemm256<P3V_EPI_F32>(p, l, s);
+    default: return P3V_ERR_ARG;
   }
 }

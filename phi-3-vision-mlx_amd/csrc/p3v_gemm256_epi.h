@@ -1,8 +1,6 @@
 // Shared by the two 256 x 256-tile GEMM kernels (p3v_gemm256.hip, p3v_gemm256pp.hip): launch parameters and the epilogue.
 #pragma once
-#include "p3v_gemm_qkv.h"
-
-#define P3V_EPI_QKV 100                // internal: the qkv projection with split + RoPE + KV append in the epilogue (p3v_gemm_qkv.h)
+#include "p3v_gemm_route.h"
 
 #define TM 256
 #define TN 256

@@ -14,13 +14,13 @@
 //     per 12 KB of weights at 32 rows), and the two halves are added IN the lane (no DPP, no LDS);
 //   * a workgroup walks `sets` of 16 output columns (SiLU: 8 gate + the 8 matching up rows), the whole K slice of the NEXT set being
 //     requested stage by stage as the current one is consumed; the K quarters of a set meet in a double-buffered LDS block (one
-//     barrier per set), where the epilogue -- none / residual / SiLU * up, or fp32 K-slice partials for p3v_splitk_reduce /
+//     barrier per set), where the epilogue -- none / residual / SiLU * up, or fp32 K-slice partials for k_splitk_reduce /
 //     k_splitk_reduce_norm -- is applied with k_gemv_mfma8's arithmetic;
 //   * no LDS for operands, so nothing limits M x K but registers: K = 3072 in one pass up to 32 rows (qkv, gate_up); o_proj and down
 //     (192 sets of 16 columns each) run as 4 K slices x 64 workgroups so that all 256 CUs stream (their reduction launch exists
 //     anyway: it also writes the next RMSNorm).
 // The RMSNorm of the input is the caller's (at these M the model runs it in the previous projection's reduction launch).
-#include "p3v_common.h"
+#include "p3v_gemm_route.h"
 
 struct RowsP {
   const bf16_t* x; const bf16_t* W; void* out; const bf16_t* resid; float* part;
@@ -160,47 +160,27 @@ __global__ void __launch_bounds__(NW * 64, 1) k_gemm_rows(RowsP p) {
   do_set(std::false_type{});
 }
 
-// ---- shapes: K slices S and the (waves, stages) of a workgroup's slice.  0 = not this kernel's.
-struct RowsPlan { int S, NW, NST; };
-static RowsPlan rows_plan(int M, int N, int K, int epilogue) {
-  const P3vTuning& t = p3v_tuning();
-  const bool silu = epilogue == P3V_EPI_SILU_MUL;
-  RowsPlan none = {0, 0, 0};
-  if (!t.gemm_rows || M <= 8 || M > 32 || N % (silu ? 8 : 16)) return none;
-  if (epilogue != P3V_EPI_NONE && epilogue != P3V_EPI_RESID_BF16 && !silu) return none;
-  const int n_sets = N / (silu ? 8 : 16);
-  if (K == 3072) return n_sets >= 512 ? RowsPlan{1, 4, 3} : RowsPlan{4, 3, 1};     // qkv / gate_up in one pass; o_proj: 4 slices of 768
-  if (K == 8192) return RowsPlan{4, 4, 2};                                          // down: 4 slices of 2048
-  return none;
-}
-
-extern "C" int p3v_gemm_rows_slices(int M, int N, int K, int epilogue) { return rows_plan(M, N, K, epilogue).S; }
-
+// The route's grid: workgroups along N -- all of a one-pass launch's CUs, a quarter of them per K slice otherwise (a workgroup's x
+// quarter is loaded once and amortised over its sets: fewer, longer workgroups keep the x traffic from L2 below the weight bytes).
 template <bool SILU, int NW, int NST, int MT, bool PART>
-static int launch_rows(const RowsP& p, int S, hipStream_t s) {
-  // workgroups along N: all of a one-pass launch's CUs, a quarter of them per K slice otherwise (a workgroup's x quarter is loaded once
-  // and amortised over its sets: fewer, longer workgroups keep the x traffic from L2 below the weight bytes)
-  const int max_wg = p3v_cdiv(256, S);
-  const int per = p3v_cdiv(p.n_sets, max_wg), gx = p3v_cdiv(p.n_sets, per);
-  hipLaunchKernelGGL((k_gemm_rows<SILU, NW, NST, MT, PART>), dim3(gx, S), dim3(NW * 64), 0, s, p);
+static int launch_rows(const RowsP& p, const p3v_gemm_launch_t& l, hipStream_t s) {
+  hipLaunchKernelGGL((k_gemm_rows<SILU, NW, NST, MT, PART>), dim3(l.grid[0], l.grid[1]), dim3(NW * 64), 0, s, p);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }
 
 template <bool SILU, int NW, int NST, bool PART>
-static int launch_rows_mt(const RowsP& p, int S, hipStream_t s) {
-  return p.M <= 16 ? launch_rows<SILU, NW, NST, 1, PART>(p, S, s) : launch_rows<SILU, NW, NST, 2, PART>(p, S, s);
+static int launch_rows_mt(const RowsP& p, const p3v_gemm_launch_t& l, hipStream_t s) {
+  return l.tile_m == 16 ? launch_rows<SILU, NW, NST, 1, PART>(p, l, s) : launch_rows<SILU, NW, NST, 2, PART>(p, l, s);
 }
 
-// one pass with the epilogue (S == 1), or the K-slice partials alone (part != nullptr): P3V_ERR_UNSUPPORTED when the shape is not planned
-int p3v_gemm_rows_launch(const p3v_gemm_args_t* a, float* part, hipStream_t s) {
-  const RowsPlan pl = rows_plan(a->M, a->N, a->K, a->epilogue);
-  if (pl.S == 0 || a->bias || (pl.S > 1) != (part != nullptr)) return P3V_ERR_UNSUPPORTED;
+// one pass with the epilogue (S == 1), or the K-slice partials alone into a->ws.  The (waves, stages) of a workgroup's slice follow
+// the route's block: 4 x 3 for K = 3072 in one pass, 3 x 1 for its 4 slices of 768, 4 x 2 for the 4 slices of K = 8192.
+int p3v_gemm_rows_launch(const p3v_gemm_args_t* a, const p3v_gemm_launch_t& l, int S, hipStream_t s) {
   const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-  const RowsP p = {a->A, a->W, a->out, (const bf16_t*)a->resid, part, a->M, a->N, a->K, a->lda, a->ldw, a->ldo, a->epilogue,
-                   a->N / (silu ? 8 : 16), silu ? 2 * a->N : a->N};
-  if (pl.S == 1) return silu ? launch_rows_mt<true, 4, 3, false>(p, 1, s) : launch_rows_mt<false, 4, 3, false>(p, 1, s);
-  if (silu) return P3V_ERR_UNSUPPORTED;                          // (no planned shape splits a SiLU projection)
-  if (pl.NW == 3) return launch_rows_mt<false, 3, 1, true>(p, pl.S, s);
-  return launch_rows_mt<false, 4, 2, true>(p, pl.S, s);
+  const RowsP p = {a->A, a->W, a->out, (const bf16_t*)a->resid, S > 1 ? (float*)a->ws : nullptr, a->M, a->N, a->K, a->lda, a->ldw, a->ldo,
+                   a->epilogue, a->N / (silu ? 8 : 16), silu ? 2 * a->N : a->N};
+  if (S == 1) return silu ? launch_rows_mt<true, 4, 3, false>(p, l, s) : launch_rows_mt<false, 4, 3, false>(p, l, s);
+  if (l.block == 3 * 64) return launch_rows_mt<false, 3, 1, true>(p, l, s);
+  return launch_rows_mt<false, 4, 2, true>(p, l, s);
 }

@@ -20,7 +20,7 @@
 //   K slices  gridDim.z; fp32 partials [S, M, ldp] in the caller's workspace, added in slice order by k_splitk_reduce (p3v_gemm.hip)
 // (tools/scratch/gemm_skinny_regw_r5.hip: the variant that keeps each wave's W fragments out of LDS -- global loads straight into a
 // register ring 8 K-tiles deep, A alone through LDS -- measured slower on every shape: profiles/r05_skinny_gemm.txt.)
-#include "p3v_gemm_qkv.h"
+#include "p3v_gemm_route.h"
 
 #define SK_BM 128
 #define SK_BK 64
@@ -70,8 +70,6 @@ struct SkinnyP {
   int kslice;                      // 0: one pass with the epilogue; else K columns per slice, fp32 partials
   QkvP q;                          // P3V_EPI_QKV only (p3v_gemm_qkv.h): head split + rotation + KV append in the epilogue
 };
-
-#define P3V_EPI_QKV 100            // internal, as in the other GEMM kernels
 
 template <int EPI, bool PART, int TN, int TM = SK_BM>
 __global__ void __launch_bounds__(512, 1) k_gemm_skinny(SkinnyP p) {
@@ -303,101 +301,40 @@ __global__ void __launch_bounds__(512, 1) k_gemm_skinny(SkinnyP p) {
   }
 }
 
-// K slices for a shape on this kernel: 0 = not one of its shapes; 1 = one pass; S > 1 = S slices + the reduction launch.
-// One workgroup per CU: the largest S <= 8 whose tiles * S still fit one round of the chip (slices of >= 6 K-tiles).
-extern "C" int p3v_gemm_rows_slices(int M, int N, int K, int epilogue);            // p3v_gemm_rows.hip: 9 .. 32 rows, weights straight to registers
-int p3v_gemm_rows_launch(const p3v_gemm_args_t* a, float* part, hipStream_t s);
-static int sk_slices(int M, int N, int K, int epilogue);
-int p3v_gemm_skinny_slices(int M, int N, int K, int epilogue) {
-  const int rs = p3v_gemm_rows_slices(M, N, K, epilogue);
-  return rs ? rs : sk_slices(M, N, K, epilogue);
-}
-static int sk_slices(int M, int N, int K, int epilogue) {
-  const P3vTuning& t = p3v_tuning();
-  const bool silu = epilogue == P3V_EPI_SILU_MUL;
-  if (t.gemm_no_skinny || M <= 8 || M > t.gemm_skinny_max_m || K % SK_BK || N % (silu ? 32 : 64)) return 0;
-  if (epilogue != P3V_EPI_NONE && epilogue != P3V_EPI_RESID_BF16 && !silu) return 0;
-  const int tiles = p3v_cdiv(M, SK_BM) * ((silu ? 2 * N : N) / SK_TN);
-  if (t.gemm_skinny_s > 0) return K % (t.gemm_skinny_s * SK_BK) ? 1 : t.gemm_skinny_s;
-  int best = 1;
-  for (int S = 2; S <= 8; ++S)
-    if (K % (S * SK_BK) == 0 && K / S >= 6 * SK_BK && tiles * S <= t.gemm_splitk_wgs) best = S;
-  return best;
-}
-
 template <int EPI, int TM>
-static int launch_skinny_tm(const SkinnyP& p, int S, hipStream_t s) {
+static int launch_skinny_tm(const SkinnyP& p, const p3v_gemm_launch_t& l, hipStream_t s) {
   typedef SkCfg<SK_TN, TM> C;
   static bool attr_set[2] = {false, false};
-  const bool part = S > 1;
+  const bool part = p.kslice != 0;
   if (!attr_set[part]) {
     const void* fn = part ? (const void*)k_gemm_skinny<EPI, true, SK_TN, TM> : (const void*)k_gemm_skinny<EPI, false, SK_TN, TM>;
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess) return P3V_ERR_HIP;
     attr_set[part] = true;
   }
-  const int n_tile = EPI == P3V_EPI_SILU_MUL ? SK_TN / 2 : SK_TN;
-  const dim3 grid(p.N / n_tile, p3v_cdiv(p.M, TM), S);
+  const dim3 grid(l.grid[0], l.grid[1], l.grid[2]);
   if (part) hipLaunchKernelGGL((k_gemm_skinny<EPI, true, SK_TN, TM>), grid, dim3(512), C::LDS, s, p);
   else hipLaunchKernelGGL((k_gemm_skinny<EPI, false, SK_TN, TM>), grid, dim3(512), C::LDS, s, p);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }
-// <= 64 rows: 64-row tiles (the A panel is two thirds of what a 128-row tile stages per K-tile; half of it would be clamped copies)
+// the route gives <= 64 rows 64-row tiles (the A panel is two thirds of what a 128-row tile stages per K-tile; half of it would be
+// clamped copies)
 template <int EPI>
-static int launch_skinny(const SkinnyP& p, int S, hipStream_t s) {
-  return p.M <= 64 && !p3v_tuning().gemm_skinny_tm128 ? launch_skinny_tm<EPI, 64>(p, S, s) : launch_skinny_tm<EPI, SK_BM>(p, S, s);
+static int launch_skinny(const SkinnyP& p, const p3v_gemm_launch_t& l, hipStream_t s) {
+  return l.tile_m == 64 ? launch_skinny_tm<EPI, 64>(p, l, s) : launch_skinny_tm<EPI, SK_BM>(p, l, s);
 }
 
-int p3v_splitk_reduce(const float* part, const p3v_gemm_args_t* a, int S, hipStream_t s);   // p3v_gemm.hip
-
-// the K-slice launch alone (fp32 partials into a->ws; *S_out slices): P3V_ERR_UNSUPPORTED, nothing launched, unless the shape is
-// one this kernel splits and the workspace holds the partials
-int p3v_gemm_skinny_partials(const p3v_gemm_args_t* a, int* S_out, hipStream_t s) {
-  const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-  const int w_rows = silu ? 2 * a->N : a->N;
-  const int RS = a->bias ? 0 : p3v_gemm_rows_slices(a->M, a->N, a->K, a->epilogue);
-  if (RS > 1 && a->ws && a->ws_bytes >= (int64_t)RS * a->M * w_rows * 4) {        // 9 .. 32 rows: the register-streaming kernel's K slices
-    if ((uintptr_t)a->ws & 15) return P3V_ERR_ARG;
-    *S_out = RS;
-    return p3v_gemm_rows_launch(a, (float*)a->ws, s);
-  }
-  if (RS == 1) return P3V_ERR_UNSUPPORTED;                       // (runs in one pass: no partials)
-  const int S = sk_slices(a->M, a->N, a->K, a->epilogue);
-  if (S <= 1 || !a->ws || a->ws_bytes < (int64_t)S * a->M * w_rows * 4) return P3V_ERR_UNSUPPORTED;
-  if ((uintptr_t)a->ws & 15) return P3V_ERR_ARG;
-  *S_out = S;
-  const SkinnyP p = {a->A, a->W, a->ws, a->resid, a->M, a->N, a->K, a->lda, a->ldw, a->ldo, a->K / S, {}};
-  if (silu) return launch_skinny<P3V_EPI_SILU_MUL>(p, S, s);
-  if (a->epilogue == P3V_EPI_RESID_BF16) return launch_skinny<P3V_EPI_RESID_BF16>(p, S, s);
-  return launch_skinny<P3V_EPI_NONE>(p, S, s);
-}
-
-// P3V_ERR_UNSUPPORTED: not a shape for this kernel (the caller goes on to the other GEMM paths).  A split that finds no workspace of
-// p3v_gemm_ws_bytes() runs as one pass.
-int p3v_gemm_skinny_try(const p3v_gemm_args_t* a, hipStream_t s) {
-  if (p3v_gemm_skinny_slices(a->M, a->N, a->K, a->epilogue) == 0) return P3V_ERR_UNSUPPORTED;
-  if (p3v_gemm_rows_slices(a->M, a->N, a->K, a->epilogue) == 1) {                  // 9 .. 32 rows, one pass
-    const int rr = p3v_gemm_rows_launch(a, nullptr, s);
-    if (rr != P3V_ERR_UNSUPPORTED) return rr;
-  }
-  int S = 1;
-  const int rc = p3v_gemm_skinny_partials(a, &S, s);
-  if (rc == P3V_OK) return p3v_splitk_reduce((const float*)a->ws, a, S, s);
-  if (rc != P3V_ERR_UNSUPPORTED) return rc;
-  if (sk_slices(a->M, a->N, a->K, a->epilogue) == 0) return P3V_ERR_UNSUPPORTED;   // (a rows shape whose slices found no workspace and that the tile kernel does not take)
-  const SkinnyP p = {a->A, a->W, a->out, a->resid, a->M, a->N, a->K, a->lda, a->ldw, a->ldo, 0, {}};
-  if (a->epilogue == P3V_EPI_SILU_MUL) return launch_skinny<P3V_EPI_SILU_MUL>(p, 1, s);
-  if (a->epilogue == P3V_EPI_RESID_BF16) return launch_skinny<P3V_EPI_RESID_BF16>(p, 1, s);
-  return launch_skinny<P3V_EPI_NONE>(p, 1, s);
+// one pass with the epilogue (S == 1), or the K-slice launch alone: fp32 partials into a->ws
+int p3v_gemm_skinny_launch(const p3v_gemm_args_t* a, const p3v_gemm_launch_t& l, int S, hipStream_t s) {
+  const SkinnyP p = {a->A, a->W, S > 1 ? a->ws : a->out, a->resid, a->M, a->N, a->K, a->lda, a->ldw, a->ldo, S > 1 ? a->K / S : 0, {}};
+  if (a->epilogue == P3V_EPI_SILU_MUL) return launch_skinny<P3V_EPI_SILU_MUL>(p, l, s);
+  if (a->epilogue == P3V_EPI_RESID_BF16) return launch_skinny<P3V_EPI_RESID_BF16>(p, l, s);
+  return launch_skinny<P3V_EPI_NONE>(p, l, s);
 }
 
 // ---- the qkv projection of a short prompt with the head split, the rotation and the KV append in the epilogue (p3v_gemm_qkv's
-// 17 .. 256-row case): one pass (the epilogue needs whole sums), Q / K tiles + V tiles in a one-dimensional grid.
-// P3V_ERR_UNSUPPORTED (nothing launched) where the shape is not this kernel's.
-int p3v_gemm_skinny_qkv(const p3v_gemm_args_t* a, const QkvP& q, hipStream_t s) {
-  const P3vTuning& t = p3v_tuning();
-  if (t.gemm_no_skinny || a->M <= 8 || a->M > t.gemm_skinny_max_m || a->K % SK_BK || a->bias) return P3V_ERR_UNSUPPORTED;
-  if ((q.nh * q.hd) % 64 || (q.nkv * q.hd) % SK_BM) return P3V_ERR_UNSUPPORTED;   // whole Q / K tiles of 32 pairs, whole V tiles of 128 dims
+// 9 .. 256-row case): one pass (the epilogue needs whole sums), Q / K tiles + V tiles in a one-dimensional grid.
+int p3v_gemm_skinny_qkv(const p3v_gemm_args_t* a, const QkvP& q, const p3v_gemm_launch_t& l, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)k_gemm_skinny<P3V_EPI_QKV, false, SK_TN>, hipFuncAttributeMaxDynamicSharedMemorySize, SkCfg<SK_TN>::LDS) != hipSuccess)
@@ -405,8 +342,7 @@ int p3v_gemm_skinny_qkv(const p3v_gemm_args_t* a, const QkvP& q, hipStream_t s) 
     attr_set = true;
   }
   const SkinnyP p = {a->A, a->W, nullptr, nullptr, a->M, a->N, a->K, a->lda, a->ldw, 0, 0, q};
-  const int mt = p3v_cdiv(a->M, SK_BM), tiles = ((q.nh + q.nkv) * q.hd / 64) * mt + (q.nkv * q.hd / SK_BM) * p3v_cdiv(a->M, 64);
-  hipLaunchKernelGGL((k_gemm_skinny<P3V_EPI_QKV, false, SK_TN>), dim3(tiles), dim3(512), SkCfg<SK_TN>::LDS, s, p);
+  hipLaunchKernelGGL((k_gemm_skinny<P3V_EPI_QKV, false, SK_TN>), dim3(l.grid[0]), dim3(512), SkCfg<SK_TN>::LDS, s, p);
   P3V_CHECK_LAUNCH();
   return P3V_OK;
 }

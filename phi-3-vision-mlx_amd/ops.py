@@ -134,6 +134,18 @@ def gemm(a, w, epilogue=EPI_NONE, bias=None, resid=None, out=None, n_out=None, p
     return out
 
 
+def gemm_route(M, N, K, epilogue=EPI_NONE, entry=L.GEMM_ENTRY_GEMM, lda=None, ldw=None, has_bias=False, ws_bytes=0, n_heads=0, n_kv=0,
+               hd=0, dst_off=0, dst_t=0, cu_count=0):
+    """What `gemm` (entry: `gemm_resid_norm`, `gemm_qkv`) launches for this call -> L.GemmRoute: status, the launches in order (kernel,
+    name, grid, block, rows), the K slices and the workspace they need (include/p3v.h: p3v_gemm_route).  The gemm_* knobs are the
+    library's settings; with `cu_count` given no device is asked."""
+    q = L.GemmRouteQuery(entry, M, N, K, K if lda is None else lda, K if ldw is None else ldw, epilogue, int(bool(has_bias)), ws_bytes,
+                         n_heads, n_kv, hd, dst_off, dst_t, cu_count)
+    r = L.GemmRoute()
+    L.check(L.lib().p3v_gemm_route(C.byref(q), C.byref(r)), "gemm_route")
+    return r
+
+
 def gemm_resid_norm(a, w, resid, norm_w, eps, normed, out=None):
     """out = resid + bf16(a @ w^T) and normed = RMSNorm(out) * norm_w from the projection's own launch sequence (the K-slice GEMM +
     ONE reduction launch that also normalises).  Returns False, nothing launched, where the library does not split the shape

@@ -158,7 +158,7 @@ def _gemm_cases():
             N = N // 2 if epi == SILU and N == 256 else N
             c.append(Case("k_gemm" if rows < 0 else "k_gemm256" if rows > 512 else "k_gemm256+k_gemm", 1030, N, K, epi,
                           knobs=(("gemm_big_rows", rows), ("gemm_128", 0)), slices=1, ld=(e + t) % 3 == 1, tag=name))
-    # split-K on k_gemm + k_splitk_reduce: S = 4 at K = 512, 8 at K = 1024 and 1536 (splitk_slices)
+    # split-K on k_gemm + k_splitk_reduce: S = 4 at K = 512, 8 at K = 1024 and 1536 (gemm_slices)
     sk = (("gemm_no_skinny", 1), ("gemm_no_splitk", 0), ("gemm_128", 1))
     for M, N, K, epi, S, ld in ((17, 128, 512, NONE, 4, False), (129, 256, 1024, RESID_BF16, 8, True), (300, 128, 1536, SILU, 8, False),
                                 (129, 128, 512, SILU, 4, True), (300, 256, 512, RESID_BF16, 4, False), (17, 256, 1536, NONE, 8, True)):

@@ -22,6 +22,9 @@ int main() {
   EXPECT(p3v_attention_ws_bytes(1, 64, 32, 96, 4) == 0);
   EXPECT(p3v_gemm_ws_bytes(128, 3072, 3072, P3V_EPI_NONE) >= 0);
   EXPECT(p3v_gemm_ws_bytes(0, 3072, 3072, P3V_EPI_NONE) == 0);
+  p3v_gemm_route_query_t rq = {P3V_GEMM_ENTRY_GEMM, 128, 3072, 8192, 8192, 8192, P3V_EPI_RESID_BF16, 0, 0, 0, 0, 0, 0, 0, 256};
+  p3v_gemm_route_t rt;
+  EXPECT(p3v_gemm_route(&rq, &rt) == P3V_OK && rt.status == P3V_OK && rt.n_launches == 1 && rt.S == 1 && rt.ws_bytes > 0 && rt.ws_short == 1);
   // tuning table: names are matched as C strings
   int v = -123;
   EXPECT(p3v_get_tuning("gemm_persistent", &v) == P3V_OK);
