@@ -236,7 +236,10 @@ int p3v_gemm_resid_norm(const p3v_gemm_args_t* gemm /* host */, const uint16_t* 
  *      GEMM's launches alone (phi.py:437-452 / 140-147: `qkv_proj` + `split` + `_rotate_half` + KVCache append; CLIP: q/k/v projections
  *      + head split).  g: A [B*L, K], W [(nh + 2 nkv) * hd, K] (q rows, k rows, v rows), epilogue P3V_EPI_NONE or P3V_EPI_BIAS; out /
  *      resid / ws unused.  P3V_ERR_UNSUPPORTED (nothing launched) wherever the route (p3v_gemm_route, entry P3V_GEMM_ENTRY_QKV)
- *      says so -- callers then run the two calls. */
+ *      says so -- callers then run the two calls.  Batch rows of ANY length: B * L > 8 is all the route asks of B and L, every token
+ *      lands at its own (b, l) however many row ends an 8-token V^T run crosses (L < 8), and nothing outside q_out, k_dst[.., dst_off ..
+ *      dst_off + L, :] and v_dst[.., :, dst_off .. dst_off + L] is written.  Heads of 32, 64, 96 and 128 dimensions (p3v_rope_kv_append
+ *      stops at 96: at 128 there are no two calls to compare with). */
 typedef struct {
   const float* cos_t; const float* sin_t;          /* as p3v_rope_kv_append; both null: plain head split */
   uint16_t* q_out; uint16_t* k_dst; uint16_t* v_dst;

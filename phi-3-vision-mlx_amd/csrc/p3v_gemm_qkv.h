@@ -10,6 +10,8 @@
 //     tile's A side, the tokens its B side (the tile is square and the K loop does not care) -- so a lane holds 4 consecutive TOKENS of
 //     one V dimension, and 8 after the v_permlane16_swap: one 16-byte store into a V^T row (rows whose length is not a multiple of 8
 //     -- CLIP's 577-token crops -- shift the run inside the row: still one dwordx4 store at even offsets, three stores at odd ones).
+//     A run that crosses a batch-row end, or the end of the prompt, goes out token by token, EACH token at its own (b, l): rows of any
+//     length L >= 1 -- a run spans two rows at L >= 8 and up to eight at L = 1 (tests/test_qkv_kernels_gpu.py: B x L = 16 x 1, 3 x 3, 5 x 5).
 // Arithmetic: exactly p3v_gemm's + p3v_rope_kv_append's (the Linear output rounded to bf16, rotation in fp32 on those values,
 // q_scale before the one rounding): bit-identical to the two launches (tests/test_kernels_gpu.py::test_gemm_qkv_fused).
 #pragma once
@@ -161,10 +163,10 @@ __device__ __forceinline__ void qkv_epilogue_vt(const QkvP& q, f32x4_t (&acc)[NI
             *(u32x3_a4*)(dst + 1) = mid;
             dst[7] = (bf16_t)(w[3] >> 16);
           }
-        } else {                                               // the ragged end of the prompt, or a run across two batch rows
-          for (int e = 0; e < 8 && t + e < M; ++e) {
+        } else {                                               // the ragged end of the prompt, or a run across batch rows: one row end
+          for (int e = 0; e < 8 && t + e < M; ++e) {           // at L >= 8, up to eight of them at L = 1 -- each token finds its own row
             int le = l + e, be = b;
-            if (le >= q.L) { le -= q.L; ++be; }
+            while (le >= q.L) { le -= q.L; ++be; }
             q.v_dst[(((size_t)be * q.nkv + head) * q.hd + d) * (size_t)q.dst_t + q.dpos0 + le] = (bf16_t)(w[e >> 1] >> (16 * (e & 1)));
           }
         }

@@ -843,8 +843,9 @@ def test_gemm_qkv_fused(ops, B, L, nh, nkv, hd, K, past, rot, bias, big):
     T = past + L + 5
     Tp = (T + 127) // 128 * 128
     half = hd // 2
-    cos = torch.rand((B, T, half), device="cuda") if rot else None
-    sin = torch.rand((B, T, half), device="cuda") if rot else None
+    tab = torch.Generator().manual_seed(405)                # (drawn on the host: a failure can be reproduced)
+    cos = torch.rand((B, T, half), generator=tab).cuda() if rot else None
+    sin = torch.rand((B, T, half), generator=tab).cuda() if rot else None
     qs = 1.3
     k0, v0 = g((B, nkv, Tp, hd), 403).cuda(), g((B, nkv, hd, Tp), 404).cuda()
     pinned = ops.set_tuning("gemm_big_rows", big)
