@@ -333,6 +333,37 @@ int p3v_attention(const p3v_attn_args_t* args /* host */, void* stream);
 /* bytes of workspace p3v_attention needs for the decode (L<=P3V_DECODE_MAX_L) path */
 int64_t p3v_attention_ws_bytes(int B, int L, int n_heads, int hd, int n_split);
 #define P3V_DECODE_MAX_L 16
+/* ---- p3v_attention's route: which kernel a call launches, with what grid, block and dynamic LDS, and whether a merge launch
+ * follows -- p3v_attention asks this one function and launches what it says (host-only, no launch).  It depends on no device
+ * property and touches no device (tests/test_attn_prompt_route_cpu.py).  A negative knob means the library's current setting
+ * (p3v_set_tuning), which for attn_pp, attn_il, attn_il_waves and combine_g may itself be -1: by shape. */
+typedef enum {
+  P3V_ATTN_PK_NONE = -1,        /* nothing is launched: a refused call, or B * L == 0 */
+  P3V_ATTN_PK_ATTN = 0,         /* k_attn: 64 queries per workgroup; split mode (L <= P3V_DECODE_MAX_L, n_split > 1) and attn_old */
+  P3V_ATTN_PK_PREFILL,          /* k_attn_prefill: 128 queries, tiles through registers: keys outside the cache, ragged capacity */
+  P3V_ATTN_PK_DMA,              /* k_attn_prefill_dma: 128 queries, LDS-DMA tiles */
+  P3V_ATTN_PK_PP,               /* k_attn_prefill_pp: 256 queries, ping-pong wave groups */
+  P3V_ATTN_PK_IL4,              /* k_attn_prefill_il<hd, 4>: interleaved, 128 queries (pre-scaled Q only) */
+  P3V_ATTN_PK_IL8,              /* k_attn_prefill_il<hd, 8>: interleaved, 256 queries */
+  P3V_ATTN_PK_COUNT
+} p3v_attn_prompt_kernel_t;
+typedef struct {
+  int B, L, n_heads, n_kv, hd, past, past_t, n_split, new_is_cache, q_prescaled;   /* as in p3v_attn_args_t */
+  int has_ws;                   /* nonzero: the call brings a workspace */
+  int attn_old, attn_no_dma, attn_pp, attn_il, attn_il_waves, combine_g;            /* the tuning knobs the route depends on */
+} p3v_attn_prompt_query_t;
+typedef struct {
+  int status;                   /* what p3v_attention returns for these fields: P3V_OK, P3V_ERR_UNSUPPORTED (hd), P3V_ERR_ARG */
+  int kernel;                   /* p3v_attn_prompt_kernel_t */
+  int grid[3], block;
+  int lds_bytes;                /* dynamic LDS of the launch (0: k_attn) */
+  int head_group;               /* dma / pp / il: heads whose query blocks are interleaved in launch order (0 elsewhere) */
+  int merge;                    /* 1: a k_attn_combine2 launch follows (split mode), else 0 */
+  int merge_grid, merge_block;
+  const char* kernel_name;      /* as a profiler prints them: "k_attn_prefill_dma<96, true>", "k_attn_combine2"; "" for no launch */
+  const char* merge_name;
+} p3v_attn_prompt_route_t;
+int p3v_attention_route(const p3v_attn_prompt_query_t* query /* host */, p3v_attn_prompt_route_t* route /* host */);
 
 /* ---- fused decode-step attention (L <= P3V_DECODE_MAX_L new tokens, no beams): head split +
  * _rotate_half + KVCache append + split-KV attention + merge in one call (phi.py:443-457, 542-548).

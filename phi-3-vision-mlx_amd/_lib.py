@@ -111,6 +111,23 @@ class AttnRoute(C.Structure):
                 ("merge_block", i32), ("fuse_form", i32), ("fo_remap", i32), ("kernel_name", C.c_char_p), ("merge_name", C.c_char_p)]
 
 
+ATTN_PK_NONE = -1                                                               # p3v_attn_prompt_kernel_t
+ATTN_PK_ATTN, ATTN_PK_PREFILL, ATTN_PK_DMA, ATTN_PK_PP, ATTN_PK_IL4, ATTN_PK_IL8 = range(6)
+
+
+class AttnPromptQuery(C.Structure):
+    """p3v_attn_prompt_query_t (include/p3v.h): a negative knob = the library's own setting."""
+    _fields_ = [("B", i32), ("L", i32), ("n_heads", i32), ("n_kv", i32), ("hd", i32), ("past", i32), ("past_t", i32), ("n_split", i32),
+                ("new_is_cache", i32), ("q_prescaled", i32), ("has_ws", i32), ("attn_old", i32), ("attn_no_dma", i32), ("attn_pp", i32),
+                ("attn_il", i32), ("attn_il_waves", i32), ("combine_g", i32)]
+
+
+class AttnPromptRoute(C.Structure):
+    """p3v_attn_prompt_route_t (include/p3v.h)."""
+    _fields_ = [("status", i32), ("kernel", i32), ("grid", i32 * 3), ("block", i32), ("lds_bytes", i32), ("head_group", i32), ("merge", i32),
+                ("merge_grid", i32), ("merge_block", i32), ("kernel_name", C.c_char_p), ("merge_name", C.c_char_p)]
+
+
 GEMM_ENTRY_GEMM, GEMM_ENTRY_RESID_NORM, GEMM_ENTRY_QKV = range(3)                # p3v_gemm_entry_t
 (GEMM_K_ROWS, GEMM_K_SKINNY, GEMM_K_SKINNY_QKV, GEMM_K_128, GEMM_K_128_QKV, GEMM_K_256, GEMM_K_256_QKV, GEMM_K_REDUCE,
  GEMM_K_REDUCE_NORM) = range(9)                                                    # p3v_gemm_kernel_t
@@ -235,6 +252,7 @@ SIGNATURES = {
     "p3v_rope_table": (i32, [vp, vp, f32, vp, vp, i32, i32, vp]),
     "p3v_rope_kv_append": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, f32, vp]),
     "p3v_attention": (i32, [C.POINTER(AttnArgs), vp]),
+    "p3v_attention_route": (i32, [C.POINTER(AttnPromptQuery), C.POINTER(AttnPromptRoute)]),   # added after round 6, no version change
     "p3v_attention_decode": (i32, [C.POINTER(AttnDecArgs), vp]),
     "p3v_attention_decode_can_fuse_oproj": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
     "p3v_attention_decode_family": (i32, [C.POINTER(AttnDecArgs), vp, vp, vp]),          # added after round 6, no version change

@@ -1,4 +1,4 @@
-// Interleaved prefill attention (round 3, late) -- included by p3v_attention.hip (types, AttnP and helpers come from there).
+// Interleaved prefill attention (round 3, late) -- included by p3v_attn_prompt.hip (types, AttnP and helpers come from there).
 //
 // What the ping-pong kernel (k_attn_prefill_pp) could not get past, measured (tools/valu_issue_rate.hip,
 // tools/mfma_valu_overlap.hip, tools/gen_slot_bench.py, tools/attn_pp_timeline.py; profiles/r03_attn_il_microbench.txt):

@@ -1,15 +1,15 @@
 // What the decode attention launchers of p3v_attention.hip and p3v_attn_family.hip share: ONE definition of the rotation of a
 // new query / key chunk (the appended K row is the same bits whichever launcher appends it), of the merge launch's block size,
-// and the declaration of the merge kernel (defined in p3v_attention.hip).
+// and the declaration of the merge kernel (defined in p3v_attention.hip; p3v_attn_prompt.hip launches it for p3v_attention's split mode).
 #pragma once
 #include "p3v_common.h"
 
 constexpr int CMB_G = 16;   // max 64-lane groups of the split-KV merge kernel
-static inline int combine_threads(int n_split) {              // measured at 41 splits: 8 groups beat 4 and 16
-  const int g = p3v_tuning().combine_g;                       // tuning knob (4 / 8 / 16)
-  if (g > 0) return 64 * g;
+static inline int combine_threads(int n_split, int g) {       // measured at 41 splits: 8 groups beat 4 and 16
+  if (g > 0) return 64 * g;                                   // g: the combine_g tuning knob (4 / 8 / 16)
   return 64 * (n_split <= 8 ? 4 : 8);
 }
+static inline int combine_threads(int n_split) { return combine_threads(n_split, p3v_tuning().combine_g); }
 __global__ void k_attn_combine2(const float* __restrict__ ws, bf16_t* __restrict__ out, int L, int nh, int hd, int n_split);
 
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));

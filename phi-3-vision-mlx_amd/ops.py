@@ -527,6 +527,17 @@ def attention(q, out, B, Lq, nh, nkv, hd, scale, causal, k_new=None, v_new=None,
     return out
 
 
+def attention_route(B, Lq, nh, nkv, hd, past=0, past_t=0, n_split=0, new_is_cache=False, q_prescaled=False, has_ws=False, attn_old=-1,
+                    attn_no_dma=-1, attn_pp=-1, attn_il=-1, attn_il_waves=-1, combine_g=-1):
+    """What `attention` launches for this call -> L.AttnPromptRoute: status, kernel and its name, grid, block, dynamic LDS, head_group and
+    the merge launch (include/p3v.h: p3v_attention_route).  A negative knob is the library's setting; no device is asked."""
+    q = L.AttnPromptQuery(B, Lq, nh, nkv, hd, int(past), past_t, n_split, int(bool(new_is_cache)), int(bool(q_prescaled)), int(bool(has_ws)),
+                          attn_old, attn_no_dma, attn_pp, attn_il, attn_il_waves, combine_g)
+    r = L.AttnPromptRoute()
+    L.check(L.lib().p3v_attention_route(C.byref(q), C.byref(r)), "attention_route")
+    return r
+
+
 def attention_decode_can_fuse_oproj(B, Lq, nh, hd, n_split, cache_t, o_n, merge_in_launch):
     """Does the fused attention + o_proj + residual launch take this shape on this device (include/p3v.h)?"""
     return bool(L.lib().p3v_attention_decode_can_fuse_oproj(B, Lq, nh, hd, n_split, cache_t, o_n, int(bool(merge_in_launch))))

@@ -1,5 +1,5 @@
 """Probing inputs and an fp64 reference for the prompt-sized attention kernels behind p3v_attention (k_attn_prefill_dma, k_attn_prefill_il,
-k_attn_prefill_pp), in the instantiations the model launches: pre-scaled Q, every key read from the cache (new_is_cache).
+k_attn_prefill_pp; csrc/p3v_attn_prompt.hip), in the instantiations the model launches: pre-scaled Q, every key read from the cache (new_is_cache).
 
 Gaussian q / K / V cannot fail here for the reason tests/attn_probe.py gives: over n keys the softmax is nearly flat, and a causal or
 pad boundary off by one, a ring slot reused a tile too early or a neighbour's kv head moves an output by ~1/n.  The inputs built here keep
@@ -29,9 +29,11 @@ the output O(1) and put most of a query's weight on a few keys whose identity sh
 
 The reference is plain fp64 on the bf16 tensors the kernel is given: s = q_in . k (q_in carries scale * log2 e already); query i of
 row b sees t iff t >= pad_len[b] and (not causal or t <= past + i); p = 2^(s - max); o = p . v / sum p; rows with past + i < pad_len[b]
-are exactly 0.  Nothing in it is rounded.  Everything here is torch / numpy on the CPU.
+are exactly 0.  Nothing in it is rounded.  Everything here is torch / numpy on the CPU; which kernel a call takes and its head_group are
+asked of the library's route (ops.attention_route: host-only, no GPU).
 """
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
 from functools import lru_cache
 
@@ -45,10 +47,37 @@ K_SPIKE, Q_MAIN, Q_SIDE = 4.0, 4.0, 3.0
 V_KEY, V_TILE = 10.0, 4.0
 UP, DOWN, TILE = 0, 1, 2
 
-# path -> (attn_pp, attn_il, attn_il_waves) for ops.set_tuning, and the kernel the launcher then takes for pre-scaled Q
+# path -> (attn_pp, attn_il, attn_il_waves) for ops.set_tuning, and the kernel the library then takes for a call whose keys all lie in
+# a cache of whole tiles (pre: Q pre-scaled or plain; il takes pre-scaled Q only)
+KNOBS = ("attn_pp", "attn_il", "attn_il_waves")
 PATHS = {"dma": (0, 0, 0), "il4": (1, 1, 4), "il8": (1, 1, 8), "pp": (1, 0, 0)}
-KERNELS = {"dma": "k_attn_prefill_dma<{hd}, true>", "il4": "k_attn_prefill_il<{hd}, 4>", "il8": "k_attn_prefill_il<{hd}, 8>",
-           "pp": "k_attn_prefill_pp<{hd}, true>"}
+KERNELS = {"dma": "k_attn_prefill_dma<{hd}, {pre}>", "il4": "k_attn_prefill_il<{hd}, 4>", "il8": "k_attn_prefill_il<{hd}, 8>",
+           "pp": "k_attn_prefill_pp<{hd}, {pre}>"}
+
+
+def kernel_of(path, hd, q_prescaled=True):
+    return KERNELS[path].format(hd=hd, pre="true" if q_prescaled else "false")
+
+
+def takes(ops, path, **call):
+    """Does the library, with the knobs of `path`, run the kernel of `path` for this call (the arguments of ops.attention_route)?"""
+    r = ops.attention_route(**call, **dict(zip(KNOBS, PATHS[path])))
+    return r.status == 0 and r.kernel_name.decode() == kernel_of(path, call["hd"], call.get("q_prescaled", False))
+
+
+@contextmanager
+def pinned(ops, path, **call):
+    """Pin the kernel of `path` for the ops.attention call about to be made: sets the three knobs, asserts from the library's route
+    (ops.attention_route(**call), the library's own settings) that this call takes that kernel, and restores the knobs."""
+    old = [ops.set_tuning(name, val) for name, val in zip(KNOBS, PATHS[path])]
+    try:
+        r = ops.attention_route(**call)
+        want = kernel_of(path, call["hd"], call.get("q_prescaled", False))
+        assert r.status == 0 and r.kernel_name.decode() == want, f"pinned {path}: the call runs {r.kernel_name.decode()!r}, not {want}"
+        yield r
+    finally:
+        for name, val in zip(KNOBS, old):
+            ops.set_tuning(name, val)
 
 
 @dataclass(frozen=True)
@@ -83,9 +112,15 @@ class Case:
 
     @property
     def head_group(self):
-        """launch_attn_prefill's rule (csrc/p3v_attention.hip)."""
-        kv_bytes, nh = self.T * self.hd * 4, self.nh
-        return nh if kv_bytes * nh <= 64 << 20 else 8 if nh % 8 == 0 and kv_bytes * 8 <= 128 << 20 else 4 if nh % 4 == 0 else nh
+        """The heads whose query blocks the launch interleaves: the route's answer (csrc/p3v_attn_prompt.hip: prompt_route)."""
+        from phi_3_vision_mlx_amd import ops
+        return ops.attention_route(**self.call).head_group
+
+    @property
+    def call(self):
+        """The arguments of ops.attention_route for the call `launch` makes."""
+        return dict(B=self.B, Lq=self.L, nh=self.nh, nkv=self.nkv, hd=self.hd, past=self.past, past_t=self.past_t, new_is_cache=True,
+                    q_prescaled=True)
 
     @property
     def id(self):
@@ -345,9 +380,7 @@ def launch(ops, pr, path, device="cuda"):
     buf0 = torch.full((2 * GUARD + n,), -77.0, dtype=BF16)
     buf0[GUARD:GUARD + n] = float("nan")
     res = {"buf0": buf0}
-    knobs = ("attn_pp", "attn_il", "attn_il_waves")
-    old = [ops.set_tuning(name, val) for name, val in zip(knobs, PATHS[path])]
-    try:
+    with pinned(ops, path, **c.call):
         for name in ("out", "out2"):
             buf = buf0.to(device)
             out = buf[GUARD:GUARD + n].view(c.B, c.L, c.nh * c.hd)
@@ -356,8 +389,5 @@ def launch(ops, pr, path, device="cuda"):
             torch.cuda.synchronize()
             res[name] = out.cpu()
             res["buf"] = buf.cpu()
-    finally:
-        for name, val in zip(knobs, old):
-            ops.set_tuning(name, val)
     res["k"], res["vt"] = k.cpu(), vt.cpu()
     return res

@@ -12,6 +12,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import prefill_probe as pfp  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
 GQA = [(8, 4), (32, 8), (4, 1)]
@@ -89,7 +91,7 @@ def test_attention_gqa(ops, orc, nh, nkv, B, L, past, pads):
     close(got[valid], ref[valid])
 
 
-@pytest.mark.parametrize("pp", [2, 1, 0], ids=["interleaved", "pingpong", "dma"])
+@pytest.mark.parametrize("pp", ["il", "pp", "dma"], ids=["interleaved", "pingpong", "dma"])
 @pytest.mark.parametrize("nh,nkv", GQA)
 @pytest.mark.parametrize("B,L,past,pads", [(1, 700, 0, None), (2, 300, 0, [0, 77]), (1, 40, 200, None), (1, 1100, 0, None)])
 def test_attention_prefill_kernels_gqa(ops, orc, pp, nh, nkv, B, L, past, pads):
@@ -105,16 +107,12 @@ def test_attention_prefill_kernels_gqa(ops, orc, pp, nh, nkv, B, L, past, pads):
     kc[:, :, :T], vc[:, :, :, :T] = k, v.transpose(2, 3)
     ref = attn_ref(orc, q_ref, k, v, scale, allowed_mask(B, L, past, pad)).transpose(1, 2).reshape(B, L, nh * hd)
     valid = ((past + torch.arange(L))[None, :] >= pad[:, None])[..., None].expand(B, L, nh * hd)
-    for waves in ((8, 4) if pp == 2 else (8,)):
+    for path in (("il8", "il4") if pp == "il" else (pp,)):
         out = torch.full((B, L, nh * hd), float("nan"), dtype=BF16).cuda()
-        saved = [ops.set_tuning("attn_pp", min(pp, 1)), ops.set_tuning("attn_il", int(pp == 2)), ops.set_tuning("attn_il_waves", waves)]
-        try:
+        with pfp.pinned(ops, path, B=B, Lq=L, nh=nh, nkv=nkv, hd=hd, past=past, past_t=Tp, new_is_cache=True, q_prescaled=True):
             ops.attention(q_in.cuda(), out, B, L, nh, nkv, hd, scale, True, past=past, k_past=kc.cuda(), v_past=vc.cuda(), past_t=Tp,
                           pad_len=pad.cuda() if pads else None, new_is_cache=True, q_prescaled=True)
             torch.cuda.synchronize()
-        finally:
-            for n, val in zip(("attn_pp", "attn_il", "attn_il_waves"), saved):
-                ops.set_tuning(n, val)
         got = out.float().cpu()
         assert torch.isfinite(got).all()
         assert (got[~valid] == 0).all()

@@ -29,7 +29,7 @@ def test_prefill_attention_matches_fp64_on_probing_inputs(ops, case, path):
     c, n = case, case.B * case.L * case.nh * case.hd
     res = pp.launch(ops, pr, path)
     out = res["out"]
-    kernel = pp.KERNELS[path].format(hd=c.hd)
+    kernel = pp.kernel_of(path, c.hd)
     # ---- accuracy over the live rows (the spot rows where the reference is built for those alone)
     got = out[:, pr.rows].double()
     finite = bool(torch.isfinite(out.float()).all())

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import prefill_probe as pfp
+
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -506,9 +508,10 @@ def test_attention(ops, orc, B, L, past, hd, nh, causal, pads):
 
 
 def _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, spike=None, seed=40, q_std=1.0, il_waves=None):
-    """Prompt-sized attention through p3v_attention with the kernel pinned (pp = 2: k_attn_prefill_il [pre-scaled q only],
-    1: k_attn_prefill_pp, 0: k_attn_prefill_dma) vs the oracle's fp32 attention.  prescaled: q goes in multiplied by scale * log2(e) and rounded once (what
-    p3v_rope_kv_append's q_scale produces); the reference then uses exactly those bf16 values divided back in fp32."""
+    """Prompt-sized attention through p3v_attention with the kernel pinned (pp = "il": k_attn_prefill_il [pre-scaled q only],
+    "pp": k_attn_prefill_pp, "dma": k_attn_prefill_dma; prefill_probe.pinned asserts that the call takes it) vs the oracle's fp32
+    attention.  prescaled: q goes in multiplied by scale * log2(e) and rounded once (what p3v_rope_kv_append's q_scale
+    produces); the reference then uses exactly those bf16 values divided back in fp32."""
     T = past + L
     Tp = (T + 63) // 64 * 64
     scale = hd ** -0.5
@@ -523,16 +526,15 @@ def _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, spi
     kc = torch.zeros((B, nh, Tp, hd), dtype=BF16)
     vc = torch.zeros((B, nh, hd, Tp), dtype=BF16)
     kc[:, :, :T], vc[:, :, :, :T] = k, v.transpose(2, 3)
-    if pp == 2 and not prescaled:
+    if pp == "il":
+        pp = "il%d" % ((8, 4)[seed & 1] if il_waves is None else il_waves)    # both workgroup sizes of the il kernel get exercised
+    call = dict(B=B, Lq=L, nh=nh, nkv=nh, hd=hd, past=past, past_t=Tp, new_is_cache=True, q_prescaled=prescaled)
+    if pp.startswith("il") and not prescaled and not pfp.takes(ops, pp, **call):
         pytest.skip("the interleaved kernel takes pre-scaled q only (the launcher never picks it otherwise)")
-    old, old_il = ops.set_tuning("attn_pp", min(pp, 1)), ops.set_tuning("attn_il", int(pp == 2))
-    old_w = ops.set_tuning("attn_il_waves", (8, 4)[seed & 1] if il_waves is None else il_waves)    # both workgroup sizes of the il kernel get exercised
-    try:
+    with pfp.pinned(ops, pp, **call):
         ops.attention(q_in.cuda(), out, B, L, nh, nh, hd, scale, causal, past=past, k_past=kc.cuda(), v_past=vc.cuda(), past_t=Tp,
                       pad_len=pad.cuda() if pads else None, new_is_cache=True, q_prescaled=prescaled)
         torch.cuda.synchronize()
-    finally:
-        ops.set_tuning("attn_pp", old), ops.set_tuning("attn_il", old_il), ops.set_tuning("attn_il_waves", old_w)
     t = torch.arange(T)[None, None, None, :]
     qpos = (past + torch.arange(L))[None, None, :, None]
     allowed = (t >= pad[:, None, None, None]) & (qpos >= pad[:, None, None, None])
@@ -548,7 +550,7 @@ def _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, spi
     return got
 
 
-@pytest.mark.parametrize("pp", [2, 1, 0], ids=["interleaved", "pingpong", "dma"])
+@pytest.mark.parametrize("pp", ["il", "pp", "dma"], ids=["interleaved", "pingpong", "dma"])
 @pytest.mark.parametrize("prescaled", [True, False], ids=["prescaled", "plain"])
 @pytest.mark.parametrize("B,L,past,hd,nh,causal,pads", [
     (1, 700, 0, 96, 2, True, None),            # 3 query blocks of 256, the last one ragged (188 rows: two idle waves)
@@ -562,11 +564,11 @@ def _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, spi
 ])
 def test_attention_prefill_kernels(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp):
     _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, il_waves=8)
-    if pp == 2:
-        _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, il_waves=4)      # 128-query workgroups
+    if pp == "il":
+        _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, prescaled, pp, il_waves=4)     # 128-query workgroups
 
 
-@pytest.mark.parametrize("pp", [2, 1, 0], ids=["interleaved", "pingpong", "dma"])
+@pytest.mark.parametrize("pp", ["il", "pp", "dma"], ids=["interleaved", "pingpong", "dma"])
 def test_attention_prefill_long_context_spot_rows(ops, orc, pp):
     """12288 queries x 12288 keys x 8 heads (K / V^T far larger than the L2: the LDS-DMA tiles arrive LATE, which is what
     exposes a missing wait or a ring slot reused too early -- the first version of the ping-pong kernel passed every
@@ -580,13 +582,11 @@ def test_attention_prefill_long_context_spot_rows(ops, orc, pp):
     q_in = (q.float() * (scale * ops.Q_PRESCALE)).to(BF16)
     vt = v.transpose(2, 3).contiguous()
     out = torch.full((B, L, nh * hd), float("nan"), dtype=BF16, device="cuda")
-    old, old_il = ops.set_tuning("attn_pp", min(pp, 1)), ops.set_tuning("attn_il", int(pp == 2))
-    try:
+    path = {"il": "il8", "pp": "pp", "dma": "dma"}[pp]                  # (the wave count by shape: 256-query workgroups at this length)
+    with pfp.pinned(ops, path, B=B, Lq=L, nh=nh, nkv=nh, hd=hd, past_t=L, new_is_cache=True, q_prescaled=True):
         for _ in range(3):                                              # races are timing-dependent: a few launches
             ops.attention(q_in, out, B, L, nh, nh, hd, scale, True, k_past=k, v_past=vt, past_t=L, new_is_cache=True, q_prescaled=True)
         torch.cuda.synchronize()
-    finally:
-        ops.set_tuning("attn_pp", old), ops.set_tuning("attn_il", old_il)
     assert torch.isfinite(out.float()).all()
     rows = torch.cat([torch.arange(0, L, 197), torch.tensor([255, 256, 4095, 4096, L - 257, L - 1])]).unique()
     qr = (q_in[0, :, rows].float().cpu() / (scale * ops.Q_PRESCALE))   # [nh, n, hd]
@@ -616,12 +616,10 @@ def test_attention_prefill_kernels_are_deterministic(ops, B, L, nh, hd, causal):
         w = w.masked_fill(torch.arange(L, device="cuda")[None, None, None, :] > rows[None, None, :, None], float("-inf"))
     ref = (torch.softmax(w, -1) @ v[:, :, :, :L].float().transpose(-1, -2)).transpose(1, 2).reshape(B, len(rows), nh * hd)
     q_pre = (q.float() * (scale * ops.Q_PRESCALE)).to(BF16)
-    kinds = [("dma", 0, 0, 0, False), ("dma", 0, 0, 0, True), ("pingpong", 1, 0, 0, False), ("pingpong", 1, 0, 0, True),
-             ("interleaved 8", 1, 1, 8, True), ("interleaved 4", 1, 1, 4, True)]
-    saved = [ops.set_tuning(n, 0) for n in ("attn_pp", "attn_il", "attn_il_waves")]
-    try:
-        for name, pp, il, nw, pre in kinds:
-            ops.set_tuning("attn_pp", pp), ops.set_tuning("attn_il", il), ops.set_tuning("attn_il_waves", nw)
+    kinds = [("dma", "dma", False), ("dma", "dma", True), ("pingpong", "pp", False), ("pingpong", "pp", True),
+             ("interleaved 8", "il8", True), ("interleaved 4", "il4", True)]
+    for name, path, pre in kinds:
+        with pfp.pinned(ops, path, B=B, Lq=L, nh=nh, nkv=nh, hd=hd, past_t=Tp, new_is_cache=True, q_prescaled=pre):
             first = None
             for rep in range(10):
                 out = torch.full((B, L, nh * hd), float("nan"), dtype=BF16, device="cuda")
@@ -640,26 +638,25 @@ def test_attention_prefill_kernels_are_deterministic(ops, B, L, nh, hd, causal):
                 else:
                     n_diff = int((out.view(torch.int16) != first.view(torch.int16)).sum())
                     assert n_diff == 0, f"{name} (pre-scaled {pre}): launch {rep} differs from launch 0 in {n_diff} output words"
-    finally:
-        for n, val in zip(("attn_pp", "attn_il", "attn_il_waves"), saved):
-            ops.set_tuning(n, val)
 
 
 @pytest.mark.parametrize("seed", range(10))
 def test_attention_prefill_interleaved_random_shapes(ops, orc, seed):
     """k_attn_prefill_il over seeded random shapes (the launcher only takes it for long single prompts; pinned here it must hold for
-    any length): 1..700 new queries over 0..400 cached keys, 1-3 rows with random left padding (sometimes a whole row's past),
+    any length the prompt path takes): 17..700 new queries over 0..400 cached keys, 1-3 rows with random left padding (sometimes a whole row's past),
     causal or not, head dim 96 / 64, 1-3 heads, modest or large score magnitudes -- first / last tile on neutral operands, idle
     waves, ragged last tile, ring wrap-around and the reference path all get hit in some combination."""
     rng = np.random.default_rng(1000 + seed)
     B, nh, hd = int(rng.integers(1, 4)), int(rng.integers(1, 4)), (96, 64)[int(rng.integers(0, 2))]
     L, past = int(rng.integers(1, 701)), int(rng.integers(0, 2)) * int(rng.integers(1, 401))
+    if L <= 16:                 # (seed 1 draws 11.)  Up to P3V_DECODE_MAX_L queries go to k_attn whatever the knobs: the pin found that this
+        L += 16                 # case had never run the interleaved kernel; 17 .. 32 queries is the shortest call that can
     causal = bool(rng.integers(0, 4)) or past > 0
     pads = [int(rng.integers(0, past + L // 2 + 1)) * int(rng.integers(0, 2)) for _ in range(B)] if rng.integers(0, 2) else None
-    _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, True, 2, seed=200 + seed, q_std=(1.0, 4.0)[int(rng.integers(0, 2))])
+    _prefill_case(ops, orc, B, L, past, hd, nh, causal, pads, True, "il", seed=200 + seed, q_std=(1.0, 4.0)[int(rng.integers(0, 2))])
 
 
-@pytest.mark.parametrize("pp", [2, 1, 0], ids=["interleaved", "pingpong", "dma"])
+@pytest.mark.parametrize("pp", ["il", "pp", "dma"], ids=["interleaved", "pingpong", "dma"])
 def test_attention_prefill_reference_jump_and_large_scores(ops, orc, pp):
     """The ping-pong kernel keeps a per-query reference for the exponent and moves it only when a tile's maximum exceeds it
     by more than 2^8 (guide T13 hazard: O, l and the pending P must be rescaled exactly once).  (a) a spiked key in the
@@ -667,9 +664,9 @@ def test_attention_prefill_reference_jump_and_large_scores(ops, orc, pp):
     magnitude ~100 (log2 units) with the FIRST tile far below the later ones; (c) the first visible tile sets the reference
     even when its scores are hugely negative (no underflow of the whole row)."""
     _prefill_case(ops, orc, 1, 600, 0, 96, 2, True, None, True, pp, spike=(0, 450, 300))
-    _prefill_case(ops, orc, 1, 600, 0, 96, 2, True, None, pp == 2, pp, spike=(0, 599, 64))
+    _prefill_case(ops, orc, 1, 600, 0, 96, 2, True, None, pp == "il", pp, spike=(0, 599, 64))
     _prefill_case(ops, orc, 1, 400, 0, 96, 1, True, None, True, pp, q_std=6.0, seed=90)
-    _prefill_case(ops, orc, 2, 577, 0, 64, 1, False, None, pp == 2, pp, q_std=8.0, seed=91)
+    _prefill_case(ops, orc, 2, 577, 0, 64, 1, False, None, pp == "il", pp, q_std=8.0, seed=91)
 
 
 @pytest.mark.parametrize("B,L,past,nh,n_split,pads", [(1, 1, 300, 4, 5, None), (2, 1, 63, 2, 1, [0, 7]), (1, 6, 130, 2, 3, None),

@@ -117,7 +117,7 @@ def test_probe_inputs_catch_every_mutant(case):
 def test_case_table_reaches_every_mechanism():
     """The shapes of the table are the ones the mechanisms need: a ragged last 256-row block, a block of one query, pads inside a tile and
     over a whole past, cached calls, head dim 64 without a mask, GQA, one tile, fewer queries than a wave, and head_group < nh under the
-    launcher's own rule (csrc/p3v_attention.hip: kv_bytes * nh > 64 MiB)."""
+    library's own rule (csrc/p3v_attn_prompt.hip, prompt_route: kv_bytes * nh > 64 MiB; Case.head_group asks the route)."""
     by = {c.id: c for c in pp.CASES}
     assert by["B1-L700-hd96"].n_tiles == 11 and 700 % 256 not in (0, 1)
     assert by["B1-L257"].L % 256 == 1

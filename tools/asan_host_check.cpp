@@ -59,6 +59,23 @@ int main() {
   p3v_attn_args_t a;
   std::memset(&a, 0, sizeof a);
   EXPECT(p3v_attention(&a, nullptr) == P3V_ERR_ARG);
+  // the prompt attention's route: null arguments, one shape per kernel, an unsupported head dim (host arithmetic, no device)
+  p3v_attn_prompt_route_t pr;
+  p3v_attn_prompt_query_t pq = {1, 300, 2, 2, 96, 0, 320, 0, 1, 1, 0, -1, -1, -1, -1, -1, -1};
+  EXPECT(p3v_attention_route(nullptr, &pr) == P3V_ERR_ARG && p3v_attention_route(&pq, nullptr) == P3V_ERR_ARG);
+  const struct { int L, n_split, has_ws, new_is_cache, attn_old, attn_pp, attn_il, attn_il_waves, kernel; const char* name; } shapes[] = {
+      {16, 4, 1, 1, 0, -1, -1, -1, P3V_ATTN_PK_ATTN, "k_attn<96>"},          {300, 0, 0, 1, 1, -1, -1, -1, P3V_ATTN_PK_ATTN, "k_attn<96>"},
+      {300, 0, 0, 0, 0, -1, -1, -1, P3V_ATTN_PK_PREFILL, "k_attn_prefill<96>"}, {300, 0, 0, 1, 0, 0, 0, -1, P3V_ATTN_PK_DMA, "k_attn_prefill_dma<96, true>"},
+      {300, 0, 0, 1, 0, 1, 0, -1, P3V_ATTN_PK_PP, "k_attn_prefill_pp<96, true>"}, {300, 0, 0, 1, 0, -1, 1, 4, P3V_ATTN_PK_IL4, "k_attn_prefill_il<96, 4>"},
+      {300, 0, 0, 1, 0, -1, 1, 8, P3V_ATTN_PK_IL8, "k_attn_prefill_il<96, 8>"}};
+  for (const auto& s : shapes) {
+    pq.L = s.L, pq.past_t = (s.L + 63) / 64 * 64, pq.n_split = s.n_split, pq.has_ws = s.has_ws, pq.new_is_cache = s.new_is_cache;
+    pq.attn_old = s.attn_old, pq.attn_pp = s.attn_pp, pq.attn_il = s.attn_il, pq.attn_il_waves = s.attn_il_waves;
+    EXPECT(p3v_attention_route(&pq, &pr) == P3V_OK && pr.status == P3V_OK && pr.kernel == s.kernel && !std::strcmp(pr.kernel_name, s.name));
+    EXPECT(pr.merge == (s.n_split > 1) && (pr.lds_bytes > 0) == (s.kernel != P3V_ATTN_PK_ATTN));
+  }
+  pq.hd = 80;
+  EXPECT(p3v_attention_route(&pq, &pr) == P3V_OK && pr.status == P3V_ERR_UNSUPPORTED && pr.kernel == P3V_ATTN_PK_NONE && !pr.kernel_name[0]);
   p3v_attn_decode_args_t d;
   std::memset(&d, 0, sizeof d);
   EXPECT(p3v_attention_decode(&d, nullptr) != P3V_OK);

@@ -1,4 +1,4 @@
-"""Timeline of ONE workgroup of k_attn_prefill_il (debug build: tools/build_variant.sh ildbg p3v_attention.hip -DP3V_IL_DEBUG=<block>).
+"""Timeline of ONE workgroup of k_attn_prefill_il (debug build: tools/build_variant.sh ildbg p3v_attn_prompt.hip -DP3V_IL_DEBUG=<block>).
 Per wave and tile iteration, cycles from the iteration's start to: end of region 1 of slot A | end of slot A | barrier passed |
 DMA issued | end of region 1 of slot B | end of slot B; and the length of the iteration."""
 import ctypes, os, sys

@@ -1,4 +1,4 @@
-"""Kernel time of k_attn_prefill_pp builds (tools/build_variant.sh <name> p3v_attention.hip -D...) -- several builds INTERLEAVED in
+"""Kernel time of k_attn_prefill_pp builds (tools/build_variant.sh <name> p3v_attn_prompt.hip -D...) -- several builds INTERLEAVED in
 one process (the chip's clock follows its thermal state: back-to-back processes are not comparable).
   python tools/attn_variant_bench.py v1,v2[:il] [shape ...]     shape = B:L:heads:hd:causal; ":il" = k_attn_prefill_il of that build"""
 import ctypes, os, sys, statistics

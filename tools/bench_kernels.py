@@ -58,16 +58,17 @@ def attn_case(name, B, L, nh, hd, causal, prescaled=None):
     out = torch.empty(B, L, nh * hd, device="cuda", dtype=torch.bfloat16)
     fl = 4 * B * nh * L * L * hd * (0.5 if causal else 1.0)
     kinds = [("dma", 0, 0), ("pingpong", 1, 0)] + ([("interleaved", 1, 1)] if prescaled else [])
-    t = {n: [] for n, _, _ in kinds}
-    for rep in range(3):                                    # the chip's clock follows its thermal state: alternate the kernels
+    t, ran = {n: [] for n, _, _ in kinds}, {}
+    for rep in range(3):                                   # the chip's clock follows its thermal state: alternate the kernels
         for n, pp, il in kinds:
             old, old_il = ops.set_tuning("attn_pp", pp), ops.set_tuning("attn_il", il)
+            ran[n] = ops.attention_route(B, L, nh, nh, hd, past_t=Tp, new_is_cache=True, q_prescaled=prescaled).kernel_name.decode()
             t[n].append(timeit(lambda i: ops.attention(q, out, B, L, nh, nh, hd, hd ** -0.5, causal, k_past=k, v_past=v, past_t=Tp, new_is_cache=True,
                                                        q_prescaled=prescaled), 1, iters=10 if L <= 8192 else 3))
             ops.set_tuning("attn_pp", old), ops.set_tuning("attn_il", old_il)
     for n, _, _ in kinds:
         ms = sorted(t[n])[1]
-        print(f"attn {name:28s} {n:11s} B={B:3d} L={L:5d} heads={nh} hd={hd}  {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TF/s", flush=True)
+        print(f"attn {name:28s} {n:11s} B={B:3d} L={L:5d} heads={nh} hd={hd}  {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TF/s  {ran[n]}", flush=True)
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "all"

@@ -31,7 +31,8 @@ for rep in range(3):
         t[n].append(timeit(fn, 1, iters=20))
         if rep == 0:
             err = (out.float() - ref).abs().max().item()
-            print(f"{n:22s} max |err| vs fp32 reference {err:.4f} (|ref| max {ref.abs().max().item():.2f})", flush=True)
+            ran = ops.attention_route(B, L, nh, nh, hd, past_t=Tp, new_is_cache=True, q_prescaled=pre).kernel_name.decode()
+            print(f"{n:22s} {ran}: max |err| vs fp32 reference {err:.4f} (|ref| max {ref.abs().max().item():.2f})", flush=True)
         ops.set_tuning("attn_pp", olds[0]), ops.set_tuning("attn_il", olds[1]), ops.set_tuning("attn_il_waves", olds[2])
 for n, *_ in kinds:
     ms = sorted(t[n])[1]

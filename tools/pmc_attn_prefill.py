@@ -13,4 +13,4 @@ ops.set_tuning("attn_il", int(pp == 2))                          # pp = 2: k_att
 for _ in range(4):
     ops.attention(q, out, 1, L, nh, nh, hd, hd ** -0.5, True, k_past=k, v_past=v, past_t=L, new_is_cache=True, q_prescaled=True)
 torch.cuda.synchronize()
-print("done")
+print("done:", ops.attention_route(1, L, nh, nh, hd, past_t=L, new_is_cache=True, q_prescaled=True).kernel_name.decode())
