@@ -117,7 +117,8 @@ int p3v_gemm_rows_slices(int M, int N, int K, int epilogue);
  * (M == 1: VALU dot products; 2 <= M <= 16: the weight rows go straight from HBM into MFMA fragments).
  * Same call sites as p3v_gemm when L*B is small.  Optional fused RMSNorm of x
  * (norm_w != null: x is normalised with norm_w/eps before use, phi.py:482,484).
- * Epilogues: NONE, RESID_BF16, SILU_MUL (W = [gate;up]), F32. */
+ * Epilogues: NONE, RESID_BF16, SILU_MUL (W = [gate;up]), F32.  Which kernel a shape takes, and which shapes none takes
+ * (P3V_ERR_UNSUPPORTED), is p3v_gemv_route's answer (below) -- for this entry and for the other formats' twins. */
 typedef struct {
   const uint16_t* x;      /* [M, K] bf16 */
   const uint16_t* W;      /* [N or 2N, K] bf16 */
@@ -125,14 +126,14 @@ typedef struct {
   const uint16_t* resid;  /* [M, N] bf16 or null; may alias out */
   const uint16_t* norm_w; /* [K] bf16 or null */
   float norm_eps;
-  int M, N, K;            /* M <= 16, K % 8 == 0 (M > 8 needs K % 512 == 0) */
+  int M, N, K;            /* M <= 16, K % 8 == 0 (otherwise P3V_ERR_ARG); the rest: p3v_gemv_route */
   int epilogue;
 } p3v_gemv_args_t;
 int p3v_gemv(const p3v_gemv_args_t* args /* host */, void* stream);
 
 /* ---- fp8 (OCP e4m3fn) weight-only projections (quantize_model=True; replaces the int4 `nn.quantize` of
  * phi_3_vision_mlx.py:264,296): W is u8 [N or 2N, K] bit patterns, w = fp8 * w_scale[row]; x, accumulation
- * and outputs as in p3v_gemv.  K in {3072, 8192}, M <= 16, N even.  Every kernel behind it sums x * fp8 in fp32 first (an e4m3 value
+ * and outputs as in p3v_gemv.  Shapes and kernels: p3v_gemv_route (P3V_GEMV_FMT_FP8).  Every kernel behind it sums x * fp8 in fp32 first (an e4m3 value
  * is exact in bf16, so each product is) and multiplies the sum by w_scale[row] afterwards, one fp32 rounding; the epilogue's roundings
  * are p3v_gemm's.  p3v_dequant_fp8 expands rows to bf16 (prefill). */
 typedef struct {
@@ -156,8 +157,8 @@ int p3v_dequant_fp8(const uint8_t* w8, const float* w_scale, uint16_t* out_bf16,
  * at load time.  p3v_unpack_b13 restores the bf16 rows bit for bit (tests). */
 int p3v_pack_b13(const uint16_t* W, int rows, int K, int silu_pairs, void* out, int32_t* info, void* stream);
 int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pairs, int exp_base, uint16_t* out_bf16, void* stream);
-/* p3v_gemv on packed weights: M = 1 only (P3V_ERR_UNSUPPORTED otherwise: the caller keeps the bf16 copy for more rows), N even,
- * K = 3072 or 8192, every epilogue and the fused RMSNorm of p3v_gemv; bit-identical to p3v_gemv on the bf16 matrix.
+/* p3v_gemv on packed weights: M = 1 only (P3V_ERR_UNSUPPORTED otherwise: the caller keeps the bf16 copy for more rows; shapes and
+ * the form of the kernel: p3v_gemv_route, P3V_GEMV_FMT_B13), every epilogue and the fused RMSNorm of p3v_gemv; bit-identical to p3v_gemv on the bf16 matrix.
  * silu_pairs must be what the matrix was packed with and equal (epilogue == P3V_EPI_SILU_MUL).
  * Knob gemv_b13_xscale (default 1): for a matrix with K = 3072 and exp_base - 1 <= 96 the kernel does not add the base back to every weight; it
  * multiplies the activations it stages by 2^(exp_base - 1) once (a power of two: every product is the same number) and feeds the
@@ -175,7 +176,7 @@ typedef struct {
 } p3v_gemv_b13_args_t;
 int p3v_gemv_b13(const p3v_gemv_b13_args_t* args /* host */, void* stream);
 /* How p3v_gemv_b13 / p3v_gemv_b13_step cut a launch of N outputs (as in `args`) on `n_cu` compute units at the current knobs
- * (gemv_b13_wpc, gemv_wpw; the end fold of p3v_gemv_b13_step runs at gemv_b13_wpc_end instead) -- the launcher's own arithmetic, callable without a GPU.  out[0] row pairs per wave, out[1] waves that
+ * (gemv_b13_wpc, gemv_wpw; the end fold of p3v_gemv_b13_step runs at gemv_b13_wpc_end instead) -- a projection of p3v_gemv_route, callable without a GPU.  out[0] row pairs per wave, out[1] waves that
  * take rows (wave i: row pairs [i * out[0], (i + 1) * out[0]), cut at the end), out[2] row-streaming waves per 4-wave workgroup,
  * out[3] workgroups. */
 int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out /* host, 4 ints */);
@@ -666,7 +667,7 @@ int p3v_step_end(const uint16_t* logits, int32_t* next_tok, int32_t* tok, int32_
  *                             serialise for ~10 us; amax_ws: P3V_GEMV_STEP_WS_BYTES bytes, 8-byte aligned: P3V_GEMV_STEP_MAX_WG
  *                             candidate records (contents irrelevant) + nine counters, 128 bytes apart, that must be ZERO before
  *                             the first launch and are left zero by every launch; `ticket` is not touched).
- * Exactly one of the two.  M = 1 row (the kernel p3v_gemv runs there), bf16 weights, K = 3072 or 8192, P3V_EPI_NONE: otherwise
+ * Exactly one of the two.  Where p3v_gemv_route (step set) names the one-row streaming kernel; otherwise
  * P3V_ERR_UNSUPPORTED and the caller
  * keeps p3v_step_begin / p3v_step_end.  Bit-identical to the separate launches. */
 #define P3V_GEMV_STEP_MAX_WG 1024
@@ -684,6 +685,47 @@ int p3v_gemv_fp8_step(const p3v_gemv_fp8_args_t* args /* host */, const p3v_gemv
 int p3v_gemv_b13_step(const p3v_gemv_b13_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
 /* and on MLX 4-bit group-64 weights (`args` as for p3v_gemv_q4, one row, no epilogue) */
 int p3v_gemv_q4_step(const p3v_gemv_q4_args_t* args /* host */, const p3v_gemv_step_t* step /* host */, void* stream);
+
+/* ---- the decode projections' route: what p3v_gemv / p3v_gemv_fp8 / p3v_gemv_q4 / p3v_gemv_b13 and their _step entries launch for
+ * a call, or the code they refuse it with.  Every rule is stated in this one function (DESIGN.md section 3.1 has the table); the eight
+ * entry points check the pointers they were given, ask it and launch what it says; p3v_gemv_b13_plan is a projection of it.  The
+ * `gemv*` knobs are read from the library's current settings (p3v_set_tuning works without a device).  cu_count <= 0 asks the current
+ * device, as the entry points do, and only where the streaming kernel's plan is part of the answer: with cu_count given the function
+ * touches no device (tests/test_gemv_route_cpu.py).  Added after round 6, no version change. */
+typedef enum { P3V_GEMV_FMT_BF16 = 0, P3V_GEMV_FMT_FP8, P3V_GEMV_FMT_Q4, P3V_GEMV_FMT_B13, P3V_GEMV_FMT_COUNT } p3v_gemv_format_t;
+typedef enum { P3V_GEMV_STEP_NONE = 0, P3V_GEMV_STEP_BEGIN = 1, P3V_GEMV_STEP_END = 2 } p3v_gemv_step_end_t;
+typedef enum {
+  P3V_GEMV_K_NONE = 0,
+  P3V_GEMV_K_GEMV,              /* k_gemv<MT>: any K % 8, x staged in LDS */
+  P3V_GEMV_K_GEMV3,             /* k_gemv3<F, MT, NST, CH> / k_gemv3_step<F, 1, NST, CH, step>: the streaming kernel, K = NST stages x CH lane loads */
+  P3V_GEMV_K_MFMA,              /* k_gemv_mfma<SILU>: 16 rows of W per workgroup, K % 1024 */
+  P3V_GEMV_K_MFMA8,             /* k_gemv_mfma8<SILU, NW, NST>: up to 8 rows of x, persistent over row sets, K = NW x NST x 256 */
+  P3V_GEMV_K_MFMA_F8,           /* k_gemv_mfma_f8<SILU> */
+  P3V_GEMV_K_MFMA8_F8,          /* k_gemv_mfma8_f8<SILU, NW, NL>: NL (in `NST`) 128-element lines per wave slice */
+  P3V_GEMV_K_GEMV8_Q4,          /* k_gemv8_q4<SILU, NW, NST>: up to 8 rows, persistent */
+  P3V_GEMV_K_ROWS_Q4,           /* k_gemm_rows_q4<SILU, NW, NST>: 9 .. 16 rows, persistent */
+  P3V_GEMV_K_COUNT
+} p3v_gemv_kernel_t;
+typedef struct {
+  int format;                   /* p3v_gemv_format_t */
+  int step;                     /* p3v_gemv_step_end_t: NONE = the plain entry */
+  int M, N, K, epilogue;
+  int has_norm, has_resid;      /* whether the call carries norm_w / resid (a residual epilogue without one is P3V_ERR_ARG) */
+  int exp_base;                 /* P3V_GEMV_FMT_B13 */
+  int cu_count;
+} p3v_gemv_route_query_t;
+typedef struct {
+  int status;                   /* P3V_OK, or the code the entry returns for this shape (then kernel is P3V_GEMV_K_NONE); P3V_ERR_HIP: no device answered for cu_count */
+  int late;                     /* a refusal only: 1 = the entry reports it after the checks of its pointers' alignment (which then win), 0 = before */
+  int kernel;                   /* p3v_gemv_kernel_t */
+  int MT, NW, NST, CH, silu, scaled;   /* the instantiation: whichever the kernel has (scaled: GemvB13<true>), 0 otherwise */
+  int grid, block, lds_bytes;
+  int lds_cap;                  /* what the kernel's dynamic-LDS limit is raised to before such a launch, once per process (0: left alone) */
+  int upw, waves, wpw;          /* the streaming kernel's plan: row pairs per wave, waves that take rows, row-streaming waves per workgroup */
+  int n_sets, sets_per_wg;      /* the persistent kernels: row sets of the launch, and how many one workgroup walks */
+  char name[64];                /* as a profiler prints it: "k_gemv3<GemvB13<true>, 1, 1, 6>" (filled by p3v_gemv_route only) */
+} p3v_gemv_route_t;
+int p3v_gemv_route(const p3v_gemv_route_query_t* query /* host */, p3v_gemv_route_t* route /* host */);
 
 /* ---- seeded sampling (temperature, top-k, top-p): added after round 6, no version change.
  * One record per row, on the device; every launch reads it and increments `counter`, so a replayed graph needs no host input.

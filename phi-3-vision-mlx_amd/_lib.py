@@ -133,6 +133,25 @@ GEMM_ENTRY_GEMM, GEMM_ENTRY_RESID_NORM, GEMM_ENTRY_QKV = range(3)               
  GEMM_K_REDUCE_NORM) = range(9)                                                    # p3v_gemm_kernel_t
 
 
+GEMV_FMT_BF16, GEMV_FMT_FP8, GEMV_FMT_Q4, GEMV_FMT_B13 = range(4)                   # p3v_gemv_format_t
+GEMV_STEP_NONE, GEMV_STEP_BEGIN, GEMV_STEP_END = range(3)                           # p3v_gemv_step_end_t
+(GEMV_K_NONE, GEMV_K_GEMV, GEMV_K_GEMV3, GEMV_K_MFMA, GEMV_K_MFMA8, GEMV_K_MFMA_F8, GEMV_K_MFMA8_F8, GEMV_K_GEMV8_Q4,
+ GEMV_K_ROWS_Q4) = range(9)                                                          # p3v_gemv_kernel_t
+
+
+class GemvRouteQuery(C.Structure):
+    """p3v_gemv_route_query_t (include/p3v.h): cu_count <= 0 = the device's own."""
+    _fields_ = [("format", i32), ("step", i32), ("M", i32), ("N", i32), ("K", i32), ("epilogue", i32), ("has_norm", i32),
+                ("has_resid", i32), ("exp_base", i32), ("cu_count", i32)]
+
+
+class GemvRoute(C.Structure):
+    """p3v_gemv_route_t (include/p3v.h)."""
+    _fields_ = [("status", i32), ("late", i32), ("kernel", i32), ("MT", i32), ("NW", i32), ("NST", i32), ("CH", i32), ("silu", i32),
+                ("scaled", i32), ("grid", i32), ("block", i32), ("lds_bytes", i32), ("lds_cap", i32), ("upw", i32), ("waves", i32),
+                ("wpw", i32), ("n_sets", i32), ("sets_per_wg", i32), ("name", C.c_char * 64)]
+
+
 class GemmRouteQuery(C.Structure):
     """p3v_gemm_route_query_t (include/p3v.h): cu_count <= 0 = the device's own."""
     _fields_ = [("entry", i32), ("M", i32), ("N", i32), ("K", i32), ("lda", i32), ("ldw", i32), ("epilogue", i32), ("has_bias", i32),
@@ -236,6 +255,7 @@ SIGNATURES = {
     "p3v_gemm_ws_bytes": (i64, [i32, i32, i32, i32]),
     "p3v_gemm_rows_slices": (i32, [i32, i32, i32, i32]),
     "p3v_gemm_route": (i32, [C.POINTER(GemmRouteQuery), C.POINTER(GemmRoute)]),               # added after round 6, no version change
+    "p3v_gemv_route": (i32, [C.POINTER(GemvRouteQuery), C.POINTER(GemvRoute)]),               # added after round 6, no version change
     "p3v_gemv": (i32, [C.POINTER(GemvArgs), vp]),
     "p3v_gemv_step": (i32, [C.POINTER(GemvArgs), C.POINTER(GemvStep), vp]),
     "p3v_gemv_fp8_step": (i32, [C.POINTER(GemvF8Args), C.POINTER(GemvStep), vp]),

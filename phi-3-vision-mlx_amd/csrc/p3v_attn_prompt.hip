@@ -1290,14 +1290,8 @@ extern "C" int p3v_attention_route(const p3v_attn_prompt_query_t* query, p3v_att
 static int launch_prompt_kernel(const p3v_attn_prompt_route_t& r, int hd64, AttnP& p, hipStream_t s) {
   const PromptKernel& k = prompt_kernels[r.kernel][hd64][p.q_prescaled];
   static bool lds_raised[P3V_ATTN_PK_COUNT][2][2];
-  if (r.lds_bytes && !lds_raised[r.kernel][hd64][p.q_prescaled]) {
-    if (hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds_bytes) != hipSuccess) return P3V_ERR_HIP;
-    lds_raised[r.kernel][hd64][p.q_prescaled] = true;
-  }
   void* args[] = {&p};
-  (void)hipLaunchKernel(k.fn, dim3(r.grid[0], r.grid[1], r.grid[2]), dim3(r.block), args, r.lds_bytes, s);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
+  return p3v_launch(k.fn, lds_raised[r.kernel][hd64][p.q_prescaled], r.lds_bytes, dim3(r.grid[0], r.grid[1], r.grid[2]), dim3(r.block), args, r.lds_bytes, s);
 }
 
 extern "C" int64_t p3v_attention_ws_bytes(int B, int L, int n_heads, int hd, int n_split) {

@@ -22,6 +22,18 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
     if (e_ != hipSuccess) return P3V_ERR_LAUNCH;             \
   } while (0)
 
+// One launch of kernel `fn` from a table of instantiations.  `lds_cap` != 0: the kernel's dynamic-LDS limit is raised to it before its
+// first such launch, once per process -- `raised` is that instantiation's own flag.
+static inline int p3v_launch(const void* fn, bool& raised, int lds_cap, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
+  if (lds_cap && !raised) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap) != hipSuccess) return P3V_ERR_HIP;
+    raised = true;
+  }
+  (void)hipLaunchKernel(fn, grid, block, args, lds, s);
+  P3V_CHECK_LAUNCH();
+  return P3V_OK;
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t u) { return __uint_as_float(((uint32_t)u) << 16); }
 
 // round-to-nearest-even through the native conversion (v_cvt_pk_bf16_f32 on gfx950: one VALU op per PAIR,

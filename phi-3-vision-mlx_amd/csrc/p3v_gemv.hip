@@ -117,22 +117,6 @@ __global__ void __launch_bounds__(256) k_gemv(GemvP p) {
   }
 }
 
-template <int MT>
-static int launch_gemv(const GemvP& p, hipStream_t s) {
-  const size_t lds = (size_t)MT * p.K * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)k_gemv<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
-      return P3V_ERR_HIP;
-    attr_set = true;
-  }
-  int blocks = p3v_cdiv(p.units, 4);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_gemv<MT>, dim3(blocks), dim3(256), lds, s, p);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Streaming variant for the B=1 decode shapes (M <= 4; K = 3072 or 8192, compile-time): gemv_stream_body (p3v_gemv3_body.h) on
 // bf16 weights -- a lane load is 16 bytes = 8 weights, nothing travels with a stage, the sum of a row is its result.
@@ -150,7 +134,6 @@ struct GemvBf16 {
   static constexpr int WPL = 8, MAX_MT = 4, MIN_WG = 1;
   static constexpr bool XSUM = false, XSCALE = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; };
-  static int wpc() { return p3v_tuning().gemv_wpc; }
   static __device__ __forceinline__ void mark(int k) { GMARK(k); }
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
@@ -496,93 +479,37 @@ __global__ void __launch_bounds__(NW * 64) k_gemv_mfma8(GemvP p, int n_sets) {
   do_set(IC0{}, std::false_type{});
 }
 
-template <bool SILU, int NW, int NST>
-static int launch_gemv_mfma8(const GemvP& p, hipStream_t s) {
-  const size_t lds = (size_t)8 * (p.K * 2 + 64);
-  static bool attr_set = false;
-  if (!attr_set && lds > 40 * 1024) {
-    if (hipFuncSetAttribute((const void*)k_gemv_mfma8<SILU, NW, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8704) != hipSuccess)
-      return P3V_ERR_HIP;
-    attr_set = true;
-  }
-  // <= 256 workgroups (one per CU: 192-256 VGPRs per wave), each walking `per` strided row sets
-  // (576 sets -> 192 x 3, 1024 -> 256 x 4, 2004 -> 251 x 8, 192 -> 192 x 1)
-  const int max_wg = p3v_tuning().gemv8_wgs;
-  const int n_sets = p3v_cdiv(p.N, SILU ? 8 : 16), per = p3v_cdiv(n_sets, max_wg), grid = p3v_cdiv(n_sets, per);
-  hipLaunchKernelGGL((k_gemv_mfma8<SILU, NW, NST>), dim3(grid), dim3(NW * 64), lds, s, p, n_sets);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
-
-static int launch_gemv_mfma(const GemvP& p, hipStream_t s) {
-  dim3 grid(p3v_cdiv(p.N, 16));
-  if (p.epi == P3V_EPI_SILU_MUL) hipLaunchKernelGGL(k_gemv_mfma<true>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_gemv_mfma<false>, grid, dim3(256), 0, s, p);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
+// ---- every instantiation p3v_gemv / p3v_gemv_step can launch, found by what gemv_route chose
+static GemvKernel bf16_gemv[] = {{(const void*)k_gemv<1>}, {(const void*)k_gemv<2>}, {(const void*)k_gemv<4>}, {(const void*)k_gemv<8>}};   // [log2 MT]
+static GemvKernel bf16_mfma[] = {{(const void*)k_gemv_mfma<false>}, {(const void*)k_gemv_mfma<true>}};                                       // [SILU]
+static GemvRowsKernel bf16_mfma8[] = {GEMV_ROWS_KERNEL(k_gemv_mfma8, 4, 1), GEMV_ROWS_KERNEL(k_gemv_mfma8, 4, 2), GEMV_ROWS_KERNEL(k_gemv_mfma8, 4, 3),
+                                      GEMV_ROWS_KERNEL(k_gemv_mfma8, 8, 2), GEMV_ROWS_KERNEL(k_gemv_mfma8, 8, 4)};
+static GemvStreamKernel bf16_stream[] = {GEMV_STREAM_STEPS(GemvBf16, 0, 1, 6), GEMV_STREAM_STEPS(GemvBf16, 0, 4, 4), GEMV_STREAM_ROWS(GemvBf16, 2, 1, 6),
+                                         GEMV_STREAM_ROWS(GemvBf16, 2, 4, 4), GEMV_STREAM_ROWS(GemvBf16, 4, 1, 6), GEMV_STREAM_ROWS(GemvBf16, 4, 4, 4)};
 
 // The first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in (gemv_stream_body<.., STEP>): only
-// on the M = 1 streaming kernel (K = 3072 or 8192); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
+// where the route's step rule says so; anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_step(const p3v_gemv_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->out) return P3V_ERR_ARG;
-  GemvStepP sp; bool begin;
-  if (const int rc = gemv_step_params(a, st, p3v_tuning().gemv_variant == 3, sp, begin)) return rc;
+  p3v_gemv_route_t r; GemvStepP sp;
+  if (const int rc = gemv_step_route(P3V_GEMV_FMT_BF16, a, 0, st, r, sp)) return rc;
   GemvP p = {a->x, a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, (a->N + 1) / 2};
-  hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv_stream<GemvBf16, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvBf16, 1, 1, 6, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv_stream<GemvBf16, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvBf16, 1, 4, 4, STEP_END>(p, s, &sp);
+  return launch_gemv_stream(bf16_stream, r, p, &sp, (hipStream_t)stream);
 }
 
 extern "C" int p3v_gemv(const p3v_gemv_args_t* a, void* stream) {
   if (!a || !a->x || !a->W || !a->out) return P3V_ERR_ARG;
-  if (a->M <= 0 || a->M > 16 || a->N <= 0 || a->K <= 0 || a->K % 8) return P3V_ERR_ARG;
-  if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && a->epilogue != P3V_EPI_SILU_MUL &&
-      a->epilogue != P3V_EPI_F32)
-    return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
-  const int mt = a->M <= 1 ? 1 : a->M <= 2 ? 2 : a->M <= 4 ? 4 : 8;
+  p3v_gemv_route_t r;
+  gemv_route({P3V_GEMV_FMT_BF16, P3V_GEMV_STEP_NONE, a->M, a->N, a->K, a->epilogue, a->norm_w != nullptr, a->resid != nullptr, 0, 0}, &r);
+  if (r.status) return r.status;
   GemvP p = {a->x, a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
              a->epilogue == P3V_EPI_SILU_MUL ? a->N : (a->N + 1) / 2};
   hipStream_t s = (hipStream_t)stream;
-  const int variant = p3v_tuning().gemv_variant;       // 1: generic kernel only; 3: streaming kernel where it applies
-  if (variant == 3 && mt == 1 && a->N % 2 == 0 && (a->K == 3072 || a->K == 8192)) {
-    if (a->K == 3072) return launch_gemv_stream<GemvBf16, 1, 1, 6>(p, s);
-    return launch_gemv_stream<GemvBf16, 1, 4, 4>(p, s);                  // 8192 = 4 stages x 4 chunks: keeps 2 waves/SIMD resident
-  }
-  // 2 <= M <= 4: the same streaming kernel with MT activation rows in LDS (full-line weight loads, 4 v_dot2c per row and
-  // 16-byte chunk): measured 2.19 vs 2.94 ms/step at B = 2 and 2.64 vs 3.26 at B = 4 against k_gemv_mfma; from M = 5 on the
-  // matrix cores take over (at MT = 8 the VALU / LDS work per weight byte catches up: 4.72 ms/step at B = 8 against 4.08
-  // with k_gemv_mfma and 3.27 with k_gemv_mfma8).
-  const int rows_variant = p3v_tuning().gemv_rows;
-  // smallest M the 8-row MFMA kernel takes: 2 since it became persistent with the RMSNorm scale in the epilogue (decode step
-  // at ctx 2531, B = 2 / 3 / 4: 2.08 / 2.43 / 2.66 ms with the MT-row streaming kernel, 1.99 / 2.16 / 2.35 with this one);
-  // P3V_GEMV8_MIN=5 restores the round-1 split
-  const int rows8_min = p3v_tuning().gemv8_min;
-  if (rows_variant && variant == 3 && a->M >= 2 && a->M <= 4 && a->M < rows8_min && a->N % 2 == 0 && a->epilogue != P3V_EPI_F32 &&
-      (a->K == 3072 || a->K == 8192)) {
-    if (a->K == 3072) return mt == 2 ? launch_gemv_stream<GemvBf16, 2, 1, 6>(p, s) : launch_gemv_stream<GemvBf16, 4, 1, 6>(p, s);
-    return mt == 2 ? launch_gemv_stream<GemvBf16, 2, 4, 4>(p, s) : launch_gemv_stream<GemvBf16, 4, 4, 4>(p, s);
-  }
-  const int rows8 = p3v_tuning().gemv_mfma8;
-  if (rows8 && a->M >= rows8_min && a->M <= 8) {
-    const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-    switch (a->K) {                                      // K = NW waves x NST stages x 256
-      case 1024: return silu ? launch_gemv_mfma8<true, 4, 1>(p, s) : launch_gemv_mfma8<false, 4, 1>(p, s);
-      case 2048: return silu ? launch_gemv_mfma8<true, 4, 2>(p, s) : launch_gemv_mfma8<false, 4, 2>(p, s);
-      case 3072: return silu ? launch_gemv_mfma8<true, 4, 3>(p, s) : launch_gemv_mfma8<false, 4, 3>(p, s);
-      case 4096: return silu ? launch_gemv_mfma8<true, 8, 2>(p, s) : launch_gemv_mfma8<false, 8, 2>(p, s);
-      case 8192: return silu ? launch_gemv_mfma8<true, 8, 4>(p, s) : launch_gemv_mfma8<false, 8, 4>(p, s);
-      default: break;
-    }
-  }
-  if (a->M >= 2 && a->K % (4 * 32 * GM_G) == 0 && !p3v_tuning().gemv_no_mfma) return launch_gemv_mfma(p, s);
-  if (a->M > 8 || (size_t)mt * a->K * 2 > 160 * 1024 - 256) return P3V_ERR_UNSUPPORTED;
-  switch (mt) {
-    case 1: return launch_gemv<1>(p, s);
-    case 2: return launch_gemv<2>(p, s);
-    case 4: return launch_gemv<4>(p, s);
-    default: return launch_gemv<8>(p, s);
+  void* args[] = {&p, &r.n_sets};
+  switch (r.kernel) {
+    case P3V_GEMV_K_GEMV3: return launch_gemv_stream(bf16_stream, r, p, nullptr, s);
+    case P3V_GEMV_K_MFMA8: return launch_gemv_rows(bf16_mfma8, r, args, s);
+    case P3V_GEMV_K_MFMA: return gemv_launch(bf16_mfma[r.silu], r, args, s);
+    default: return gemv_launch(bf16_gemv[__builtin_ctz(r.MT)], r, args, s);
   }
 }

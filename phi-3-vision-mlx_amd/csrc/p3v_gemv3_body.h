@@ -1,5 +1,5 @@
 // The streaming M = 1 GEMV of the decode step, written ONCE for every weight format: gemv_stream_body, the two kernels around it
-// (k_gemv3 / k_gemv3_step), their launcher and the argument check of the p3v_gemv*_step entry points.  A weight format is a policy
+// (k_gemv3 / k_gemv3_step), their launch from a table of instantiations and what the p3v_gemv*_step entry points do alike.  A weight format is a policy
 // struct F -- GemvBf16 (p3v_gemv.hip), GemvF8 (p3v_gemv_fp8.hip), GemvQ4 (p3v_gemv_q4.hip) -- that supplies only what differs:
 //   P           the kernel's parameter struct (x, W, out, resid, norm_w, eps, M, N, K, epi, units + the format's own pointers)
 //   WPL         weights per lane load (8 bf16 / 16 e4m3 in 16 bytes, 16 nibbles in 8 bytes);  MAX_MT: x rows it can carry (1 unless bf16)
@@ -11,10 +11,9 @@
 //   XSCALE      the scaled 13-bit form (GemvB13<true>, p3v_gemv_b13.hip) wants the staged activations times its matrix's factor: stage_x
 //               (a pair on its way to LDS), x_unfit (does this thread's part of the row take the factor?) and dot_exact, the dot of
 //               the plain second loop that a workgroup with an unfit row runs on the row as it was
-//   wpc         the format's waves-per-CU tuning knob;  mark: timing stamp hook (tools/gemv_timeline.py: bf16 and the 13-bit codes;
-//               0 entry, 1 exit, 2 first dot)
-//   MIN_WG      workgroups per CU the kernels are compiled to fit (__launch_bounds__): 1 = whatever the registers allow; a format
-//               that asks for more also supplies wpc_end, the waves per CU of its STEP_END launch, which keeps the default bound
+//   mark        timing stamp hook (tools/gemv_timeline.py: bf16 and the 13-bit codes; 0 entry, 1 exit, 2 first dot)
+//   MIN_WG      workgroups per CU the kernels are compiled to fit (__launch_bounds__): 1 = whatever the registers allow; the STEP_END
+//               launch keeps the default bound (the waves per CU of every launch are gemv_route's, p3v_gemv_route.hip)
 // (fo_project, the o_proj stage of the fused attention launches in p3v_attention.hip, repeats this arithmetic from the p3v_dot_*.h
 // helpers; it does not share the body.  Two fused launches that did were removed in round 4: DESIGN.md section 3.1.)
 #pragma once
@@ -144,7 +143,7 @@ __device__ __forceinline__ void gemv_step_end_tail(const GemvStepP* sp, const Ar
 //     older x loads while the weights stream in;
 //   * (row pair, K stage) software pipeline with two register buffers: stage s+1 is in flight (2*CH lane loads per lane) while stage s
 //     is reduced; the residual needed by the epilogue travels with the stage (no dependent load at the end of a row);
-//   * grid = F::wpc() waves per CU, each wave owning a contiguous run of row pairs (a pure streaming read on this chip peaks at
+//   * grid = the format's waves per CU (gemv_route), each wave owning a contiguous run of row pairs (a pure streaming read on this chip peaks at
 //     2 blocks x 256 threads per CU, see tools/stream_floor.hip).
 // K = NST stages x CH lane loads x 64 lanes x F::WPL weights, compile-time.
 // wpw: waves of the 4-wave workgroup that take rows (4, or 3: wave 3 then only helps with the prologue).  1536 streaming waves
@@ -382,62 +381,49 @@ __global__ void __launch_bounds__(256, STEP == STEP_END ? 1 : F::MIN_WG) k_gemv3
   gemv_stream_body<F, MT, NST, CH, STEP>(p, units_per_wave, wpw, &sp);
 }
 
-// How a launch of `units` row pairs is cut up, for the launcher and for p3v_gemv_b13_plan alike: row pairs per wave, waves that take
-// rows, row-streaming waves per 4-wave workgroup.  Wave i owns row pairs [i * upw, (i + 1) * upw), cut at `units`.
-struct GemvPlan { int upw, waves, wpw; };
-static inline GemvPlan gemv_stream_plan(int units, int n_cu, int wpc, int forced_wpw) {
-  GemvPlan g;
-  g.upw = p3v_cdiv(units, (long)n_cu * (wpc < 1 ? 1 : wpc));
-  if (g.upw < 1) g.upw = 1;
-  g.waves = p3v_cdiv(units, g.upw);
-  g.wpw = p3v_gemv_wpw(g.waves, n_cu, forced_wpw);        // 4 or 3 row-streaming waves per workgroup
-  return g;
+// ---- launching: gemv_route (p3v_gemv_route.hip) holds every rule of what a decode projection call launches; an entry point checks the
+// pointers it was given, asks it and launches what it says from its tables of instantiations (below).  A kernel the route names and
+// no table holds is an error, never another kernel.
+void gemv_route(const p3v_gemv_route_query_t& q, p3v_gemv_route_t* r);
+
+struct GemvKernel { const void* fn; bool lds_raised; };       // one instantiation, and whether its dynamic-LDS limit has been raised
+static inline int gemv_launch(GemvKernel& k, const p3v_gemv_route_t& r, void** args, hipStream_t s) {
+  return p3v_launch(k.fn, k.lds_raised, r.lds_cap, dim3(r.grid), dim3(r.block), args, r.lds_bytes, s);
+}
+// the instantiations <SILU, NW, NST> of a rows kernel
+struct GemvRowsKernel { int NW, NST; GemvKernel k[2]; };
+#define GEMV_ROWS_KERNEL(f, NW, NST) {NW, NST, {{(const void*)f<false, NW, NST>}, {(const void*)f<true, NW, NST>}}}
+template <int n>
+static int launch_gemv_rows(GemvRowsKernel (&tab)[n], const p3v_gemv_route_t& r, void** args, hipStream_t s) {
+  for (GemvRowsKernel& e : tab)
+    if (e.NW == r.NW && e.NST == r.NST) return gemv_launch(e.k[r.silu], r, args, s);
+  return P3V_ERR_UNSUPPORTED;
+}
+// the instantiations of the streaming kernel for one format: k[step] (one row: k_gemv3 and the two k_gemv3_step; more rows: k_gemv3)
+struct GemvStreamKernel { int MT, NST, CH, scaled; GemvKernel k[3]; };
+#define GEMV_STREAM_STEPS(F, scaled, NST, CH) \
+  {1, NST, CH, scaled, {{(const void*)k_gemv3<F, 1, NST, CH>}, {(const void*)k_gemv3_step<F, 1, NST, CH, STEP_BEGIN>}, {(const void*)k_gemv3_step<F, 1, NST, CH, STEP_END>}}}
+#define GEMV_STREAM_ROWS(F, MT, NST, CH) {MT, NST, CH, 0, {{(const void*)k_gemv3<F, MT, NST, CH>}, {nullptr}, {nullptr}}}
+template <class P, int n>
+static int launch_gemv_stream(GemvStreamKernel (&tab)[n], const p3v_gemv_route_t& r, P& p, GemvStepP* sp, hipStream_t s) {
+  const int step = !sp ? STEP_NONE : sp->tok ? STEP_BEGIN : STEP_END;
+  int upw = r.upw, wpw = r.wpw;
+  void* args[] = {&p, &upw, &wpw, sp};
+  for (GemvStreamKernel& e : tab)
+    if (e.MT == r.MT && e.NST == r.NST && e.CH == r.CH && e.scaled == r.scaled && e.k[step].fn) return gemv_launch(e.k[step], r, args, s);
+  return P3V_ERR_UNSUPPORTED;
 }
 
-template <class F, int MT, int NST, int CH, int STEP = STEP_NONE>
-static int launch_gemv_stream(const typename F::P& p, hipStream_t s, const GemvStepP* sp = nullptr) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return P3V_ERR_HIP;
-    n_cu = pr.multiProcessorCount;
-  }
-  int wpc = F::wpc();
-  if constexpr (STEP == STEP_END && F::MIN_WG > 1) wpc = F::wpc_end();   // (that kernel is not bounded to MIN_WG workgroups a CU)
-  const GemvPlan g = gemv_stream_plan(p.units, n_cu, wpc, p3v_tuning().gemv_wpw);
-  const int upw = g.upw, waves = g.waves, wpw = g.wpw;
-  constexpr size_t K = (size_t)NST * CH * 64 * F::WPL, lds = MT * K * 2 + (F::XSUM ? K / 4 : 0);   // x as bf16 (+ the piece sums)
-  if constexpr (lds > 48 * 1024) {                       // (bf16, four x rows of K = 8192)
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)k_gemv3<F, MT, NST, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
-        return P3V_ERR_HIP;
-      attr_set = true;
-    }
-  }
-  if constexpr (STEP != STEP_NONE) {
-    if (p3v_cdiv(waves, wpw) > P3V_GEMV_STEP_MAX_WG) return P3V_ERR_UNSUPPORTED;       // (amax_ws holds one candidate per workgroup and row)
-    hipLaunchKernelGGL((k_gemv3_step<F, MT, NST, CH, STEP>), dim3(p3v_cdiv(waves, wpw)), dim3(256), lds, s, p, upw, wpw, *sp);
-  } else {
-    hipLaunchKernelGGL((k_gemv3<F, MT, NST, CH>), dim3(p3v_cdiv(waves, wpw)), dim3(256), lds, s, p, upw, wpw);
-  }
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
-// What p3v_gemv_step, p3v_gemv_fp8_step and p3v_gemv_q4_step check alike once their own pointers are known to be there, A = that
-// entry point's argument struct: exactly one end, one row, K = 3072 or 8192, no epilogue (`kernel_on`: the streaming kernel is the one
-// p3v_gemv* would run) -- anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.  P3V_OK: `sp` is
-// filled, `begin` says which end.
+// What the four p3v_gemv*_step entries do alike once their own pointers are known to be there, A = that entry point's argument struct:
+// exactly one end, the route of that end (anything but the one-row streaming kernel reports P3V_ERR_UNSUPPORTED and the caller keeps
+// the separate launches), the step struct's own pointers (`own_ok`: what the entry asks of its own beyond them).  P3V_OK: `r` is
+// the launch, `sp` is filled.
 template <class A>
-static int gemv_step_params(const A* a, const p3v_gemv_step_t* st, bool kernel_on, GemvStepP& sp, bool& begin) {
-  begin = st->tok != nullptr;
+static int gemv_step_route(int format, const A* a, int exp_base, const p3v_gemv_step_t* st, p3v_gemv_route_t& r, GemvStepP& sp, bool own_ok = true) {
+  const bool begin = st->tok != nullptr;
   if (begin == (st->next_tok != nullptr)) return P3V_ERR_ARG;   // exactly one of the two ends
-  if (a->M <= 0 || a->N <= 0 || a->K <= 0) return P3V_ERR_ARG;
-  // one row only: that is where p3v_gemv* itself runs this kernel (2 .. 8 rows go to the MFMA kernels, whose sums associate
-  // differently -- a folded step must stay bit-identical to the eager one)
-  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192) || !kernel_on || a->epilogue != P3V_EPI_NONE) return P3V_ERR_UNSUPPORTED;
+  gemv_route({format, begin ? P3V_GEMV_STEP_BEGIN : P3V_GEMV_STEP_END, a->M, a->N, a->K, a->epilogue, a->norm_w != nullptr, a->resid != nullptr, exp_base, 0}, &r);
+  if (r.status && !r.late) return r.status;
   if (begin) {
     if (!st->embed_table || !st->x_out || !st->cos_t || !st->sin_t || !st->d_past || !st->cos_out || !st->sin_out || st->vocab <= 0) return P3V_ERR_ARG;
     if (((uintptr_t)st->embed_table | (uintptr_t)st->x_out) & 15) return P3V_ERR_ARG;
@@ -445,7 +431,8 @@ static int gemv_step_params(const A* a, const p3v_gemv_step_t* st, bool kernel_o
     if (!a->x || !st->tok_out || !st->history || !st->d_step || !st->d_past || !st->ticket || !st->amax_ws) return P3V_ERR_ARG;
     if ((uintptr_t)st->amax_ws & 7) return P3V_ERR_ARG;
   }
+  if (!own_ok) return P3V_ERR_ARG;
   sp = {st->tok, st->embed_table, st->vocab, st->x_out, st->cos_t, st->sin_t, st->d_past, st->cos_out, st->sin_out, st->tab_t,
         st->half_dim, st->next_tok, st->tok_out, st->history, st->d_step, st->d_past, st->ticket, st->amax_ws, st->max_steps};
-  return P3V_OK;
+  return r.status;
 }

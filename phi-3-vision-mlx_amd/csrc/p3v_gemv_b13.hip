@@ -37,11 +37,8 @@ template <bool SCALED> struct GemvB13 {
   typedef GemvB13P P;
   static constexpr int WPL = 8, MAX_MT = 1, MIN_WG = 4;
   static constexpr bool XSUM = false, XSCALE = SCALED;
-  // 4 workgroups a CU (at most 128 VGPRs): the decode's VALU operations want the fourth wave of a SIMD, and
-  // gemv_b13_wpc = 16 puts it there (gate_up: 4096 waves, all resident)
+  // 4 workgroups a CU (at most 128 VGPRs): the decode's VALU operations want the fourth wave of a SIMD (gemv_route puts it there)
   template <int CH> using Stage = B13Stage<CH, !SCALED>;   // (the scaled form needs no base in the pipeline)
-  static int wpc() { return p3v_tuning().gemv_b13_wpc; }
-  static int wpc_end() { return p3v_tuning().gemv_b13_wpc_end; }   // the vocabulary head's fold: 16 waves a CU would not be resident
   static __device__ __forceinline__ void mark(int k) { B13MARK(k); }
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int, int c0, Stage<CH>& st) {
@@ -253,56 +250,39 @@ extern "C" int p3v_unpack_b13(const void* packed, int rows, int K, int silu_pair
 }
 
 // ---------------------------------------------------------------- entry points: the twins of p3v_gemv_fp8 / p3v_gemv_fp8_step, one row only
-// The scaled form (GemvB13<true>) serves a matrix whose factor 2^(base - 1) leaves the activations room: base - 1 <= 96, so that every
-// |x| < 2^32 fits (a row that does not falls back inside the kernel) -- at K = 3072 (qkv, gate_up, the vocabulary head).  K = 8192
-// (down) keeps the exact decode: its waves stage 16 KB of x for ONE row pair each, the staging sits in front of the first dot and the
-// loop's VALU work hides behind the stream either way (measured 8.86 -> 9.02 us scaled, profiles/pack13_xscale_step_trace_summary.txt),
-// so that instantiation is not built.  gemv_b13_xscale = 0 keeps the exact decode everywhere.
-#define B13_XSCALE_MAX_SHIFT 96
-static int b13_params(const p3v_gemv_b13_args_t* a, GemvB13P& p, bool& scaled) {
-  if (a->M <= 0 || a->N <= 0) return P3V_ERR_ARG;
-  if (a->M != 1 || a->N % 2 || (a->K != 3072 && a->K != 8192)) return P3V_ERR_UNSUPPORTED;
-  if (a->exp_base < 1 || a->exp_base > 224 || ((uintptr_t)a->W & 15)) return P3V_ERR_ARG;
-  if ((a->silu_pairs != 0) != (a->epilogue == P3V_EPI_SILU_MUL)) return P3V_ERR_ARG;   // the row pairing is part of the packing
-  scaled = p3v_tuning().gemv_b13_xscale != 0 && a->exp_base - 1 <= B13_XSCALE_MAX_SHIFT && a->K == 3072;
-  p = {a->x, (const uint32_t*)a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
-       a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2, b13_cc(a->exp_base)};
-  return P3V_OK;
+// every instantiation they can launch, found by what gemv_route chose (the scaled form at K = 8192 is not built: see the route)
+static GemvStreamKernel b13_stream[] = {GEMV_STREAM_STEPS(GemvB13<true>, 1, 1, 6), GEMV_STREAM_STEPS(GemvB13<false>, 0, 1, 6), GEMV_STREAM_STEPS(GemvB13<false>, 0, 4, 4)};
+
+// what the entries ask of their own pointers beyond null checks: the container's alignment, and the row pairing, which is part of the packing
+static bool b13_own_ok(const p3v_gemv_b13_args_t* a) { return !((uintptr_t)a->W & 15) && (a->silu_pairs != 0) == (a->epilogue == P3V_EPI_SILU_MUL); }
+static GemvB13P b13_params(const p3v_gemv_b13_args_t* a) {
+  return {a->x, (const uint32_t*)a->W, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
+          a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2, b13_cc(a->exp_base)};
 }
 
 extern "C" int p3v_gemv_b13_plan(int N, int K, int epilogue, int n_cu, int* out) {
   if (!out || N <= 0 || n_cu <= 0) return P3V_ERR_ARG;
-  if (N % 2 || (K != 3072 && K != 8192)) return P3V_ERR_UNSUPPORTED;
-  const GemvPlan g = gemv_stream_plan(epilogue == P3V_EPI_SILU_MUL ? N : N / 2, n_cu, GemvB13<true>::wpc(), p3v_tuning().gemv_wpw);
-  out[0] = g.upw; out[1] = g.waves; out[2] = g.wpw; out[3] = p3v_cdiv(g.waves, g.wpw);
+  p3v_gemv_route_t r;
+  gemv_route({P3V_GEMV_FMT_B13, P3V_GEMV_STEP_NONE, 1, N, K, epilogue == P3V_EPI_SILU_MUL ? P3V_EPI_SILU_MUL : P3V_EPI_NONE, 0, 0, 1, n_cu}, &r);
+  if (r.status) return r.status;
+  out[0] = r.upw; out[1] = r.waves; out[2] = r.wpw; out[3] = r.grid;
   return P3V_OK;
-}
-
-static int b13_launch_step(const GemvB13P& p, int K, bool scaled, bool begin, const GemvStepP& sp, hipStream_t s) {
-  if (K == 8192) return begin ? launch_gemv_stream<GemvB13<false>, 1, 4, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<false>, 1, 4, 4, STEP_END>(p, s, &sp);
-  if (scaled) return begin ? launch_gemv_stream<GemvB13<true>, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<true>, 1, 1, 6, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv_stream<GemvB13<false>, 1, 1, 6, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvB13<false>, 1, 1, 6, STEP_END>(p, s, &sp);
 }
 
 extern "C" int p3v_gemv_b13_step(const p3v_gemv_b13_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->out) return P3V_ERR_ARG;
-  GemvStepP sp; bool begin, scaled;
-  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
-  GemvB13P p;
-  if (const int rc = b13_params(a, p, scaled)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  return b13_launch_step(p, a->K, scaled, begin, sp, s);
+  p3v_gemv_route_t r; GemvStepP sp;
+  if (const int rc = gemv_step_route(P3V_GEMV_FMT_B13, a, a->exp_base, st, r, sp, b13_own_ok(a))) return rc;
+  GemvB13P p = b13_params(a);
+  return launch_gemv_stream(b13_stream, r, p, &sp, (hipStream_t)stream);
 }
 
 extern "C" int p3v_gemv_b13(const p3v_gemv_b13_args_t* a, void* stream) {
   if (!a || !a->x || !a->W || !a->out) return P3V_ERR_ARG;
-  if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && a->epilogue != P3V_EPI_SILU_MUL &&
-      a->epilogue != P3V_EPI_F32)
-    return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
-  GemvB13P p; bool scaled;
-  if (const int rc = b13_params(a, p, scaled)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (a->K == 8192) return launch_gemv_stream<GemvB13<false>, 1, 4, 4>(p, s);
-  return scaled ? launch_gemv_stream<GemvB13<true>, 1, 1, 6>(p, s) : launch_gemv_stream<GemvB13<false>, 1, 1, 6>(p, s);
+  p3v_gemv_route_t r;
+  gemv_route({P3V_GEMV_FMT_B13, P3V_GEMV_STEP_NONE, a->M, a->N, a->K, a->epilogue, a->norm_w != nullptr, a->resid != nullptr, a->exp_base, 0}, &r);
+  if (r.status) return r.status;
+  if (!b13_own_ok(a)) return P3V_ERR_ARG;
+  GemvB13P p = b13_params(a);
+  return launch_gemv_stream(b13_stream, r, p, nullptr, (hipStream_t)stream);
 }

@@ -28,7 +28,6 @@ struct GemvF8 {
   static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
   static constexpr bool XSUM = false, XSCALE = false;
   template <int CH> struct Stage { u32x4_t w[2][CH]; float scale[2]; };
-  static int wpc() { return p3v_tuning().gemv_f8_wpc; }   // (a stage is half the bytes of the bf16 kernel's: twice the waves keep as many in flight; 8: 1.321, 16: 1.301, 24: 1.333 ms/step)
   static __device__ __forceinline__ void mark(int) {}
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
@@ -294,20 +293,6 @@ __global__ void __launch_bounds__(NW * 64) k_gemv_mfma8_f8(GemvF8P p) {
   }
 }
 
-template <bool SILU, int NW, int NL>
-static int launch_gemv_mfma8_f8(const GemvF8P& p, hipStream_t s) {
-  const size_t lds = (size_t)8 * (p.K * 2 + 64);
-  static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)k_gemv_mfma8_f8<SILU, NW, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess)
-      return P3V_ERR_HIP;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_gemv_mfma8_f8<SILU, NW, NL>), dim3(p3v_cdiv(p.N, SILU ? 8 : 16)), dim3(NW * 64), lds, s, p);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
 // ---------------------------------------------------------------- fp8 -> bf16 (prefill scratch)
 __global__ void __launch_bounds__(256) k_dequant_fp8(const u32x4_t* __restrict__ w8, const float* __restrict__ scale,
                                                      u32x4_t* __restrict__ out, int chunks_per_row, long total) {
@@ -337,37 +322,33 @@ extern "C" int p3v_dequant_fp8(const uint8_t* w8, const float* scale, uint16_t* 
   return P3V_OK;
 }
 
+// ---- every instantiation p3v_gemv_fp8 / p3v_gemv_fp8_step can launch, found by what gemv_route chose
+static GemvKernel f8_mfma[] = {{(const void*)k_gemv_mfma_f8<false>}, {(const void*)k_gemv_mfma_f8<true>}};   // [SILU]
+static GemvRowsKernel f8_mfma8[] = {GEMV_ROWS_KERNEL(k_gemv_mfma8_f8, 4, 6), GEMV_ROWS_KERNEL(k_gemv_mfma8_f8, 8, 8)};
+static GemvStreamKernel f8_stream[] = {GEMV_STREAM_STEPS(GemvF8, 0, 1, 3), GEMV_STREAM_STEPS(GemvF8, 0, 2, 4)};
+
 // p3v_gemv_step on e4m3 weights: the first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in
-// (one row, K = 3072 or 8192, no epilogue); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
+// where the route's step rule says so; anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_fp8_step(const p3v_gemv_fp8_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->w_scale || !a->out) return P3V_ERR_ARG;
-  GemvStepP sp; bool begin;
-  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
-  const GemvF8P p = {a->x, a->W, a->w_scale, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
-  hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv_stream<GemvF8, 1, 1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvF8, 1, 1, 3, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv_stream<GemvF8, 1, 2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvF8, 1, 2, 4, STEP_END>(p, s, &sp);
+  p3v_gemv_route_t r; GemvStepP sp;
+  if (const int rc = gemv_step_route(P3V_GEMV_FMT_FP8, a, 0, st, r, sp)) return rc;
+  GemvF8P p = {a->x, a->W, a->w_scale, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
+  return launch_gemv_stream(f8_stream, r, p, &sp, (hipStream_t)stream);
 }
 
 extern "C" int p3v_gemv_fp8(const p3v_gemv_fp8_args_t* a, void* stream) {
   if (!a || !a->x || !a->W || !a->w_scale || !a->out) return P3V_ERR_ARG;
-  if (a->M <= 0 || a->M > 16 || a->N <= 0 || a->N % 2 || (a->K != 3072 && a->K != 8192)) return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && a->epilogue != P3V_EPI_SILU_MUL &&
-      a->epilogue != P3V_EPI_F32)
-    return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
+  p3v_gemv_route_t r;
+  gemv_route({P3V_GEMV_FMT_FP8, P3V_GEMV_STEP_NONE, a->M, a->N, a->K, a->epilogue, a->norm_w != nullptr, a->resid != nullptr, 0, 0}, &r);
+  if (r.status) return r.status;
   GemvF8P p = {a->x, a->W, a->w_scale, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
                a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2};
   hipStream_t s = (hipStream_t)stream;
-  if (a->M == 1) return a->K == 3072 ? launch_gemv_stream<GemvF8, 1, 1, 3>(p, s) : launch_gemv_stream<GemvF8, 1, 2, 4>(p, s);
-  if (a->M >= 5 && a->M <= 8 && !p3v_tuning().gemv_no_mfma8) {
-    const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-    if (a->K == 3072) return silu ? launch_gemv_mfma8_f8<true, 4, 6>(p, s) : launch_gemv_mfma8_f8<false, 4, 6>(p, s);
-    return silu ? launch_gemv_mfma8_f8<true, 8, 8>(p, s) : launch_gemv_mfma8_f8<false, 8, 8>(p, s);
+  void* args[] = {&p};
+  switch (r.kernel) {
+    case P3V_GEMV_K_GEMV3: return launch_gemv_stream(f8_stream, r, p, nullptr, s);
+    case P3V_GEMV_K_MFMA8_F8: return launch_gemv_rows(f8_mfma8, r, args, s);
+    default: return gemv_launch(f8_mfma[r.silu], r, args, s);
   }
-  dim3 grid(p3v_cdiv(a->N, 16));
-  if (a->epilogue == P3V_EPI_SILU_MUL) hipLaunchKernelGGL(k_gemv_mfma_f8<true>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_gemv_mfma_f8<false>, grid, dim3(256), 0, s, p);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
 }

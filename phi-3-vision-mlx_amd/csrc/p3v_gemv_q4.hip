@@ -32,7 +32,6 @@ struct GemvQ4 {
   static constexpr int WPL = 16, MAX_MT = 1, MIN_WG = 1;
   static constexpr bool XSUM = true, XSCALE = false;
   template <int CH> struct Stage { u32x2_t w[2][CH]; uint32_t sb[2][CH]; };
-  static int wpc() { return p3v_tuning().gemv_q4_wpc; }
   static __device__ __forceinline__ void mark(int) {}
   template <int K, int CH>
   static __device__ __forceinline__ void load(const P& p, int r0, int r1, int c0, Stage<CH>& st) {
@@ -90,16 +89,16 @@ extern "C" int p3v_dequant_q4(const uint32_t* w4, const uint32_t* sb, uint16_t* 
   return P3V_OK;
 }
 
+static GemvStreamKernel q4_stream[] = {GEMV_STREAM_STEPS(GemvQ4, 0, 1, 3), GEMV_STREAM_STEPS(GemvQ4, 0, 2, 4)};
+
 // p3v_gemv_step on MLX 4-bit weights: the first / last projection of a replayed greedy step with p3v_step_begin / p3v_step_end folded in
-// (one row, K = 3072 or 8192, no epilogue); anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
+// where the route's step rule says so; anything else reports P3V_ERR_UNSUPPORTED and the caller keeps the separate launches.
 extern "C" int p3v_gemv_q4_step(const p3v_gemv_q4_args_t* a, const p3v_gemv_step_t* st, void* stream) {
   if (!a || !st || !a->W || !a->sb || !a->out) return P3V_ERR_ARG;
-  GemvStepP sp; bool begin;
-  if (const int rc = gemv_step_params(a, st, true, sp, begin)) return rc;
-  const GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
-  hipStream_t s = (hipStream_t)stream;
-  if (a->K == 3072) return begin ? launch_gemv_stream<GemvQ4, 1, 1, 3, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvQ4, 1, 1, 3, STEP_END>(p, s, &sp);
-  return begin ? launch_gemv_stream<GemvQ4, 1, 2, 4, STEP_BEGIN>(p, s, &sp) : launch_gemv_stream<GemvQ4, 1, 2, 4, STEP_END>(p, s, &sp);
+  p3v_gemv_route_t r; GemvStepP sp;
+  if (const int rc = gemv_step_route(P3V_GEMV_FMT_Q4, a, 0, st, r, sp)) return rc;
+  GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue, a->N / 2};
+  return launch_gemv_stream(q4_stream, r, p, &sp, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -459,56 +458,28 @@ __global__ void __launch_bounds__(NW * 64) k_gemv8_q4(RowsQ4P p, const bf16_t* n
   do_set(std::false_type{});
 }
 
-template <bool SILU, int NW, int NST>
-static int launch_gemv8_q4(const RowsQ4P& p, const bf16_t* norm_w, float eps, hipStream_t s) {
-  const size_t lds = (size_t)8 * (p.K * 2 + 32);
-  static bool attr_set = false;
-  if (!attr_set && lds > 40 * 1024) {
-    if (hipFuncSetAttribute((const void*)k_gemv8_q4<SILU, NW, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8704) != hipSuccess)
-      return P3V_ERR_HIP;
-    attr_set = true;
-  }
-  const int per = p3v_cdiv(p.n_sets, p3v_tuning().gemv_q4_rows_wgs), gx = p3v_cdiv(p.n_sets, per);
-  hipLaunchKernelGGL((k_gemv8_q4<SILU, NW, NST>), dim3(gx), dim3(NW * 64), lds, s, p, norm_w, eps);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
-
-template <bool SILU, int NW, int NST>
-static int launch_rows_q4(const RowsQ4P& p, hipStream_t s) {
-  const int per = p3v_cdiv(p.n_sets, p3v_tuning().gemv_q4_rows_wgs), gx = p3v_cdiv(p.n_sets, per);
-  hipLaunchKernelGGL((k_gemm_rows_q4<SILU, NW, NST>), dim3(gx), dim3(NW * 64), 0, s, p);
-  P3V_CHECK_LAUNCH();
-  return P3V_OK;
-}
+// ---- every instantiation p3v_gemv_q4 can launch beside the streaming ones (q4_stream), found by what gemv_route chose
+static GemvRowsKernel q4_gemv8[] = {GEMV_ROWS_KERNEL(k_gemv8_q4, 4, 3), GEMV_ROWS_KERNEL(k_gemv8_q4, 8, 4)};
+static GemvRowsKernel q4_rows[] = {GEMV_ROWS_KERNEL(k_gemm_rows_q4, 4, 3), GEMV_ROWS_KERNEL(k_gemm_rows_q4, 8, 4)};
 
 extern "C" int p3v_gemv_q4(const p3v_gemv_q4_args_t* a, void* stream) {
   if (!a || !a->x || !a->W || !a->sb || !a->out) return P3V_ERR_ARG;
-  if (a->M >= 2 && a->M <= 16 && (a->K == 3072 || a->K == 8192) && (!a->norm_w || a->M <= 8) && a->N > 0) {
-    // 2 .. 8 rows: k_gemv8_q4 (input RMSNorm optional); 9 .. 16: k_gemm_rows_q4 (the caller normalises)
-    const bool silu = a->epilogue == P3V_EPI_SILU_MUL;
-    if (a->N % (silu ? 8 : 16)) return P3V_ERR_UNSUPPORTED;
-    if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && !silu && a->epilogue != P3V_EPI_F32) return P3V_ERR_UNSUPPORTED;
-    if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
-    if (((uintptr_t)a->x | (uintptr_t)a->W) & 15) return P3V_ERR_ARG;
-    const RowsQ4P q = {a->x, a->W, a->sb, a->out, a->resid, a->M, a->N, a->K, a->epilogue, a->N / (silu ? 8 : 16)};
-    hipStream_t s = (hipStream_t)stream;
-    if (a->M <= 8 && p3v_tuning().gemv_q4_rows8) {
-      if (a->norm_w && ((uintptr_t)a->norm_w & 15)) return P3V_ERR_ARG;
-if (a->K == 3072) return silu ? launch_gemv8_q4<true, 4, 3>(q, a->norm_w, a->norm_eps, s) : launch_gemv8_q4<false, 4, 3>(q, a->norm_w, a->norm_eps, s);
-      return silu ? launch_gemv8_q4<true, 8, 4>(q, a->norm_w, a->norm_eps, s) : launch_gemv8_q4<false, 8, 4>(q, a->norm_w, a->norm_eps, s);
-    }
-    if (a->norm_w) return P3V_ERR_UNSUPPORTED;
-    if (a->K == 3072) return silu ? launch_rows_q4<true, 4, 3>(q, s) : launch_rows_q4<false, 4, 3>(q, s);
-    return silu ? launch_rows_q4<true, 8, 4>(q, s) : launch_rows_q4<false, 8, 4>(q, s);
-  }
-  if (a->M != 1 || a->N <= 0 || a->N % 2 || (a->K != 3072 && a->K != 8192)) return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue != P3V_EPI_NONE && a->epilogue != P3V_EPI_RESID_BF16 && a->epilogue != P3V_EPI_SILU_MUL &&
-      a->epilogue != P3V_EPI_F32)
-    return P3V_ERR_UNSUPPORTED;
-  if (a->epilogue == P3V_EPI_RESID_BF16 && !a->resid) return P3V_ERR_ARG;
-  GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
-               a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2};
+  p3v_gemv_route_t r;
+  gemv_route({P3V_GEMV_FMT_Q4, P3V_GEMV_STEP_NONE, a->M, a->N, a->K, a->epilogue, a->norm_w != nullptr, a->resid != nullptr, 0, 0}, &r);
+  if (r.status && !r.late) return r.status;
   hipStream_t s = (hipStream_t)stream;
-  return a->K == 3072 ? launch_gemv_stream<GemvQ4, 1, 1, 3>(p, s) : launch_gemv_stream<GemvQ4, 1, 2, 4>(p, s);
+  if (r.kernel == P3V_GEMV_K_GEMV3) {
+    GemvQ4P p = {a->x, a->W, a->sb, a->out, a->resid, a->norm_w, a->norm_eps, a->M, a->N, a->K, a->epilogue,
+                 a->epilogue == P3V_EPI_SILU_MUL ? a->N : a->N / 2};
+    return launch_gemv_stream(q4_stream, r, p, nullptr, s);
+  }
+  // the rows kernels load x and W in 16-byte units (and k_gemv8_q4 the norm weights)
+  if (((uintptr_t)a->x | (uintptr_t)a->W) & 15) return P3V_ERR_ARG;
+  if (r.kernel == P3V_GEMV_K_GEMV8_Q4 && ((uintptr_t)a->norm_w & 15)) return P3V_ERR_ARG;
+  if (r.status) return r.status;
+  RowsQ4P q = {a->x, a->W, a->sb, a->out, a->resid, a->M, a->N, a->K, a->epilogue, r.n_sets};
+  const bf16_t* norm_w = a->norm_w;
+  float eps = a->norm_eps;
+  void* args[] = {&q, &norm_w, &eps};
+  return r.kernel == P3V_GEMV_K_GEMV8_Q4 ? launch_gemv_rows(q4_gemv8, r, args, s) : launch_gemv_rows(q4_rows, r, args, s);
 }

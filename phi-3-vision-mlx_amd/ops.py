@@ -249,6 +249,17 @@ def gemv(x, w, epilogue=EPI_NONE, resid=None, norm_w=None, norm_eps=0.0, out=Non
     return out
 
 
+def gemv_route(M, N, K, epilogue=EPI_NONE, fmt="bf16", step=L.GEMV_STEP_NONE, has_norm=False, has_resid=True, exp_base=0, cu_count=0):
+    """What `gemv` / `gemv_fp8` / `gemv_q4` / `gemv_b13` (fmt: a `_weight_format` name) or, with `step`, `gemv_step_begin` /
+    `gemv_step_end` launch for this call -> L.GemvRoute: status, kernel and its instantiation, name, grid, block, LDS, the streaming
+    plan (include/p3v.h: p3v_gemv_route).  The gemv* knobs are the library's settings; with `cu_count` given no device is asked."""
+    q = L.GemvRouteQuery(("bf16", "fp8", "q4", "b13").index(fmt), step, M, N, K, epilogue, int(bool(has_norm)), int(bool(has_resid)),
+                         exp_base, cu_count)
+    r = L.GemvRoute()
+    L.check(L.lib().p3v_gemv_route(C.byref(q), C.byref(r)), "gemv_route")
+    return r
+
+
 def resample_u8(src, out_len, axis, coeffs, bounds):
     """One pass of Pillow's 8-bit bilinear resample (phi.py:301) along `axis` (0 = rows, 1 = columns) of a uint8 image
     [H, W, C]; coeffs [out_len, ksize] int32, bounds [out_len, 2] int32 (processor.pil_bilinear_coeffs)."""

@@ -69,6 +69,7 @@ behind (every case); everything outside [M, N] -- for PATCH: outside the remappe
 back bit-identical.  p3v_gemv has no strides: its cases are guarded only.
 """
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
 from functools import lru_cache
 
@@ -216,6 +217,34 @@ def _gemv_cases():
                              (9, 100, 2048, RESID_BF16, {"norm": True})):
         c.append(gv("k_gemv_mfma", M, N, K, epi, mf, **kw))
     return tuple(c)
+
+
+def gemv_claim(r, fmt="bf16"):
+    """The kernel of an ops.gemv_route answer in the shorthand of a case's `kernel` field: k_gemv<MT>, k_gemv3<MT> (bf16) or
+    k_gemv3<policy> (the other formats), and the bare template name of every other kernel."""
+    name = r.name.decode()
+    base = name.split("<")[0]
+    if base == "k_gemv3":
+        return f"k_gemv3<{r.MT}>" if fmt == "bf16" else f"k_gemv3<{name[len('k_gemv3<'):].split(',')[0].split('<')[0]}>"
+    return name if base == "k_gemv" else base
+
+
+@contextmanager
+def pinned(ops, case, cu_count=0):
+    """Pin the kernel of `case` for the call about to be made: sets the case's knobs, for a GEMV case asserts from the library's route
+    (ops.gemv_route, the library's own settings; cu_count = 0: this device) that the call runs the kernel the case's `kernel` field
+    claims, and restores the knobs."""
+    old = [(name, ops.set_tuning(name, value)) for name, value in case.knobs]
+    try:
+        if case.entry == "gemv":
+            fmt = {"bf16": "bf16", "f8": "fp8", "q4": "q4"}[getattr(case, "fmt", "bf16")]
+            r = ops.gemv_route(case.M, case.N, case.K, case.epi, fmt=fmt, has_norm=case.norm, cu_count=cu_count)
+            got = gemv_claim(r, fmt) if r.status == 0 else f"refused: {r.status}"
+            assert got == case.kernel, f"pinned {case.id}: the call runs {r.name.decode() or got!r}, not {case.kernel}"
+        yield
+    finally:
+        for name, value in reversed(old):
+            ops.set_tuning(name, value)
 
 
 GEMM_CASES, GEMV_CASES = _gemm_cases(), _gemv_cases()

@@ -58,7 +58,7 @@ import torch
 
 import proj_probe as pp
 from glue_probe import BF16, F32, F64, GUARD, _gen, bracket, needed_scale, to_bf16, unique_share, worst, worst_abs  # noqa: F401 (re-exported for the tests)
-from proj_probe import EPS, MIN_KEPT, MIN_UNIQUE, NNZ, NONE, OUT_F32, RESID_BF16, SILU, sentinel  # noqa: F401
+from proj_probe import EPS, MIN_KEPT, MIN_UNIQUE, NNZ, NONE, OUT_F32, RESID_BF16, SILU, pinned, sentinel  # noqa: F401 (pinned: a QCase's `fmt` names its entry)
 
 F16, F8, U8 = torch.float16, torch.float8_e4m3fn, torch.uint8
 FAMILIES = pp.FAMILIES

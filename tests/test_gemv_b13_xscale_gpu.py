@@ -82,7 +82,9 @@ def case():
     cache.clear()
 
 
-def run_both(ops, x, w, epi, nw, N, seed=13):
+def run_both(ops, x, w, epi, nw, N, knob, seed=13):
+    """(the packing, p3v_gemv's output, p3v_gemv_b13's), the latter pinned: the library's route says that the call runs the form the
+    test is about -- the scaled one exactly at knob = 1, K = 3072 and a base whose factor leaves the activations room."""
     if epi == "norm_silu":
         pk = ops.pack_b13(w, silu_pairs=True)
         kw = dict(epilogue=ops.EPI_SILU_MUL, norm_w=nw, norm_eps=1e-5)
@@ -91,6 +93,10 @@ def run_both(ops, x, w, epi, nw, N, seed=13):
         kw = {"none": {}, "norm": dict(norm_w=nw, norm_eps=1e-5), "f32": dict(epilogue=ops.EPI_F32),
               "resid": dict(epilogue=ops.EPI_RESID_BF16, resid=g((1, N), seed).cuda())}[epi]
     assert pk is not None
+    r = ops.gemv_route(1, N, pk.K, kw.get("epilogue", ops.EPI_NONE), fmt="b13", has_norm="norm_w" in kw, exp_base=pk.base)
+    scaled = knob == 1 and pk.K == 3072 and pk.base - 1 <= MAX_SHIFT
+    want = "k_gemv3<GemvB13<%s>, 1, %s>" % ("true" if scaled else "false", "1, 6" if pk.K == 3072 else "4, 4")
+    assert r.status == 0 and r.name.decode() == want, f"the call runs {r.name.decode()!r}, not {want}"
     return pk, ops.gemv(x, w, **kw), ops.gemv_b13(x, pk, **kw)
 
 
@@ -103,8 +109,8 @@ def test_scaled_gemv_is_the_bf16_gemv(ops, case, xscale, K, N, epi, e_top, knob)
     xscale(knob)
     x, nw, rows = case(K)
     w = moved(rows[:2 * N if epi == "norm_silu" else N], e_top)
-    pk, ref, out = run_both(ops, x, w, epi, nw, N)
-    assert pk.base - 1 == e_top - 31 <= MAX_SHIFT                            # 96: the edge of the scaled form; 69: a small shift
+    pk, ref, out = run_both(ops, x, w, epi, nw, N, knob)
+    assert pk.base - 1 == e_top - 31 <= MAX_SHIFT                           # 96: the edge of the scaled form; 69: a small shift
     assert ref.shape == (1, N) and same_bits(out, ref)
     assert torch.isfinite(ref.float()).all() and ref.float().abs().max() > 0
 
@@ -137,7 +143,7 @@ def test_activation_probes_on_an_eligible_matrix(ops, case, xscale, K, kind, epi
     _, nw, rows = case(K)
     N = 66
     x = probe_x(kind, K, 20 + K)
-    pk, ref, out = run_both(ops, x, rows[:N].contiguous(), epi, nw, N)
+    pk, ref, out = run_both(ops, x, rows[:N].contiguous(), epi, nw, N, knob)
     assert pk.base - 1 == MAX_SHIFT
     assert same_but_nan(out, ref)
     if kind in ("zeros", "denormal", "largest", "unfit"):
@@ -154,7 +160,7 @@ def test_ineligible_matrix_keeps_the_exact_decode(ops, case, xscale, K, epi, kno
     x, nw, rows = case(K)
     N = 66
     w = moved(rows[:2 * N if epi == "norm_silu" else N], 130)
-    pk, ref, out = run_both(ops, x, w, epi, nw, N)
+    pk, ref, out = run_both(ops, x, w, epi, nw, N, knob)
     assert pk.base - 1 == 99 > MAX_SHIFT
     assert same_bits(out, ref) and torch.isfinite(ref.float()).all()
 

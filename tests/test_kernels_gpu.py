@@ -1545,8 +1545,10 @@ def test_gemv_q4_rows_2_to_16(ops, N, K, epi, M):
         return
     # 2 .. 8 rows (k_gemv8_q4): the input RMSNorm rides along -- the value p3v_rmsnorm writes (bf16, exact in fp16), so the fused call
     # equals the two calls up to the summation order of the squares (a last-bit difference of r on a handful of elements)
+    assert ops.gemv_route(M, N, K, e, fmt="q4").name.decode().startswith("k_gemv8_q4<")
     ops.set_tuning("gemv_q4_rows8", 0)                             # k_gemm_rows_q4 (also what 9 .. 16 rows run): same product, other order
     try:
+        assert ops.gemv_route(M, N, K, e, fmt="q4").name.decode().startswith("k_gemm_rows_q4<")
         near(ops.gemv_q4(x.cuda(), w4, sb, e, resid=res.cuda() if epi == "resid" else None), ref)
     finally:
         ops.set_tuning("gemv_q4_rows8", 1)

@@ -59,6 +59,14 @@ def test_table_reaches_every_kernel():
         assert {c.epi for c in pp.CASES if group(c) == "k_gemm256" and c.tag == tag} == set(range(9)) - {pp.PATCH}
 
 
+def test_gemv_cases_reach_the_kernel_they_name():
+    """The knobs of every p3v_gemv case pin the kernel its `kernel` field claims: asked of the library's route on 256 CUs (no device)."""
+    from phi_3_vision_mlx_amd import ops
+    for case in pp.GEMV_CASES:
+        with pp.pinned(ops, case, cu_count=256):
+            pass
+
+
 @pytest.mark.parametrize("family", pp.FAMILIES)
 @pytest.mark.parametrize("case", pp.CASES, ids=ids)
 def test_reference_passes_in_every_order(case, family):

@@ -31,14 +31,8 @@ def _used(s):
 
 
 def _pinned(ops, case, call):
-    old = []
-    try:
-        for name, value in case.knobs:
-            old.append((name, ops.set_tuning(name, value)))
+    with qp.pinned(ops, case):
         return call()
-    finally:
-        for name, value in reversed(old):
-            ops.set_tuning(name, value)
 
 
 def _ptr(t):

@@ -82,6 +82,14 @@ def test_table_reaches_every_kernel_and_epilogue():
             assert c.M == 1 and c.N in (2, 130, 4102)
 
 
+def test_gemv_cases_reach_the_kernel_they_name():
+    """The knobs of every GEMV case pin the kernel its `kernel` field claims: asked of the library's route on 256 CUs (no device)."""
+    from phi_3_vision_mlx_amd import ops
+    for case in qp.GEMV_CASES:
+        with qp.pinned(ops, case, cu_count=256):
+            pass
+
+
 @pytest.mark.parametrize("family", qp.FAMILIES)
 @pytest.mark.parametrize("case", qp.CASES, ids=ids)
 def test_reference_passes_in_every_order(case, family):

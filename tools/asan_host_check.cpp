@@ -76,6 +76,36 @@ int main() {
   }
   pq.hd = 80;
   EXPECT(p3v_attention_route(&pq, &pr) == P3V_OK && pr.status == P3V_ERR_UNSUPPORTED && pr.kernel == P3V_ATTN_PK_NONE && !pr.kernel_name[0]);
+  // the decode projections' route: null arguments, one shape per kernel, a refused shape (cu_count given: host arithmetic, no device)
+  p3v_gemv_route_t gr;
+  p3v_gemv_route_query_t gq = {P3V_GEMV_FMT_BF16, P3V_GEMV_STEP_NONE, 1, 264, 3072, P3V_EPI_NONE, 0, 1, 0, 256};
+  EXPECT(p3v_gemv_route(nullptr, &gr) == P3V_ERR_ARG && p3v_gemv_route(&gq, nullptr) == P3V_ERR_ARG);
+  const struct { int format, step, M, N, K, epilogue, exp_base, kernel; const char* name; } gshapes[] = {
+      {P3V_GEMV_FMT_BF16, 0, 1, 101, 520, P3V_EPI_NONE, 0, P3V_GEMV_K_GEMV, "k_gemv<1>"},
+      {P3V_GEMV_FMT_BF16, 0, 1, 264, 3072, P3V_EPI_NONE, 0, P3V_GEMV_K_GEMV3, "k_gemv3<GemvBf16, 1, 1, 6>"},
+      {P3V_GEMV_FMT_B13, 2, 1, 4102, 3072, P3V_EPI_NONE, 97, P3V_GEMV_K_GEMV3, "k_gemv3_step<GemvB13<true>, 1, 1, 6, 2>"},
+      {P3V_GEMV_FMT_BF16, 0, 9, 264, 1024, P3V_EPI_SILU_MUL, 0, P3V_GEMV_K_MFMA, "k_gemv_mfma<true>"},
+      {P3V_GEMV_FMT_BF16, 0, 8, 264, 8192, P3V_EPI_NONE, 0, P3V_GEMV_K_MFMA8, "k_gemv_mfma8<false, 8, 4>"},
+      {P3V_GEMV_FMT_FP8, 0, 2, 24, 3072, P3V_EPI_NONE, 0, P3V_GEMV_K_MFMA_F8, "k_gemv_mfma_f8<false>"},
+      {P3V_GEMV_FMT_FP8, 0, 5, 24, 8192, P3V_EPI_SILU_MUL, 0, P3V_GEMV_K_MFMA8_F8, "k_gemv_mfma8_f8<true, 8, 8>"},
+      {P3V_GEMV_FMT_Q4, 0, 8, 272, 3072, P3V_EPI_NONE, 0, P3V_GEMV_K_GEMV8_Q4, "k_gemv8_q4<false, 4, 3>"},
+      {P3V_GEMV_FMT_Q4, 0, 9, 272, 8192, P3V_EPI_NONE, 0, P3V_GEMV_K_ROWS_Q4, "k_gemm_rows_q4<false, 8, 4>"}};
+  for (const auto& s : gshapes) {
+    gq.format = s.format, gq.step = s.step, gq.M = s.M, gq.N = s.N, gq.K = s.K, gq.epilogue = s.epilogue, gq.exp_base = s.exp_base;
+    EXPECT(p3v_gemv_route(&gq, &gr) == P3V_OK && gr.status == P3V_OK && gr.kernel == s.kernel && !std::strcmp(gr.name, s.name));
+    EXPECT(gr.grid > 0 && gr.block > 0 && (gr.upw > 0) == (s.kernel == P3V_GEMV_K_GEMV3));
+  }
+  gq.format = P3V_GEMV_FMT_Q4, gq.step = 0, gq.M = 2, gq.N = 100, gq.K = 3072;                                 // N % 16
+  EXPECT(p3v_gemv_route(&gq, &gr) == P3V_OK && gr.status == P3V_ERR_UNSUPPORTED && gr.kernel == P3V_GEMV_K_NONE && !gr.name[0]);
+  gq.format = 7;
+  EXPECT(p3v_gemv_route(&gq, &gr) == P3V_OK && gr.status == P3V_ERR_ARG);
+  p3v_gemv_args_t gv;
+  std::memset(&gv, 0, sizeof gv);
+  EXPECT(p3v_gemv(nullptr, nullptr) == P3V_ERR_ARG && p3v_gemv(&gv, nullptr) == P3V_ERR_ARG);
+  gv.x = buf; gv.W = buf; gv.out = buf; gv.M = 17; gv.N = 16; gv.K = 3072;                                   // more rows than any kernel takes
+  EXPECT(p3v_gemv(&gv, nullptr) == P3V_ERR_ARG);
+  gv.M = 9; gv.K = 520;                                                                                      // no kernel for this shape
+  EXPECT(p3v_gemv(&gv, nullptr) == P3V_ERR_UNSUPPORTED);
   p3v_attn_decode_args_t d;
   std::memset(&d, 0, sizeof d);
   EXPECT(p3v_attention_decode(&d, nullptr) != P3V_OK);
