@@ -1001,6 +1001,60 @@ int p3v_spec_end(const uint16_t* logits, const p3v_spec_state_t* state /* host *
 int p3v_ngram_propose(const int32_t* ctx, int n, int K, int n_max, int n_min, int vocab, int32_t* draft, int32_t* n_draft,
                       void* stream);
 
+/* ---- beam search: the tail of a beam step and the K/V reorder behind it (added after round 6, no version change).
+ * The rule (beam.py states it once more in NumPy and plain Python; the kernels are held to it bit for bit):
+ *   State: W beams, 2 <= W <= P3V_BEAM_MAX, in rows 0 .. W-1 of a B = W slot state (every beam of a request has the same
+ *   length, so the state's one offset fits them); cum[W] fp32, each beam's summed log-probability.
+ *   Selection, step t: logits [R, n] bf16 contiguous and cum_in[R]; R = 1 at t = 0 (the one prefill row, cum_in = 0), R = W
+ *   afterwards; n >= 2W.
+ *   1. A row that is UNDEFINED by point 1 of the logprobs rule (a NaN, a +inf, no finite logit) FAILS the step.
+ *   2. A row's candidates are its 2W tokens of largest value, ties to the lower index (p3v_topk's order); each carries
+ *      logprob(i) by steps 2 - 6 of the logprobs rule and score = cum_in[r] + logprob, ONE fp32 addition (a -inf is an
+ *      ordinary value).
+ *   3. All R * 2W candidates are ordered by (score descending, r ascending, place in the row's list ascending): a total
+ *      order, whose first 2W entries are the global best 2W.
+ *   4. Walk those 2W entries, j = 0, 1, ...: a candidate whose token is `eos` is recorded as FINISHED (parent r, score) iff
+ *      j < W and is ignored otherwise; any other candidate becomes the next beam k: tok[k], parent[k] = r, cum[k] = score;
+ *      stop at W beams.  (W beams always exist: a row holds at most one EOS, so at most W of the 2W entries are EOS.)
+ *   5. *d_step += 1 and *d_past += 1, done once, as p3v_step_end does.
+ *   6. Record t (t = *d_step before point 5) goes to PINNED host memory with plain 4-byte stores, P3V_BEAM_REC_INTS words:
+ *      {status, n_fin, tok[8], parent[8], cum bits[8], fin_parent[8], fin_score bits[8]}, unused entries -1; nothing is
+ *      written when t lies outside [0, rec_cap).  A FAILED step writes status = 1, n_fin = 0 and -1 everywhere else; on the
+ *      device tok[k] = -1 (the host raises, as on the plain step's negative token), parent[k] = k, cum stays, and the
+ *      counters advance.
+ *   Reorder: beam k continues row parent[k].  The prompt's columns are equal in every row (p3v_kv_fork), so only the window
+ *   [c0a, min(ceil8(*d_past), T)) moves: c0a = the prompt's end rounded DOWN to 8 columns, a launch constant; *d_past is read
+ *   AFTER point 5, so the column the step appended is inside.  The window is whole 8-column (16-byte) pieces on purpose:
+ *   below the prompt's end the columns are equal in all rows, at or above *d_past they are not yet live, so V^T needs no
+ *   sub-word edges.  Rows with parent[k] == k are not touched; every other row k < W gets row parent[k]'s window, K [T, hd]
+ *   rows and V^T hd runs, all layers and kv heads.  In place that is a read / write hazard (a swap, a 3-cycle), so the move
+ *   is two launches through caller-supplied staging, GATHER (phase 0): stage[k] <- row parent[k], then SCATTER (phase 1):
+ *   row k <- stage[k].  No byte outside the moved rows' windows changes.
+ * p3v_beam_state_t: every pointer is device memory unless stated.
+ *   tok [W] the next step's rows, parent [W], cum [W] fp32 (read as cum_in[0 .. R), written in place by the last workgroup)
+ *   cand_id / cand_score [P3V_BEAM_MAX * 2 * P3V_BEAM_MAX] scratch; ticket [1]: ZERO before the first launch, left zero
+ *   rec [rec_cap][P3V_BEAM_REC_INTS] PINNED HOST memory
+ * p3v_beam_end: R workgroups of 1024 threads, the last to arrive merges.  P3V_ERR_ARG, nothing launched: a null pointer, W
+ * outside 2..P3V_BEAM_MAX, R not in {1, W}, n < 2W, rec_cap < 0; P3V_ERR_UNSUPPORTED: n > 65536.
+ * p3v_kv_permute: k [nl, B, nkv, T, hd] and v [nl, B, nkv, hd, T] bf16 (p3v_kv_copy's layouts), B >= W; stage_k
+ * [nl, W, nkv, stage_cols, hd], stage_v [nl, W, nkv, hd, stage_cols]; parent [W] and d_past [1] are DEVICE words, read by the
+ * launch.  The grid is fixed for the capacity min(stage_cols, T - c0a); workgroups beyond the live window exit.  Defensive
+ * rule: a parent[k] outside [0, W) leaves row k alone and the window is clamped to T and to c0a + stage_cols -- whatever the
+ * device words hold, nothing outside the buffers is read or written.  P3V_ERR_UNSUPPORTED, nothing launched: elem_size != 2
+ * (the int8 cache), hd * 2 % 16, T % 8.  P3V_ERR_ARG: null or misaligned (16 bytes) pointers, W outside 2..P3V_BEAM_MAX,
+ * B < W, c0a outside [0, T] or not a multiple of 8, stage_cols < 8 or not a multiple of 8, a phase other than 0 / 1. */
+#define P3V_BEAM_MAX 8
+#define P3V_BEAM_REC_INTS (2 + 5 * P3V_BEAM_MAX)
+typedef struct {
+  int32_t* tok; int32_t* parent; float* cum; int32_t* cand_id; float* cand_score; int32_t* ticket;
+  int32_t* rec; int32_t* d_step; int32_t* d_past;
+  int32_t rec_cap;
+} p3v_beam_state_t;
+int p3v_beam_end(const uint16_t* logits, const p3v_beam_state_t* state /* host */, int R, int W, int n, int eos, void* stream);
+int p3v_kv_permute(void* k, void* v, int B, int T, const int32_t* parent /* device */, int W, int c0a,
+                   const int32_t* d_past /* device */, void* stage_k, void* stage_v, int stage_cols, int phase, int nl, int nkv,
+                   int hd, int elem_size, void* stream);
+
 /* ---- embeddings: final RMSNorm + pooling + L2 normalisation, fp32 out (added after round 6, no version change).
  * x [B, L, hidden] bf16 is the last layer's output BEFORE model.norm, w [hidden] bf16, start [B] int32 in device memory the
  * count of left-pad columns of each row (0 <= start[b] < L; read in P3V_POOL_MEAN only, values outside are clamped), out

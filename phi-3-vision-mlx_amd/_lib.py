@@ -234,6 +234,14 @@ class SpecState(C.Structure):
                 ("ctx_cap", i32), ("hist_cap", i32), ("rec_cap", i32), ("n_max", i32), ("n_min", i32)]
 
 
+class BeamState(C.Structure):
+    """p3v_beam_state_t: the loop state of the beam step's tail (include/p3v.h)."""
+    _fields_ = [("tok", vp), ("parent", vp), ("cum", vp), ("cand_id", vp), ("cand_score", vp), ("ticket", vp),
+                ("rec", vp), ("d_step", vp), ("d_past", vp), ("rec_cap", i32)]
+
+
+BEAM_MAX = 8                                     # P3V_BEAM_MAX
+BEAM_REC_INTS = 2 + 5 * BEAM_MAX                 # P3V_BEAM_REC_INTS
 SPEC_REC_INTS, SPEC_CTL_INTS, SPEC_NGRAM_CAP = 18, 8, 8     # P3V_SPEC_REC_INTS, P3V_SPEC_CTL_INTS, P3V_SPEC_NGRAM_CAP
 SPEC_CTL_N, SPEC_CTL_NDRAFT, SPEC_CTL_FORCED, SPEC_CTL_REPLAY, SPEC_CTL_NLIMIT, SPEC_CTL_ACC = range(6)
 KV_COPY_MAX_JOBS = 4                             # P3V_KV_COPY_MAX_JOBS
@@ -318,6 +326,8 @@ SIGNATURES = {
     "p3v_ngram_propose": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "p3v_kv_copy": (i32, [C.POINTER(KvCopyJob), i32, i32, i32, i32, i32, vp]),
     "p3v_kv_fork": (i32, [C.POINTER(KvFork), i32, i32, i32, i32, vp]),                   # added after round 6, no version change
+    "p3v_beam_end": (i32, [vp, C.POINTER(BeamState), i32, i32, i32, i32, vp]),             # added after round 6, no version change
+    "p3v_kv_permute": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "p3v_embed_pool": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, i64, vp]),   # added after round 6, no version change
     "p3v_embed_pool_ws_bytes": (i64, [i32, i32, i32, i32]),
     "p3v_sim_topk": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),               # added after round 6, no version change

@@ -549,6 +549,87 @@ def speculative_loop(model, ids, token, cache, n_steps, K, streamer, token_stopp
     return last
 
 
+def beam_loop(model, logits_row, cache, W, max_tokens, length_penalty=1.0, share=False):
+    """Beam search of width W behind one prompt's prefill (include/p3v.h "beam search"; the host's part is beam.Search):
+    model.beam_start forks the B = 1 state into W rows and launches step 0, every further step is one replay of the captured
+    beam step with no host input, so the device runs up to two replays ahead; records are read from pinned memory behind an
+    event.  When the search is done the overrun records are dropped and the offset rewound past them (model.beam_sync).  A
+    failed step raises, as a negative token does in greedy_loop.  Returns (the beam.Search, the B = W cache)."""
+    from . import beam as beam_mod
+    search = beam_mod.Search(W, max_tokens, ID_EOS, length_penalty)
+    g = model.beam_start(cache, logits_row, W, ID_EOS, share=share)
+    bcache, rec, pending, enq, t = g["cache"], g["rec"], [], 1, 0
+    ev = torch.cuda.Event()
+    ev.record()
+    pending.append(ev)
+    try:
+        while True:
+            while len(pending) < 3 and enq < max_tokens:
+                model.beam_step(bcache)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append(ev)
+                enq += 1
+            pending.pop(0).synchronize()
+            t += 1
+            if search.add(rec[t - 1].numpy().copy()):
+                break
+    finally:
+        model.beam_sync(bcache, t)
+    return search, bcache
+
+
+def _generate_beam(model, processor, prompt, images, max_tokens, verbose, return_tps, mute, prefix_cache, share_prefix, W,
+                   length_penalty, beam_info):
+    """`_generate` with num_beams = W >= 2: one prefill, `beam_loop`, the best pooled hypothesis' text."""
+    why = model.beam_refusal(None, W) if hasattr(model, "beam_refusal") else "beam search needs the device model's captured step (this model class has none)"
+    if why:
+        raise ValueError(why)
+    if not isinstance(max_tokens, int) or max_tokens < 1:
+        raise ValueError(f"num_beams={W}: max_tokens must be a positive integer, got {max_tokens!r}")
+    digests = None
+    if prefix_cache is not None and images is not None:
+        from .prefix import image_digests
+        digests = image_digests(images)
+    dict_input = processor(prompt, images)
+    tic = Tic()
+    if prefix_cache is not None:
+        logits, cache = _prefill_with_store(model, prefix_cache, dict_input, digests, max_tokens, {}, False)
+    else:
+        logits, cache = model(**dict_input, max_tokens=max_tokens)
+    prompt_time = tic()
+    search, _ = beam_loop(model, logits[:, -1, :], cache, W, max_tokens, length_penalty, share=bool(share_prefix))
+    hyps = search.result()
+    result = processor.tokenizer.decode(hyps[0]["token_ids"])
+    gen_time, steps = tic(), len(search.steps)
+    if beam_info is not None:
+        beam_info.update(hypotheses=[dict(h) for h in hyps], steps=steps)
+    if not mute:
+        print(result, "\n", flush=True)
+    prompt_len = dict_input["input_ids"].size
+    prompt_tps, gen_tps = prompt_len / prompt_time, max(steps - 1, 0) / gen_time
+    if verbose:
+        print(f"\nPrompt: {prompt_tps:.2f} tokens-per-sec ({prompt_len} tokens / {prompt_time:.1f} sec)")
+        print(f"Generate: {gen_tps:.2f} beam steps-per-sec ({steps} steps of {W} beams / {gen_time:.1f} sec)")
+    return (prompt_tps, gen_tps) if return_tps else result
+
+
+def _check_beam(num_beams, length_penalty, prompt, temperature, top_k, top_p, seed, speculate, n, best_of, logprobs, repetition_penalty,
+                presence_penalty, frequency_penalty, logit_bias, guided_regex, guided_choice, guided_json, early_stop, adapter):
+    """(W, length_penalty) of a call, W = 1: the plain path.  Every refusal of beam search that needs no model, as a ValueError."""
+    from . import beam as beam_mod
+    W, lp = beam_mod.check_request(num_beams, length_penalty)
+    if W == 1:
+        return W, lp
+    batched = isinstance(prompt, list)
+    beam_mod.check_request(W, lp, batched=batched)
+    sampled = not sampling_mod.greedy(sampling_mod.rows(1, temperature, top_k, top_p, seed))
+    pen = penalties_mod.rows(1, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+    return beam_mod.check_request(W, lp, batched, sampled, bool(speculate), (n, best_of) not in ((1, None), (1, 1)), logprobs is not None,
+                                  not penalties_mod.off(pen), not (guided_regex is None and guided_choice is None and guided_json is None),
+                                  bool(early_stop), adapter is not None)
+
+
 def _check_speculate(model, speculate, batched, sampled, early_stop):
     """The refusals of speculative decoding: a ValueError that names the limit, never a silent fallback."""
     K = int(speculate)
@@ -592,7 +673,7 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
               stream=True, mute=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None, prefix_cache=None,
               speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0, presence_penalty=0.0,
               frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None, share_prefix=False,
-              guided_regex=None, guided_choice=None, guided_json=None):
+              guided_regex=None, guided_choice=None, guided_json=None, num_beams=1, length_penalty=1.0, beam_info=None):
     """Greedy decoding loop (reference phi_3_vision_mlx.py:376-409).  speculate=K > 0 (one prompt, greedy): prompt-lookup
     drafts verified K at a time (`speculative_loop`) -- the same tokens, fewer passes over the weights; spec_info (a dict)
     receives steps / drafted / accepted / emitted.  speculate=0 -- the default -- is the plain path, launch for launch.  adapter: the name of one adapter of the model's bank
@@ -634,9 +715,25 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     output is the JSON text of an instance of the schema, in declared key order with at most one space after ':' and ','
     (guide.json_regex lists the keywords it translates and the ones it refuses by name).  It is a third kind of guide and
     excludes the other two for the same prompt; a schema may need more than 255 states and then travels in the wide,
-    class-compressed form of the same record and kernel (include/p3v.h: P3V_GUIDE_WIDE), bounded by 65,536 table entries."""
+    class-compressed form of the same record and kernel (include/p3v.h: P3V_GUIDE_WIDE), bounded by 65,536 table entries.
+    num_beams=W (2..8; ONE prompt, greedy, bf16 KV cache): beam search under the rule of include/p3v.h ("beam search") -- one
+    prefill forked into W rows, one replay of the captured beam step per token (`beam_loop`), the text of the best pooled
+    hypothesis returned; a hypothesis of l tokens scores sum_logprob / l ** length_penalty (length_penalty >= 0, default 1.0).
+    beam_info (a dict) receives "hypotheses" (the pool, best first: token_ids, score, sum_logprob, finished) and "steps".
+    Everything beam search does not run beside raises a ValueError that names it.  num_beams=1 -- the default -- is the plain
+    path, launch for launch."""
     if images is not None and isinstance(prompt, list):
         raise ValueError("Images cannot be provided when prompt is a list")
+    num_beams, length_penalty = _check_beam(num_beams, length_penalty, prompt, temperature, top_k, top_p, seed, speculate, n, best_of,
+                                            logprobs, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, guided_regex,
+                                            guided_choice, guided_json, early_stop, adapter)
+    if num_beams > 1:
+        if share_prefix:
+            why = model.family_refusal() if hasattr(model, "family_refusal") else "share_prefix needs the device model (this model class has no family table)"
+            if why:
+                raise ValueError(why)
+        return _generate_beam(model, processor, prompt, images, max_tokens, verbose, return_tps, mute, prefix_cache, share_prefix,
+                              num_beams, length_penalty, beam_info)
     n, fam = parallel_mod.check(n, best_of)
     if share_prefix:
         why = model.family_refusal() if hasattr(model, "family_refusal") else "share_prefix needs the device model (this model class has no family table)"
@@ -772,8 +869,9 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
              apply_chat_template=True, enable_api=False, temperature=0.0, top_k=0, top_p=1.0, seed=None, adapter=None,
              prefix_cache=None, speculate=0, spec_info=None, logprobs=None, logprob_info=None, repetition_penalty=1.0,
              presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, n=1, best_of=None, family_info=None,
-             share_prefix=False, guided_regex=None, guided_choice=None, guided_json=None):
-    """reference phi_3_vision_mlx.py:1324-1374, plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
+             share_prefix=False, guided_regex=None, guided_choice=None, guided_json=None, num_beams=1, length_penalty=1.0,
+             beam_info=None):
+    """reference phi_3_vision_mlx.py:1324-1374, plus beam search (`num_beams=W`, `length_penalty`, `beam_info`, see `_generate`), plus n completions of one prompt from ONE prefill (`n`, `best_of`: a list of n
     strings, see `_generate`), plus speculative greedy decoding (`speculate=K`, see `_generate`), seeded sampling (`_generate`; temperature 0 = greedy, the default) and
     per-request LoRA adapters (`adapter`: a name of the bank `load_adapters` attached, or one name / None per prompt) and the
     prompt prefix cache (`prefix_cache`: a prefix.PrefixCache the caller keeps between calls; single prompts only) and token
@@ -784,7 +882,10 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
     JSON text of an instance of a JSON schema, see `_generate`)."""
     if "<|api_input|>" in prompt and enable_api:
         raise NotImplementedError("the <|api_input|> tool hook is outside the inference hot path of this build")
-    n, fam = parallel_mod.check(n, best_of)                      # before a model is loaded or run
+    num_beams, length_penalty = _check_beam(num_beams, length_penalty, prompt, temperature, top_k, top_p, seed, speculate, n, best_of,
+                                            logprobs, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, guided_regex,
+                                            guided_choice, guided_json, early_stop, adapter)   # before a model is loaded or run
+    n, fam = parallel_mod.check(n, best_of)
     why = parallel_mod.refusal(fam, isinstance(prompt, list), speculate)
     if why:
         raise ValueError(why)
@@ -806,7 +907,8 @@ def generate(prompt, images=None, preload=None, blind_model=False, quantize_mode
                      **({"share_prefix": True} if share_prefix else {}),
                      **({} if guided_regex is None and guided_choice is None else
                         dict(guided_regex=guided_regex, guided_choice=guided_choice)),
-                     **({} if guided_json is None else dict(guided_json=guided_json)))
+                     **({} if guided_json is None else dict(guided_json=guided_json)),
+                     **({} if num_beams == 1 else dict(num_beams=num_beams, length_penalty=length_penalty, beam_info=beam_info)))
 
 
 # ----------------------------------------------------------------------------- score

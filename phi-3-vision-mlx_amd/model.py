@@ -1489,6 +1489,129 @@ class Phi3VModel:
         st.offset = g["n0"] - 1 + (n_emit if not (n_emit and g["history"][n_emit - 1] < 0) else 0)
         return g["history"][:n_emit].tolist()
 
+    # ------------------------------------------------------------------ beam search (include/p3v.h "beam search", beam.py)
+    def beam_refusal(self, st=None, W=None):
+        """Why this model (and the B = 1 state of a finished prefill) cannot run beam steps -- a sentence that names the limit --
+        or None."""
+        cfg = self.cfg
+        if W is not None and (isinstance(W, bool) or not isinstance(W, int) or not 2 <= W <= ops.L.BEAM_MAX):
+            return f"num_beams must be 1 (off) or an integer in 2..{ops.L.BEAM_MAX} (P3V_BEAM_MAX), got {W!r}"
+        if getattr(cfg, "use_quantized_cache", False):
+            fmt = getattr(cfg, "cache_format", "int8")
+            return f"beam search needs the bf16 KV cache: the reorder has no {fmt} form (cache_format={fmt!r} is not supported)"
+        if self._bank:
+            return "beam search does not run on an adapter bank (rows of one request would need one table entry each)"
+        if st is not None and (st.B != 1 or st.slots):
+            return "beam search starts from the B = 1 state of one prompt's prefill (not a batch, not a slot state of the continuous engine)"
+        if W is not None and cfg.vocab_size < 2 * W:
+            return f"beam search needs a vocabulary of at least 2 * num_beams = {2 * W} tokens"
+        return None
+
+    def _build_beam_graph(self, st, W, eos):
+        """Capture ONE beam step of a B = W state beside whatever else it holds, over loop-state buffers of its own: the step head
+        on tok[W] -> the layers at B = W (the path n completions take; the family launch where the state has a table) -> final
+        norm + lm_head on W rows -> p3v_beam_end -> the reorder's gather and scatter.  The window of the reorder starts at the
+        prompt's end rounded down to 8 columns, a launch constant: the state is one request's.  The capture's warm-up run is a
+        step like any other (it writes the not-yet-live column st.offset and moves bytes only among equal prompt columns and that
+        column); `beam_start` arms the loop state afterwards."""
+        cfg, w, dev = self.cfg, self.w, self.device
+        n_tok = max(1, st.max_tokens)
+        g = dict(W=W, eos=int(eos), tok=torch.zeros((W,), dtype=I32, device=dev), parent=torch.zeros((W,), dtype=I32, device=dev),
+                 cum=torch.zeros((W,), dtype=F32, device=dev),
+                 cand_id=torch.zeros((2 * ops.L.BEAM_MAX * ops.L.BEAM_MAX,), dtype=I32, device=dev),
+                 cand_score=torch.zeros((2 * ops.L.BEAM_MAX * ops.L.BEAM_MAX,), dtype=F32, device=dev),
+                 ticket=torch.zeros((1,), dtype=I32, device=dev), d_past=torch.zeros((1,), dtype=I32, device=dev),
+                 d_step=torch.zeros((1,), dtype=I32, device=dev),
+                 # pinned host memory, written by p3v_beam_end itself: one record per step
+                 rec=torch.full((n_tok + 2, ops.L.BEAM_REC_INTS), -1, dtype=I32).pin_memory(),
+                 x=torch.empty((W, cfg.hidden_size), dtype=BF16, device=dev),
+                 logits=torch.empty((W, cfg.vocab_size), dtype=BF16, device=dev), n_replays=0)
+        g["state"] = ops.beam_state(g)
+        bufs = g["bufs"] = self._plan(st, W, 1, fuse_o=False, captured=True)
+        kv = self._state_kv(st)
+        c0a = g["c0a"] = st.offset // 8 * 8
+        g["stage"] = ops.kv_permute_stage(kv, W, max(8, (st.T - c0a + 7) // 8 * 8))
+
+        def forward():
+            self._layers(g["x"], st, W, 1, 0, 1, bufs=bufs, d_past=g["d_past"],
+                         step_begin=dict(tok=g["tok"], table=w["model.embed_tokens.weight"], cos_o=bufs["plan"].rope_cos, sin_o=bufs["plan"].rope_sin))
+            self._proj(g["x"], "lm_head.weight", norm_w=w["model.norm.weight"], out=g["logits"], h=bufs["h"])
+
+        def select():
+            ops.beam_end(g["logits"], g["state"], W, eos)
+
+        def reorder():
+            for phase in (0, 1):
+                ops.kv_permute(kv, g["parent"], W, c0a, g["d_past"], g["stage"], phase)
+
+        def step():
+            forward(), select(), reorder()
+        g["parts"], g["step"] = (forward, select, reorder), step
+        g["d_past"].fill_(st.offset)
+        g["gemm_ws"] = {}
+        g["graph"] = self._capture(step, g["gemm_ws"])
+        return g
+
+    @_on_device
+    def beam_start(self, cache, logits_row, W, eos, share=False):
+        """Start a beam search of width W behind ONE prompt's prefill: `cache` is its B = 1 cache, `logits_row` its last logits
+        row.  The state is forked into W rows (`fork_state`; share: registered as a family where parallel.family_pays says so --
+        the shared columns are never permuted, so the table stays valid), the step is captured on the new state
+        (`st.graphs[("beam", W)]`), the loop state armed, and step 0 -- the selection from the one prefill row, R = 1 -- launched.
+        Returns the capture's buffers; `g["cache"]` is the B = W cache the steps run on."""
+        st1 = cache[0].state
+        W = int(W) if isinstance(W, (int, np.integer)) and not isinstance(W, bool) else W
+        why = self.beam_refusal(st1, W)
+        if why:
+            raise ValueError(why)
+        row = logits_row.reshape(1, -1).to(self.device, BF16).contiguous()
+        if row.shape[1] != self.cfg.vocab_size:
+            raise ValueError(f"beam_start: one row of {self.cfg.vocab_size} logits, got {tuple(logits_row.shape)}")
+        bcache = self.fork_state(st1, W, share=share)
+        st = bcache[0].state
+        self._sync_epoch(st)
+        if st.family is None:                                    # every beam state takes the family launch, shared prefix or not: ONE
+            self.set_families(st, [], create=True)               # split plan, so a search's records do not depend on `share`
+        g = st.graphs[("beam", W)] = self._build_beam_graph(st, W, eos)
+        g["cache"], g["S0"] = bcache, st.offset
+        g["cum"].zero_(), g["d_step"].zero_(), g["ticket"].zero_(), g["rec"].fill_(-1)
+        g["d_past"].fill_(st.offset - 1)                         # step 0 appends no column: its count of one brings the length to st.offset
+        ops.beam_end(row, g["state"], W, eos)
+        g["n_replays"] = 1
+        st.graphs["beam"] = g                                    # the armed capture
+        return g
+
+    @_on_device
+    def beam_step(self, cache, eager=False):
+        """One beam step through its captured graph (after `beam_start`, on `g["cache"]`): feeds the W beams' tokens, selects the
+        next W from their 2W best continuations each, writes record `n_replays` to the capture's pinned `rec`, advances the
+        device's counters and reorders the cache rows -- no host input, so steps replay back to back.  The host's `st.offset` is
+        NOT advanced here (`beam_sync`).  eager=True runs the same launches outside the graph.  Returns the capture's buffers."""
+        st = cache[0].state
+        g = st.graphs.get("beam")
+        if g is None or st.epoch != self.epoch:
+            raise RuntimeError("beam_step: no armed capture on this state (model.beam_start)")
+        if g["n_replays"] >= max(1, st.max_tokens) or g["S0"] + g["n_replays"] > st.T:
+            raise ValueError(f"KV cache overflow: beam step {g['n_replays']} of a run of {st.max_tokens} tokens (prompt + max_tokens = {st.T})")
+        if eager:
+            with ops.owned_gemm_workspace(g["gemm_ws"], frozen=True):
+                g["step"]()
+        else:
+            g["graph"].launch()
+        g["n_replays"] += 1
+        return g
+
+    @_on_device
+    def beam_sync(self, cache, n_records=None):
+        """Wait for the steps enqueued so far and set the host's offset behind record `n_records - 1` (default: every record so
+        far; fewer: the overrun steps are dropped, their columns lie beyond the offset).  Returns the records, int32 [n, 42]."""
+        st = cache[0].state
+        g = st.graphs["beam"]
+        torch.cuda.current_stream().synchronize()
+        n = g["n_replays"] if n_records is None else max(1, min(int(n_records), g["n_replays"]))
+        st.offset = g["S0"] + n - 1
+        return g["rec"][:n].numpy().copy()
+
     # ------------------------------------------------------------------ seeded sampling (include/p3v.h: p3v_sample_row_t)
     @_on_device
     def set_sampling(self, st, records, row0=0):

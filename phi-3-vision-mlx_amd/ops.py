@@ -1124,6 +1124,54 @@ def ngram_propose(ctx, n, K, n_max, n_min, vocab, draft, n_draft):
             "ngram_propose")
 
 
+def beam_state(g):
+    """p3v_beam_state_t over the loop-state buffers of a beam capture (model._build_beam_graph): tok / parent [W] int32, cum [W]
+    fp32, cand_id int32 / cand_score fp32 [BEAM_MAX * 2 * BEAM_MAX], ticket, d_step, d_past [1] int32 on the device; rec
+    [rec_cap, BEAM_REC_INTS] int32 in pinned host (or device) memory."""
+    for k in ("tok", "parent", "cand_id", "ticket", "d_step", "d_past"):
+        _chk(g[k], I32, k)
+    _chk(g["cum"], F32, "cum"), _chk(g["cand_score"], F32, "cand_score")
+    W = g["tok"].numel()
+    if g["parent"].numel() != W or g["cum"].numel() != W or min(g["cand_id"].numel(), g["cand_score"].numel()) < 2 * L.BEAM_MAX * L.BEAM_MAX:
+        raise ValueError("beam_state: tok / parent / cum hold W words, cand_id / cand_score 128")
+    rec = g["rec"]
+    if rec.dtype != I32 or not rec.is_contiguous() or not (rec.is_pinned() or rec.is_cuda) or rec.dim() != 2 or rec.shape[1] != L.BEAM_REC_INTS:
+        raise ValueError("beam_state: rec must be contiguous int32 [rec_cap, P3V_BEAM_REC_INTS] in pinned host (or device) memory")
+    return L.BeamState(_p(g["tok"]), _p(g["parent"]), _p(g["cum"]), _p(g["cand_id"]), _p(g["cand_score"]), _p(g["ticket"]), _p(rec),
+                       _p(g["d_step"]), _p(g["d_past"]), rec.shape[0])
+
+
+def beam_end(logits, state, W, eos):
+    """Tail of a beam step (p3v_beam_end): logits [R, n] bf16, R = 1 (the prefill row) or W -> the next beams, the record, the
+    counters.  Raises for what the library refuses."""
+    _chk(logits, BF16, "logits")
+    R, n = logits.shape
+    L.check(L.lib().p3v_beam_end(_p(logits), C.byref(state), R, int(W), n, int(eos), _stream()), "beam_end")
+
+
+def kv_permute_stage(cache, W, stage_cols):
+    """Staging buffers of `kv_permute` for a bf16 cache (k, vt): [nl, W, nkv, stage_cols, hd] and [nl, W, nkv, hd, stage_cols]."""
+    nl, _, nkv, _, hd, dt = _kv_side(cache, "kv_permute")
+    return (torch.empty(nl, W, nkv, stage_cols, hd, dtype=dt, device=cache[0].device),
+            torch.empty(nl, W, nkv, hd, stage_cols, dtype=dt, device=cache[0].device))
+
+
+def kv_permute(cache, parent, W, c0a, d_past, stage, phase):
+    """One launch of the beam reorder (p3v_kv_permute): phase 0 gathers the window [c0a, ceil8(*d_past)) of row parent[k] into
+    stage[k], phase 1 scatters stage[k] into row k, for every k < W with parent[k] != k.  bf16 caches only: the int8 cache
+    raises (P3V_ERR_UNSUPPORTED), as everything else the library refuses."""
+    nl, B, nkv, T, hd, dt = _kv_side(cache, "kv_permute")
+    _chk(parent, I32, "parent"), _chk(d_past, I32, "d_past")
+    if parent.numel() < W or d_past.numel() < 1:
+        raise ValueError("kv_permute: parent holds W words, d_past one")
+    sk, sv = stage
+    _chk(sk, dt, "stage_k"), _chk(sv, dt, "stage_v")
+    if sk.dim() != 5 or tuple(sk.shape) != (nl, W, nkv, sk.shape[3], hd) or tuple(sv.shape) != (nl, W, nkv, hd, sk.shape[3]):
+        raise ValueError("kv_permute: stage must be [nl, W, nkv, cols, hd] and [nl, W, nkv, hd, cols]")
+    L.check(L.lib().p3v_kv_permute(_p(cache[0]), _p(cache[1]), B, T, _p(parent), int(W), int(c0a), _p(d_past), _p(sk), _p(sv),
+                                   sk.shape[3], int(phase), nl, nkv, hd, 2 if dt == BF16 else 1, _stream()), "kv_permute")
+
+
 def store_token(tok, history, d_step, tok_next=None):
     B, max_steps = history.shape
     L.check(L.lib().p3v_store_token(_p(tok), _p(history), _p(d_step), _p(tok_next), B, max_steps, _stream()), "store_token")

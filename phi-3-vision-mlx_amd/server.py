@@ -47,6 +47,11 @@
      "n": 1 reproduces its text; "logprobs" has one object per response.  At temperature 0 the n responses are equal.  A bad
      value, a list of prompts with n > 1, a server started with --merge, or an explicit "speculate" > 0 beside n > 1 -> 400
      with the reason.  Served by the one-request path and by --continuous; without "n" a response is byte for byte today's.)
+    (extension: "num_beams": W (2 .. 8; 1 or absent: today's request) and "length_penalty": p (>= 0, default 1.0) -- beam
+     search for ONE prompt (with or without an image) on the one-request path (api.generate(num_beams=...): include/p3v.h
+     "beam search"); "responses" has the best hypothesis' text and the response gains "beam": {"score", "steps"}.  A bad
+     value, a list of prompts, temperature > 0, an explicit "speculate" > 0, n / best_of, logprobs, penalties, logit_bias, a
+     guide, an adapter, a server started with --continuous or --merge, or a process group -> 400 with the reason.)
     (extension: "images": [null | "data:image/...;base64,..." per prompt] -- the reference's endpoint is text-only.
      Only INLINE images by default: a path or URL in a request body would let any client make the server open local files
      or fetch arbitrary URLs.  `ImagePolicy(allow_dir=..., allow_hosts=...)` / `--image-dir` / `--image-host` opt in to an
@@ -91,7 +96,7 @@ MODEL_NAME = "phi-3-vision"
 
 
 def in_use(sampling=None, adapter=None, logprobs=None, penalties=None, n=None, best_of=None, speculate=0, cache_prompt=None, info=None,
-           guide=None):
+           guide=None, beam=None):
     """The keywords of the options a request really uses -- what the handler passes to a backend's `submit`, what
     ContinuousBackend passes to the engine's `generate`, and what a queued job keeps.  The rules, stated once:
 
@@ -100,11 +105,12 @@ def in_use(sampling=None, adapter=None, logprobs=None, penalties=None, n=None, b
       * sampling, adapter, logprobs, penalties and guide are present only when not None;
       * n and best_of (both) are present only for a family -- m > 1 rows; the caller passes n=None otherwise;
       * speculate is present only when K > 0;
+      * beam ({"num_beams": W, "length_penalty": p}) is present only for W > 1;
       * cache_prompt is present only when not None, and the handler passes it on only to a backend with a prefix store;
       * info (the dict a backend reports into) is present only when not None; the handler makes one exactly when the request is
-        a family, asks for logprobs, speculates (K > 0), or the backend has a prefix store."""
+        a family, asks for logprobs, speculates (K > 0), searches with beams, or the backend has a prefix store."""
     kw = {k: v for k, v in (("sampling", sampling), ("adapter", adapter), ("logprobs", logprobs), ("penalties", penalties),
-                            ("cache_prompt", cache_prompt), ("info", info), ("guide", guide)) if v is not None}
+                            ("cache_prompt", cache_prompt), ("info", info), ("guide", guide), ("beam", beam)) if v is not None}
     if n is not None:
         kw.update(n=n, best_of=best_of)
     if speculate:
@@ -252,6 +258,32 @@ def parse_speculate(request, n_prompts, engine, sampling=None):
     if explicit:
         raise ValueError(why)
     return 0                                    # (the server-wide default applies where it can; only an explicit field is refused)
+
+
+def parse_beam(request, prompts, images, engine, sampling=None, adapter=None, speculate_explicit=False, family=None, logprobs=None,
+               penalties=None, guide=None):
+    """The "num_beams" and "length_penalty" fields of a request body -> None (absent, or num_beams = 1: today's request) or
+    {"num_beams": W, "length_penalty": p}.  ValueError (-> 400) naming the limit on a bad value, and for W > 1 wherever beam
+    search does not run: a backend without it (--continuous, --merge), the batch-sharded path, and everything
+    beam.check_request refuses (a list of prompts, sampling, an explicit "speculate" > 0, n / best_of, logprobs, penalties,
+    a guide, an adapter)."""
+    from .beam import check_request
+    if request.get("num_beams") is None and request.get("length_penalty") is None:
+        return None
+    W, lp = check_request(request.get("num_beams", 1), request.get("length_penalty", 1.0))
+    if W == 1:
+        return None
+    if not getattr(engine, "beam", False):
+        raise ValueError(f"num_beams={W}: beam search runs on the one-request path only: this server was started with --continuous "
+                         "or --merge (beams in the batched engine are not built)")
+    check_request(W, lp, batched=len(prompts) != 1 or isinstance(request.get("prompt"), list),
+                  sampled=sampling is not None and any(float(r["temperature"]) > 0 for r in sampling), speculate=speculate_explicit,
+                  family=family is not None, logprobs=logprobs is not None, penalties=penalties is not None, guides=guide is not None,
+                  adapter=adapter is not None)
+    sharded = getattr(engine, "sharded_fn", None)                # (an image rides along, as a family's does: api.generate takes it)
+    if sharded is not None and sharded(prompts, None):
+        raise ValueError(f"num_beams={W}: beam search is not available{_SHARDED}")
+    return {"num_beams": W, "length_penalty": lp}
 
 
 def parse_logprobs(request, n_prompts):
@@ -486,7 +518,7 @@ class EngineQueue:
 
     def __init__(self, generate_fn, max_batch=64, window_s=0.005, merge=False, max_tokens_cap=4096, timeout_s=600.0,
                  length_fn=None, window_tokens=4096, device=None, sharded_fn=None, adapter_names=(), speculate=False,
-                 speculate_default=0, decode_fn=None, vocab_size=None, share_refusal=None, embed_fn=None, embed_refusal=None):
+                 speculate_default=0, decode_fn=None, vocab_size=None, share_refusal=None, embed_fn=None, embed_refusal=None, beam=False):
         # embed_fn(prompts, images, pooling, normalize, adapter) -> (vectors [n, H], prompt tokens per prompt): /v1/embeddings, run
         # by the worker thread in order with generation; None: the path does not exist (404).  embed_refusal: why it cannot be
         # served here (-> 400), or None
@@ -497,6 +529,7 @@ class EngineQueue:
         self.decode_fn = decode_fn                              # token id -> text piece (the "tokens" of a logprobs response)
         # speculate: generate_fn takes `speculate=K, spec_info=dict` (one prompt, greedy); never with merge (B > 1 batches)
         self.speculate, self.speculate_default = bool(speculate) and not merge, int(speculate_default)
+        self.beam = bool(beam) and not merge                    # generate_fn takes `beam={...}, beam_info=dict` (one prompt); never merged
         self.adapter_names = list(adapter_names)                # what generate_fn's `adapter` keyword may name (GET /v1/adapters)
         # sharded_fn(prompts, images) -> True when generate_fn would run that request on the batch-sharded path (dist.py), which
         # does not sample: the handler answers 400 to a sampled request bound there
@@ -511,9 +544,9 @@ class EngineQueue:
         self.thread.start()
 
     def submit(self, prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, info=None, logprobs=None,
-               penalties=None, n=None, best_of=None, guide=None):
+               penalties=None, n=None, best_of=None, guide=None, beam=None):
         job = _Job(prompts, max(1, min(int(max_tokens), self.max_tokens_cap)), images,
-                   in_use(sampling, adapter, logprobs, penalties, n, best_of, guide=guide), speculate, info)
+                   in_use(sampling, adapter, logprobs, penalties, n, best_of, guide=guide, beam=beam), speculate, info)
         self.jobs.put(job)
         if not job.done.wait(self.timeout_s):
             raise TimeoutError(f"no result within {self.timeout_s} s")
@@ -545,7 +578,7 @@ class EngineQueue:
         """merge=False: `first` alone.  merge=True: plus every queued job with the same max_tokens that fits and keeps the
         RoPE regime of each member unchanged, waiting at most `window_s` for stragglers."""
         def alone(job):                         # image / adapter requests and families are never merged
-            return job.images is not None or "adapter" in job.opts or "n" in job.opts
+            return job.images is not None or "adapter" in job.opts or "n" in job.opts or "beam" in job.opts
         group, n, held = [first], len(first.prompts), []
         if not self.merge or alone(first):
             return group
@@ -595,12 +628,15 @@ class EngineQueue:
                 # that did not ask (sampled jobs merge only with sampled jobs).  Each statistics dict comes in with what fills it;
                 # speculate: one greedy prompt, never a family, never merged (self.speculate excludes merge).
                 opts, fam = first.opts, "n" in first.opts
-                spec = 0 if fam else first.speculate
+                beam = opts.get("beam")
+                spec = 0 if fam or beam else first.speculate
                 kw = {k: opts[k] for k in ("adapter", "n", "best_of") if k in opts}
                 for k in ("logprobs", "penalties", "guide") + (() if spec else ("sampling",)):
                     if any(k in j.opts for j in group):
                         kw[k] = [v for j in group for v in (j.opts.get(k) or [None] * len(j.prompts))]
-                lp_info, fam_info, stats = {}, {}, {}
+                lp_info, fam_info, stats, beam_info = {}, {}, {}, {}
+                if beam:
+                    kw.update(beam=beam, beam_info=beam_info)
                 if "logprobs" in kw:
                     kw["logprob_info"] = lp_info
                 if fam:
@@ -615,6 +651,9 @@ class EngineQueue:
                     if len(out) != opts["n"]:
                         raise RuntimeError(f"generate returned {len(out)} texts for n = {opts['n']}")
                     flat = out                                  # (one result per completion from here on)
+                if beam and first.info is not None:
+                    best = (beam_info.get("hypotheses") or [{}])[0]
+                    first.info["beam"] = {"score": best.get("score"), "steps": int(beam_info.get("steps", 0))}
                 if spec and first.info is not None:
                     first.info["speculation"] = {k: int(stats.get(k, 0)) for k in ("steps", "drafted", "accepted")}
                 out = [out] if isinstance(out, str) else list(out)
@@ -732,6 +771,10 @@ def make_handler(engine, image_policy=None):
                 logprobs = parse_logprobs(request, len(prompts))
                 penalties = parse_penalties(request, len(prompts), vocab_of(engine))
                 guide = parse_guide(request, len(prompts))
+                beam = parse_beam(request, prompts, images, engine, sampling, adapter, bool(speculate) and "speculate" in request, family,
+                                  logprobs, penalties, guide)
+                if beam is not None:
+                    speculate = 0                               # (the server-wide default steps aside)
                 sharded = None if family is not None else getattr(engine, "sharded_fn", None)   # (a family runs api.generate, images too)
                 asked = {"sampling": sampling, "adapter": adapter, "logprobs": logprobs, "penalties": penalties, "guide": guide}
                 for option, where, message, explicit_only in REFUSALS:      # in order: the first that fails answers
@@ -745,10 +788,10 @@ def make_handler(engine, image_policy=None):
                 self._send(400, {"error": str(e)})
                 return
             store = prefix_counters(engine) is not None         # a backend with a prefix store reports what each prompt reused
-            info = {} if family is not None or logprobs is not None or speculate or store else None
+            info = {} if family is not None or logprobs is not None or speculate or store or beam is not None else None
             try:
                 kw = in_use(sampling, adapter, logprobs, penalties, *(family or (None, None)), speculate, cache_prompt if store else None, info,
-                            guide=guide)
+                            guide=guide, beam=beam)
                 responses = engine.submit(prompts, max_tokens, *([images] if images is not None else []), **kw)
             except Exception as e:              # noqa: BLE001
                 self._send(500, {"error": f"{type(e).__name__}: {e}"})
@@ -756,9 +799,13 @@ def make_handler(engine, image_policy=None):
             out = {"model": MODEL_NAME, "responses": responses}
             if sampling is not None:
                 out["seeds"] = [r["seed"] for r in sampling] if family is None else list(info.get("seeds", []))
+            if beam is not None:
+                from .logprobs import finite_or_none
+                got = info.get("beam") or {}
+                out["beam"] = {"score": finite_or_none(got.get("score")), "steps": int(got.get("steps", 0))}
             if speculate:
                 out["speculation"] = info.get("speculation", {"steps": 0, "drafted": 0, "accepted": 0})
-            elif info is not None and (prefix_counters(engine) is not None or (logprobs is None and family is None)):
+            elif info is not None and (prefix_counters(engine) is not None or (logprobs is None and family is None and beam is None)):
                 out["cached_tokens"] = list(info.get("cached_tokens", [0] * len(prompts)))
             if logprobs is not None:
                 from .api import ID_EOS
@@ -935,9 +982,12 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
         return images is not None or (dist.is_available() and dist.is_initialized())
 
     def generate_fn(prompts, max_tokens, images=None, sampling=None, adapter=None, speculate=0, spec_info=None, logprobs=None,
-                    logprob_info=None, penalties=None, n=None, best_of=None, family_info=None, guide=None):
+                    logprob_info=None, penalties=None, n=None, best_of=None, family_info=None, guide=None, beam=None, beam_info=None):
         import torch.distributed as dist
         kw = generate_kwargs(sampling, adapter, logprobs, penalties, n, best_of, speculate, len(prompts), guide)
+        if beam:                                                     # one prompt (image or not), one prefill forked into the beams
+            kw.update(beam, beam_info=beam_info, images=None if images is None else images[0],
+                      **({"share_prefix": True} if share_prefix else {}))
         if "logprobs" in kw:
             kw["logprob_info"] = logprob_info
         if "speculate" in kw:
@@ -966,7 +1016,7 @@ def run(port=8000, synthetic=False, blind_model=False, merge=False, continuous=F
     grouped = dist.is_available() and dist.is_initialized()          # a process group: batches go down the batch-sharded path
     httpd, engine = serve(generate_fn, embed_fn=embed_fn, **({"embed_refusal": EMBED_NOT_BUILT} if grouped else {}),
                           port=port, host=host, merge=merge, length_fn=length_fn, device=preload[0].device,
-                          image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True,
+                          image_policy=image_policy, sharded_fn=sharded_fn, adapter_names=list(adapters or {}), speculate=True, beam=True,
                           speculate_default=speculate, decode_fn=lambda i: processor.tokenizer.decode([int(i)]),
                           vocab_size=getattr(getattr(preload[0], "cfg", None), "vocab_size", None),
                           **({"share_refusal": preload[0].family_refusal()} if share_prefix and hasattr(preload[0], "family_refusal") else {}))
