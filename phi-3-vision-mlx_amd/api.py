@@ -34,6 +34,7 @@ from . import logprobs as logprobs_mod
 from . import penalties as penalties_mod
 from . import guide as guide_mod
 from . import parallel as parallel_mod
+from . import row_options
 from .steps import kind_for
 from .config import is_vision, load_config, make_config, phi3v_config_dict, tiny_config_dict
 from .processor import Phi3FProcessor, Phi3VProcessor
@@ -346,25 +347,8 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
     re-plan the rows' states are rebuilt by walking the tokens fed so far.  None: the replays and launches of today."""
     # the ONE kind of step the arguments ask for (steps.py); an eager model class has none of its methods: the reference's loop
     kind = kind_for(sampling is not None, penalties is not None, guides is not None, logprobs is not None)
-    graph_step = getattr(model, kind.method, None)
-    if penalties is not None and (graph_step is None or not hasattr(model, "penal_step")):
-        raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
-    if guides is not None and (graph_step is None or not hasattr(model, "guide_step")):
-        raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
-    records = want_dev = None
-    if sampling is not None:
-        records = sampling_mod.pack(sampling, counter=1)
-        if graph_step is not None:
-            model.set_sampling(cache[0].state, records)
-        else:                                                       # an eager model: the records ride with the loop
-            records = records.to(token.device)
-    if logprobs is not None:
-        if graph_step is not None:
-            model.set_logprobs(cache[0].state, logprobs.wants)
-        else:                                                       # an eager model: one eager launch per step
-            want_dev = torch.tensor(logprobs.wants, dtype=torch.int32, device=token.device)
-    if kind.sampled and sampling is None:                           # the penalised / guided tail is the sampled one: greedy records
-        model.set_sampling(cache[0].state, sampling_mod.pack([(0.0, 0, 1.0, 0)] * token.shape[0], counter=1))
+    graph_step, records, want_dev = row_options.begin_loop(model, getattr(cache[0], "state", None), kind, token, sampling,
+                                                           logprobs and logprobs.wants, penalties is not None, guides is not None)
 
     def slot(g_):
         """the pinned records of the replay just enqueued ([B, 20], valid once the step has run)"""
@@ -472,19 +456,8 @@ def greedy_loop(model, token, cache, n_steps, streamer, token_stopper, logit_sto
             st.scrub(st.offset, st.offset + i - n_done)             # (their cache rows hold NaN: 0 x NaN would poison every later step)
             i, pending = n_done, None
             token = torch.tensor(taken, dtype=torch.int32, device=token0.device).view(-1, 1) if n_done else token0
-            if records is not None:                                 # the draw index rewinds with the offset: step n_done draws n_done + 1
-                model.set_sampling(st, sampling_mod.pack(sampling, counter=1 + n_done))
-            if penalties is not None:
-                # the tables may hold the dropped steps' counts: rebuild them from the prompt and the tokens FED so far (steps
-                # 0 .. n_done - 1 were fed the prefill token and the first n_done - 1 delivered ones; the next step counts its own)
-                fed = ([_rows(token0)] + delivered)[:n_done]
-                model.rebuild_penalties(st, penalties["prompt_ids"], np.asarray(fed, dtype=np.int32).T if n_done else None,
-                                        0, penalties.get("pad"))
-            if guides is not None:                                  # the states may hold the dropped steps' walks: walk again
-                fed = ([_rows(token0)] + delivered)[:n_done]
-                model.set_guides(st, guides["dfas"], 0, states=[
-                    guide_mod.replay_state(d, guides["table"], [f[b] for f in fed], guides["eos"])
-                    for b, d in enumerate(guides["dfas"])])
+            fed = ([_rows(token0)] + delivered)[:n_done] if penalties is not None or guides is not None else None
+            row_options.rebuild(model, st, n_done, fed, sampling, penalties, guides)
             print("[phi3v] a decode step timed out in the fused attention + o_proj launch (is another process using this GPU?): "
                   "continuing with separate launches", file=sys.stderr)
 
@@ -727,18 +700,14 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     num_beams, length_penalty = _check_beam(num_beams, length_penalty, prompt, temperature, top_k, top_p, seed, speculate, n, best_of,
                                             logprobs, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, guided_regex,
                                             guided_choice, guided_json, early_stop, adapter)
-    if num_beams > 1:
-        if share_prefix:
-            why = model.family_refusal() if hasattr(model, "family_refusal") else "share_prefix needs the device model (this model class has no family table)"
-            if why:
-                raise ValueError(why)
-        return _generate_beam(model, processor, prompt, images, max_tokens, verbose, return_tps, mute, prefix_cache, share_prefix,
-                              num_beams, length_penalty, beam_info)
-    n, fam = parallel_mod.check(n, best_of)
+    n, fam = parallel_mod.check(n, best_of)                     # (beam search: _check_beam has left n = 1 alone)
     if share_prefix:
         why = model.family_refusal() if hasattr(model, "family_refusal") else "share_prefix needs the device model (this model class has no family table)"
         if why:
             raise ValueError(why)
+    if num_beams > 1:
+        return _generate_beam(model, processor, prompt, images, max_tokens, verbose, return_tps, mute, prefix_cache, share_prefix,
+                              num_beams, length_penalty, beam_info)
     if fam > 1:                                                 # (n == 1: the model is not asked anything here)
         cfg_ = getattr(model, "cfg", None)
         why = parallel_mod.refusal(fam, isinstance(prompt, list), speculate,
@@ -760,9 +729,8 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
     guides = guide_mod.per_prompt(len(prompt) if isinstance(prompt, list) else 1, guided_regex, guided_choice, guided_json)
     guide_mod.refuse_speculation(guides, speculate)
     guide_state = None
+    row_options.on_device(model, None, pen is not None, guides is not None)   # (refused before anything runs)
     if guides is not None:                                      # compiled and checked against the vocabulary before anything runs
-        if not hasattr(model, "set_guides"):
-            raise ValueError("guided decoding needs the device model's captured step (this model class has none)")
         table = guide_mod.vocab_for(processor.tokenizer, model.cfg.vocab_size)
         for d in guides:
             if d is not None:
@@ -803,33 +771,19 @@ def _generate(model, processor, prompt, images=None, max_tokens=512, verbose=Tru
         if adapter is not None:
             model.set_row_adapters(cache[0].state, [adapter] * fam)
         logits = logits[:, -1:, :].expand(fam, -1, -1).contiguous()
-    first, pen_state = logits[:, -1, :], None
-    if pen is not None:                                         # records + prompt bits first: the prefill token is penalised too
-        if not hasattr(model, "set_penalties"):
-            raise ValueError("penalties and logit_bias need the device model's captured step (this model class has none)")
-        ids2 = np.asarray(dict_input["input_ids"])
-        ids2 = ids2[None] if ids2.ndim == 1 else ids2
-        pad = (np.asarray(mask).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if mask is not None else None
-        if fam:                                                 # every row of the family starts from the prompt's bits
-            ids2, pad = np.repeat(ids2, fam, axis=0), (None if pad is None else np.repeat(pad, fam))
-        pen_state = dict(prompt_ids=ids2, pad=pad)
-        model.set_penalties(cache[0].state, penalties_mod.pack(pen), ids2, 0,
-                            bias=penalties_mod.bias_table(pen, logits.shape[-1]), pad=pad)
-        first = model.penalized_logits(cache[0].state, logits)
-    if guide_state is not None:                                 # behind the penalties: the mask works on the adjusted rows
-        model.set_guide_vocab(guide_state["table"], guide_state["eos"])
-        model.set_guides(cache[0].state, guide_state["dfas"])
-        first = model.guided_logits(cache[0].state, first)
-    if sampled is None:
-        token = model_ops.argmax(first.contiguous())[:, None]
-    else:                                                       # draw 0 of every row: from the prefill logits
-        token = model_ops.sample(first, sampling_mod.pack(sampled, counter=0).to(logits.device))[:, None]
-    streamer(_rows(token))                                      # D2H copy = the per-token sync the reference has (mx.eval)
+    # the rows' tables, then the first token and its record from the prefill logits (row_options: the engine's order of calls);
+    # the one D2H copy of the token = the per-token sync the reference has (mx.eval)
+    st, spans = getattr(cache[0], "state", None), [(0, logits.shape[0])]
+    asked = row_options.Asked(sampled, pen, guide_state and guide_state["dfas"], lp_wants, alone=True)
+    if row_options.on_device(model):
+        row_options.install(model, st, spans, asked, dict_input, processor)
+    token, first, words = row_options.first_tokens(model, st, spans, asked, logits)
+    pen_state = None if pen is None else dict(zip(("prompt_ids", "pad"), row_options.prompt_bits(dict_input, fam)))
+    streamer(first)
     collector = None
-    if lp_wants is not None:                                    # the first token's record: from the prefill logits
+    if lp_wants is not None:
         collector = logprobs_mod.Collector(lp_wants)
-        collector.add(model_ops.logprobs(logits[:, -1, :], token.reshape(-1).to(torch.int32).contiguous(),
-                                         torch.tensor(lp_wants, dtype=torch.int32, device=logits.device)))
+        collector.add(words)
     prompt_time = tic()
     if speculate:
         stats = {}

@@ -48,6 +48,8 @@ import threading
 import numpy as np
 import torch
 
+from . import row_options
+from .logprobs import unpack as _unpack_records
 from .steps import kind_for
 from .request import (GUIDE_ARGS, LOGPROB_ARGS, N_ARGS, PENALTY_ARGS, PREFIX_ARGS, RequestOptions, _check_adapter, adapter_list,  # noqa: F401
                       carry, options_per_prompt, requested_logprobs, requested_n, requested_penalties)
@@ -336,39 +338,11 @@ class ContinuousEngine:
             self._leave_family([r.row])
             self.rows[r.row] = None
             self.st.pad_len[r.row:r.row + 1].fill_(self.window)  # every key masked: the row idles at zero cost of correctness
-            self._options_over(r.row, [r])
+            row_options.release(self.model, self.st, r.row, row_options.Asked.of([r]))
         r.done.set()
         r.settle()                                               # (the last member of a family sets its head's family_done)
 
     _finish = _release
-
-    def _options_over(self, row0, reqs, if_made=False):
-        """Rows row0 .. row0+n-1 stop carrying the options of the requests that held them: a row's next occupant costs the
-        log-probability launch one early exit, and is neither penalised by this one's record nor masked by its guide.  Each
-        table is touched only if one of the requests used it; if_made (a failed prefill, which may have stopped before a table
-        was made): and only if the state has it."""
-        st, n = self.st, len(reqs)
-        for field, table, end in (("logprobs", "logprob_want", lambda: self.model.set_logprobs(st, [-1] * n, row0)),
-                                  ("penalties", "penalty", lambda: self.model.clear_penalties(st, row0, n)),
-                                  ("guide", "guide", lambda: self.model.clear_guides(st, row0, n))):
-            if any(getattr(r, field) is not None for r in reqs) and not (if_made and getattr(st, table, None) is None):
-                end()
-
-    def _vacate(self, table, clear, spans):
-        """Newcomers that do not use an option take rows (spans: [(row0, n)]) whose previous occupant may have: where the state
-        has that option's table, the rows' records become inactive."""
-        if getattr(self.st, table, None) is not None:
-            for row0, n in spans:
-                getattr(self.model, clear)(self.st, row0, n)
-
-    def _first_tokens(self, logits, row0, penalized, guided):
-        """The first token of rows row0 .. row0+n-1, drawn from prefill logits under the rows' sampling records (a greedy row:
-        temperature 0 = the arg-max): of the adjusted rows if penalised, behind the guide mask if guided."""
-        if penalized:
-            logits = self.model.penalized_logits(self.st, logits, row0)
-        if guided:
-            logits = self.model.guided_logits(self.st, logits, row0)
-        return self.model.sample_logits(self.st, logits, row0)
 
     def _fail_all(self, error):
         with self.lock:
@@ -399,12 +373,6 @@ class ContinuousEngine:
         except Exception as e:                                  # noqa: BLE001
             self.dead = e
             self._fail_all(RuntimeError(f"engine is down: {e!r}"))
-
-    def _set_guides(self, guides, row0):
-        """The rows' guides (None: an inactive record) at their start states; the vocabulary table goes to the model once."""
-        from . import guide as guide_mod
-        self.model.set_guide_vocab(guide_mod.vocab_for(self.processor.tokenizer, self.model.cfg.vocab_size), ID_EOS)
-        self.model.set_guides(self.st, guides, row0)
 
     def _rearm_workspace(self):
         """The in-launch split-KV merge expects an all-sentinel workspace (ops.attention_ws); after a poisoned step a late
@@ -461,122 +429,66 @@ class ContinuousEngine:
             r.row = row0 + i
         inputs = collate_requests([r.inputs for r in group]) if n > 1 else group[0].inputs
         hit = group[0].hit if n == 1 else None                   # a request with a hit is prefilled alone (_admit)
-        kw_prefix = {} if hit is None else {"prefix": hit}       # (without a hit: prefill_slot is called exactly as without a store)
         for r in group:
             r.hit = None                                         # (the handle must not pin a store entry once it is served)
         if self.adapter_names():
             # the rows' adapters (None -> -1: a refilled row must not keep its last occupant's) BEFORE their prefill reads them
             self.model.set_row_adapters(st, [r.adapter for r in group], row0)
-        sampled, penalized, guided, scored = (any(getattr(r, f) is not None for r in group)
-                                              for f in ("sampling", "penalties", "guide", "logprobs"))
-        if not penalized:
-            self._vacate("penalty", "clear_penalties", [(row0, n)])
-        if not guided:
-            self._vacate("guide", "clear_guides", [(row0, n)])
-        if guided:                                               # the rows' regions and start states BEFORE the first token is drawn
-            self._set_guides([r.guide for r in group], row0)
-        if penalized:
-            # the rows' records and prompt bits BEFORE the first token is drawn: it comes from the adjusted prefill logits
-            from . import penalties as penalties_mod
-            prows = [r.penalties or penalties_mod.INACTIVE for r in group]
-            ids2 = np.asarray(inputs["input_ids"])
-            ids2 = ids2[None] if ids2.ndim == 1 else ids2
-            pad = (np.asarray(inputs["mask"]).reshape(ids2.shape) == 0).sum(1).astype(np.int32) if "mask" in inputs else None
-            self.model.set_penalties(st, penalties_mod.pack(prows), ids2, row0,
-                                     bias=penalties_mod.bias_table(prows, self.model.cfg.vocab_size), pad=pad)
-        # 1. the records: a group with any of the three options draws its first token under them (greedy members: temperature
-        # 0), counters reset -- draw 0 comes from the prefill logits; a plain group writes greedy records only where a sampled
-        # request may have had these rows before
-        drawn = sampled or penalized or guided
-        if drawn or getattr(st, "sample_rows", None) is not None:
-            self.model.set_sampling(st, _pack([r.sampling or _GREEDY for r in group], counter=0), row0)
-        # 2. the prefill: its logits kept where the first token is drawn or scored (the plain call otherwise: no keyword)
-        if drawn or scored:
-            toks, logits = self.model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-        else:
-            toks = self.model.prefill_slot(st, row0, inputs, **kw_prefix)
-        # 3. the first token: drawn, or the prefill's own arg-max
-        if drawn:
-            toks = self._first_tokens(logits, row0, penalized, guided)
-        first = toks.reshape(-1).tolist()
-        if min(first) < 0:
-            raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
-        if scored:
-            # the rows' wants into the table (-1 for the members that did not ask), the first token's record from the prefill logits
-            self.model.set_logprobs(st, [-1 if r.logprobs is None else r.logprobs for r in group], row0)
-            recs0 = _unpack_records(self.model.logprobs_of(st, logits, toks, row0))
-            for r, rec0 in zip(group, recs0):
-                if r.logprobs is not None:
-                    r.logprob_records.append(rec0)
-        if hit is not None:
-            group[0].cached_tokens = int(hit[1])
-        self._capture(group)                                     # (after the NaN check: a poisoned row is never captured)
+        toks, first = self._prefill_rows(group, [(row0, n)], inputs, hit)
         g["tok"][row0:row0 + n].copy_(toks.reshape(-1))
-        for r, t in zip(group, first):
-            self.rows[r.row] = r
-            self.joined_mid_flight += int(busy)
-            r.tokens.append(t)
-            if t == ID_EOS or len(r.tokens) >= r.max_tokens:
-                self._release(r)
+        self._seat(group, first, busy)
 
     def _prefill_family(self, head, rows, busy):
-        """n completions of one prompt: every row gets its records first (adapter, penalties and prompt bits, sampling with its
-        own seed and draw counter 0, log-probability want), the prompt is prefilled ONCE into rows[0] -- with a prefix hit or
-        a capture, as any single request -- and forked into the other rows (model.fork_rows: their K/V columns, position
-        tables and pad_len); then every row's first token is drawn from the ONE prefill logits row under its own record.  The
-        rows need not be adjacent: every setter is called per row."""
+        """n completions of one prompt: every row gets its records first (adapter, then row_options.install), the prompt is
+        prefilled ONCE into rows[0] -- with a prefix hit or a capture, as any single request -- and forked into the other rows
+        (model.fork_rows: their K/V columns, position tables and pad_len); then every row's first token is drawn from the ONE
+        prefill logits row under its own record.  The rows need not be adjacent: every setter is called per row."""
         st, model, members = self.st, self.model, head.members
         g = model.decode_graph(st)
         for r, row in zip(members, rows):
             r.row = row
-        row0, inputs = rows[0], head.inputs
         hit, head.hit = head.hit, None
-        kw_prefix = {} if hit is None else {"prefix": hit}
         if self.adapter_names():
             for row in rows:
                 model.set_row_adapters(st, [head.adapter], row)
-        penalized, sampled, scored = head.penalties is not None, head.sampling is not None, head.logprobs is not None
-        if not penalized:
-            self._vacate("penalty", "clear_penalties", [(row, 1) for row in rows])
-        if penalized:
-            from . import penalties as penalties_mod
-            ids2 = np.asarray(inputs["input_ids"]).reshape(1, -1)
-            bias = penalties_mod.bias_table([head.penalties], model.cfg.vocab_size)
-            for row in rows:
-                model.set_penalties(st, penalties_mod.pack([head.penalties]), ids2, row, bias=bias)
-        guided = head.guide is not None
-        if not guided:
-            self._vacate("guide", "clear_guides", [(row, 1) for row in rows])
-        if guided:                                              # the leader's row; fork_rows hands region and start state to the others
-            self._set_guides([head.guide], row0)
-        if sampled or penalized or guided or getattr(st, "sample_rows", None) is not None:
-            for r in members:                                    # (greedy family on a state with records: greedy records, counters reset)
-                model.set_sampling(st, _pack([r.sampling or _GREEDY], counter=0), r.row)
-        if sampled or penalized or scored or guided:
-            toks0, logits = model.prefill_slot(st, row0, inputs, return_logits=True, **kw_prefix)
-        else:
-            toks0, logits = model.prefill_slot(st, row0, inputs, **kw_prefix), None
-        model.fork_rows(st, row0, rows[1:], pad=st.offset - head.S)
-        if self.share_prefix:                                   # columns [pad, offset) of the rows are identical from here on
-            from .parallel import families_without
-            self.families = families_without(self.families, rows) + [(tuple(rows), int(st.offset))]
-            model.set_families(st, self.families)
-        if sampled or penalized or guided:
-            toks = torch.cat([self._first_tokens(logits, r.row, penalized, guided) for r in members]).reshape(-1)
-        else:
-            toks = toks0.reshape(-1)[:1].expand(len(members))    # greedy: the one arg-max serves every row
-        first = toks.tolist()
-        if min(first) < 0:
-            raise RuntimeError(f"device prefill failed: NaN logits (token ids {first})")
-        if scored:
-            for r, t in zip(members, toks):
-                model.set_logprobs(st, [r.logprobs], r.row)
-                r.logprob_records.append(_unpack_records(model.logprobs_of(st, logits, t.reshape(1), r.row))[0])
-        if hit is not None:
-            head.cached_tokens = int(hit[1])
-        self._capture([head])                                    # (after the NaN check: a poisoned row is never captured)
+
+        def fork():
+            model.fork_rows(st, rows[0], rows[1:], pad=st.offset - head.S)
+            if self.share_prefix:                               # columns [pad, offset) of the rows are identical from here on
+                from .parallel import families_without
+                self.families = families_without(self.families, rows) + [(tuple(rows), int(st.offset))]
+                model.set_families(st, self.families)
+        _, first = self._prefill_rows(members, [(row, 1) for row in rows], head.inputs, hit, fork)
         for r, t in zip(members, first):
             g["tok"][r.row:r.row + 1].fill_(t)
+        self._seat(members, first, busy)
+
+    def _prefill_rows(self, reqs, spans, inputs, hit, fork=None):
+        """The rows' option tables, ONE prefill into the first row (its logits kept where the first token is drawn or scored; the
+        plain call otherwise: no keyword, and without a hit exactly as without a store), `fork` (a family: the other rows), the
+        first tokens and their records (row_options), the prefix capture (after the NaN check).  -> (tokens on the device, as a list)"""
+        st, model, row0 = self.st, self.model, spans[0][0]
+        asked = row_options.Asked.of(reqs, lead_guide=fork is not None)
+        row_options.install(model, st, spans, asked, inputs, self.processor)
+        kw = {} if hit is None else {"prefix": hit}
+        if asked.drawn or asked.wants is not None:
+            toks, logits = model.prefill_slot(st, row0, inputs, return_logits=True, **kw)
+        else:
+            toks, logits = model.prefill_slot(st, row0, inputs, **kw), None
+        if fork is not None:
+            fork()
+            toks = toks.reshape(-1)[:1].expand(len(reqs))        # greedy: the one arg-max serves every row
+        toks, first, words = row_options.first_tokens(model, st, spans, asked, logits, toks)
+        for r, rec in zip(reqs, _unpack_records(words) if words is not None else ()):
+            if r.logprobs is not None:
+                r.logprob_records.append(rec)
+        if hit is not None:
+            reqs[0].cached_tokens = int(hit[1])
+        self._capture(reqs if fork is None else reqs[:1])
+        return toks, first
+
+    def _seat(self, reqs, first, busy):
+        for r, t in zip(reqs, first):
             self.rows[r.row] = r
             self.joined_mid_flight += int(busy)
             r.tokens.append(t)
@@ -644,7 +556,7 @@ class ContinuousEngine:
                         if self.rows[x.row] is x:
                             self.rows[x.row] = None
                         self.st.pad_len[x.row:x.row + 1].fill_(self.window)
-                        self._options_over(x.row, [x], if_made=True)
+                        row_options.release(self.model, self.st, x.row, row_options.Asked.of([x]), if_made=True)
                     del x.logprob_records[:], x.tokens[:]
                 head.fail(e)
         admit = [r for r in admit if len(r.members) == 1]
@@ -666,7 +578,7 @@ class ContinuousEngine:
                         self.rows[r.row] = None
                     self.st.pad_len[r.row:r.row + 1].fill_(self.window)
                     del r.logprob_records[:]
-                self._options_over(row0, group, if_made=True)
+                row_options.release(self.model, self.st, row0, row_options.Asked.of(group), if_made=True)
                 if n == 1:
                     group[0].fail(e)
                     continue
@@ -748,14 +660,6 @@ class ContinuousEngine:
     generate = generate
 
 
-_GREEDY = (0.0, 0, 1.0, 0)
-
-
-def _unpack_records(words):
-    from .logprobs import unpack
-    return unpack(words)
-
-
 # What rides beside a request's inputs (request.py has the keys, their one reader and their one writer).  Each helper returns a
 # COPY of a B = 1 `processor(...)` result with one carrier added, so the option travels through a router or a fleet with the
 # inputs; the processor's own result is not touched, and `submit` checks the values.
@@ -790,11 +694,6 @@ def n_args(inputs, n, best_of=None):
 def cache_args(inputs, image_digests=None, cache_prompt=True, prefix_len=None):
     """... the request's prefix-cache arguments."""
     return carry(inputs, PREFIX_ARGS, RequestOptions(image_digests=image_digests, cache_prompt=cache_prompt, prefix_len=prefix_len))
-
-
-def _pack(rows_, counter=0):
-    from .sampling import pack
-    return pack(rows_, counter)
 
 
 def leaf_engines(front):

@@ -51,6 +51,25 @@ def _on_device(fn):
     return wrapped
 
 
+_ATTR = {flag: attr for flag, attr, _ in steps.NEEDS}      # an option's flag -> the CacheState attribute of its table
+_OFF = {"logprobs": -1}         # the word that makes a row of an option's table inactive, by flag (steps.FLAGS); the others: 0
+
+
+def _shared_table(name, doc):
+    return property(lambda self: self.shared.get(name), doc=doc)
+
+
+def _records(table):
+    """The per-row records of an option's table (CacheState): the table itself, or the `rows` of a penalty or guide state."""
+    return table["rows"] if isinstance(table, dict) else table
+
+
+def _last_rows(logits, row0):
+    """(the last position's rows of prefill logits [n, L, V] or [n, V], the slice of state rows row0 .. row0+n-1 they belong to)"""
+    last = logits[:, -1, :] if logits.dim() == 3 else logits
+    return last, slice(row0, row0 + last.shape[0])
+
+
 V_PREFIX = "model.vision_embed_tokens.img_processor.vision_model."
 E_PREFIX = "model.vision_embed_tokens."
 
@@ -140,37 +159,31 @@ class CacheState:
         self.serving = False                                    # owned by a long-lived server (engine.py): see _plan
         self.fresh_rows = False                                 # a rows_view whose columns left of its offset hold nothing its rows may see
         self.row_adapter = None                                 # adapter bank: int32 [B] slot per row, made on first use (model._state_rows)
-        self.sample_rows = None                                 # sampling records int32 [B, 6] (model.set_sampling)
         # shared-prefix decode (model.set_families): the device table int32 [B, 18] of ops.attention_decode_family, made on first
         # use -- from then on the state's L = 1 steps take that launch, whatever the table holds --, the host's copy of it and the
         # families it was built from [(rows, share_end)]
         self.family = self.family_host = None
         self.families = []
 
-    @property
-    def logprob_want(self):
-        """The log-probability want-table, int32 [B] on the device (-1 = off), or None before `model.set_logprobs` made it.  It
-        lives with `shared`: the leases of a captured-prefill entry share their captures, which bake its address in."""
-        return self.shared.get("logprob_want")
-
-    @property
-    def penalty(self):
-        """The penalty state (model.set_penalties): a dict of the rows' records (int32 [B, 4]), their `seen` table (int32 [B, n]:
-        the uint32 words of the rule), the adjusted-logits buffer (bf16 [B, n]) and, once a request brought one, the bias table
-        (fp32 [B, n]) -- or None before the first penalised request.  With `shared`, as the want-table is."""
-        return self.shared.get("penalty")
-
-    @property
-    def guide(self):
-        """The guide state (model.set_guides): a dict of the rows' records (int32 [B, 4]) and their table regions (`delta` int16
-        [B, 256, 256]: the uint16 entries; `accept` uint8 [B, 256]) -- or None before the first guided request.  With `shared`,
-        as the penalty state is."""
-        return self.shared.get("guide")
+    # The tables of the per-row options (steps.NEEDS names them, model._option_table makes them), each None until made.  They live
+    # with `shared`: the leases of a captured-prefill entry share their captures, which bake the tables' addresses in -- a later
+    # lease must write the SAME tensors, not some of its own.
+    sample_rows = _shared_table("sample_rows", """The sampling records, int32 [B, 6] on the device, or None before
+        `model.set_sampling` made them.""")
+    logprob_want = _shared_table("logprob_want", """The log-probability want-table, int32 [B] on the device (-1 = off), or None
+        before `model.set_logprobs` made it.""")
+    penalty = _shared_table("penalty", """The penalty state (model.set_penalties): a dict of the rows' records (int32 [B, 4]),
+        their `seen` table (int32 [B, n]: the uint32 words of the rule), the adjusted-logits buffer (bf16 [B, n]) and, once a
+        request brought one, the bias table (fp32 [B, n]) -- or None before the first penalised request.""")
+    guide = _shared_table("guide", """The guide state (model.set_guides): a dict of the rows' records (int32 [B, 4]) and their
+        table regions (`delta` int16 [B, 256, 256]: the uint16 entries; `accept` uint8 [B, 256]) -- or None before the first
+        guided request.""")
 
     def rows_view(self, rows, offset, S):
         """Batch rows `rows` (a slice) as a cache of their own at `offset`, for a prompt of S tokens (model.prefill_slot): the same
-        buffers sliced, no captured graphs, none of the slot state's roles (slots, serving, sampling records; the caller names the
-        rows' adapters).  fresh_rows: columns left of `offset` hold nothing these rows may see (pad_len >= offset)."""
+        buffers sliced, no captured graphs, none of the slot state's roles (slots, serving; the caller names the rows' adapters;
+        the option tables are the whole state's, and nothing reads them on a view).  fresh_rows: columns left of `offset` hold
+        nothing these rows may see (pad_len >= offset)."""
         view = copy.copy(self)
         view.B = rows.stop - rows.start
         view.S = S
@@ -180,7 +193,6 @@ class CacheState:
         view.slots = False
         view.serving = False
         view.row_adapter = None
-        view.sample_rows = None
         view.family = view.family_host = None                   # (the table is the whole state's: a view's rows are single rows)
         view.families = []
         view.mlx4 = False                                       # (the view carries k / v alone, never the 4-bit prompt codes)
@@ -1618,20 +1630,14 @@ class Phi3VModel:
         """Write the per-row sampling records (sampling.pack: int32 [n, 6] on the host) of rows row0 .. row0+n-1 of a state (one
         H2D copy, outside any graph).  Rows never written are greedy (temperature 0).  The records live with the state's decode
         graphs and are read -- and their counters advanced -- by `sample_logits` and every replay of `sample_step`."""
-        if st.sample_rows is None:
-            # (kept with `shared`, as the want-table is: the leases of a captured-prefill entry share their sampled captures,
-            #  which bake the records' address in -- a later lease must write the SAME tensor, not one of its own)
-            st.sample_rows = st.shared.get("sample_rows")
-            if st.sample_rows is None or st.sample_rows.shape[0] != st.B:
-                st.sample_rows = st.shared["sample_rows"] = torch.zeros((st.B, 6), dtype=I32, device=self.device)
-        st.sample_rows[row0:row0 + records.shape[0]].copy_(records)
+        self._option_table(st, "sampled")[row0:row0 + records.shape[0]].copy_(records)
 
     @_on_device
     def sample_logits(self, st, logits, row0=0):
         """The first token of rows row0 .. row0+n-1 from their prefill logits ([n, L, V] or [n, V]) under their records (the
         draw index is the record's counter, 0 after `set_sampling(..., counter=0)`).  int32 [n, 1] on the device."""
-        last = logits[:, -1, :] if logits.dim() == 3 else logits
-        return ops.sample(last, st.sample_rows[row0:row0 + last.shape[0]])[:, None]
+        last, rows = _last_rows(logits, row0)
+        return ops.sample(last, st.sample_rows[rows])[:, None]
 
     # ------------------------------------------------------------------ captures of the step kinds (steps.py has the table)
     # what a warm-up run of a kind moves beside the loop state, by flag: it is saved before the capture and put back after it
@@ -1665,22 +1671,33 @@ class Phi3VModel:
             for kind in steps.with_flag(flag):
                 g.pop(kind.capture, None)
 
-    def _greedy_records(self, st):
-        """Greedy sampling records (all rows at temperature 0) where the state has none: the penalised tail is the sampled one."""
-        if st.sample_rows is None:
-            self.set_sampling(st, torch.zeros((0, 6), dtype=I32))
+    # ------------------------------------------------------------------ the option tables of a state (steps.NEEDS; CacheState)
+    def _option_table(self, st, flag, bias=False):
+        """The state's table of the option with that flag, made on first use at the shapes ops.L names, every row inactive (greedy
+        sampling records, penalty and guide records their kernels copy through, wants of -1).  bias: the penalty state's [B,
+        vocab] bias table too.  What is made replaces a pointer -- or a null -- the captures with that flag baked in: dropped."""
+        attr, zeros = _ATTR[flag], functools.partial(torch.zeros, dtype=I32, device=self.device)
+        B, V, L = st.B, self.cfg.vocab_size, ops.L
+        t = st.shared.get(attr)
+        if t is None or _records(t).shape[0] != B:
+            t = st.shared[attr] = {
+                "sampled": lambda: zeros((B, L.C.sizeof(L.SampleRow) // 4)),
+                "penalized": lambda: dict(rows=zeros((B, L.PENALTY_WORDS)), seen=zeros((B, V)),
+                                          adj=torch.empty((B, V), dtype=BF16, device=self.device), bias=None),
+                "guided": lambda: dict(rows=zeros((B, L.GUIDE_WORDS)), delta=zeros((B, 256, 256), dtype=torch.int16),
+                                       accept=zeros((B, 256), dtype=torch.uint8)),
+                "logprobs": lambda: zeros((B,)).fill_(_OFF["logprobs"])}[flag]()
+            self._drop_captures(st, flag)
+        if bias and t["bias"] is None:
+            t["bias"] = zeros((B, V), dtype=F32)
+            self._drop_captures(st, flag)
+        return t
 
-    def _ensure_penalty_state(self, st):
-        """The state's penalty state, made on first use with every row inactive (p3v_penalize copies such a row through) and no
-        bias table; a new one drops the captures that read the old."""
-        pen = st.penalty
-        if pen is None or pen["seen"].shape[0] != st.B:
-            V, dev = self.cfg.vocab_size, self.device
-            pen = st.shared["penalty"] = dict(rows=torch.zeros((st.B, ops.L.PENALTY_WORDS), dtype=I32, device=dev),
-                                              seen=torch.zeros((st.B, V), dtype=I32, device=dev),
-                                              adj=torch.empty((st.B, V), dtype=BF16, device=dev), bias=None)
-            self._drop_captures(st, "penalized")
-        return pen
+    def _clear(self, st, flag, row0=0, n=None):
+        """Rows row0 .. row0+n-1 (default: to the end) become inactive for an option, where the state has its table."""
+        t = st.shared.get(_ATTR[flag])
+        if t is not None:
+            _records(t)[row0:None if n is None else row0 + n].fill_(_OFF.get(flag, 0))
 
     # ------------------------------------------------------------------ penalties and logit_bias (include/p3v.h: p3v_penalty_row_t)
     @_on_device
@@ -1692,15 +1709,11 @@ class Phi3VModel:
         adjusted-logits buffer ([B, vocab] each) and greedy sampling records where the state has none (the penalised step's tail
         is the sampled one); the first call WITH a bias makes the [B, vocab] bias table -- captures made before it baked a null
         pointer in and are dropped.  One H2D copy per operand and one scatter, outside any graph."""
-        V, dev = self.cfg.vocab_size, self.device
         n = records.shape[0]
-        pen = self._ensure_penalty_state(st)
-        self._greedy_records(st)
+        pen = self._option_table(st, "penalized", bias=bias is not None)
+        self._option_table(st, "sampled")
         if bias is not None:
-            if pen["bias"] is None:
-                pen["bias"] = torch.zeros((st.B, V), dtype=F32, device=dev)
-                self._drop_captures(st, "penalized")
-            pen["bias"][row0:row0 + n].copy_(torch.as_tensor(np.ascontiguousarray(bias, dtype=np.float32)).view(n, V))
+            pen["bias"][row0:row0 + n].copy_(torch.as_tensor(np.ascontiguousarray(bias, dtype=np.float32)).view(n, self.cfg.vocab_size))
         pen["rows"][row0:row0 + n].copy_(records)
         self.rebuild_penalties(st, prompt_ids, None, row0, pad)
 
@@ -1726,8 +1739,7 @@ class Phi3VModel:
     @_on_device
     def clear_penalties(self, st, row0=0, n=None):
         """Rows row0 .. row0+n-1 (default: to the end) become inactive: the penalised step copies their logits through."""
-        if st.penalty is not None:
-            st.penalty["rows"][row0:None if n is None else row0 + n].zero_()
+        self._clear(st, "penalized", row0, n)
 
     @_on_device
     def penalized_logits(self, st, logits, row0=0):
@@ -1737,8 +1749,7 @@ class Phi3VModel:
         pen = st.penalty
         if pen is None:
             raise RuntimeError("penalized_logits: no penalty state on this state (model.set_penalties)")
-        last = logits[:, -1, :] if logits.dim() == 3 else logits
-        rows = slice(row0, row0 + last.shape[0])
+        last, rows = _last_rows(logits, row0)
         return ops.penalize(last, pen["rows"][rows], pen["seen"][rows], None if pen["bias"] is None else pen["bias"][rows])
 
     # ------------------------------------------------------------------ guided decoding (include/p3v.h: p3v_guide_row_t, guide.py)
@@ -1776,17 +1787,10 @@ class Phi3VModel:
         from . import guide as guide_mod
         if getattr(self, "_guide_vocab", None) is None:
             raise RuntimeError("set_guides: no vocabulary table on this model (model.set_guide_vocab)")
-        dev, n = self.device, len(guides)
+        n = len(guides)
         if row0 < 0 or row0 + n > st.B:
             raise ValueError(f"set_guides: rows {row0} .. {row0 + n - 1} are outside the state's {st.B}")
-        gd = st.guide
-        if gd is None or gd["rows"].shape[0] != st.B:
-            gd = st.shared["guide"] = dict(rows=torch.zeros((st.B, ops.L.GUIDE_WORDS), dtype=I32, device=dev),
-                                           delta=torch.zeros((st.B, 256, 256), dtype=torch.int16, device=dev),
-                                           accept=torch.zeros((st.B, 256), dtype=torch.uint8, device=dev))
-            self._drop_captures(st, "guided")
-        self._ensure_penalty_state(st)
-        self._greedy_records(st)
+        gd = [self._option_table(st, flag) for flag in ("guided", "penalized", "sampled")][0]
         recs = []
         for i, dfa in enumerate(guides):
             recs.append(guide_mod.record(dfa, 1 if states is None else states[i]))
@@ -1802,8 +1806,7 @@ class Phi3VModel:
     @_on_device
     def clear_guides(self, st, row0=0, n=None):
         """Rows row0 .. row0+n-1 (default: to the end) become inactive: the guided step does not touch them."""
-        if st.guide is not None:
-            st.guide["rows"][row0:None if n is None else row0 + n].zero_()
+        self._clear(st, "guided", row0, n)
 
     @_on_device
     def guided_logits(self, st, logits, row0=0):
@@ -1813,8 +1816,8 @@ class Phi3VModel:
         gd = st.guide
         if gd is None:
             raise RuntimeError("guided_logits: no guide state on this state (model.set_guides)")
-        last = (logits[:, -1, :] if logits.dim() == 3 else logits).clone()
-        return self._guide_mask(last, gd, slice(row0, row0 + last.shape[0]), None)
+        last, rows = _last_rows(logits, row0)
+        return self._guide_mask(last.clone(), gd, rows, None)
 
     # ------------------------------------------------------------------ token log-probabilities (include/p3v.h: p3v_logprob_t)
     @_on_device
@@ -1825,9 +1828,7 @@ class Phi3VModel:
         wants = torch.as_tensor(list(wants), dtype=I32)
         if wants.numel() and (int(wants.min()) < -1 or int(wants.max()) > ops.L.LOGPROBS_MAX):
             raise ValueError(f"set_logprobs: entries are -1 (off) or 0..{ops.L.LOGPROBS_MAX}")
-        if st.logprob_want is None:
-            st.shared["logprob_want"] = torch.full((st.B,), -1, dtype=I32, device=self.device)
-        st.logprob_want[row0:row0 + wants.numel()].copy_(wants)
+        self._option_table(st, "logprobs")[row0:row0 + wants.numel()].copy_(wants)
 
     @_on_device
     def logprobs_of(self, st, logits, tokens, row0=0):
@@ -1836,8 +1837,8 @@ class Phi3VModel:
         logits.  int32 [n, 20] on the device (logprobs.unpack); rows at -1 are left zero."""
         if st.logprob_want is None:
             raise RuntimeError("logprobs_of: no want-table on this state (model.set_logprobs)")
-        last = logits[:, -1, :] if logits.dim() == 3 else logits
-        return ops.logprobs(last, tokens.reshape(-1).to(I32).contiguous(), st.logprob_want[row0:row0 + last.shape[0]])
+        last, rows = _last_rows(logits, row0)
+        return ops.logprobs(last, tokens.reshape(-1).to(I32).contiguous(), st.logprob_want[rows])
 
     @_on_device
     def __call__(self, input_ids, pixel_values=None, image_sizes=None, positions=None, cache=None, pids=None, mask=None,

@@ -19,6 +19,7 @@ from . import _lib as L
 
 SEED_MOD = 1 << 64
 RECORD_WORDS = 6                      # sizeof(p3v_sample_row_t) / 4
+GREEDY = (0.0, 0, 1.0, 0)             # the (temperature, top_k, top_p, seed) of a row that takes the arg-max
 
 
 def _per_row(name, v, B):

@@ -5,12 +5,15 @@ given; never a tensor's contents.
 
     python tests/golden/gen_golden_step_calls.py        # rewrites tests/golden/step_calls.json
 
-Two recordings:
+Three recordings:
   "engine"  ContinuousEngine, a request with each combination of {sampling, penalties (with a logit_bias), guide, logprobs} in six
             situations: alone in one slot, in a group of two beside a plain request, as a family of three, followed in its slot by
             a plain request, with `prefill_slot` raising for the group, with `prefill_slot` raising for the family.  Per situation
             the ordered model calls, the step methods taken until idle and how each request ended.
   "loop"    api.greedy_loop on CPU tensors (the one-sync-per-token path), the same combinations, four steps each.
+  "generate" api._generate around that loop, the same combinations, each as one prompt, as two prompts and as n = 3 completions of
+            one prompt: the prefill call, the fork, the setters and the first token's draw and record.  `api.model_ops` is replaced
+            by a logging stub for the run (its kernels refuse CPU tensors); its calls are logged as `model_ops.name(...)`.
 Sampling always carries a seed, so nothing is random.
 """
 import itertools
@@ -71,6 +74,19 @@ class Recorder:
         self.log, self.steps = [], []
         self.raises = raises                                      # "group": prefill_slot raises for n > 1; "all": always
 
+    def __call__(self, **kw):
+        """The prefill of `_generate`: zero logits of the last position and a one-layer cache over a new State."""
+        self._note("model", (), (), kw)
+        B, S = np.asarray(kw["input_ids"]).shape
+        return torch.zeros((B, 1, VOCAB)), [type("L", (), {"state": State(B, S + kw["max_tokens"])})()]
+
+    def fork_state(self, st, *a, **kw):
+        self._note("fork_state", ("n",), a, kw)
+        return [type("L", (), {"state": State(a[0], st.T)})()]
+
+    def set_row_adapters(self, st, *a, **kw):
+        self._note("set_row_adapters", ("names", "row0"), a, kw)
+
     def _note(self, name, names, args, kw, **extra):
         vals = dict(zip(names, args))
         vals.update(kw)
@@ -110,6 +126,9 @@ class Recorder:
         from phi_3_vision_mlx_amd import penalties
         st.penalty = True
         self._note("set_penalties", ("records", "prompt_ids", "row0"), a, kw, flags=[r["flags"] for r in penalties.unpack(a[0])])
+
+    def rebuild_penalties(self, st, *a, **kw):
+        self._note("rebuild_penalties", ("prompt_ids", "emitted", "row0", "pad"), a, kw)
 
     def clear_penalties(self, st, *a, **kw):
         self._note("clear_penalties", ("row0", "n"), a, kw)
@@ -239,8 +258,60 @@ def record_loop():
     return {"cpu": out}
 
 
+class OpsLog:
+    """Stands in for `api.model_ops` while `_generate` runs on the Recorder: the three launches it makes itself, logged."""
+
+    def __init__(self, m):
+        self.m = m
+
+    def argmax(self, *a, **kw):
+        self.m._note("model_ops.argmax", ("logits",), a, kw)
+        return torch.arange(400, 400 + a[0].shape[0], dtype=torch.int32)
+
+    def sample(self, *a, **kw):
+        from phi_3_vision_mlx_amd import sampling
+        recs = sampling.unpack(a[1])
+        self.m._note("model_ops.sample", ("logits", "records"), a, kw, counter=[r["counter"] for r in recs],
+                     greedy=[r["temperature"] == 0.0 for r in recs])
+        return torch.arange(500, 500 + a[0].shape[0], dtype=torch.int32)
+
+    def logprobs(self, *a, **kw):
+        from phi_3_vision_mlx_amd import logprobs
+        self.m._note("model_ops.logprobs", ("logits", "tokens", "wants"), a, kw, want=a[2].tolist())
+        return torch.zeros((a[0].shape[0], logprobs.RECORD_WORDS), dtype=torch.int32)
+
+
+def record_generate():
+    from phi_3_vision_mlx_amd import api, row_options
+    from phi_3_vision_mlx_amd.processor import ByteTokenizer, Phi3FProcessor
+    proc = Phi3FProcessor(tokenizer=ByteTokenizer())
+    shapes = {"one": ("a prompt", {}), "two": (["a prompt", "another, longer"], {}), "n3": ("a prompt", {"n": 3})}
+    out, real_ops = {}, api.model_ops
+    for combo in COMBOS:
+        kw = {}
+        if "sampling" in combo:
+            kw.update(temperature=0.7, top_k=5, seed=11)
+        if "penalties" in combo:
+            kw.update(repetition_penalty=1.3, logit_bias={"5": -2.0})
+        if "guide" in combo:
+            kw.update(guided_regex="[0-9]+")
+        if "logprobs" in combo:
+            kw.update(logprobs=2)
+        for shape, (prompt, kw_shape) in shapes.items():
+            m, info = Recorder(), {}
+            api.model_ops = row_options.model_ops = OpsLog(m)
+            try:
+                result = api._generate(m, proc, prompt, max_tokens=5, verbose=False, mute=True, logprob_info=info, **kw, **kw_shape)
+            finally:
+                api.model_ops = row_options.model_ops = real_ops
+            out.setdefault("+".join(combo) or "plain", {})[shape] = {
+                "calls": m.log, "steps": m.steps, "results": len(result) if isinstance(result, list) else 1,
+                "collected": [None if t is None else len(t) for t in info["token_ids"]] if info else None}
+    return out
+
+
 def record_all():
-    return {"engine": record_engine(), "loop": record_loop()}
+    return {"engine": record_engine(), "loop": record_loop(), "generate": record_generate()}
 
 
 def dumps(rec):

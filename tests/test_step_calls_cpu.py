@@ -1,7 +1,8 @@
-"""The callers of the decode step -- ContinuousEngine and api.greedy_loop -- make the calls on the model they made before the
-eight step kinds were stated in one table: every combination of sampling, penalties, guide and logprobs, in six engine situations
-and in the loop, against the recording in tests/golden/step_calls.json (written by tests/golden/gen_golden_step_calls.py from the
-code as it stood before steps.py; no model, no GPU)."""
+"""The callers of the decode step -- ContinuousEngine, api.greedy_loop and api._generate around it -- make the calls on the model
+that tests/golden/step_calls.json records: every combination of sampling, penalties, guide and logprobs, in six engine situations,
+in the loop, and in _generate for one prompt, two prompts and n = 3 (written by tests/golden/gen_golden_step_calls.py; no model,
+no GPU).  The engine and loop parts are as recorded before steps.py; since row_options.py the family's setters come in the group's
+order, and _generate makes the engine's calls for the first token (set_sampling + sample_logits, set_logprobs + logprobs_of)."""
 import json
 
 import pytest
@@ -28,13 +29,15 @@ def test_the_matrix_covers_every_combination_and_situation(got):
     assert len(gen.COMBOS) == 16 and len(set(gen.COMBOS)) == 16
     assert len(got["engine"]) == 16 and all(sorted(v) == sorted(gen.SITUATIONS) for v in got["engine"].values())
     assert len(got["loop"]["cpu"]) == 16
+    assert len(got["generate"]) == 16 and all(sorted(v) == ["n3", "one", "two"] for v in got["generate"].values())
     # every step method is taken somewhere, and a plain request is driven by the greedy step alone
     assert {s for v in got["engine"].values() for c in v.values() for s in c["steps"]} == set(gen.STEPS)
     assert {s for c in got["loop"]["cpu"].values() for s in c["steps"]} == set(gen.STEPS)
+    assert {s for v in got["generate"].values() for c in v.values() for s in c["steps"]} == set(gen.STEPS)
     assert set(got["engine"]["plain"]["alone"]["steps"]) == {"greedy_step"}
 
 
-@pytest.mark.parametrize("part", ["engine", "loop"])
+@pytest.mark.parametrize("part", ["engine", "loop", "generate"])
 def test_calls_on_the_model(got, golden, part):
     have = json.loads(json.dumps(got[part], sort_keys=True))
     assert sorted(have) == sorted(golden[part])

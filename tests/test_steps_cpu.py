@@ -114,6 +114,26 @@ def test_a_method_raises_when_the_state_lacks_what_its_kind_needs_and_only_then(
             assert {s for s in SETTERS.values() if s in str(e.value)} == {SETTERS[a] for a in needed - have}
 
 
+@pytest.mark.parametrize("flag", steps.FLAGS)
+def test_making_one_option_s_table_makes_exactly_what_needs_names_for_it(flag):
+    """The model's one make-or-get helper and CacheState's properties follow steps.NEEDS: a state that had only one option's table
+    made reports that attribute, and no other, as made -- an option added to the table alone (or to the model alone) fails here."""
+    from phi_3_vision_mlx_amd.model import CacheState, Phi3VModel, _records
+    assert [f for f, _, _ in steps.NEEDS] == list(steps.FLAGS)
+    me = types.SimpleNamespace(cfg=types.SimpleNamespace(vocab_size=40), device="cpu", _drop_captures=Phi3VModel._drop_captures)
+    st = object.__new__(CacheState)
+    st.B, st.shared, st.graphs = 3, {}, {"greedy": {k.capture: object() for k in steps.ALL}}
+    assert all(getattr(st, attr) is None for _, attr, _ in steps.NEEDS)
+    made = Phi3VModel._option_table(me, st, flag)
+    assert {attr for _, attr, _ in steps.NEEDS if getattr(st, attr) is not None} == {ATTRS[flag]}
+    assert getattr(st, ATTRS[flag]) is made and _records(made).shape[0] == 3
+    assert Phi3VModel._option_table(me, st, flag) is made                             # (the second call gets, it does not make)
+    # what baked the old pointer (or its absence) in is gone: the captures of the kinds with that flag, and no others
+    assert set(st.graphs["greedy"]) == {k.capture for k in steps.ALL if not getattr(k, flag)}
+    for k in steps.ALL:
+        assert (k.missing(st) == []) == (not any(getattr(k, f) for f in steps.FLAGS if f != flag)), k
+
+
 def test_the_model_class_has_the_table_s_methods_and_each_reaches_replay_with_its_kind():
     from phi_3_vision_mlx_amd.model import Phi3VModel
     seen = []
